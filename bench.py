@@ -6,7 +6,19 @@ prints ONE JSON line on rank 0.  A "step" is one substep (src/mpm.cpp:452-575) o
 BASELINE.json's metric is quoted on: config C3 = 256^3 grid, 100^3 cells x 8 = 8 000 000 Drucker-Prager sand
 particles, fp32, inputs resident in HBM before the timed region.
 
-Sequence:  W warm-up substeps (untimed) | a short untimed pass with every phase bracketed by hipEvents (phase
+Plain run (the default): set-up | W warm-up substeps (untimed) | barrier | K timed substeps, no event anywhere | barrier | the
+line: metric, value, unit, ms_per_step (= one timed substep), higher_is_better, dtype, config.  Nothing else is measured.
+--full adds everything below (the roofline, the phase table, the per-rank tables of N > 1 and the extra objects of the line);
+the timed region of a --full run then brackets the dominant kernel as described next.
+--dump-outputs DIR (one GPU): after the timed substeps, the particle state they left (the arrays get_particles hands a caller: x,
+v, B, F, aux, gid, id, states) for a fixed, seeded sample of DUMP_SAMPLE creation ids, one DIR/<field>.npy each, float32
+(integer fields as float64).  The scene is a seeded lattice: the same arguments give the same inputs, run after run.  Such a run
+steps in the deterministic mode from its first substep (config.deterministic of the line): the default substep orders a cell's
+particles by the arrival of atomics, so its sums differ in the last bits from run to run, and once the block has hit the floor
+(~2 000 C3 substeps) the flow amplifies that into different states; in-cell order by creation id makes the timed path, and so
+the dump, the same bits every run.  Its ms_per_step is that mode's (about 0.045 ms more per C3 substep than a plain run).
+
+Sequence (--full):  W warm-up substeps (untimed) | a short untimed pass with every phase bracketed by hipEvents (phase
 table, picks the dominant kernel) | barrier | K timed substeps, only the dominant kernel bracketed and only in every 4th of
 them (an event record idles the GPU for ~5 us: bracketing all phases would add ~20 us per substep, the dominant kernel in
 every substep 2 % of a C3 substep; roofline.launches_timed says how many launches the mean is over) | barrier.
@@ -15,7 +27,7 @@ N > 1 (bricks + halo exchange): before that sequence the bo
 the exchange behind the interior kernels at the price of three more launches) is timed on and off over a dozen untimed
 substeps, max over ranks, and the faster way is kept: config.overlap_split (MPMHIP_TILE_OVERLAP=0|1 pins it).
 
-Extra objects on the line:
+Extra objects on the line (--full):
   roofline      dominant kernel (the slower of k_p2g / k_g2p): algorithmic bytes per launch / its average launch
                 duration over the K timed substeps, hipEvents recorded on the ctx stream (mpmhip_set_profiling).
                 Algorithmic bytes per particle: P2G 100 B particle read + 16 B per touched grid node
@@ -82,7 +94,8 @@ def build_sim(tm, cfg, device):
     lo = res // 2 - cells // 2
     sim = tm.create_simulation3("mpm").initialize(dict(res=(res,) * 3, delta_x=1.0 / res, base_delta_t=cfg.get("dt", 1e-4),
                                                        gravity=(0, -10, 0), device=device,
-                                                       keep_apic_b=bool(cfg.get("keep_apic_b", False))))
+                                                       keep_apic_b=bool(cfg.get("keep_apic_b", False)),
+                                                       deterministic=bool(cfg.get("deterministic", False))))
     sim.set_levelset(tm.mpm.LevelSet(friction=-1.0).add_plane((0, 1, 0), d=-0.1))  # sticky floor y = 0.1
     from taichi_mpm_amd.tiled import scene_groups
     for typ, lo, n in scene_groups(cfg):  # C5: one cube per corner of a 2x2x2 arrangement, materials alternating
@@ -100,6 +113,26 @@ def substeps_to_impact(cfg, g=10.0, floor=0.1):
 
 VIRTUAL_BUDGET_S = 60.0  # N = 1: the `virtual` block of the line takes K = 8 first, then 2 and 4 while the block stays below this
 EVOLVE_AFTER_IMPACT = 400  # substeps run after the block has touched the floor before the `evolved` state is timed
+DUMP_SAMPLE = 1 << 18  # --dump-outputs: particles written (~32 MB at 124 bytes each, under the 64 MB the dump may take)
+DUMP_SEED = 20261016
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(sim, out_dir, n_seeded):
+    """--dump-outputs DIR: the arrays get_particles hands a caller after the last timed substep (x, v, B, F, aux, gid, id, states),
+    restricted to a fixed, seeded sample of creation ids (the scene numbers its particles 0 .. n_seeded - 1), one DIR/<field>.npy
+    each in creation-id order: float32, integer fields as float64 (exact).  A particle deleted on the way is simply absent
+    (id.npy says which rows are there)."""
+    p = sim.get_particles(sort_by_id=True)
+    pick = np.random.default_rng(DUMP_SEED).choice(n_seeded, size=min(DUMP_SAMPLE, n_seeded), replace=False)
+    rows = np.isin(p["id"], pick)
+    out = {name: np.ascontiguousarray(a[rows], dtype=np.float64 if a.dtype.kind in "iu" else np.float32) for name, a in p.items()}
+    if sum(a.nbytes for a in out.values()) > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: the sample exceeds %d bytes" % DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return int(rows.sum())
 
 
 def evolve_to_impact(sim, cfg):
@@ -520,7 +553,19 @@ def main():
     ap.add_argument("--virtual", type=int, default=0, metavar="K",
                     help="diagnostic, not the metric: run the K-brick tiled job as K ctx on ONE GPU (exchanges are local "
                          "copies) and print per-rank phase times = the per-GPU compute of a K-GPU run without the wire")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: phase table, roofline, per-rank tables (N > 1), the second wire "
+                         "of --wire both and the extra objects of the line (deterministic, evolved, virtual, c5, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="one GPU: after the timed substeps, write the particle state they left (a fixed, seeded sample of %d "
+                         "particles) as DIR/<field>.npy" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.wire == "both" and not args.full:
+        ap.error("--wire both measures a second wire: add --full")
+    if args.dump_outputs and (args.gpus != 1 or args.virtual > 1 or os.environ.get("MPMHIP_FORCE_TILED") == "1"):
+        ap.error("--dump-outputs is for the one-GPU job (--gpus 1, no --virtual, no MPMHIP_FORCE_TILED)")
 
     # stdout carries exactly ONE line (the JSON): native libraries print banners to fd 1 (RCCL prints its version
     # block when the first communicator is created), so fd 1 points at stderr until the result is ready
@@ -604,6 +649,8 @@ def main():
                 staged, wire = True, "gloo, staged through host memory (RCCL probe failed; --allow-staged)"
 
     cfg = dict(CONFIGS[args.config])
+    if args.dump_outputs:  # (see the docstring: the outputs of the default substep are not reproducible bit for bit)
+        cfg["deterministic"] = True
     if args.cells:  # reduced problem (tests, smoke runs): NOT the metric's configuration — the line says so
         cfg["cells"] = args.cells
         cfg["desc"] += " [REDUCED: cube edge %d cells]" % args.cells
@@ -630,13 +677,21 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(warmup, steps):
+    def measure(warmup, steps, phases=True):
         """W untimed warm-up substeps | a short untimed pass with every phase bracketed (phase table, picks the
         dominant transfer kernel) | barrier | K timed substeps with only the dominant kernel bracketed | barrier.
         Returns (seconds, phase table in ms per substep with the dominant kernel taken from the timed region, which
-        kernel dominates, profile of the timed region)."""
+        kernel dominates, profile of the timed region).  phases=False (a plain run): no phase pass and no event in the
+        timed region; returns (seconds, None, None, None)."""
         job.run(warmup)
         job.synchronize()
+        if not phases:
+            barrier()
+            t0 = time.perf_counter()
+            job.run(steps)
+            job.synchronize()
+            barrier()
+            return time.perf_counter() - t0, None, None, None
         job.set_profiling(1)
         job.run(min(10, max(steps, 1)))
         phase_prof = job.profile()
@@ -717,7 +772,9 @@ def main():
         print("bench.py[rank %d]: overlap split %s (%.4f ms per substep with, %.4f without)" % (rank, overlap_note["kept"], t_on, t_off),
               file=sys.stderr, flush=True)
     dog.phase("measurement", 900)
-    elapsed, ms, dom, prof = measure(args.warmup, args.steps)
+    elapsed, ms, dom, prof = measure(args.warmup, args.steps, phases=args.full)
+    if args.dump_outputs:  # (before anything else runs on the ctx: the state the last timed substep left)
+        dump_outputs(job.sim, args.dump_outputs, n_local)
     dog.phase("report", 900)
     PHASES = ("sort", "p2g", "exchange", "grid", "g2p")
 
@@ -740,7 +797,7 @@ def main():
                 "per_rank": [{k: float(tab[r, i]) for i, k in enumerate(names)} for r in range(world)]}
 
     tiled_info = None
-    if world > 1 or force_tiled:
+    if args.full and (world > 1 or force_tiled):
         tiled_info = rank_table(ms, elapsed)
         tiled_info["wire"] = native_wire or ("torch" if data_group is not None else "staged")
         if native_wire and hasattr(job, "totals"):
@@ -775,7 +832,7 @@ def main():
     else:
         n_total = n_local
     copy_gbs = None
-    if world == 1 and not force_tiled:  # what a plain streaming copy reaches on THIS box, measured after the timed region
+    if args.full and world == 1 and not force_tiled:  # what a plain streaming copy reaches on THIS box, measured after the timed region
         try:
             copy_gbs = job.sim.copy_bandwidth(1 << 30, 5)
         except Exception as e:
@@ -786,14 +843,9 @@ def main():
             dist.destroy_process_group()
         return
 
-    tag = args.config + ("_evolved" if args.state == "evolved" else "")
-    roof, both_frac, n_per_gpu, nodes = roofline_of(ms, dom, prof, tag)
-    roof["measured_copy_GBs"] = copy_gbs  # plain float4 copy kernel on this box (read + written bytes)
-    roof["frac_of_measured_copy"] = (roof["achieved"] / copy_gbs) if copy_gbs else None
     value = n_total * args.steps / elapsed
-    whole_step_bytes = n_per_gpu * 252.0 + nodes * 16.0 * 5
     state_desc = ("the lattice the reference's benchmark seeds (8 particles per cell, F = I, slots in sorted order): the best "
-                  "case; see `evolved` for the same scene after the block has hit the floor")
+                  "case; see `evolved` (--full) for the same scene after the block has hit the floor")
     if args.state == "evolved":
         state_desc = "%d substeps after the block hit the floor (--state evolved)" % EVOLVE_AFTER_IMPACT
     out = {
@@ -805,15 +857,24 @@ def main():
         "config": {"workload": cfg["desc"], "particles": n_total, "dt": cfg.get("dt", 1e-4), "parallelism": job.parallelism, "wire": wire,
                    "overlap_split": overlap_note,
                    "timed": "full substep: sort+reorder, P2G, grid normalise+boundary, G2P, boundary cleanup",
+                   "deterministic": bool(cfg.get("deterministic", False)),
                    "state": state_desc},
-        "roofline": roof,
-        "phases_ms_per_step": ms,
-        "tiled": tiled_info,
-        "p2g_plus_g2p_particle_steps_per_s": n_per_gpu / ((ms["p2g"] + ms["g2p"]) * 1e-3),
-        "p2g_plus_g2p_hbm_frac_algorithmic": both_frac,
-        "whole_step_hbm_frac_algorithmic": whole_step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
     }
-    if world == 1 and not force_tiled:
+    if args.full:
+        tag = args.config + ("_evolved" if args.state == "evolved" else "")
+        roof, both_frac, n_per_gpu, nodes = roofline_of(ms, dom, prof, tag)
+        roof["measured_copy_GBs"] = copy_gbs  # plain float4 copy kernel on this box (read + written bytes)
+        roof["frac_of_measured_copy"] = (roof["achieved"] / copy_gbs) if copy_gbs else None
+        whole_step_bytes = n_per_gpu * 252.0 + nodes * 16.0 * 5
+        out.update({
+            "roofline": roof,
+            "phases_ms_per_step": ms,
+            "tiled": tiled_info,
+            "p2g_plus_g2p_particle_steps_per_s": n_per_gpu / ((ms["p2g"] + ms["g2p"]) * 1e-3),
+            "p2g_plus_g2p_hbm_frac_algorithmic": both_frac,
+            "whole_step_hbm_frac_algorithmic": whole_step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
+        })
+    if args.full and world == 1 and not force_tiled and not cfg.get("deterministic"):
         # the same K substeps with the cells in creation-id order behind every sort (bitwise reproducible runs): what the mode costs
         try:
             job.sim.set_deterministic(True)
@@ -829,7 +890,7 @@ def main():
                                     "what": "mpmhip_config.deterministic: k_cell_order_blocks behind every sort (in-cell order by creation id; the ids in a 4-byte array the key writers keep)"}
         except Exception as e:
             out["deterministic"] = {"error": repr(e)}
-    if world == 1 and not force_tiled and args.state == "lattice" and not args.no_evolved:
+    if args.full and world == 1 and not force_tiled and args.state == "lattice" and not args.no_evolved:
         # the same scene after impact, on the same ctx: the state the lattice number flatters
         try:
             after = EVOLVE_AFTER_IMPACT
@@ -851,7 +912,7 @@ def main():
                 out["evolved"]["warning"] = "%d of %d particles were deleted before the timed region" % (n_per_gpu - e_n, n_per_gpu)
         except Exception as e:
             out["evolved"] = {"error": repr(e)}
-    if world == 1 and not force_tiled and not args.no_virtual and args.config == "c3" and not args.cells and args.state == "lattice":
+    if args.full and world == 1 and not force_tiled and not args.no_virtual and args.config == "c3" and not args.cells and args.state == "lattice":
         # The only multi-GPU evidence one GPU can give, on the same box and in the same process as the headline: the K bricks of the
         # workload as K ctx on this GPU (the library's own loop, halo exchange and migration over the local wire; the ranks' kernels
         # run one after another on one stream, so the time per rank is what one rank alone on a device computes per substep).
@@ -879,7 +940,7 @@ def main():
             out["virtual"] = vout
         except Exception as e:
             out["virtual"] = {"error": repr(e)}
-    if world == 1 and not force_tiled and not args.no_c5 and args.config == "c3" and not args.cells and args.state == "lattice":
+    if args.full and world == 1 and not force_tiled and not args.no_c5 and args.config == "c3" and not args.cells and args.state == "lattice":
         # BASELINE configs[4] (512^3 / 64 M mixed particles: the configuration the >= 6x at 8 GPUs is claimed for) on THIS GPU in one ctx,
         # then as 8 virtual ranks (one 8 M cluster each): the same proxy as `virtual`, driver-timed
         try:
@@ -890,7 +951,7 @@ def main():
             out["c5"] = c5_block(tm, args)
         except Exception as e:
             out["c5"] = {"error": repr(e)}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             from oracle import refmpm
             out["cpu_baseline"] = cpu_baseline_reference(cfg) if refmpm.available() else cpu_baseline(cfg)

@@ -374,7 +374,9 @@ int mpmhip_comm_destroy(mpmhip_ctx *ctx);
 /* loopback check of the binding: world-sized all-gather + a grouped send / receive ring (to self when world == 1) on device
  * buffers, verified on the host; collective over the ranks */
 int mpmhip_comm_selftest(mpmhip_ctx *ctx);
-/* partition + plan + buffers; replaces mpmhip_set_partition / mpmhip_set_halo.  Synchronises. */
+/* partition + plan + buffers; replaces mpmhip_set_partition / mpmhip_set_halo.  Synchronises.  A ctx of an IPC job set up again
+ * on the IPC wire with an unchanged arena size keeps its arena (zeroed) and its handle; mpmhip_tiled_ipc_connect then keeps
+ * the mappings of the peers' arenas whose handles are unchanged. */
 int mpmhip_tiled_setup(mpmhip_ctx *ctx, const mpmhip_tiled_config *cfg, const int32_t *cuts_x, const int32_t *cuts_y,
                        const int32_t *cuts_z);
 int mpmhip_tiled_ipc_handle(mpmhip_ctx *ctx, uint8_t handle[MPMHIP_IPC_HANDLE_BYTES]);

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 cd $R
 python -m pytest tests -m gpu -q --durations=10 > $O/r06_final_pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> $O/r06_final_pytest_gpu.txt
-( time python bench.py ) > $O/r06_final_bench_c3.json 2> $O/r06_final_bench_c3.err
+( time python bench.py --full ) > $O/r06_final_bench_c3.json 2> $O/r06_final_bench_c3.err
 bash profiles/run_profile.sh r06_z > /dev/null 2>&1
 bash profiles/run_profile.sh r06_z_evolved --state evolved > /dev/null 2>&1
 bash profiles/r06_census.sh r06_z > /dev/null 2>&1

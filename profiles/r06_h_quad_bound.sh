@@ -7,11 +7,11 @@ cd $R
 line() { grep '^{' | tail -1; }
 for rep in 1 2 3; do
 for A in 0 192 64 128; do
-  MPMHIP_LIB_VARIANT=ablate MPMHIP_ABLATE=$A python bench.py --no-evolved --no-virtual --steps 40 --warmup 10 --no-cpu-baseline 2>/dev/null | line > $O/r06_h_quad_${A}_$rep.json
+  MPMHIP_LIB_VARIANT=ablate MPMHIP_ABLATE=$A python bench.py --full --no-evolved --no-virtual --steps 40 --warmup 10 --no-cpu-baseline 2>/dev/null | line > $O/r06_h_quad_${A}_$rep.json
 done
 done
 for A in 0 192; do
-  MPMHIP_LIB_VARIANT=ablate MPMHIP_ABLATE=$A python bench.py --state evolved --no-evolved --no-virtual --steps 40 --warmup 10 --no-cpu-baseline 2>/dev/null | line > $O/r06_h_quad_ev_${A}.json
+  MPMHIP_LIB_VARIANT=ablate MPMHIP_ABLATE=$A python bench.py --full --state evolved --no-evolved --no-virtual --steps 40 --warmup 10 --no-cpu-baseline 2>/dev/null | line > $O/r06_h_quad_ev_${A}.json
 done
 python - <<'P'
 import json, glob, os

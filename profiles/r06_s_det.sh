@@ -10,7 +10,7 @@ for form in 1 0; do
     python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-virtual --no-evolved --no-c5 > $O/r06_s_det_form$form.log 2>&1
   cp $W/t_kernel_stats.csv $O/r06_s_det_form${form}_kernel_stats.csv
   for st in lattice evolved; do
-    MPMHIP_DETERMINISTIC=1 MPMHIP_CELL_ORDER=$form python $R/bench.py --state $st --no-cpu-baseline --no-virtual --no-evolved 2>/dev/null | grep '^{' | tail -1 > $O/r06_s_det_form${form}_$st.json
+    MPMHIP_DETERMINISTIC=1 MPMHIP_CELL_ORDER=$form python $R/bench.py --full --state $st --no-cpu-baseline --no-virtual --no-evolved 2>/dev/null | grep '^{' | tail -1 > $O/r06_s_det_form${form}_$st.json
   done
 done
-python $R/bench.py --no-cpu-baseline --no-virtual 2>/dev/null | grep '^{' | tail -1 > $O/r06_s_bench.json
+python $R/bench.py --full --no-cpu-baseline --no-virtual 2>/dev/null | grep '^{' | tail -1 > $O/r06_s_bench.json

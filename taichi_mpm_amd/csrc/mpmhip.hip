@@ -272,6 +272,7 @@ struct mpmhip_ctx {
       float4 *recv[2] = {nullptr, nullptr}, *inbox = nullptr;
       double *red[2] = {nullptr, nullptr};  // reduction tables (tiled_api.h: tn_reduce_*)
       void *ipc_base = nullptr;  // mapped with hipIpcOpenMemHandle (closed on destroy)
+      uint8_t handle[MPMHIP_IPC_HANDLE_BYTES] = {};  // the handle ipc_base was opened from
     };
     struct Mig { std::vector<int64_t> counts; std::vector<int> rank_bounds /* [world][6]: lo3, hi3 base cells, before the records moved */; int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}; float speed = 0.0f; int64_t total = 0, n_out = 0, n_in = 0; } mig;
     bool on = false, connected = false, exch_on_side = false;
@@ -288,6 +289,8 @@ struct mpmhip_ctx {
     uint64_t total = 0, halo_cap = 0, inbox_cap = 0;
     size_t arena_bytes = 0, table_bytes = 0, recv_bytes = 0, mig_send_cap = 0;
     char *arena = nullptr;
+    uint8_t handle[MPMHIP_IPC_HANDLE_BYTES] = {};  // the arena's IPC handle, made once per arena (mpmhip_tiled_ipc_handle)
+    bool handle_valid = false;
     uint32_t *flags = nullptr, *table[2] = {nullptr, nullptr}, *row = nullptr, *d_done = nullptr;
     float4 *send = nullptr, *recv[2] = {nullptr, nullptr}, *inbox = nullptr, *mig_send = nullptr;
     DevBox *d_boxes[2] = {nullptr, nullptr};

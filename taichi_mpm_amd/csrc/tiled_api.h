@@ -611,12 +611,19 @@ int tn_energy(mpmhip_ctx *c, double out[3]) {
   return tn_reduce_finish(c, out, 3, MPMHIP_REDUCE_SUM);
 }
 
-void tn_free(mpmhip_ctx *c) {
+// keep_ipc (an IPC job set up again, mpmhip_tiled_setup): the arena, its handle and the mappings of the peers' arenas stay in the
+// ctx for the new set-up to take over or release.  Freeing an exported arena and exporting / opening a fresh one in the same
+// processes is not reliable in the HIP runtime: a re-wired two-rank job then waited in vain for its peer's epochs, or the export
+// of the fresh arena failed (bench.py --wire both on ranks that share a GPU, tests/test_gpu_tiled.py)
+void tn_release(mpmhip_ctx *c, bool keep_ipc) {
   auto &N = c->tn;
-  for (auto &p : N.peers)
-    if (p.ipc_base) (void)hipIpcCloseMemHandle(p.ipc_base);
-  N.peers.clear();
-  if (N.arena) (void)hipFree(N.arena);
+  keep_ipc = keep_ipc && N.wire == MPMHIP_WIRE_IPC && N.arena;
+  if (!keep_ipc) {
+    for (auto &p : N.peers)
+      if (p.ipc_base) (void)hipIpcCloseMemHandle(p.ipc_base);
+    N.peers.clear();
+    if (N.arena) (void)hipFree(N.arena);
+  }
   if (N.send) (void)hipFree(N.send);
   if (N.mig_send) (void)hipFree(N.mig_send);
   if (N.row) (void)hipFree(N.row);
@@ -629,8 +636,19 @@ void tn_free(mpmhip_ctx *c) {
   if (N.ev_a) (void)hipEventDestroy(N.ev_a);
   if (N.ev_b) (void)hipEventDestroy(N.ev_b);
   if (N.comm && rccl_api()->handle) (void)rccl_api()->CommDestroy((ncclComm_t)N.comm);
-  N = mpmhip_ctx::TiledNative();
+  mpmhip_ctx::TiledNative kept;
+  if (keep_ipc) {
+    kept.wire = N.wire;
+    kept.arena = N.arena;
+    kept.arena_bytes = N.arena_bytes;
+    kept.peers.swap(N.peers);
+    memcpy(kept.handle, N.handle, sizeof kept.handle);
+    kept.handle_valid = N.handle_valid;
+  }
+  N = std::move(kept);
 }
+
+void tn_free(mpmhip_ctx *c) { tn_release(c, false); }
 
 }  // namespace
 
@@ -731,8 +749,9 @@ int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int3
   void *keep_comm = c->tn.comm;
   const int keep_rank = c->tn.comm_rank, keep_world = c->tn.comm_world;
   c->tn.comm = nullptr;
-  tn_free(c);
+  tn_release(c, cfg->wire == MPMHIP_WIRE_IPC);
   auto &N = c->tn;
+  const size_t kept_bytes = N.arena ? N.arena_bytes : 0;  // (an IPC job set up again: its arena is taken over below if the layout holds)
   N.comm = keep_comm; N.comm_rank = keep_rank; N.comm_world = keep_world;
   N.loop_rccl = loop_rccl;
   if (N.comm && !loop_rccl && (N.comm_world != cfg->world || N.comm_rank != cfg->rank)) return fail(c, MPMHIP_EINVAL, "the communicator is rank %d of %d, the partition rank %d of %d", N.comm_rank, N.comm_world, cfg->rank, cfg->world);
@@ -767,8 +786,21 @@ int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int3
   const size_t recv_bytes = ((sizeof(float4) * N.halo_cap + 255) / 256) * 256;
   N.arena_bytes = TN_FLAG_BYTES + TN_RED_BYTES + 2 * table_bytes + 2 * recv_bytes + sizeof(float4) * 11 * N.inbox_cap;
   const bool peer_wire = N.wire == MPMHIP_WIRE_IPC || N.wire == MPMHIP_WIRE_LOCAL;
-  hipError_t e;
-  if (N.wire == MPMHIP_WIRE_IPC) {
+  if (N.arena && (kept_bytes != N.arena_bytes || N.peers.size() != (size_t)N.world)) {
+    for (auto &p : N.peers)
+      if (p.ipc_base) (void)hipIpcCloseMemHandle(p.ipc_base);
+    N.peers.clear();
+    (void)hipFree(N.arena);
+    N.arena = nullptr;
+    N.handle_valid = false;
+  }
+  std::vector<mpmhip_ctx::TiledNative::Peer> mapped;  // (the kept mappings of the peers' arenas)
+  mapped.swap(N.peers);
+  hipError_t e = hipSuccess;
+  if (N.arena) {
+    // the kept arena: zeroed below like a fresh one (every rank has synchronised its stream and passed the caller's barrier, so no
+    // peer writes into it until the job is connected again)
+  } else if (N.wire == MPMHIP_WIRE_IPC) {
     // written by kernels of other devices while kernels of this one poll and read it: fine-grained (coherent at system
     // scope while kernels run); MPMHIP_TILE_COARSE=1 allocates ordinary device memory instead (single-device tests)
     const bool coarse = getenv("MPMHIP_TILE_COARSE") && atoi(getenv("MPMHIP_TILE_COARSE")) != 0;
@@ -785,6 +817,11 @@ int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int3
   N.table_bytes = table_bytes; N.recv_bytes = recv_bytes;
   N.peers.assign((size_t)N.world, mpmhip_ctx::TiledNative::Peer());
   N.peers[cfg->rank] = self;
+  for (size_t p = 0; p < mapped.size(); p++)  // (mpmhip_tiled_ipc_connect keeps a mapping whose peer hands over the same handle)
+    if ((int)p != cfg->rank && mapped[p].ipc_base) {
+      N.peers[p].ipc_base = mapped[p].ipc_base;
+      memcpy(N.peers[p].handle, mapped[p].handle, sizeof mapped[p].handle);
+    }
   if (!peer_wire || N.loop_rccl) HIPCHK(c, dmalloc(&N.send, (size_t)N.halo_cap));
   HIPCHK(c, dmalloc(&N.row, (size_t)TN_ROW));
   HIPCHK(c, hipMemset(N.row, 0, sizeof(uint32_t) * TN_ROW));
@@ -812,10 +849,14 @@ int mpmhip_tiled_ipc_handle(mpmhip_ctx *c, uint8_t handle[MPMHIP_IPC_HANDLE_BYTE
   if (!c || !handle) return MPMHIP_EINVAL;
   if (!c->tn.on || c->tn.wire != MPMHIP_WIRE_IPC) return fail(c, MPMHIP_EINVAL, "ipc_handle needs mpmhip_tiled_setup with MPMHIP_WIRE_IPC");
   HIPCHK(c, hipSetDevice(c->device));
-  hipIpcMemHandle_t h;
-  static_assert(sizeof h == MPMHIP_IPC_HANDLE_BYTES, "hipIpcMemHandle_t size");
-  HIPCHK(c, hipIpcGetMemHandle(&h, c->tn.arena));
-  memcpy(handle, &h, sizeof h);
+  if (!c->tn.handle_valid) {  // (once per arena: a kept arena hands out the handle its peers have opened)
+    hipIpcMemHandle_t h;
+    static_assert(sizeof h == MPMHIP_IPC_HANDLE_BYTES, "hipIpcMemHandle_t size");
+    HIPCHK(c, hipIpcGetMemHandle(&h, c->tn.arena));
+    memcpy(c->tn.handle, &h, sizeof h);
+    c->tn.handle_valid = true;
+  }
+  memcpy(handle, c->tn.handle, MPMHIP_IPC_HANDLE_BYTES);
   return MPMHIP_OK;
 }
 
@@ -847,9 +888,15 @@ int mpmhip_tiled_ipc_connect(mpmhip_ctx *c, const uint8_t *handles) {
   for (int p = 0; p < N.world; p++) {
     if (p == c->T.rank) continue;
     auto &P = N.peers[p];
+    const uint8_t *hp = handles + (size_t)p * MPMHIP_IPC_HANDLE_BYTES;
+    if (P.ipc_base && memcmp(P.handle, hp, sizeof P.handle) == 0) {  // the peer kept its arena: so does this mapping
+      tn_carve(P, static_cast<char *>(P.ipc_base), table_bytes, recv_bytes);
+      continue;
+    }
     if (P.ipc_base) { (void)hipIpcCloseMemHandle(P.ipc_base); P.ipc_base = nullptr; }
     hipIpcMemHandle_t h;
-    memcpy(&h, handles + (size_t)p * MPMHIP_IPC_HANDLE_BYTES, sizeof h);
+    memcpy(&h, hp, sizeof h);
+    memcpy(P.handle, hp, sizeof P.handle);
     void *base = nullptr;
     hipError_t e = hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess);
     if (e != hipSuccess) return fail(c, MPMHIP_EHIP, "hipIpcOpenMemHandle of rank %d's arena: %s", p, hipGetErrorString(e));

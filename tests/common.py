@@ -1,4 +1,6 @@
 """Shared seeded scene builders for oracle and GPU parity tests."""
+import os
+
 import numpy as np
 
 from oracle import oracle as orc
@@ -57,3 +59,30 @@ def make_state(x, type_name, dx, density=400.0, ppc=8, seed=1, vel_scale=1.0, pe
 def rel_l2(a, b):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN_PART_BYTES = 900_000  # raw bytes per file of a fixture: compressed, every committed file stays under 1 MiB
+
+
+def save_golden(name, **arrays):
+    """tests/golden/<name>.npz, split into <name>.npz, <name>.2.npz, ... of at most GOLDEN_PART_BYTES raw bytes each"""
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if parts[-1] and size + v.nbytes > GOLDEN_PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(GOLDEN, name + (".npz" if i == 0 else ".%d.npz" % (i + 1))), **part)
+
+
+def load_golden(name):
+    """{key: array} of a fixture written by save_golden (all its parts)"""
+    out, i = dict(np.load(os.path.join(GOLDEN, name + ".npz"))), 2
+    while os.path.exists(os.path.join(GOLDEN, "%s.%d.npz" % (name, i))):
+        out.update(np.load(os.path.join(GOLDEN, "%s.%d.npz" % (name, i))))
+        i += 1
+    return out

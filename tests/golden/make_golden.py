@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from oracle import oracle as orc  # noqa: E402  (only for the parameter rows / type ids the fixtures carry)
 from oracle import refmpm as ref  # noqa: E402
-from tests.common import MAT_KW, lattice_cube, make_state  # noqa: E402
+from tests.common import MAT_KW, lattice_cube, make_state, save_golden  # noqa: E402
 
 RES, DX, DT = 32, 1.0 / 32, 1e-4
 PLANES = [(0.0, 1.0, 0.0, -0.3)]
@@ -238,7 +238,7 @@ def shapes_fixture(here):
                 out[key] = np.concatenate([d["x"], d["v"], d["F"], d["aux"][:, None]], 1)
                 out[key + "_ids"] = d["id"]
     import json
-    np.savez_compressed(os.path.join(here, "ref_shapes.npz"), res=RES, dx=DX, dt=DT, cases=json.dumps(
+    save_golden("ref_shapes", res=RES, dx=DX, dt=DT, cases=json.dumps(
         {k: dict(shapes=[list(map(float, sh)) for sh in c["shapes"]], friction=c["friction"], cfg=c["cfg"],
                  shapes1=[list(map(float, sh)) for sh in c["shapes1"]] if "shapes1" in c else None, t1=c.get("t1", 1.0))
          for k, c in cases.items()}), **out)
@@ -295,7 +295,7 @@ def mpm2d_fixture(here):
             sim.close()
             out["%s_%s" % (name, mat)] = np.concatenate([d["x"], d["v"], d["F"], d["B"], d["aux"][:, None]], 1)
             out["%s_%s_ids" % (name, mat)] = d["id"]
-    np.savez_compressed(os.path.join(here, "ref_mpm2d.npz"), res=res, dx=dx, dt=dt, cases=json.dumps(MPM2D_CASES), **out)
+    save_golden("ref_mpm2d", res=res, dx=dx, dt=dt, cases=json.dumps(MPM2D_CASES), **out)
     print("mpm2d:", len(x), "particles")
 
 

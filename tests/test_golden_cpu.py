@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.common import rel_l2
+from tests.common import load_golden, rel_l2
 
 HERE = os.path.dirname(__file__)
 GOLD = sorted(glob.glob(os.path.join(HERE, "golden", "substep_*.npz")))
@@ -103,7 +103,7 @@ def test_oracle_kernels_and_friction_match_the_reference(orc):
 
 
 def _shape_cases():
-    g = np.load(os.path.join(HERE, "golden", "ref_shapes.npz"))
+    g = load_golden("ref_shapes")
     return g, json.loads(str(g["cases"]))
 
 

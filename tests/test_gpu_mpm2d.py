@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.common import rel_l2
+from tests.common import load_golden, rel_l2
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(__file__)
@@ -36,7 +36,7 @@ def _levelset(tm, rows, friction):
 
 
 def _cases():
-    g = np.load(os.path.join(HERE, "golden", "ref_mpm2d.npz"))
+    g = load_golden("ref_mpm2d")
     cases = json.loads(str(g["cases"]))
     return g, cases, [(c, m) for c in cases for m in MATS if "%s_%s" % (c, m) in g]
 

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.common import lattice_cube, make_state, rel_l2
+from tests.common import lattice_cube, load_golden, make_state, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -105,7 +105,7 @@ def test_device_materials_match_the_reference(tm, mat):
 
 
 def _shape_cases():
-    g = np.load(os.path.join(HERE, "golden", "ref_shapes.npz"))
+    g = load_golden("ref_shapes")
     return g, json.loads(str(g["cases"]))
 
 

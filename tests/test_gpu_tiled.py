@@ -725,7 +725,7 @@ def test_bench_multi_rank_path_end_to_end_on_one_gpu(tm, nproc, bricks, hook, co
         env["MPMHIP_NO_IPC_FALLBACK"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(nproc), "--config", config,
-           "--steps", "8", "--warmup", "4"] + (["--cells", "16"] if config == "c5" else []) + (["--allow-staged"] if hook == "staged" else []) + \
+           "--steps", "8", "--warmup", "4", "--full"] + (["--cells", "16"] if config == "c5" else []) + (["--allow-staged"] if hook == "staged" else []) + \
           (["--wire", "both"] if both else [])
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=root)
     if hook == "refuse":

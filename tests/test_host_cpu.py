@@ -190,6 +190,52 @@ def test_bench_and_examples_are_importable_without_a_gpu():
         py_compile.compile(os.path.join(root, "examples", f), doraise=True)
 
 
+def test_bench_dump_outputs_writes_the_same_seeded_float_sample_every_run(tmp_path):
+    """bench.py --dump-outputs: every field get_particles hands a caller, for one fixed, seeded sample of creation ids, as
+    float32 (integer fields as float64), at most 64 MB even for the 64 M-particle configuration; a deleted particle is absent"""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    widths = {"x": 3, "v": 3, "B": 9, "F": 9, "aux": 1, "gid": 1, "id": 1, "states": 1}
+    assert bench.DUMP_SAMPLE * sum(8 if k in ("gid", "id", "states") else 4 * w for k, w in widths.items()) <= bench.DUMP_LIMIT_BYTES
+    n = 3 * bench.DUMP_SAMPLE
+    deleted = np.arange(0, n, 97)
+
+    class Sim:
+        def get_particles(self, sort_by_id=True):
+            assert sort_by_id
+            ids = np.setdiff1d(np.arange(n, dtype=np.int32), deleted)
+            p = {k: (ids[:, None] + np.arange(w, dtype=np.float32) / 16).astype(np.float32).squeeze() for k, w in widths.items()}
+            p.update(gid=ids % 2, id=ids, states=ids % 3)
+            return p
+    kept = [bench.dump_outputs(Sim(), str(tmp_path / d), n) for d in ("a", "b")]
+    assert kept[0] == kept[1] < bench.DUMP_SAMPLE
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in widths) and sorted(os.listdir(tmp_path / "b")) == files
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), got[f[:-4]])
+    ids = got["id"]
+    assert ids.dtype == np.float64 and len(ids) == kept[0] and np.all(np.diff(ids) > 0) and not np.isin(ids, deleted).any()
+    assert got["gid"].dtype == got["states"].dtype == np.float64 and np.array_equal(got["states"], ids % 3)
+    assert got["x"].dtype == got["F"].dtype == np.float32 and got["F"].shape == (len(ids), 9)
+    assert np.array_equal(got["x"][:, 0], ids.astype(np.float32))
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_bench_refuses_what_a_run_cannot_deliver():
+    """argument errors end bench.py before it touches a device: no timed step, a dump of a multi-GPU job, --wire both without --full"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for extra, why in ((["--steps", "0"], "--steps"), (["--gpus", "2", "--dump-outputs", "out"], "one-GPU job"),
+                       (["--gpus", "2", "--wire", "both"], "add --full")):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra, capture_output=True, text=True, timeout=120, cwd=root)
+        assert r.returncode == 2 and why in r.stderr and not r.stdout, (extra, r.stdout, r.stderr)
+
+
 def test_roofline_traffic_is_withheld_when_the_kernel_is_not_the_one_the_counters_ran_on():
     """bench.py divides the committed PMC bytes by a freshly timed launch: that is only a measurement while the loaded library's
     kernel IS the kernel the PMC passes ran on.  profiles/traffic_*.json record the kernels' code hashes (make_traffic.py --lib,
