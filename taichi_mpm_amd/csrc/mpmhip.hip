@@ -21,7 +21,8 @@
 //                         of the grid pass where that pass walks it (small problems, tiled contexts)
 //          k_perm_keyed   sorted position -> particle slot (k_perm after k_rank)
 //   P2G    k_p2g   one wavefront per active 4x4x4-cell block, ONE LANE PER CELL: register accumulation of the
-//                  27x4 node contributions over the cell's particles (records prefetched two particles ahead),
+//                  27x4 node contributions over the cell's particles (the wave loads two particles of every cell
+//                  at a time, whole records per load instruction, into LDS, one window ahead),
 //                  ordered non-atomic float4 merge into the block's 6^3-node LDS tile, tile written out whole
 //                                                                                (src/transfer.cpp:467-569)
 //   grid   k_grid  sums the <=8 overlapping block tiles of every touched grid block, normalises,
