@@ -56,9 +56,7 @@ __device__ __forceinline__ void g2p_particle(const Params &P, const float scale,
       b1xy = fma2(splat2(w0i), T1xy, b1xy); b1zw = fma2(splat2(w0i), T1zw, b1zw);
       b2xy = fma2(splat2(w0i), T2xy, b2xy); b2zw = fma2(splat2(w0i), T2zw, b2zw);
     };
-    if (!MPM_ABLATE(P, 4)) {
-      plane(0, w0[0], e0[0]); plane(1, w0[1], e0[1]); plane(2, w0[2], e0[2]);
-    }
+    plane(0, w0[0], e0[0]); plane(1, w0[1], e0[1]); plane(2, w0[2], e0[2]);
     float v0 = vxy.x, v1 = vxy.y, v2 = vzw.x;
     mat3 b;
     b(0, 0) = b0xy.x; b(1, 0) = b0xy.y; b(2, 0) = b0zw.x;
@@ -88,8 +86,7 @@ __device__ __forceinline__ void g2p_particle(const Params &P, const float scale,
     F.m[7] = g2.w; F.m[8] = g3.x;
     float aux = g0.w;
     mat3 stress;
-    if (!MPM_ABLATE(P, 2)) plasticity_and_force<MATS, true>(g, cdg, F, aux, stress, reinterpret_cast<float *>(lane_lds));  // :950 + next substep's :509
-    else stress = cdg;
+    plasticity_and_force<MATS, true>(g, cdg, F, aux, stress, reinterpret_cast<float *>(lane_lds));  // :950 + next substep's :509
     float nx0 = fmaf(v0, P.dt, x0), nx1 = fmaf(v1, P.dt, x1), nx2 = fmaf(v2, P.dt, x2);  // :951
     if (P.clamp_pos) {  // generic path only (optimized = false): p.pos clamped into [0, res - eps], :668-670
       nx0 = fminf(fmaxf(nx0 * P.idx, 0.0f), (float)P.res[0] - 1e-6f) * P.dx;
@@ -132,7 +129,7 @@ __device__ __forceinline__ void g2p_particle(const Params &P, const float scale,
       B1 = make_float4(b.m[4], b.m[5], b.m[6], b.m[7]);
       B2 = make_float4(b.m[8], 0.0f, 0.0f, 0.0f);
     }
-    out_slot = MPM_ABLATE(P, 1) ? INVALID : pos;
+    out_slot = pos;
 }
 
 // ------------------------------------------------------------------------------------------------ G2P

@@ -10,14 +10,9 @@
 #pragma once
 #include "k_rigid.h"
 
-#ifndef MPM_RIGID_P2G_MINW
-#define MPM_RIGID_P2G_MINW 2
-#endif
-#ifndef MPM_RIGID_G2P_MINW
-#define MPM_RIGID_G2P_MINW 2
-#endif
-
 namespace mpm {
+
+constexpr int RIGID_P2G_MIN_WAVES = 2, RIGID_G2P_MIN_WAVES = 2;  // __launch_bounds__ waves per SIMD of k_p2g_rigid / k_g2p_rigid
 
 struct RigidXfer {
   CdfDev C;
@@ -71,7 +66,7 @@ __device__ __forceinline__ void load_state_tile(const CdfDev &C, int bx, int by,
 // normal) and its stress term go to the body as an impulse at the node instead (:425-444).
 constexpr int P2GR_LIST = 1024;
 template <uint32_t MATS = MAT_ALL>  // material set of the ctx (mpm_math.h): the impulse walk evaluates calculate_force()
-__global__ __launch_bounds__(64, MPM_RIGID_P2G_MINW) void k_p2g_rigid(Params P, const float4 *__restrict__ rp, const float4 *__restrict__ rg,
+__global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P, const float4 *__restrict__ rp, const float4 *__restrict__ rg,
                                                   const Counters *__restrict__ cnt, const uint32_t *__restrict__ act_blk,
                                                   const uint32_t *__restrict__ cell_start, const uint32_t *__restrict__ perm,
                                                   const GroupParams *__restrict__ groups, float4 *__restrict__ tiles,
@@ -276,7 +271,7 @@ __global__ __launch_bounds__(64, MPM_RIGID_P2G_MINW) void k_p2g_rigid(Params P, 
 // momentum (:800-804) and is pushed back by the penalty term when it is slightly inside (:821-832), the body receiving
 // the opposite impulse.  Everything after the gather is k_g2p's (same record layout, same key / deletion logic).
 template <uint32_t MATS = MAT_ALL>
-__global__ __launch_bounds__(256, MPM_RIGID_G2P_MINW) void k_g2p_rigid(Params P, const float4 *__restrict__ rg, float4 *__restrict__ rg_out,
+__global__ __launch_bounds__(256, RIGID_G2P_MIN_WAVES) void k_g2p_rigid(Params P, const float4 *__restrict__ rg, float4 *__restrict__ rg_out,
                                                    float4 *__restrict__ rp_out, float4 *__restrict__ rb_out,
                                                    const Counters *__restrict__ cnt, const uint32_t *__restrict__ act_blk,
                                                    const uint32_t *__restrict__ act_start, const uint32_t *__restrict__ perm,

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "mpm_math.h"
@@ -79,19 +80,13 @@ struct Params {
   int particle_collision;  // particle_collision_resolution after G2P (src/mpm.cpp:566-569)
   int clamp_pos;     // generic transfer path (optimized = false): positions clamped into [0, res - eps] (src/transfer.cpp:668-670)
   int test_small_rank;  // TEST KNOB (env MPMHIP_TEST_SMALL_RANK, results valid): a 3-bit rank field in k_rank's packed words
-  int ablate;        // only read by -DMPMHIP_ABLATE_BUILD libraries (profiles/ A/B builds; results invalid): env MPMHIP_ABLATE,
-                     // 1 no G2P stores, 2 no constitutive update, 4 no 27-tap gather, 8 no P2G merge, 16 / 32 P2G capped at 8 / 6
-                     // particles per cell, 64 / 128 P2G writes 150 of 216 tile nodes / the grid pass reads 5 of 8 tiles (quad-tile bound).  The default
-                     // library compiles every use of it away (MPM_ABLATE below is the constant false).
+  int reserved;      // (unused: keeps pidc, and with it every kernel's argument offsets, where they were)
   uint32_t *pidc;    // deterministic mode only (else null): creation id per SLOT, 4 bytes beside key[] — whoever writes a slot's key writes
                      // its id here (k_g2p / k_g2p_packed / k_g2p_rigid at the sorted position, k_build_keys, k_import), so k_cell_order
                      // gathers 4-byte words instead of one 64-byte record line per particle (k_sort.h)
 };
-#ifdef MPMHIP_ABLATE_BUILD
-#define MPM_ABLATE(P, bit) (((P).ablate & (bit)) != 0)
-#else
-#define MPM_ABLATE(P, bit) false
-#endif
+// Params is every transfer kernel's first argument, passed by value: a layout change moves the argument loads of all of them
+static_assert(offsetof(Params, pidc) == 96 && sizeof(Params) == 104, "Params layout");
 
 // multi-GPU tiling (include/mpmhip.h, "Multi-GPU tiling"): partition of the cell space into bricks + halo boxes
 struct Tiling {

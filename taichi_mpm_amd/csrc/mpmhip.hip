@@ -63,6 +63,7 @@
 #include <map>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <hipcub/hipcub.hpp>  // one plain device sort (the reference's order of the rigid boundary particles, rigid_api.h)
@@ -70,10 +71,6 @@
 #include <rccl/rccl.h>  // types and prototypes only (tiled_api.h): librccl is dlopen'ed, this library does not link it
 
 
-#ifndef MPM_G2P_MINW
-#define MPM_G2P_MINW 2  // __launch_bounds__ waves/SIMD of k_g2p.  (256, 3) states the 168-VGPR budget explicitly but was measured 3 % slower
-                        // (profiles/r03_h_ab_refactor.txt: w2 against default); the budget is guarded by tests/test_kernel_budget_cpu.py instead
-#endif
 #include "mpm_common.h"
 #include "k_sort.h"
 #include "k_particles.h"
@@ -93,6 +90,26 @@
 
 // ================================================================================================ host side
 using namespace mpm;
+
+// __launch_bounds__ waves/SIMD of k_g2p.  (256, 3) states the 168-VGPR budget explicitly but was measured 3 % slower
+// (profiles/r03_h_ab_refactor.txt: w2 against default); the budget is guarded by tests/test_kernel_budget_cpu.py instead
+constexpr int G2P_MIN_WAVES = 2;
+// One material in the ctx (mask = 1u << t): the instantiation of a transfer kernel that carries only that material's
+// calculate_force(), pick(std::integral_constant<uint32_t, 1u << t>()); several materials: fallback.  The materials in SKIP keep the
+// fallback and are not instantiated.
+template <uint32_t SKIP, class K, class Pick, int... T>
+static K one_material(uint32_t mask, K fallback, Pick pick, std::integer_sequence<int, T...>) {
+  K k = fallback;
+  auto one = [&](auto bit) {
+    if constexpr ((decltype(bit)::value & MAT_ALL & ~SKIP) != 0u) { if (mask == bit.value) k = pick(bit); }
+  };
+  (one(std::integral_constant<uint32_t, 1u << T>()), ...);
+  return k;
+}
+template <uint32_t SKIP = 0, class K, class Pick>
+static K one_material(uint32_t mask, K fallback, Pick pick) {
+  return one_material<SKIP>(mask, fallback, pick, std::make_integer_sequence<int, 32>());
+}
 
 static thread_local std::string g_create_error;
 
@@ -150,7 +167,6 @@ struct mpmhip_ctx {
   bool ordered = false;       // the records lie in the order of the last sort (k_g2p wrote them at their sorted positions)
   bool compact = false;       // ... and the live ones occupy exactly [0, cnt->n_sorted): n_slots may shrink to that
   int p2g_wgs = 16384;        // workgroups of k_p2g (env MPMHIP_P2G_WGS)
-  int p2g_split = 11;         // tuning knob (env MPMHIP_P2G_SPLIT): 10*NS + PS, see do_p2g
   int g2p_wgs = 0;            // workgroups of k_g2p; 0: by size (env MPMHIP_G2P_WGS pins it)
   int n_cus = 256;            // compute units of the device
   int g2p_packed = -1;        // k_g2p_packed instead of k_g2p: -1 by size (from 2 M slots on; no rigid bodies, no tiling), 0 never, 1 wherever it
@@ -159,7 +175,6 @@ struct mpmhip_ctx {
   int rigid_wgs = 2048;       // workgroups of k_p2g_rigid (one per wave slot of the device), twice those of k_g2p_rigid (env MPMHIP_RIGID_WGS: tuning)
   uint32_t rank_runs_mul = 3; // k_rank takes its LDS-hash path when runs * this > slots (env MPMHIP_RANK_RUNS_MUL: tuning)
   int ct_blocks = 0;          // blocks per chunk of k_cell_table: 0 by size, 16, 32, 64 (env MPMHIP_CT_BLOCKS: tuning)
-  int g2p_minw = 12;          // tuning knob (env MPMHIP_G2P_MINW): 10 + __launch_bounds__ waves/SIMD of k_g2p
   int reorder_interval = 0;   // physical reorder every this many substeps (0 = never); env MPMHIP_REORDER_INTERVAL
   float t = 0.0f, request_t = 0.0f;  // `real` accumulators, as in the reference (src/mpm.h:99, mpm.cpp:573)
   int64_t substeps = 0;
@@ -262,9 +277,6 @@ struct mpmhip_ctx {
   bool ov_active = false, interior_done = false;  // state of the substep in flight
   const DevBox *d_boxes_cur = nullptr;  // the box table the pack / grid kernels of the substep in flight read
   bool dirichlet = false;      // mpmhip_set_dirichlet
-#ifdef MPMHIP_TIMING_BUILD
-  unsigned long long *p2g_tlog = nullptr;  // [3 max_blocks]: begin, end (100 MHz wall clock), fullest cell << 32 | particles of the block
-#endif
   // the native data plane of a tiled run (tiled_api.h): plan, arena, wire, migration state
   struct TiledNative {
     struct Box { int peer; int lo[3], hi[3]; uint64_t vol, off, peer_off; };  // off / peer_off: float4 nodes into this rank's / the peer's buffers
@@ -280,7 +292,7 @@ struct mpmhip_ctx {
     bool defer_signal = false, signal_deferred = false;  // local job: the ranks' epochs are published by ONE launch of the group (tiled_api.h)
     bool loop_rccl = false;               // MPMHIP_WIRE_LOCAL_RCCL: a local job whose halo boxes travel by RCCL self-sends (tiled_api.h)
     std::vector<mpmhip_ctx *> local_ctx;  // the ranks of a local job (mpmhip_tiled_connect_local)
-    bool wait_merged = false, merge_signal_wait = true;  // IPC wire, no overlap split: signal + wait of a substep in one launch
+    bool wait_merged = false;  // IPC wire, no overlap split: signal + wait of a substep in one launch
     int world = 1, wire = 0;
     int clip_lo[3] = {0, 0, 0}, clip_hi[3] = {0, 0, 0};
     std::vector<int> occ;  // [world][6]: every rank's occupancy box (lo3, hi3, nodes): node_box(r) is cut to it (tiled_api.h: plan)
@@ -476,13 +488,11 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   if (!c) return fail(nullptr, MPMHIP_ENOMEM, "host allocation failed");
   c->cfg = *cfg;
   c->device = cfg->device;
-  if (const char *e = getenv("MPMHIP_G2P_MINW")) c->g2p_minw = atoi(e);
   if (const char *e = getenv("MPMHIP_G2P_WGS")) c->g2p_wgs = atoi(e) > 0 ? atoi(e) : 0;
   if (const char *e = getenv("MPMHIP_RIGID_CONCURRENT")) c->rigid.concurrent = atoi(e);
   if (const char *e = getenv("MPMHIP_RIGID_WGS")) c->rigid_wgs = atoi(e) > 1 ? atoi(e) : 2048;
   if (const char *e = getenv("MPMHIP_RANK_RUNS_MUL")) c->rank_runs_mul = (uint32_t)atoi(e);
   if (const char *e = getenv("MPMHIP_CT_BLOCKS")) c->ct_blocks = atoi(e);
-  if (const char *e = getenv("MPMHIP_P2G_SPLIT")) c->p2g_split = atoi(e);
   if (const char *e = getenv("MPMHIP_G2P_PACKED")) c->g2p_packed = atoi(e);
   if (const char *e = getenv("MPMHIP_P2G_WGS")) c->p2g_wgs = atoi(e) > 0 ? atoi(e) : 16384;
   if (const char *e = getenv("MPMHIP_GRID_WALK")) c->grid_walk = atoi(e);
@@ -493,11 +503,6 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   if (const char *e = getenv("MPMHIP_DETERMINISTIC")) c->deterministic = atoi(e) != 0;
   if (const char *e = getenv("MPMHIP_CELL_ORDER")) c->cell_order_form = atoi(e) != 0;
   if (const char *e = getenv("MPMHIP_CELL_ORDER_WGS")) c->cell_order_wgs = std::max(1, atoi(e));
-#ifdef MPMHIP_ABLATE_BUILD
-  const int ablate = getenv("MPMHIP_ABLATE") ? atoi(getenv("MPMHIP_ABLATE")) : 0;
-#else
-  const int ablate = 0;  // (the default library has no ablation paths: MPM_ABLATE is the constant false)
-#endif
   auto bail = [&](int code) { g_create_error = c->err; mpmhip_destroy(c); return code; };
   if (hipSetDevice(c->device) != hipSuccess) { fail(c, MPMHIP_EHIP, "hipSetDevice failed"); return bail(MPMHIP_EHIP); }
   Params &P = c->P;
@@ -515,7 +520,6 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   P.clean_boundary = cfg->clean_boundary;
   P.store_b = cfg->discard_apic_b ? 0 : 1;
   P.clamp_pos = cfg->generic_path ? 1 : 0;
-  P.ablate = ablate;
   P.test_small_rank = getenv("MPMHIP_TEST_SMALL_RANK") ? atoi(getenv("MPMHIP_TEST_SMALL_RANK")) : 0;
   memset(&c->LS, 0, sizeof c->LS);
   c->LS.particle_collision = cfg->particle_collision;
@@ -559,8 +563,8 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   A(dmalloc(&c->cell_start, (size_t)mb * BC + 1));
   // key-indexed cell counters (256 B per block of the WHOLE block space: 67 MB at 128^3, 537 MB at 256^3..508^3): with them the ranks
   // need no block table and share a launch with it (k_sort_front); grids of 2^24 blocks (res > 508) keep the four-launch sort
-  const int sort_v1 = getenv("MPMHIP_SORT_V1") ? atoi(getenv("MPMHIP_SORT_V1")) : 0;  // (A/B: 1 four launches, no table; 2 four launches, table allocated)
-  c->sort_keyed = c->NB <= (1u << 21) && sort_v1 == 0;  // (the table itself is allocated behind every other buffer, below)
+  const bool sort_v1 = getenv("MPMHIP_SORT_V1") && atoi(getenv("MPMHIP_SORT_V1")) != 0;  // (A/B and tests: the four launches)
+  c->sort_keyed = c->NB <= (1u << 21) && !sort_v1;  // (the table itself is allocated behind every other buffer, below)
   A(dmalloc(&c->nbr, (size_t)mb * 32));
   A(dmalloc(&c->own_list, (size_t)mb * 8));
   c->bt_slots = (P.nbw + 255) / 256;
@@ -577,10 +581,9 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
     void *dp = nullptr;
     A(hipHostGetDevicePointer(&dp, c->h_pinned, 0));
     c->d_stats = reinterpret_cast<FillStats *>(reinterpret_cast<uint32_t *>(dp) + mpmhip_ctx::FILL_STATS_WORD);
-    if (getenv("MPMHIP_NO_STATS_STORE") && atoi(getenv("MPMHIP_NO_STATS_STORE"))) c->d_stats = nullptr;  // (A/B: the round-4 copy instead)
   }
   A(dmalloc(&c->d_groups, (size_t)c->groups_cap));
-  if (e == hipSuccess && c->NB <= (1u << 21) && sort_v1 != 1) {
+  if (e == hipSuccess && c->sort_keyed) {
     // (an optimisation's table, 256 B per block of the whole block space: 67 MB at 128^3, 537 MB from 256^3 to 508^3.  A device that
     // cannot spare it keeps the four-launch sort instead of failing the create — or a later mpmhip_reserve, a tiled arena, the next
     // rank sharing the device: the table is only taken while it is at most an eighth of what is free NOW, behind every other buffer)
@@ -1064,9 +1067,9 @@ static int do_sort(mpmhip_ctx *c) {
   // With the key-indexed counters (k_sort_front) 16 is the best or within 3 us of it at every size (profiles/r05_s_ct_blocks.txt: a rank
   // of 4 M 47.5 -> 44 us, C3 after impact 89.6 -> 86.5, the lattice 67.3 -> 64.2 where 32 gives 61.5): the plain table of that form keeps
   // 1 100..1 340 chunks resident in one round.
-  const bool keyed_ct = c->sort_keyed && c->cellcnt_key != nullptr;
+  const bool keyed = c->sort_keyed && c->cellcnt_key != nullptr;
   const int ct = (c->ct_blocks == 16 || c->ct_blocks == 32 || c->ct_blocks == 64) ? c->ct_blocks
-                 : (keyed_ct || c->n_slots < (2 << 20) ? 16 : (c->n_slots < (6 << 20) ? 32 : 64));
+                 : (keyed || c->n_slots < (2 << 20) ? 16 : (c->n_slots < (6 << 20) ? 32 : 64));
   const uint32_t bt_chunks = (P.nbw + 255) / 256, ct_chunks = (P.max_blocks + ct - 1) / ct;
   // Owner list of the grid pass (k_sort.h, k_grid.h): below 2 M slots it takes the pass from 17 to 7.5 us (1 M particles) for 2..3 us
   // in k_rank + k_cell_table; a tiled ctx always builds it (the per-block walk with the halo-box code in it thrashes the instruction
@@ -1078,7 +1081,6 @@ static int do_sort(mpmhip_ctx *c) {
   if ((epoch & 0x7FFFFFu) == 0u) epoch = ++c->sort_epoch;  // (k_cell_table's scan words keep 23 bits of it; 0 = never published)
   // (single-pass scans: never more workgroups than are resident at once, see k_sort.h)
   const uint32_t rank_wgs = std::max(1u, std::min<uint32_t>((P.n_slots + RANK_BATCH - 1) / RANK_BATCH, c->rank_wgs_cap));
-  const bool keyed = c->sort_keyed && c->cellcnt_key != nullptr;
   const uint32_t bt_wgs = std::min(bt_chunks, keyed ? scan_limit(c, (const void *)k_sort_front) : scan_limit(c, (const void *)k_block_table));
   if (keyed) {
     // block table and in-cell ranks in ONE launch (k_sort_front): the ranks count into key-indexed counters and need no table
@@ -1132,8 +1134,7 @@ static int do_sort(mpmhip_ctx *c) {
   }
   // (k_cell_table's last chunk stores (live particles, active blocks, owner entries) of this sort straight into the pinned page,
   // never waited for: the host picks the G2P walk by how full the blocks are (g2p_is_packed) and sizes the grid pass's launch
-  // from numbers that may be a few substeps old — until round 5 a hipMemcpyAsync every 16th sort, i.e. a blit kernel in the loop)
-  if (!c->d_stats && (c->sort_epoch & 15u) == 1u) (void)hipMemcpyAsync(c->h_pinned + mpmhip_ctx::FILL_STATS_WORD, c->cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+  // from numbers that may be a few substeps old)
   c->sorted = true;
   c->keys_valid = false;  // key[] now holds k_rank's packed (rank, cell index) words
   c->pidc_valid = false;
@@ -1213,38 +1214,17 @@ static int do_p2g(mpmhip_ctx *c, int phase = 0) {
     c->affine_valid = true;
   }
   // one wavefront per block (all 27 nodes, all particles) measured fastest at 256^3 / 8 M: 0.187 ms against
-  // 0.237 (two waves splitting the nodes) and 0.225 (two waves splitting the particles); knob: 10*NS + PS.  Splitting
-  // the particles does not help small problems either (128^3 / 1 M, where only 2 448 waves exist: 34 us with one wave per
-  // block, 37 with two, 48 with four)
-  auto kern = k_p2g<1, 1, 2>;
-  int nt = 64;
-#ifdef MPMHIP_TUNING_VARIANTS  // (A/B libraries only, profiles/: the default library carries the one kernel that was kept)
-  switch (c->p2g_split) {
-    case 21: kern = k_p2g<2, 1, 3>; nt = 128; break;
-    case 12: kern = k_p2g<1, 2, 2>; nt = 128; break;
-    default: break;
-  }
-#endif
+  // 0.237 (two waves splitting the nodes) and 0.225 (two waves splitting the particles).  Splitting the particles does
+  // not help small problems either (128^3 / 1 M, where only 2 448 waves exist: 34 us with one wave per block, 37 with
+  // two, 48 with four)
   const bool rigid = rigid_active(c);
-  if (rigid) { kern = k_p2g<1, 1, 2, true>; nt = 64; }
   hipStream_t rs = c->stream;
   if (rigid) { if (int rc = rigid_fork(c, &rs, 1)) return rc; }
-  hipLaunchKernelGGL(kern, dim3(c->p2g_wgs), dim3(nt), 0, c->stream, c->P,
+  hipLaunchKernelGGL(rigid ? k_p2g<true> : k_p2g<false>, dim3(c->p2g_wgs), dim3(64), 0, c->stream, c->P,
                      (const float4 *)c->rp, c->cnt, c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, c->T, phase,
-                     rigid ? (const uint8_t *)c->rigid.d_blk_rigid : (const uint8_t *)nullptr
-#ifdef MPMHIP_TIMING_BUILD
-                     , c->p2g_tlog
-#endif
-                     );
+                     rigid ? (const uint8_t *)c->rigid.d_blk_rigid : (const uint8_t *)nullptr);
   if (rigid) {  // blocks near a body (block_op_rigid), then RigidBody::apply_tmp_velocity (src/transfer.cpp:578-580)
-    auto rk = k_p2g_rigid<MAT_ALL>;
-    switch (material_mask(c)) {  // one material in the ctx: the kernel that carries only its calculate_force()
-#define MPM_ONE_MATERIAL(t) case 1u << (t): rk = k_p2g_rigid<1u << (t)>; break;
-      MPM_ONE_MATERIAL(MPMHIP_VISCO) MPM_ONE_MATERIAL(MPMHIP_SNOW) MPM_ONE_MATERIAL(MPMHIP_LINEAR) MPM_ONE_MATERIAL(MPMHIP_JELLY)
-      MPM_ONE_MATERIAL(MPMHIP_WATER) MPM_ONE_MATERIAL(MPMHIP_SAND) MPM_ONE_MATERIAL(MPMHIP_VON_MISES) MPM_ONE_MATERIAL(MPMHIP_ELASTIC)
-#undef MPM_ONE_MATERIAL
-      default: break;
-    }
+    auto rk = one_material(material_mask(c), k_p2g_rigid<MAT_ALL>, [](auto m) { return k_p2g_rigid<m.value>; });
     hipLaunchKernelGGL(rk, dim3(c->rigid_wgs), dim3(64), 0, rs, c->P, (const float4 *)c->rp, (const float4 *)c->rg, c->cnt,
                        c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, rigid_xfer(c));
     if (int rc = rigid_join(c, rs)) return rc;
@@ -1314,48 +1294,22 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
   constexpr uint32_t NO_VISCO = MAT_ALL & ~(1u << MPMHIP_VISCO);
   const uint32_t mask = material_mask(c);
   const bool rigid = rigid_active(c), no_visco = !(mask & (1u << MPMHIP_VISCO));
-  auto kern = sb ? (no_visco ? k_g2p<256, MPM_G2P_MINW, true, true, false, NO_VISCO> : k_g2p<256, 2, true, true>)
-                 : (no_visco ? k_g2p<256, MPM_G2P_MINW, true, false, false, NO_VISCO> : k_g2p<256, 2, true, false>);
-  int nt = 256;
-#ifdef MPMHIP_TUNING_VARIANTS  // (A/B libraries only: 3 / 4 waves per SIMD spill, 128-entry chunks measured slower — DESIGN.md §4)
-  switch (c->g2p_minw) {  // tuning knob: 10 + waves/SIMD target; 23: 128-entry chunks
-    case 13: kern = sb ? k_g2p<256, 3, true, true> : k_g2p<256, 3, true, false>; break;
-    case 14: kern = sb ? k_g2p<256, 4, true, true> : k_g2p<256, 4, true, false>; break;
-    case 23: kern = sb ? k_g2p<128, 3, true, true> : k_g2p<128, 3, true, false>; nt = 128; break;
-    default: break;
-  }
-#endif
+  auto kern = sb ? (no_visco ? k_g2p<256, G2P_MIN_WAVES, true, true, false, NO_VISCO> : k_g2p<256, 2, true, true>)
+                 : (no_visco ? k_g2p<256, G2P_MIN_WAVES, true, false, false, NO_VISCO> : k_g2p<256, 2, true, false>);
   if (rigid) {
-    kern = sb ? (no_visco ? k_g2p<256, MPM_G2P_MINW, true, true, true, NO_VISCO> : k_g2p<256, 2, true, true, true>)
-              : (no_visco ? k_g2p<256, MPM_G2P_MINW, true, false, true, NO_VISCO> : k_g2p<256, 2, true, false, true>);
-    if (!sb) switch (mask) {
-#define MPM_ONE_MATERIAL(t) case 1u << (t): kern = k_g2p<256, MPM_G2P_MINW, true, false, true, 1u << (t)>; break;
-      MPM_ONE_MATERIAL(MPMHIP_VISCO) MPM_ONE_MATERIAL(MPMHIP_SNOW) MPM_ONE_MATERIAL(MPMHIP_LINEAR) MPM_ONE_MATERIAL(MPMHIP_JELLY)
-      MPM_ONE_MATERIAL(MPMHIP_WATER) MPM_ONE_MATERIAL(MPMHIP_SAND) MPM_ONE_MATERIAL(MPMHIP_VON_MISES) MPM_ONE_MATERIAL(MPMHIP_ELASTIC)
-#undef MPM_ONE_MATERIAL
-      default: break;
-    }
+    kern = sb ? (no_visco ? k_g2p<256, G2P_MIN_WAVES, true, true, true, NO_VISCO> : k_g2p<256, 2, true, true, true>)
+              : (no_visco ? k_g2p<256, G2P_MIN_WAVES, true, false, true, NO_VISCO> : k_g2p<256, 2, true, false, true>);
+    if (!sb) kern = one_material(mask, kern, [](auto m) { return k_g2p<256, G2P_MIN_WAVES, true, false, true, m.value>; });
   } else if (!sb) {
-    switch (mask) {
-#define MPM_ONE_MATERIAL(t) case 1u << (t): kern = k_g2p<256, MPM_G2P_MINW, true, false, false, 1u << (t)>; break;
-      MPM_ONE_MATERIAL(MPMHIP_VISCO) MPM_ONE_MATERIAL(MPMHIP_SNOW) MPM_ONE_MATERIAL(MPMHIP_LINEAR) MPM_ONE_MATERIAL(MPMHIP_JELLY)
-      MPM_ONE_MATERIAL(MPMHIP_WATER) MPM_ONE_MATERIAL(MPMHIP_SAND) MPM_ONE_MATERIAL(MPMHIP_VON_MISES) MPM_ONE_MATERIAL(MPMHIP_ELASTIC)
-#undef MPM_ONE_MATERIAL
-      default: break;
-    }
+    kern = one_material(mask, kern, [](auto m) { return k_g2p<256, G2P_MIN_WAVES, true, false, false, m.value>; });
   }
   // packed chunks (k_g2p_packed.h): -3.5 us of 303 on the lattice of C3, -14 us of 373 after impact; at 1 M particles +7 us of 50
   // (768 workgroups with a handful of chunks each: the walk's set-up is not amortised) — hence by size
   // (one-material instantiations only: they stay below the 168 VGPRs of three workgroups per CU — 163 to 167; the kernel for
   // mixed materials would have 177, the visco one 183: those scenes keep k_g2p)
-  decltype(&k_g2p_packed<256, MPM_G2P_MINW, false, 1u << MPMHIP_SAND>) pk = nullptr;
-  if (g2p_is_packed(c, phase)) switch (mask) {
-#define MPM_ONE_MATERIAL(t) case 1u << (t): pk = k_g2p_packed<256, MPM_G2P_MINW, false, 1u << (t)>; break;
-      MPM_ONE_MATERIAL(MPMHIP_SNOW) MPM_ONE_MATERIAL(MPMHIP_LINEAR) MPM_ONE_MATERIAL(MPMHIP_JELLY) MPM_ONE_MATERIAL(MPMHIP_WATER)
-      MPM_ONE_MATERIAL(MPMHIP_SAND) MPM_ONE_MATERIAL(MPMHIP_VON_MISES) MPM_ONE_MATERIAL(MPMHIP_ELASTIC)
-#undef MPM_ONE_MATERIAL
-      default: break;
-    }
+  decltype(&k_g2p_packed<256, G2P_MIN_WAVES, false, 1u << MPMHIP_SAND>) pk = nullptr;
+  if (g2p_is_packed(c, phase))
+    pk = one_material<1u << MPMHIP_VISCO>(mask, pk, [](auto m) { return k_g2p_packed<256, G2P_MIN_WAVES, false, m.value>; });
   if (pk) {
     // four times the device's resident set (three workgroups per CU): with equal work items what is left of the launch's tail is
     // the partly filled last round — 4 096 workgroups are 5.33 rounds of 768.  At C3, lattice / after impact: 3 072 -> 287 / 336 us,
@@ -1363,11 +1317,7 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
     const int wgs = c->g2p_wgs > 0 ? c->g2p_wgs : (c->n_slots < (2 << 20) ? 768 : 12 * c->n_cus);
     hipLaunchKernelGGL(pk, dim3(wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg, (float4 *)c->rg2, (float4 *)c->rp2,
                        (float4 *)c->rb2, c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
-                       c->blk_flag, (const LevelSetDev *)c->d_LS, (const uint32_t *)c->chunk_blk
-#ifdef MPMHIP_TIMING_BUILD
-                       , c->p2g_tlog
-#endif
-                       );
+                       c->blk_flag, (const LevelSetDev *)c->d_LS, (const uint32_t *)c->chunk_blk);
     c->sorted = false; c->keys_valid = true; c->affine_valid = true;
     c->pidc_valid = c->P.pidc != nullptr;
     if (!c->P.store_b) c->b_stale = true;
@@ -1379,18 +1329,11 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
   // workgroups per CU = 768) walking ~6 chunks each WITH the record prefetch beats one chunk per workgroup: 51.9 -> 46.1 us at
   // 1 M particles (profiles/r04_b_knobs.txt; 512 and 1 024 are slower again)
   const int g2p_wgs = c->g2p_wgs > 0 ? c->g2p_wgs : (c->n_slots < (2 << 20) ? 768 : 4096);
-  hipLaunchKernelGGL(kern, dim3(g2p_wgs), dim3(nt), 0, c->stream, c->P, (const float4 *)c->rg, (float4 *)c->rg2, (float4 *)c->rp2,
+  hipLaunchKernelGGL(kern, dim3(g2p_wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg, (float4 *)c->rg2, (float4 *)c->rp2,
                      (float4 *)c->rb2, c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
                      c->blk_flag, (const LevelSetDev *)c->d_LS, phase_box(c->T), phase);
   if (rigid) {
-    auto rk = k_g2p_rigid<MAT_ALL>;
-    switch (mask) {
-#define MPM_ONE_MATERIAL(t) case 1u << (t): rk = k_g2p_rigid<1u << (t)>; break;
-      MPM_ONE_MATERIAL(MPMHIP_VISCO) MPM_ONE_MATERIAL(MPMHIP_SNOW) MPM_ONE_MATERIAL(MPMHIP_LINEAR) MPM_ONE_MATERIAL(MPMHIP_JELLY)
-      MPM_ONE_MATERIAL(MPMHIP_WATER) MPM_ONE_MATERIAL(MPMHIP_SAND) MPM_ONE_MATERIAL(MPMHIP_VON_MISES) MPM_ONE_MATERIAL(MPMHIP_ELASTIC)
-#undef MPM_ONE_MATERIAL
-      default: break;
-    }
+    auto rk = one_material(mask, k_g2p_rigid<MAT_ALL>, [](auto m) { return k_g2p_rigid<m.value>; });
     hipLaunchKernelGGL(rk, dim3(c->rigid_wgs / 2), dim3(256), 0, rs, c->P, (const float4 *)c->rg, (float4 *)c->rg2, (float4 *)c->rp2,
                        (float4 *)c->rb2, c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
                        c->blk_flag, (const LevelSetDev *)c->d_LS, rigid_xfer(c));
@@ -3410,20 +3353,3 @@ int mpmhip_debug_plasticity(mpmhip_ctx *c, int32_t material, const float params[
 }  // extern "C"
 
 #include "tiled_api.h"
-
-#ifdef MPMHIP_TIMING_BUILD
-// (variant library only; not part of include/mpmhip.h) per-block stamps of the NEXT k_p2g launches (enable), or their read-back
-extern "C" int mpmhip_timing_p2g_blocks(mpmhip_ctx *c, int32_t enable, unsigned long long *out, int64_t capacity_blocks) {
-  if (!c) return MPMHIP_EINVAL;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (out && c->p2g_tlog) {
-    const int64_t n = std::min<int64_t>(capacity_blocks, c->P.max_blocks);
-    HIPCHK(c, hipMemcpy(out, c->p2g_tlog, sizeof(unsigned long long) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-  }
-  if (enable && !c->p2g_tlog) HIPCHK(c, dmalloc(&c->p2g_tlog, (size_t)c->P.max_blocks * 3));
-  if (enable) HIPCHK(c, hipMemset(c->p2g_tlog, 0, sizeof(unsigned long long) * 3 * (size_t)c->P.max_blocks));
-  if (!enable && c->p2g_tlog) { (void)hipFree(c->p2g_tlog); c->p2g_tlog = nullptr; }
-  return MPMHIP_OK;
-}
-#endif

@@ -245,7 +245,7 @@ int tn_exchange_start(mpmhip_ctx *c) {
   auto &N = c->tn;
   if (N.boxes.empty()) return MPMHIP_OK;
   if (N.wire != MPMHIP_WIRE_RCCL && !N.loop_rccl) {  // peer wires: k_halo_pack wrote the boxes into the peers' buffers; publish the epoch
-    N.wait_merged = N.wire == MPMHIP_WIRE_IPC && !c->ov_active && N.merge_signal_wait;
+    N.wait_merged = N.wire == MPMHIP_WIRE_IPC && !c->ov_active;
     if (N.wait_merged) {  // (nothing runs between signal and wait: one launch; see k_epoch_signal_wait)
       hipLaunchKernelGGL(k_epoch_signal_wait, dim3(1), dim3(64), 0, c->stream, c->d_boxes_cur, (int)N.boxes.size(), (const uint32_t *)N.flags,
                          (const int *)N.d_halo_idx, (int)N.halo_peers.size(), N.epoch, N.timeout_ticks, c->cnt);
@@ -767,7 +767,6 @@ int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int3
   N.k = 0; N.next_migration = N.migrate_interval;
   N.occ.assign((size_t)N.world * 6, 0);
   N.occ_valid = false; N.initial_scan = false;
-  N.merge_signal_wait = !(getenv("MPMHIP_TILE_MERGE_WAIT") && atoi(getenv("MPMHIP_TILE_MERGE_WAIT")) == 0);  // (A/B knob)
   N.timeout_ticks = 100000000ull * (unsigned long long)std::max(1, getenv("MPMHIP_TILE_WAIT_S") ? atoi(getenv("MPMHIP_TILE_WAIT_S")) : 20);
   // worst-case halo volume over all ranks: the clip box = the whole grid (so that every rank lays its arena out alike)
   const int full_lo[3] = {0, 0, 0}, full_hi[3] = {c->P.res[0] + 1, c->P.res[1] + 1, c->P.res[2] + 1};
@@ -981,7 +980,7 @@ int64_t mpmhip_tiled_advance_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int64
       return fail(ctxs[r], MPMHIP_EINVAL, "MPMHIP_WIRE_LOCAL_RCCL: the ranks of the job must share one stream (mpmhip_set_stream)");
   }
   // ranks that share ONE stream publish their halo epochs with one launch behind the last rank's pack (k_epoch_signal_group)
-  bool one_stream = n_ctx > 1 && n_ctx <= MPMHIP_MAX_HALO_BOXES && !(getenv("MPMHIP_TILE_GROUP_SIGNAL") && atoi(getenv("MPMHIP_TILE_GROUP_SIGNAL")) == 0);
+  bool one_stream = n_ctx > 1 && n_ctx <= MPMHIP_MAX_HALO_BOXES;
   for (int r = 1; r < n_ctx; r++) one_stream = one_stream && ctxs[r]->stream == ctxs[0]->stream && ctxs[r]->device == ctxs[0]->device;
   bool scan0 = false;
   for (int r = 0; r < n_ctx; r++) scan0 = scan0 || !ctxs[r]->tn.occ_valid;

@@ -44,11 +44,11 @@ BUDGET = {
     # k_g2p_packed (large problems without rigid bodies / tiling): the same occupancy class with four block tiles in LDS
     "_ZN3mpm12k_g2p_packedILi256ELi2ELb0ELj64EEE": (168, (2950, 3950), 53 * 1024),   # sand
     "_ZN3mpm12k_g2p_packedILi256ELi2ELb0ELj128EEE": (168, (2950, 3950), 53 * 1024),  # von Mises: the fullest of the seven instantiated
-    "_ZN3mpm5k_p2gILi1ELi1ELi2ELb0EEE": (256, (900, 1450), 16 * 1024),  # the default P2G (one wave per block)
+    "_ZN3mpm5k_p2gILb0EEE": (256, (900, 1450), 16 * 1024),  # P2G (one wave per block)
     # the plain kernels of a ctx WITH rigid bodies (they skip the flagged blocks): same occupancy class as without —
     # k_g2p<RIGID> runs beside k_g2p_rigid, whose 255-register workgroups only find room when this one leaves it
     "_ZN3mpm5k_g2pILi256ELi2ELb1ELb0ELb1ELj64EEE": (168, (2800, 3750), 53 * 1024),
-    "_ZN3mpm5k_p2gILi1ELi1ELi2ELb1EEE": (256, (900, 1500), 16 * 1024),
+    "_ZN3mpm5k_p2gILb1EEE": (256, (900, 1500), 16 * 1024),
 }
 
 
