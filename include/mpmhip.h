@@ -102,7 +102,11 @@ typedef struct {
                              * scene, the packed and the per-block G2P walk, the three- and the four-launch sort, and a tiled job over any
                              * wire then give identical bits; a K-rank job differs from the one-ctx run only by how the <= 8 block tiles of
                              * a halo node are grouped into rank partials.  Costs one more launch per sort (bench.py reports it).
-                             * Not covered: the impulse / torque sums of CPIC rigid bodies and calculate_energy (float atomics).
+                             * Also covered: the impulse / torque sums of CPIC rigid bodies (per flagged block a row of per-body sums,
+                             * added in block order by one more launch per transfer — independent of launch sizes, the second stream and
+                             * the slots) and calculate_energy (partial sums per node block / per sorted particle range, added in a fixed
+                             * order; both grid walks give the same bits).  Switching the mode on takes effect from the next substep.
+                             * Not covered: the 2D solver (mpmhip2d_*: grid float atomics, no such mode) and the asynchronous steppers.
                              * The reference's sort key is unique for the same purpose: (offset >> 5) << 25 | i, src/mpm.cpp:785-795.
                              * env MPMHIP_DETERMINISTIC=0/1 overrides */
   int32_t reserved[2];

@@ -74,13 +74,23 @@ __device__ __forceinline__ float4 halo_total(const float4 acc, const int n_boxes
   return tot;
 }
 
+// MODE 5: the kinetic energy of the deterministic mode — each node block's sum (the same expression and the same lane tree in both
+// walks: node_block_ke) is STORED at its slot 8 a + o of `energy`, and k_sum_fixed adds the slots in ascending order.  Slot a*8+o is
+// canonical (a: the Morton rank of the active block), so the list walk and the per-block walk give the same bits.
+__device__ __forceinline__ double node_block_ke(const float4 &acc, bool counted) {
+  double ke = (acc.w != 0.0f && counted) ? 0.5 * ((double)acc.x * acc.x + (double)acc.y * acc.y + (double)acc.z * acc.z) / acc.w : 0.0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ke += __shfl_xor(ke, off);
+  return ke;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k_grid_list(Params P, const Counters *__restrict__ cnt,
                                                    const uint32_t *__restrict__ nbr, const uint32_t *__restrict__ own_list,
                                                    const float4 *__restrict__ tiles, float4 *__restrict__ gridv,
                                                    uint32_t *__restrict__ fat_slot, double *__restrict__ energy, Tiling T,
                                                    const DevBox *__restrict__ boxes, LevelSetDev LS, int phase) {
-  static_assert(MODE == 0 || MODE == 4, "the list walk serves the substep's pass and the energy");
+  static_assert(MODE == 0 || MODE == 4 || MODE == 5, "the list walk serves the substep's pass and the energy");
   const int l = threadIdx.x & 63;
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
   // (the first work item is requested before the number of work items is known: the list has 8 max_blocks entries)
@@ -133,6 +143,11 @@ __global__ __launch_bounds__(256) void k_grid_list(Params P, const Counters *__r
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) ke += __shfl_xor(ke, off);
       if (l == 0) atomicAdd(energy, ke);
+      continue;
+    }
+    if (MODE == 5) {
+      const double ke = node_block_ke(acc, !counted_elsewhere);
+      if (l == 0) energy[slot] = ke;
       continue;
     }
     float v[3] = {acc.x, acc.y, acc.z};
@@ -285,6 +300,11 @@ __global__ __launch_bounds__(256) void k_grid_blocks(Params P, const Counters *_
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off);
         if (l == 0) atomicAdd(reinterpret_cast<double *>(dense), e);
+        return;
+      }
+      if (MODE == 5) {
+        const double e = node_block_ke(acc, true);
+        if (l == 0) reinterpret_cast<double *>(dense)[slot] = e;
         return;
       }
       float v[3] = {acc.x, acc.y, acc.z};

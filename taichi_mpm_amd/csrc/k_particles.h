@@ -111,6 +111,42 @@ __global__ void k_debug_allowed_dt(GroupParams g, int64_t n, const float *F, con
   }
 }
 
+// MPMParticle::potential_energy() of one particle -> pe, as k_potential_energy below computes it (kept apart from that kernel: as a
+// shared helper it moved one instruction of the default kernel); false: the type does not define it in the reference
+__device__ __forceinline__ bool potential_of(const RecG &r, const GroupParams &g, float &pe) {
+  mat3 F;
+#pragma unroll
+  for (int k = 0; k < 9; k++) F.m[k] = r.F[k];
+  const float mu = g.p[2], la = g.p[3], vol = g.p[1];
+  if (g.type == MPMHIP_LINEAR) {
+    float n2 = 0.0f, tr = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < 3; b++) {
+        const float eab = 0.5f * (F(a, b) + F(b, a)) - (a == b ? 1.0f : 0.0f);
+        n2 = fmaf(eab, eab, n2);
+        if (a == b) tr += eab;
+      }
+    pe = vol * (mu * n2 + 0.5f * la * tr * tr);
+    return true;
+  } else if (g.type == MPMHIP_JELLY || g.type == MPMHIP_ELASTIC) {
+    mat3 U; float lam[3], s[3];
+    sym_eig3_FFt(F, U, lam);
+    const float J = mat_det(F);
+    signed_sigma(lam, J, s);
+    if (g.type == MPMHIP_JELLY) {  // |F - R|_F^2 = sum (sigma - 1)^2
+      const float n2 = (s[0] - 1) * (s[0] - 1) + (s[1] - 1) * (s[1] - 1) + (s[2] - 1) * (s[2] - 1);
+      pe = vol * (mu * n2 + 0.5f * la * (J - 1.0f) * (J - 1.0f));
+    } else {
+      const float l0 = logf(fabsf(s[0])), l1 = logf(fabsf(s[1])), l2 = logf(fabsf(s[2]));
+      const float sum = l0 + l1 + l2;
+      pe = vol * (mu * (l0 * l0 + l1 * l1 + l2 * l2) + 0.5f * la * sum * sum);
+    }
+    return true;
+  }
+  return false;
+}
 // sum of MPMParticle::potential_energy() (src/particles.cpp:323-327 linear, :400-407 jelly, :785-796 elastic;
 // the other types do not define it in the reference: TC_NOT_IMPLEMENTED) -> out[0]; out[1] counts particles of
 // types without a potential energy
@@ -159,6 +195,48 @@ __global__ __launch_bounds__(256) void k_potential_energy(Params P, const RecG *
     atomicAdd(&out[0], e);
     if (bad != 0.0) atomicAdd(&out[1], bad);
   }
+}
+// The deterministic mode: in the SORTED order, which neither the slots nor a physical reorder change.  A fixed launch of
+// POT_WAVES waves: lane l of wave w adds the sorted positions w 64 + l, w 64 + l + POT_WAVES 64, ... in turn, a fixed lane tree gives
+// the wave's sum, stored at parts[w] (k_sum_fixed adds the waves in ascending w).  The count of particles without a potential energy
+// is exact in any order.
+constexpr uint32_t POT_WAVES = 4096;  // (launched as POT_WAVES / 4 workgroups of 256)
+__global__ __launch_bounds__(256) void k_potential_energy_sorted(const Counters *__restrict__ cnt, const uint32_t *__restrict__ perm,
+                                                                 const RecG *__restrict__ rg, const GroupParams *__restrict__ groups,
+                                                                 double *__restrict__ parts, double *bad_out) {
+  double e = 0.0, bad = 0.0;
+  const uint32_t n = cnt->n_sorted;
+  for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += POT_WAVES * 64u) {
+    const RecG r = rg[perm[p]];
+    if (r.pid < 0) continue;
+    const GroupParams g = groups[r.gid];
+    float pe;
+    if (potential_of(r, g, pe)) e += pe;
+    else bad += 1.0;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { e += __shfl_xor(e, off); bad += __shfl_xor(bad, off); }
+  if ((threadIdx.x & 63) == 0) {
+    parts[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = e;
+    if (bad != 0.0) atomicAdd(bad_out, bad);
+  }
+}
+// out[0] = the sum of v[0 .. min(*count, max_count) * per) (count null: max_count * per) in a fixed order: thread t adds t, t + 1024,
+// ... in turn, then a fixed tree
+__global__ __launch_bounds__(1024) void k_sum_fixed(const double *__restrict__ v, const uint32_t *__restrict__ count, uint32_t max_count,
+                                                    uint32_t per, double *out) {
+  __shared__ double red[1024];
+  const int t = threadIdx.x;
+  const uint32_t n = (count ? min(*count, max_count) : max_count) * per;
+  double s = 0.0;
+  for (uint32_t i = t; i < n; i += 1024) s += v[i];
+  red[t] = s;
+  __syncthreads();
+  for (int h = 512; h > 0; h >>= 1) {
+    if (t < h) red[t] += red[t + h];
+    __syncthreads();
+  }
+  if (t == 0) out[0] = red[0];
 }
 
 

@@ -145,6 +145,48 @@ __device__ __forceinline__ void acc_flush_wave(ImpulseAcc &A, RigidBodyDev *rb) 
   }
 }
 
+// The deterministic mode (mpmhip_config.deterministic).  Float atomics add in the order the waves arrive, so the bits of a body's
+// impulse depended on scheduling, launch sizes and the second stream.  In this mode the colour-aware kernels write, for every
+// flagged block a, the block's sum per body into ROW a of a buffer (plain stores; the sums inside a block are formed in a fixed
+// order — the deterministic sort fixes the block's particle order), and k_rigid_rows_apply adds the rows of the flagged blocks in
+// ascending a (the Morton order of the active blocks) in a fixed tree.  Which workgroup took a block, the order of rigid_list and
+// the particles' slots then decide nothing.  The variants are picked by MAT_DET in the material-set template argument, so the
+// default instantiations stay as they are.
+constexpr uint32_t MAT_DET = 0x80000000u;  // (above every material bit, mpm_math.h: MAT_ALL)
+constexpr int IMP_ROW = MAX_RIGID * 6;      // floats per row: impulse and torque of every body
+// a lane's own sums into its own column of an LDS array [IMP_ROW][64] (k_p2g_rigid: a lane that meets a second body)
+__device__ __forceinline__ void acc_flush_lane_cols(ImpulseAcc &A, float (*cols)[64], int lane) {
+  if (A.body >= 0) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { cols[A.body * 6 + k][lane] += A.imp[k]; cols[A.body * 6 + 3 + k][lane] += A.trq[k]; }
+  }
+  acc_init(A);
+}
+// fixed-tree sum over the 64 lanes (every lane ends with the same bits: the two operands of each step are the same pair on both lanes)
+__device__ __forceinline__ float wave_sum_fixed(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// acc_flush_wave with the six atomics replaced by a wave-private LDS row (sums[IMP_ROW]): the wave's successive chunks add to it in
+// their order; all 64 lanes must call this together
+__device__ __forceinline__ void acc_flush_wave_row(ImpulseAcc &A, float *sums) {
+  unsigned long long pending = __ballot(A.body >= 0);
+  while (pending) {
+    const int leader = __ffsll((long long)pending) - 1;
+    const int body = __shfl(A.body, leader);
+    const bool mine = A.body == body;
+    float v[6];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { v[k] = wave_sum_fixed(mine ? A.imp[k] : 0.0f); v[3 + k] = wave_sum_fixed(mine ? A.trq[k] : 0.0f); }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) sums[body * 6 + k] += v[k];
+    }
+    if (mine) acc_init(A);
+    pending = __ballot(A.body >= 0);
+  }
+}
 // node (i, j, k) of the colored distance field: tags (24 bits), body id of the closest triangle (-1: none), distance (world)
 __device__ __forceinline__ void cdf_node(const CdfDev &C, const Params &P, int i, int j, int k, uint32_t &tags, int &rid, float &dist) {
   tags = 0; rid = -1; dist = 0.0f;
@@ -652,6 +694,48 @@ __global__ void k_rigid_apply_tmp(RigidBodyDev *rb, int nb) {
   rot_apply(B.R, u, w);
 #pragma unroll
   for (int k = 0; k < 3; k++) { B.omega[k] += w[k]; B.tmp_imp[k] = 0.0f; B.tmp_trq[k] = 0.0f; }
+}
+// The deterministic mode's k_rigid_apply_tmp: the sums of body blockIdx.x + 1 are those of the rows of the flagged blocks (k_p2g_rigid /
+// k_g2p_rigid, MAT_DET): thread t adds the rows a = t, t + 1024, ... in turn, then a fixed tree over the threads; the result replaces
+// tmp_imp / tmp_trq (nothing else adds to them in this mode) and is applied at once.  (Rows of blocks without the flag are read but
+// not added: the loads then do not wait for the flag.)
+__global__ __launch_bounds__(1024) void k_rigid_rows_apply(Params P, const Counters *__restrict__ cnt, const uint8_t *__restrict__ blk_rigid,
+                                                           const float *__restrict__ rows, RigidBodyDev *rb) {
+  __shared__ float red[6][1024];
+  const int b = blockIdx.x + 1, t = threadIdx.x;
+  const uint32_t na = min(cnt->n_active, P.max_blocks);
+  float s[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  for (uint32_t a = t; a < na; a += 1024) {
+    const bool flagged = blk_rigid[a] != 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const float r = rows[(size_t)a * IMP_ROW + b * 6 + k];
+      s[k] += flagged ? r : 0.0f;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) red[k][t] = s[k];
+  __syncthreads();
+  for (int h = 512; h > 0; h >>= 1) {
+    if (t < h) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) red[k][t] += red[k][t + h];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {  // (k_rigid_apply_tmp's arithmetic, restated: as a shared helper it changed that kernel's code)
+    RigidBodyDev &B = rb[b];
+    const float imp[3] = {red[0][0], red[1][0], red[2][0]}, trq[3] = {red[3][0], red[4][0], red[5][0]};
+    float tb[3], u[3], w[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) B.vel[k] += imp[k] * B.inv_mass;
+#pragma unroll
+    for (int c = 0; c < 3; c++) tb[c] = B.R[c] * trq[0] + B.R[3 + c] * trq[1] + B.R[6 + c] * trq[2];
+    rot_apply(B.inv_I, tb, u);
+    rot_apply(B.R, u, w);
+#pragma unroll
+    for (int k = 0; k < 3; k++) { B.omega[k] += w[k]; B.tmp_imp[k] = 0.0f; B.tmp_trq[k] = 0.0f; }
+  }
 }
 
 __device__ __forceinline__ void quat_to_R(const float q[4], float R[9]) {

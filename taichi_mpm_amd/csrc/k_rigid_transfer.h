@@ -18,7 +18,7 @@ struct RigidXfer {
   CdfDev C;
   RigidBodyDev *rb;
   const BndRec *bnd;
-  const uint8_t *blk_rigid;
+  float *imp_rows;  // deterministic mode: [max_blocks][IMP_ROW] the flagged blocks' impulse sums (k_rigid.h: MAT_DET); else unused
   const uint32_t *rigid_list, *n_rigid;  // the flagged blocks as a list (k_blk_rigid)
   const float4 *rp_in;  // the current RecP set (G2P reads the particle's own velocity from it)
   float penalty, pushing_force;
@@ -64,6 +64,9 @@ __device__ __forceinline__ void load_state_tile(const CdfDev &C, int bx, int by,
 // block_op_rigid of rasterize_optimized (src/transfer.cpp:367-463): a node of the other colour receives nothing; the
 // particle's momentum change against the body's surface velocity (friction_project with the particle's boundary
 // normal) and its stress term go to the body as an impulse at the node instead (:425-444).
+// Deterministic mode (MATS carries MAT_DET, k_rigid.h): the boundary list is compacted in (particle, lane) order by ballot and prefix
+// instead of an LDS counter; a lane's impulses go into its own LDS column per body instead of the atomics, and the block's row is
+// the fixed-tree sum of the 64 columns.
 constexpr int P2GR_LIST = 1024;
 template <uint32_t MATS = MAT_ALL>  // material set of the ctx (mpm_math.h): the impulse walk evaluates calculate_force()
 __global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P, const float4 *__restrict__ rp, const float4 *__restrict__ rg,
@@ -76,9 +79,15 @@ __global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P,
   __shared__ RigidLite srb[MAX_RIGID];
   __shared__ uint32_t blist[P2GR_LIST];  // the block's boundary particles: (position in the block's sorted range) << 6 | cell
   __shared__ uint32_t bcount;
+  constexpr bool DET = (MATS & MAT_DET) != 0u;
+  constexpr uint32_t MSET = MATS & ~MAT_DET;
+  __shared__ float cols[DET ? IMP_ROW : 1][64];  // (deterministic mode) lane l's sums per (body, component) in cols[.][l]
   const uint32_t na = min(cnt->n_active, P.max_blocks);
   const int lane = threadIdx.x;
   load_rigid_lite(srb, X.rb, lane, 64);  // (visible behind the first block's barrier)
+  if constexpr (DET) {
+    for (int e = 0; e < IMP_ROW; e++) cols[e][lane] = 0.0f;  // (each lane only ever touches its own column)
+  }
   const int cx = lane >> 4, cy = (lane >> 2) & 3, cz = lane & 3;
   const int nbase = (cx * TS + cy) * TS + cz;
   const uint32_t nr = min(*X.n_rigid, na);
@@ -103,6 +112,7 @@ __global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P,
 #pragma unroll
     for (int n = 0; n < 27; n++) acc[n][0] = acc[n][1] = acc[n][2] = acc[n][3] = 0.0f;
     bool any_other = false;
+    uint32_t nlisted = 0u;  // (deterministic mode: entries listed so far, wave-uniform among the lanes still walking)
     {
       float4 nq0, nq1, nq2, nq3, nh3;
       size_t inext = 0;
@@ -135,7 +145,14 @@ __global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P,
           if (cdf_incompatible(stile[nbase + (i3 * TS + j) * TS + k], pstate)) other |= 1u << n;
         }
         any_other = any_other || other != 0u;
-        if (other != 0u) {
+        if constexpr (DET) {
+          const unsigned long long lm = __ballot(other != 0u);
+          if (other != 0u) {
+            const uint32_t slot = nlisted + (uint32_t)__popcll(lm & ((1ull << lane) - 1ull));
+            if (slot < (uint32_t)P2GR_LIST) blist[slot] = ((p - blk0) << 6) | (uint32_t)lane;
+          }
+          nlisted += (uint32_t)__popcll(lm);
+        } else if (other != 0u) {
           const uint32_t slot = atomicAdd(&bcount, 1u);
           if (slot < (uint32_t)P2GR_LIST) blist[slot] = ((p - blk0) << 6) | (uint32_t)lane;
         }
@@ -178,9 +195,15 @@ __global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P,
       __builtin_amdgcn_wave_barrier();
       asm volatile("" ::: "memory");
     }
+    if constexpr (DET) {  // the lanes that walked longest hold the full count
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) nlisted = max(nlisted, (uint32_t)__shfl_xor((int)nlisted, off));
+      if (lane == 0) bcount = nlisted;
+    }
     // second pass: the listed particles, one per lane (if the list overflowed: cell by cell, every particle re-tested)
     ImpulseAcc ia;
     acc_init(ia);
+    uint32_t touched = 0u;  // (deterministic mode: bodies this lane has sums for)
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
     const uint32_t nlist = bcount;
@@ -228,7 +251,7 @@ __global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P,
       const float4 h0 = rg[icur * 4 + 0], h1 = rg[icur * 4 + 1], h2 = rg[icur * 4 + 2];
       mat3 F;
       F.m[0] = h1.x; F.m[1] = h1.y; F.m[2] = h1.z; F.m[3] = h1.w; F.m[4] = h2.x; F.m[5] = h2.y; F.m[6] = h2.z; F.m[7] = h2.w; F.m[8] = h3.x;
-      mat3 dtF = calculate_force<MATS>(groups[__float_as_uint(h3.y)], F, h0.w);  // delta_t * calculate_force()
+      mat3 dtF = calculate_force<MSET>(groups[__float_as_uint(h3.y)], F, h0.w);  // delta_t * calculate_force()
 #pragma unroll
       for (int e = 0; e < 9; e++) dtF.m[e] *= P.dt;
       while (other) {
@@ -254,10 +277,33 @@ __global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P,
 #pragma unroll
         for (int c = 0; c < 3; c++)
           imp[c] = mass * w * (v[c] - pv[c]) + (dtF(c, 0) * gr[0] + dtF(c, 1) * gr[1] + dtF(c, 2) * gr[2]);
+        if constexpr (DET) {
+          if (ia.body >= 0 && ia.body != rid) acc_flush_lane_cols(ia, cols, lane);
+          touched |= 1u << rid;
+        }
         acc_add(ia, X.rb, rid, imp, gp, B.pos);
       }
     }
-    acc_flush_wave(ia, X.rb);  // the wave's impulses: six atomics per body
+    if constexpr (DET) {  // row a: per (body, component) the fixed-tree sum of the 64 columns
+      acc_flush_lane_cols(ia, cols, lane);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) touched |= (uint32_t)__shfl_xor((int)touched, off);
+      float out0 = 0.0f, out1 = 0.0f;  // entry e of the row: lane e (e < 64) / lane e - 64
+      for (int b = 0; b < MAX_RIGID; b++) {
+        if (!((touched >> b) & 1u)) continue;  // wave-uniform
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+          const int e = b * 6 + k;
+          const float s = wave_sum_fixed(cols[e][lane]);
+          cols[e][lane] = 0.0f;
+          if (lane == (e & 63)) { if (e < 64) out0 = s; else out1 = s; }
+        }
+      }
+      X.imp_rows[(size_t)a * IMP_ROW + lane] = out0;
+      if (lane < IMP_ROW - 64) X.imp_rows[(size_t)a * IMP_ROW + 64 + lane] = out1;
+    } else {
+      acc_flush_wave(ia, X.rb);  // the wave's impulses: six atomics per body
+    }
     __syncthreads();
     for (int t = lane; t < TN; t += 64) tiles[(size_t)a * TN + t] = tile[t];
     __syncthreads();
@@ -270,6 +316,8 @@ __global__ __launch_bounds__(64, RIGID_P2G_MIN_WAVES) void k_p2g_rigid(Params P,
 // body's surface motion plus a push along the boundary normal (:757-784); a particle near a boundary loses its affine
 // momentum (:800-804) and is pushed back by the penalty term when it is slightly inside (:821-832), the body receiving
 // the opposite impulse.  Everything after the gather is k_g2p's (same record layout, same key / deletion logic).
+// Deterministic mode (MATS carries MAT_DET, k_rigid.h): a lane has at most one impulse per chunk; each wave adds its chunks' fixed-tree
+// sums to a wave-private LDS row in chunk order, and the block's row is ((w0 + w1) + w2) + w3 of the four waves.
 template <uint32_t MATS = MAT_ALL>
 __global__ __launch_bounds__(256, RIGID_G2P_MIN_WAVES) void k_g2p_rigid(Params P, const float4 *__restrict__ rg, float4 *__restrict__ rg_out,
                                                    float4 *__restrict__ rp_out, float4 *__restrict__ rb_out,
@@ -282,9 +330,15 @@ __global__ __launch_bounds__(256, RIGID_G2P_MIN_WAVES) void k_g2p_rigid(Params P
   __shared__ float4 tile[TN];
   __shared__ uint32_t stile[TN];
   __shared__ RigidLite srb[MAX_RIGID];
+  constexpr bool DET = (MATS & MAT_DET) != 0u;
+  constexpr uint32_t MSET = MATS & ~MAT_DET;
+  __shared__ float wsum[DET ? 4 : 1][IMP_ROW];  // (deterministic mode) every wave's sums over the block's chunks
   const uint32_t na = min(cnt->n_active, P.max_blocks);
   const int tid = threadIdx.x;
   load_rigid_lite(srb, X.rb, tid, 256);  // (visible behind the first block's barriers)
+  if constexpr (DET) {
+    for (int e = tid; e < 4 * IMP_ROW; e += 256) wsum[e / IMP_ROW][e % IMP_ROW] = 0.0f;  // (visible behind the first block's barriers)
+  }
   const float scale = -4.0f * P.idx * P.dt;
   const uint32_t nr = min(*X.n_rigid, na);
   for (uint32_t li = blockIdx.x; li < nr; li += gridDim.x) {
@@ -404,7 +458,7 @@ __global__ __launch_bounds__(256, RIGID_G2P_MIN_WAVES) void k_g2p_rigid(Params P
         F.m[7] = g2.w; F.m[8] = g3.x;
         float aux = g0.w;
         mat3 stress;
-        plasticity_and_force<MATS>(g, cdg, F, aux, stress);
+        plasticity_and_force<MSET>(g, cdg, F, aux, stress);
         float nx0 = fmaf(v[0], P.dt, x0), nx1 = fmaf(v[1], P.dt, x1), nx2 = fmaf(v[2], P.dt, x2);
         if (bn.near && bn.dist < -0.05f * P.dx && bn.dist > -P.dx * 0.3f) {  // :821-832
           const float dv[3] = {bn.dist * bn.n[0] * X.penalty, bn.dist * bn.n[1] * X.penalty, bn.dist * bn.n[2] * X.penalty};
@@ -457,8 +511,17 @@ __global__ __launch_bounds__(256, RIGID_G2P_MIN_WAVES) void k_g2p_rigid(Params P
           rb_out[o * 3 + 2] = make_float4(b.m[8], 0.0f, 0.0f, 0.0f);
         }
       }
-      acc_flush_wave(ia, X.rb);
+      if constexpr (DET) acc_flush_wave_row(ia, wsum[tid >> 6]);
+      else acc_flush_wave(ia, X.rb);
       flag_block(blk_flag, bkey);
+    }
+    if constexpr (DET) {  // row a, then the wave rows are cleared for the next block
+      __syncthreads();
+      if (tid < IMP_ROW) {
+        X.imp_rows[(size_t)a * IMP_ROW + tid] = ((wsum[0][tid] + wsum[1][tid]) + wsum[2][tid]) + wsum[3][tid];
+#pragma unroll
+        for (int w = 0; w < 4; w++) wsum[w][tid] = 0.0f;
+      }
     }
   }
 }

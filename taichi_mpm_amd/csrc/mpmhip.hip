@@ -199,6 +199,8 @@ struct mpmhip_ctx {
   uint32_t *h_pinned = nullptr;  // 64 KiB of pinned host memory for small readbacks (counters, migration table)
   static constexpr int FILL_STATS_WORD = 16368;  // word offset of the block-fill statistics in that page (do_sort, g2p_is_packed)
   double *d_energy = nullptr;
+  double *d_energy_parts = nullptr;  // deterministic mode: [8 energy_parts_cap + POT_WAVES] the partial sums of calculate_energy (energy_end_det)
+  size_t energy_parts_cap = 0;
   int counts_cap = 0;
   bool compact_requested = false;
   bool in_substep = false;
@@ -257,6 +259,8 @@ struct mpmhip_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int concurrent = 7;                  // which pairs run side by side: 1 P2G, 2 G2P, 4 rasterisation | sort (env MPMHIP_RIGID_CONCURRENT; 0: one stream)
     uint32_t *d_rigid_list = nullptr;  // [max_blocks + 1] the flagged blocks as a list; its length is d_counters[CDF_POOLS + 1]
+    float *d_imp_rows = nullptr;       // deterministic mode only: [imp_rows_cap][IMP_ROW] per flagged block its impulse sums (k_rigid.h)
+    size_t imp_rows_cap = 0;
     uint32_t *d_counters = nullptr;  // [0, CDF_POOLS) pages handed out per sub-pool, [CDF_POOLS] cutting_counter
     uint32_t max_pages = 0;
     uint32_t gather_epoch = 0;  // stamps the boundary records of the particles the last gather_cdf visited
@@ -663,10 +667,10 @@ void mpmhip_destroy(mpmhip_ctx *c) {
   if (c->async.store.h_tbl_pin) hipHostFree(c->async.store.h_tbl_pin);
   { auto &S = c->async.store; hipFree(S.g); hipFree(S.w); hipFree(S.g2); hipFree(S.w2); hipFree(S.tag); hipFree(S.tag2); hipFree(S.id);
     hipFree(S.id2); hipFree(S.best); hipFree(S.d_scan); hipFree(S.d_tbl); hipFree(S.d_rank); hipFree(S.d_cnt); }
-  hipFree(c->cnt); hipFree(c->d_groups); hipFree(c->d_boxes); hipFree(c->d_LS); hipFree(c->d_counts); hipFree(c->d_bounds); if (c->h_pinned) hipHostFree(c->h_pinned); hipFree(c->d_energy);
+  hipFree(c->cnt); hipFree(c->d_groups); hipFree(c->d_boxes); hipFree(c->d_LS); hipFree(c->d_counts); hipFree(c->d_bounds); if (c->h_pinned) hipHostFree(c->h_pinned); hipFree(c->d_energy); hipFree(c->d_energy_parts);
   { auto &R = c->rigid; hipFree(R.d_rb); hipFree(R.d_smp); hipFree(R.d_elems); hipFree(R.cdf.slot); hipFree(R.cdf.page_key); hipFree(R.cdf.mind);
     hipFree(R.cdf.tags); hipFree(R.cdf.rpage); hipFree(R.d_bnd); if (R.side) { hipStreamSynchronize(R.side); hipStreamDestroy(R.side); } if (R.ev_fork) hipEventDestroy(R.ev_fork); if (R.ev_join) hipEventDestroy(R.ev_join);
-    hipFree(R.d_blk_rigid); hipFree(R.d_rigid_list); hipFree(R.d_counters); hipFree(R.d_joints);
+    hipFree(R.d_blk_rigid); hipFree(R.d_rigid_list); hipFree(R.d_counters); hipFree(R.d_joints); hipFree(R.d_imp_rows);
     hipFree(R.d_smp_rank); hipFree(R.d_ls_keys[0]); hipFree(R.d_ls_keys[1]); hipFree(R.d_ls_vals[0]); hipFree(R.d_ls_vals[1]); hipFree(R.d_ls_tmp); }
   tn_free(c);
   if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -1206,6 +1210,7 @@ static uint32_t material_mask(const mpmhip_ctx *c) {
   return mask;
 }
 static int do_rigid_apply_tmp(mpmhip_ctx *c);
+static int rigid_imp_rows(mpmhip_ctx *c);
 
 static int do_p2g(mpmhip_ctx *c, int phase = 0) {
   if (!c->affine_valid) {
@@ -1224,7 +1229,10 @@ static int do_p2g(mpmhip_ctx *c, int phase = 0) {
                      (const float4 *)c->rp, c->cnt, c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, c->T, phase,
                      rigid ? (const uint8_t *)c->rigid.d_blk_rigid : (const uint8_t *)nullptr);
   if (rigid) {  // blocks near a body (block_op_rigid), then RigidBody::apply_tmp_velocity (src/transfer.cpp:578-580)
-    auto rk = one_material(material_mask(c), k_p2g_rigid<MAT_ALL>, [](auto m) { return k_p2g_rigid<m.value>; });
+    // (deterministic mode: the all-material form with the impulse rows, summed by do_rigid_apply_tmp)
+    auto rk = c->deterministic ? k_p2g_rigid<MAT_ALL | MAT_DET>
+                               : one_material(material_mask(c), k_p2g_rigid<MAT_ALL>, [](auto m) { return k_p2g_rigid<m.value>; });
+    if (c->deterministic) { if (int rc = rigid_imp_rows(c)) return rc; }
     hipLaunchKernelGGL(rk, dim3(c->rigid_wgs), dim3(64), 0, rs, c->P, (const float4 *)c->rp, (const float4 *)c->rg, c->cnt,
                        c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, rigid_xfer(c));
     if (int rc = rigid_join(c, rs)) return rc;
@@ -1239,25 +1247,27 @@ static int do_grid(mpmhip_ctx *c, int mode, int phase = 0) {
   // every tiled ctx): one wave per touched grid block, launched at the size of the list as the last sort reported it (+ 12 %; the
   // walk is a grid-stride loop, so a stale number costs time, never correctness).  Otherwise, and for the dense views: the walks
   // of rounds 1-4 — per block at >= 2 M slots, per (block, candidate) below.
-  if ((mode == 0 || mode == 4) && c->list_valid) {
+  if ((mode == 0 || mode == 4 || mode == 5) && c->list_valid) {
     const volatile FillStats *fs = reinterpret_cast<const volatile FillStats *>(c->h_pinned + mpmhip_ctx::FILL_STATS_WORD);
     uint64_t n_own = fs->n_own;
     if (n_own == 0) n_own = std::min<uint64_t>((uint64_t)c->P.max_blocks * 8u, 32768u);  // (before the first sort has reported)
     int wgs = (int)std::min<uint64_t>(8192u, std::max<uint64_t>(64u, (n_own + n_own / 8 + 3) / 4 + 8));
     if (c->grid_wgs > 0) wgs = c->grid_wgs;
-    hipLaunchKernelGGL(mode == 0 ? k_grid_list<0> : k_grid_list<4>, dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, (const uint32_t *)c->nbr,
+    hipLaunchKernelGGL(mode == 0 ? k_grid_list<0> : (mode == 4 ? k_grid_list<4> : k_grid_list<5>), dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, (const uint32_t *)c->nbr,
                        (const uint32_t *)c->own_list, c->tiles, c->gridv, c->fat_slot, reinterpret_cast<double *>(c->dense), c->T,
                        c->d_boxes_cur, c->LS, phase);
     return launch_check(c, "grid");
   }
-  if (mode == 4 && c->T.n_boxes > 0)
+  if ((mode == 4 || mode == 5) && c->T.n_boxes > 0)
     // (only the owner-list walk knows which rank counts a halo node's kinetic energy — the lowest that holds mass on it; the per-block
     // walk would add every halo node on every rank that holds it)
     return fail(c, MPMHIP_EINVAL, "calculate_energy of a tiled ctx needs the owner-list walk of the grid pass: do not set MPMHIP_GRID_WALK=0");
   const bool per_cand = mode == 0 && c->n_slots < (2 << 20);  // small per-GPU problem: latency-bound, see k_grid.h
   auto kern = mode == 0 ? (per_cand ? k_grid_blocks<0, true> : k_grid_blocks<0, false>)
                         : (mode == 1 ? k_grid_blocks<1, false>
-                                     : (mode == 2 ? k_grid_blocks<2, false> : (mode == 3 ? k_grid_blocks<3, false> : k_grid_blocks<4, false>)));
+                                     : (mode == 2 ? k_grid_blocks<2, false>
+                                                  : (mode == 3 ? k_grid_blocks<3, false>
+                                                               : (mode == 4 ? k_grid_blocks<4, false> : k_grid_blocks<5, false>))));
   int wgs = per_cand ? 16384 : 4096;
   if (c->grid_wgs > 0 && mode == 0) wgs = c->grid_wgs;
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, c->act_blk, c->bits, c->wprefix, c->tiles,
@@ -1333,7 +1343,9 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
                      (float4 *)c->rb2, c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
                      c->blk_flag, (const LevelSetDev *)c->d_LS, phase_box(c->T), phase);
   if (rigid) {
-    auto rk = one_material(mask, k_g2p_rigid<MAT_ALL>, [](auto m) { return k_g2p_rigid<m.value>; });
+    auto rk = c->deterministic ? k_g2p_rigid<MAT_ALL | MAT_DET>
+                               : one_material(mask, k_g2p_rigid<MAT_ALL>, [](auto m) { return k_g2p_rigid<m.value>; });
+    if (c->deterministic) { if (int rc = rigid_imp_rows(c)) return rc; }
     hipLaunchKernelGGL(rk, dim3(c->rigid_wgs / 2), dim3(256), 0, rs, c->P, (const float4 *)c->rg, (float4 *)c->rg2, (float4 *)c->rp2,
                        (float4 *)c->rb2, c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
                        c->blk_flag, (const LevelSetDev *)c->d_LS, rigid_xfer(c));
@@ -1928,19 +1940,48 @@ static int energy_begin(mpmhip_ctx *c) {
   }
   return MPMHIP_OK;
 }
+// The deterministic mode stores every partial sum at a canonical place and adds them in a fixed order (k_grid.h: MODE 5,
+// k_particles.h: k_potential_energy_sorted, k_sum_fixed): the kinetic energy per node block at its slot 8 a + o, the potential energy
+// per wave of a fixed launch over the particles in sorted order.
+static int energy_end_det(mpmhip_ctx *c) {
+  const size_t mb = c->P.max_blocks;
+  if (c->energy_parts_cap < mb) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_energy_parts); c->d_energy_parts = nullptr; c->energy_parts_cap = 0;
+    HIPCHK(c, dmalloc(&c->d_energy_parts, mb * 8 + POT_WAVES));
+    c->energy_parts_cap = mb;
+  }
+  double *kin = c->d_energy_parts, *pot = c->d_energy_parts + 8 * mb, *acc = c->d_energy;
+  HIPCHK(c, hipMemsetAsync(kin, 0, 8 * mb * sizeof(double), c->stream));  // (node blocks no walk visits: not owned, not in phase)
+  float4 *const dense_saved = c->dense;
+  c->dense = reinterpret_cast<float4 *>(kin);  // k_grid<5> stores into its `dense` argument
+  int rc = do_grid(c, 5);
+  c->dense = dense_saved;
+  if (rc) return rc;
+  const uint32_t *n_active = &c->cnt->n_active;
+  hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(1024), 0, c->stream, (const double *)kin, n_active, (uint32_t)mb, 8u, acc);
+  hipLaunchKernelGGL(k_potential_energy_sorted, dim3(POT_WAVES / 4), dim3(256), 0, c->stream, (const Counters *)c->cnt,
+                     (const uint32_t *)c->perm, (const RecG *)c->rg, (const GroupParams *)c->d_groups, pot, acc + 2);
+  hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(1024), 0, c->stream, (const double *)pot, (const uint32_t *)nullptr, POT_WAVES, 1u, acc + 1);
+  return launch_check(c, "energy (deterministic)");
+}
 static int energy_end(mpmhip_ctx *c, double out[3]) {
   int rc;
   if (!c->d_energy) HIPCHK(c, dmalloc(&c->d_energy, 4));
   HIPCHK(c, hipMemsetAsync(c->d_energy, 0, 4 * sizeof(double), c->stream));
-  float4 *const dense_saved = c->dense;
-  c->dense = reinterpret_cast<float4 *>(c->d_energy);  // k_grid<4> accumulates into its `dense` argument
-  rc = do_grid(c, 4);
-  c->dense = dense_saved;
-  if (rc) return rc;
+  if (c->deterministic) {
+    if ((rc = energy_end_det(c))) return rc;
+  } else {
+    float4 *const dense_saved = c->dense;
+    c->dense = reinterpret_cast<float4 *>(c->d_energy);  // k_grid<4> accumulates into its `dense` argument
+    rc = do_grid(c, 4);
+    c->dense = dense_saved;
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_potential_energy, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const RecG *)c->rg,
+                       (const GroupParams *)c->d_groups, c->d_energy + 1);
+    if ((rc = launch_check(c, "potential_energy"))) return rc;
+  }
   double *acc = c->d_energy;
-  hipLaunchKernelGGL(k_potential_energy, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const RecG *)c->rg,
-                     (const GroupParams *)c->d_groups, acc + 1);
-  if ((rc = launch_check(c, "potential_energy"))) return rc;
   double *h = reinterpret_cast<double *>(c->h_pinned + 12288);  // (pinned: behind the reductions' staging)
   HIPCHK(c, hipMemcpyAsync(h, acc, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2237,6 +2278,7 @@ int mpmhip_reserve(mpmhip_ctx *c, int64_t max_particles) {
       c->list_clear_epoch = c->sort_epoch;
       A(regrow(&c->tiles, 0, m * TN, false)); A(regrow(&c->gridv, 0, m * 8 * BC, false));
       if (c->rigid.d_blk_rigid) { A(regrow(&c->rigid.d_blk_rigid, 0, m + 1, true)); A(regrow(&c->rigid.d_rigid_list, 0, m + 1, false)); }
+      if (c->rigid.d_imp_rows) { A(regrow(&c->rigid.d_imp_rows, 0, m * IMP_ROW, false)); c->rigid.imp_rows_cap = m; }
       if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "growing the block table to %lld failed: %s", (long long)mb, hipGetErrorString(e));
       c->P.max_blocks = (uint32_t)mb;
       HIPCHK(c, hipMemset(c->fat_slot, 0, sizeof(uint32_t) * (size_t)c->NB));  // slots of the old grid array

@@ -140,7 +140,7 @@ static int rigid_enable(mpmhip_ctx *c) {
 
 static RigidXfer rigid_xfer(mpmhip_ctx *c) {
   RigidXfer X;
-  X.C = c->rigid.cdf; X.rb = c->rigid.d_rb; X.bnd = c->rigid.d_bnd; X.blk_rigid = c->rigid.d_blk_rigid;
+  X.C = c->rigid.cdf; X.rb = c->rigid.d_rb; X.bnd = c->rigid.d_bnd; X.imp_rows = c->rigid.d_imp_rows;
   X.rigid_list = c->rigid.d_rigid_list; X.n_rigid = c->rigid.d_counters + CDF_POOLS + 1;
   X.rp_in = (const float4 *)c->rp;
   X.penalty = c->rigid.penalty; X.pushing_force = c->rigid.pushing_force;
@@ -175,7 +175,23 @@ static int do_rigid_block_flags(mpmhip_ctx *c) {
                      R.d_blk_rigid, c->act_start, R.d_rigid_list, R.d_counters + CDF_POOLS + 1);
   return launch_check(c, "rigid block flags");
 }
+// the impulse rows of the deterministic mode: allocated when the mode meets a body, one row per block of the block table
+static int rigid_imp_rows(mpmhip_ctx *c) {
+  auto &R = c->rigid;
+  if (R.d_imp_rows && R.imp_rows_cap >= c->P.max_blocks) return MPMHIP_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (R.side) HIPCHK(c, hipStreamSynchronize(R.side));
+  (void)hipFree(R.d_imp_rows); R.d_imp_rows = nullptr; R.imp_rows_cap = 0;
+  HIPCHK(c, dmalloc(&R.d_imp_rows, (size_t)c->P.max_blocks * IMP_ROW));
+  R.imp_rows_cap = c->P.max_blocks;
+  return MPMHIP_OK;
+}
 static int do_rigid_apply_tmp(mpmhip_ctx *c) {
+  if (c->deterministic) {  // the rows the colour-aware kernel just wrote, summed in a fixed order and applied (k_rigid.h)
+    hipLaunchKernelGGL(k_rigid_rows_apply, dim3((int)c->rigid.bodies.size() - 1), dim3(1024), 0, c->stream, c->P, (const Counters *)c->cnt,
+                       (const uint8_t *)c->rigid.d_blk_rigid, (const float *)c->rigid.d_imp_rows, c->rigid.d_rb);
+    return launch_check(c, "rigid apply_tmp_velocity (deterministic)");
+  }
   hipLaunchKernelGGL(k_rigid_apply_tmp, dim3(1), dim3(64), 0, c->stream, c->rigid.d_rb, (int)c->rigid.bodies.size());
   return launch_check(c, "rigid apply_tmp_velocity");
 }
