@@ -65,6 +65,7 @@ class MPM<2> {
     c.particle_collision = config.get("particle_collision", false);
     c.max_particles = (int64_t)config.get("max_particles", (double)(1 << 20));
     c.device = config.get("device", 0);
+    c.deterministic = config.get("deterministic", false);  // (no reference key: bitwise reproducible runs, include/mpmhip.h)
     verbose_bgeo = config.get("verbose_bgeo", false);   // src/visualize.cpp:22
     frame_directory = config.get("frame_directory", "");  // injected by the python driver, async_mpm.py:49
     frame_count = 0;
@@ -181,6 +182,8 @@ class MPM<2> {
   // --- time stepping
   virtual void step(real dt) { check(mpmhip2d_step(ctx_, dt), ctx_); frame++; }  // src/mpm.cpp:428-439 (dt < 0: one substep)
   virtual void substep() { check(mpmhip2d_substep(ctx_), ctx_); }         // :452-575
+  // config key `deterministic` of a live simulation, from the next substep on (include/mpmhip.h: mpmhip2d_set_deterministic)
+  void set_deterministic(bool on = true) { check(mpmhip2d_set_deterministic(ctx_, on ? 1 : 0), ctx_); }
   virtual real get_current_time() const { return (real)mpmhip2d_current_time(ctx_); }
   virtual int64_t get_num_particles() const { const int64_t n = mpmhip2d_num_particles(ctx_); check((int)std::min<int64_t>(n, 0), ctx_); return n; }
   // every live particle, ordered by creation id (slots are not a stable handle)

@@ -106,7 +106,8 @@ typedef struct {
                              * added in block order by one more launch per transfer — independent of launch sizes, the second stream and
                              * the slots) and calculate_energy (partial sums per node block / per sorted particle range, added in a fixed
                              * order; both grid walks give the same bits).  Switching the mode on takes effect from the next substep.
-                             * Not covered: the 2D solver (mpmhip2d_*: grid float atomics, no such mode) and the asynchronous steppers.
+                             * The 2D solver has its own form of the mode (mpmhip2d_config.deterministic below: a cell sort and a
+                             * gather P2G).  Not covered: the asynchronous steppers, 2D and 3D.
                              * The reference's sort key is unique for the same purpose: (offset >> 5) << 25 | i, src/mpm.cpp:785-795.
                              * env MPMHIP_DETERMINISTIC=0/1 overrides */
   int32_t reserved[2];
@@ -523,11 +524,27 @@ typedef struct {
   int32_t clean_boundary, particle_collision;
   int64_t max_particles;
   int32_t device;
-  int32_t reserved[3];
+  int32_t deterministic;    /* 1 = bitwise reproducible runs (env MPMHIP_DETERMINISTIC=0/1 overrides).  The default substep scatters
+                             * with global float atomics (grid, body impulses), so its last bits depend on arrival order.  With the
+                             * mode a substep is a function of the particle set (state + creation id) and the bodies only — not of
+                             * slot order, launch sizes or arrival order: the particles are sorted by cell, every cell in ascending
+                             * (creation id, slot), each particle's P2G record is stored once, every node of the dense grid sums its
+                             * nine cells in a fixed order and is written with one plain store; the impulses particles hand to
+                             * bodies are summed per workgroup in a fixed tree and the rows added in a fixed order.  No float atomic
+                             * remains on the path.  With duplicate creation ids the run is still valid, but the order inside a cell
+                             * — and so the last bits — then depends on the slots.  Not covered: the asynchronous 2D stepper's pools,
+                             * gathers and appends. */
+  int32_t reserved[2];
 } mpmhip2d_config;
 int mpmhip2d_create(const mpmhip2d_config *cfg, mpmhip2d_ctx **out);
 void mpmhip2d_destroy(mpmhip2d_ctx *ctx);
 const char *mpmhip2d_last_error(const mpmhip2d_ctx *ctx);
+/* mpmhip2d_config.deterministic of a live ctx; takes effect from the next substep */
+int mpmhip2d_set_deterministic(mpmhip2d_ctx *ctx, int32_t on);
+/* the creation ids of the n resident slots, in slot order (the 2D counterpart of mpmhip_upload(MPMHIP_F_ID): a scene uploaded in
+ * another order keeps its particles' names).  n must equal the slot count, every id must be >= 0; a deleted slot stays deleted;
+ * the counter new particles take their ids from is raised to max + 1.  Refused on a resident asynchronous stepper. */
+int mpmhip2d_upload_ids(mpmhip2d_ctx *ctx, int64_t n, const int32_t *ids);
 /* MPM<2>::apply_dirichlet_boundary_conditions (src/mpm.cpp:374-399): grid nodes with x < distance_left move with
  * (velocity_left, 0), nodes with x > 1 - distance_right with (velocity_right, 0) — config keys dirichlet_boundary_radius,
  * dirichlet_distance_left / _right, dirichlet_boundary_velocity, dirichlet_boundary_left / _right */

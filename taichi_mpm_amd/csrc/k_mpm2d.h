@@ -451,13 +451,15 @@ __global__ __launch_bounds__(256) void k_grid(Params P, LevelSetDev LS, float *_
 
 // resample — src/transfer.cpp:585-687 (same-colour branch), then clear_boundary_particles (src/mpm.cpp:582-633) and
 // particle_collision_resolution (:414-426)
-__global__ __launch_bounds__(256) void k_g2p(Params P, LevelSetDev LS, int64_t n, float *__restrict__ x, float *__restrict__ v,
-                                             float *__restrict__ F, float *__restrict__ B, float *__restrict__ aux,
-                                             const int32_t *__restrict__ gid, int32_t *__restrict__ pid,
+// One particle.  DET (the deterministic mode, k_mpm2d_det.h): the penalty impulse goes into the caller's column of sums
+// (imp_col[(3 body + c) * 256]) instead of the body's words.
+template <bool DET>
+__device__ __forceinline__ void g2p_particle(const Params &P, const LevelSetDev &LS, const int64_t p, float *__restrict__ x,
+                                             float *__restrict__ v, float *__restrict__ F, float *__restrict__ B,
+                                             float *__restrict__ aux, const int32_t *__restrict__ gid, int32_t *__restrict__ pid,
                                              const GroupParams *__restrict__ groups, const float *__restrict__ grid,
-                                             unsigned int *__restrict__ n_dead, RigidArgs2 R) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n || pid[p] < 0) return;
+                                             unsigned int *__restrict__ n_dead, const RigidArgs2 &R, float *imp_col) {
+  if (pid[p] < 0) return;
   float xx[2] = {x[2 * p], x[2 * p + 1]}, vv[2] = {v[2 * p], v[2 * p + 1]};
   int b[2];
   if (!alive_pos(P, xx, vv, b)) {  // (only reachable for freshly uploaded particles: deleted like the reference's clean-up)
@@ -529,7 +531,13 @@ __global__ __launch_bounds__(256) void k_g2p(Params P, LevelSetDev LS, int64_t n
     nv[0] -= dv[0]; nv[1] -= dv[1];
     if (rigid_id != -1) {
       const float imp[2] = {dv[0] * g.p[0], dv[1] * g.p[0]};
-      tmp_impulse2(R.rb + rigid_id, imp, xx);
+      if (DET) {
+        const float a0 = xx[0] - R.rb[rigid_id].pos[0], a1 = xx[1] - R.rb[rigid_id].pos[1];
+        imp_col[(3 * rigid_id + 0) * 256] += imp[0]; imp_col[(3 * rigid_id + 1) * 256] += imp[1];
+        imp_col[(3 * rigid_id + 2) * 256] += a0 * imp[1] - a1 * imp[0];
+      } else {
+        tmp_impulse2(R.rb + rigid_id, imp, xx);
+      }
     }
   }
   int nb[2];
@@ -553,6 +561,15 @@ __global__ __launch_bounds__(256) void k_g2p(Params P, LevelSetDev LS, int64_t n
     pid[p] = -1;
     atomicAdd(n_dead, 1u);
   }
+}
+__global__ __launch_bounds__(256) void k_g2p(Params P, LevelSetDev LS, int64_t n, float *__restrict__ x, float *__restrict__ v,
+                                             float *__restrict__ F, float *__restrict__ B, float *__restrict__ aux,
+                                             const int32_t *__restrict__ gid, int32_t *__restrict__ pid,
+                                             const GroupParams *__restrict__ groups, const float *__restrict__ grid,
+                                             unsigned int *__restrict__ n_dead, RigidArgs2 R) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  g2p_particle<false>(P, LS, p, x, v, F, B, aux, gid, pid, groups, grid, n_dead, R, nullptr);
 }
 
 }  // namespace mpm2d

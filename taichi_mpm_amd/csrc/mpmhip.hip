@@ -85,6 +85,7 @@
 #include "k_bgeo.h"
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
+#include "k_mpm2d_det.h"
 #include "k_async2d.h"
 
 
@@ -2698,6 +2699,19 @@ struct mpmhip2d_ctx {
   mpm2d::Joints2 joints{};     // MPM<2>::articulations ('rotation' joints)
   int joint_iterations = 100;  // 'articulation_iterations'
   float base_dt = 0.0f;        // the configured "base_delta_t" (P.dt is what the next substep uses: the async stepper sets it per advance)
+  // deterministic mode (mpmhip2d_config.deterministic, k_mpm2d_det.h): the cell sort's counters and index, the staged P2G
+  // records, the impulse rows; allocated when the mode is first used (det2_reserve), freed with the ctx
+  struct Det2 {
+    bool on = false;
+    int64_t cap = 0;                 // particles the per-particle arrays hold
+    uint32_t *count = nullptr, *start = nullptr;   // [nodes + 1]; start[nodes] = live particles
+    uint32_t *off = nullptr, *unordered = nullptr, *idx = nullptr;
+    int32_t *key = nullptr;
+    float4 *rec = nullptr;           // [3 cap]
+    float *rows = nullptr;           // [ceil(cap / 256)][DET_ROW]; entries behind 3 * bodies are never written nor read
+    void *scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+  } det;
   // AsyncMPM<2> (async2d_api.h): the block scheduler + the device store of pool / backup containers (k_async2d.h)
   struct Async2 : AsyncSched {
     bool resident = false, pending_counters = false;
@@ -2727,6 +2741,13 @@ static void a2_free(mpmhip2d_ctx *m) {
 static int a2_drop_view(mpmhip2d_ctx *m);
 static int a2_grow_particles(mpmhip2d_ctx *m, int64_t need);
 int mpmhip2d_async_step(mpmhip2d_ctx *m, float dt);
+static void det2_free(mpmhip2d_ctx *m) {
+  auto &D = m->det;
+  hipFree(D.count); hipFree(D.start); hipFree(D.off); hipFree(D.unordered); hipFree(D.idx); hipFree(D.key); hipFree(D.rec); hipFree(D.rows);
+  hipFree(D.scan_tmp);
+  D.count = D.start = D.off = D.unordered = D.idx = nullptr; D.key = nullptr; D.rec = nullptr; D.rows = nullptr; D.scan_tmp = nullptr;
+  D.cap = 0; D.scan_bytes = 0;
+}
 static thread_local std::string g_2d_create_error;
 static int fail2d(mpmhip2d_ctx *m, int code, const std::string &msg) {
   (m ? m->err : g_2d_create_error) = msg;
@@ -2760,6 +2781,8 @@ int mpmhip2d_create(const mpmhip2d_config *cfg, mpmhip2d_ctx **out) {
   P.g[0] = cfg->gravity[0]; P.g[1] = cfg->gravity[1];
   P.particle_gravity = cfg->particle_gravity; P.apic_damping = cfg->apic_damping; P.rpic_damping = cfg->rpic_damping;
   P.clean_boundary = cfg->clean_boundary; P.particle_collision = cfg->particle_collision; P.clamp_pos = 1;
+  m->det.on = cfg->deterministic != 0;
+  if (const char *e = getenv("MPMHIP_DETERMINISTIC")) m->det.on = atoi(e) != 0;
   memset(&m->LS, 0, sizeof m->LS);
   m->cap = cfg->max_particles;
   const size_t c = (size_t)m->cap, nodes = (size_t)(P.res[0] + 1) * (P.res[1] + 1);
@@ -2785,6 +2808,7 @@ void mpmhip2d_destroy(mpmhip2d_ctx *m) {
   if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
   hipFree(m->x); hipFree(m->v); hipFree(m->F); hipFree(m->B); hipFree(m->aux); hipFree(m->gid); hipFree(m->pid); hipFree(m->grid);
   hipFree(m->n_dead); hipFree(m->d_groups);
+  det2_free(m);
   hipFree(m->d_rb); hipFree(m->d_smp); hipFree(m->d_elems); hipFree(m->d_mind); hipFree(m->d_tags); hipFree(m->d_states); hipFree(m->d_bnd);
   a2_free(m);
   hipFree(m->d_smp_rank); hipFree(m->d_ls_tmp);
@@ -2963,6 +2987,97 @@ static int rigid2_advect(mpmhip2d_ctx *m) {
   return MPMHIP_OK;
 }
 
+int mpmhip2d_set_deterministic(mpmhip2d_ctx *m, int32_t on) {
+  if (!m) return MPMHIP_EINVAL;
+  m->det.on = on != 0;
+  return MPMHIP_OK;
+}
+int mpmhip2d_upload_ids(mpmhip2d_ctx *m, int64_t n, const int32_t *ids) {
+  if (!m || !ids) return MPMHIP_EINVAL;
+  if (m->async.resident) return fail2d(m, MPMHIP_EINVAL, "upload_ids: not on a resident asynchronous stepper (its pools hold the ids)");
+  if (n != m->n) return fail2d(m, MPMHIP_EINVAL, "upload_ids: n = " + std::to_string(n) + " but the simulation holds " + std::to_string(m->n) + " slots");
+  int32_t top = -1;
+  for (int64_t i = 0; i < n; i++) {
+    if (ids[i] < 0) return fail2d(m, MPMHIP_EINVAL, "upload_ids: ids must be >= 0");
+    top = std::max(top, ids[i]);
+  }
+  if (n == 0) return MPMHIP_OK;
+  if (top == INT32_MAX) return fail2d(m, MPMHIP_EINVAL, "upload_ids: id out of range");
+  HIPCHK2D(m, hipSetDevice(m->device));
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  std::vector<int32_t> h((size_t)n);
+  HIPCHK2D(m, hipMemcpy(h.data(), m->pid, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n; i++) h[i] = h[i] < 0 ? -1 : ids[i];  // (a deleted slot stays deleted)
+  HIPCHK2D(m, hipMemcpy(m->pid, h.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  m->next_pid = std::max(m->next_pid, top + 1);
+  return MPMHIP_OK;
+}
+// the mode's arrays: per node the counters and cell starts (+ 1: start[nodes] is the number of live particles), per particle the
+// index, the staged records and a row of impulse sums per 256 sorted positions
+static int det2_reserve(mpmhip2d_ctx *m) {
+  auto &D = m->det;
+  const size_t nodes = (size_t)(m->P.res[0] + 1) * (m->P.res[1] + 1);
+  hipError_t e = hipSuccess;
+  auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  if (!D.count) {
+    A(dmalloc(&D.count, nodes + 1)); A(dmalloc(&D.start, nodes + 1));
+    size_t bytes = 0;
+    A(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, D.count, D.start, (int)(nodes + 1), m->stream));
+    if (e == hipSuccess) A(hipMalloc(&D.scan_tmp, std::max<size_t>(bytes, 16)));
+    D.scan_bytes = bytes;
+  }
+  if (e == hipSuccess && D.cap < m->cap) {
+    HIPCHK2D(m, hipStreamSynchronize(m->stream));
+    hipFree(D.off); hipFree(D.unordered); hipFree(D.idx); hipFree(D.key); hipFree(D.rec); hipFree(D.rows);
+    D.off = D.unordered = D.idx = nullptr; D.key = nullptr; D.rec = nullptr; D.rows = nullptr; D.cap = 0;
+    const size_t c = (size_t)m->cap;
+    A(dmalloc(&D.off, c)); A(dmalloc(&D.unordered, c)); A(dmalloc(&D.idx, c)); A(dmalloc(&D.key, c)); A(dmalloc(&D.rec, 3 * c));
+    A(dmalloc(&D.rows, ((c + 255) / 256) * (size_t)mpm2d::DET_ROW));
+    if (e == hipSuccess) D.cap = m->cap;
+  }
+  if (e != hipSuccess) {
+    det2_free(m);
+    return fail2d(m, MPMHIP_ENOMEM, std::string("deterministic mode: ") + hipGetErrorString(e));
+  }
+  return MPMHIP_OK;
+}
+// P2G of the mode (k_mpm2d_det.h): cell sort, staged records, gather; with bodies the stage kernel leaves the impulse rows
+static int det2_p2g(mpmhip2d_ctx *m, const mpm2d::RigidArgs2 &R) {
+  auto &D = m->det;
+  const size_t nodes = (size_t)(m->P.res[0] + 1) * (m->P.res[1] + 1);
+  const dim3 pg((unsigned)((m->n + 255) / 256)), wg(256);
+  const uint32_t *total = D.start + nodes;
+  HIPCHK2D(m, hipMemsetAsync(D.count, 0, sizeof(uint32_t) * (nodes + 1), m->stream));
+  hipLaunchKernelGGL(mpm2d::k2d_count, pg, wg, 0, m->stream, m->P, m->n, (const float *)m->x, (const float *)m->v, m->pid, D.key, D.off, D.count,
+                     m->n_dead);
+  size_t bytes = D.scan_bytes;
+  HIPCHK2D(m, hipcub::DeviceScan::ExclusiveSum(D.scan_tmp, bytes, D.count, D.start, (int)(nodes + 1), m->stream));
+  hipLaunchKernelGGL(mpm2d::k2d_fill, pg, wg, 0, m->stream, m->n, (const int32_t *)D.key, (const uint32_t *)D.off, (const uint32_t *)D.start,
+                     D.unordered);
+  hipLaunchKernelGGL(mpm2d::k2d_order, pg, wg, 0, m->stream, m->n, (const int32_t *)D.key, (const int32_t *)m->pid, (const uint32_t *)D.start,
+                     (const uint32_t *)D.unordered, D.idx);
+  const int nb = (int)m->bodies.size();
+  const dim3 tg((unsigned)((m->P.res[1] + 1 + mpm2d::DET_TJ - 1) / mpm2d::DET_TJ), (unsigned)((m->P.res[0] + 1 + mpm2d::DET_TI - 1) / mpm2d::DET_TI));
+  if (R.enabled) {
+    hipLaunchKernelGGL(mpm2d::k2d_stage<true>, pg, wg, 0, m->stream, m->P, total, (const uint32_t *)D.idx, (const float *)m->x, m->v,
+                       (const float *)m->F, (const float *)m->B, (const float *)m->aux, (const int32_t *)m->gid,
+                       (const GroupParams *)m->d_groups, D.rec, R, nb, D.rows);
+    hipLaunchKernelGGL(mpm2d::k2d_gather<true>, tg, wg, 0, m->stream, m->P, (const uint32_t *)D.start, (const float4 *)D.rec, m->grid, R);
+  } else {
+    hipLaunchKernelGGL(mpm2d::k2d_stage<false>, pg, wg, 0, m->stream, m->P, total, (const uint32_t *)D.idx, (const float *)m->x, m->v,
+                       (const float *)m->F, (const float *)m->B, (const float *)m->aux, (const int32_t *)m->gid,
+                       (const GroupParams *)m->d_groups, D.rec, R, nb, D.rows);
+    hipLaunchKernelGGL(mpm2d::k2d_gather<false>, tg, wg, 0, m->stream, m->P, (const uint32_t *)D.start, (const float4 *)D.rec, m->grid, R);
+  }
+  HIPCHK2D(m, hipGetLastError());
+  return MPMHIP_OK;
+}
+// the impulse rows of the launch before (k2d_stage or k2d_g2p: each is applied before the next one writes) added to the bodies
+static void det2_rows_apply(mpmhip2d_ctx *m) {
+  const size_t nodes = (size_t)(m->P.res[0] + 1) * (m->P.res[1] + 1);
+  hipLaunchKernelGGL(mpm2d::k2d_rows_apply, dim3((unsigned)m->bodies.size() - 1), dim3(64), 0, m->stream, m->d_rb, (const float *)m->det.rows,
+                     (const uint32_t *)(m->det.start + nodes));
+}
 static int substep2d(mpmhip2d_ctx *m);
 int mpmhip2d_substep(mpmhip2d_ctx *m) {  // MPM<2>::substep, src/mpm.cpp:452-575
   if (!m) return MPMHIP_EINVAL;
@@ -2974,27 +3089,43 @@ static int substep2d(mpmhip2d_ctx *m) {
   const size_t nodes = (size_t)(m->P.res[0] + 1) * (m->P.res[1] + 1);
   m->P.t = m->t;
   const dim3 pg((unsigned)std::max<int64_t>((m->n + 255) / 256, 1)), gg((unsigned)((nodes + 255) / 256)), wg(256);
-  HIPCHK2D(m, hipMemsetAsync(m->grid, 0, sizeof(float) * 3 * nodes, m->stream));
+  const bool det = m->det.on && m->n > 0;  // (no particles: the default path, which then only clears the grid)
+  if (det) {
+    if (int rc = det2_reserve(m)) return rc;
+  } else {
+    HIPCHK2D(m, hipMemsetAsync(m->grid, 0, sizeof(float) * 3 * nodes, m->stream));  // (the mode's gather writes every node)
+  }
   const mpm2d::RigidArgs2 R = rigid_args2(m);
   if (R.enabled) {
     if (m->joints.n)  // articulate, between the sort and rasterize_rigid_boundary (src/mpm.cpp:466-471)
       hipLaunchKernelGGL(mpm2d::k2_articulate, dim3(1), dim3(64), 0, m->stream, m->d_rb, m->joints, m->joint_iterations);
     if (int rc = rigid2_pre(m)) return rc;
   }
-  if (m->n)
-    hipLaunchKernelGGL(mpm2d::k_p2g, pg, wg, 0, m->stream, m->P, m->n, (const float *)m->x, m->v, (const float *)m->F,
-                       (const float *)m->B, (const float *)m->aux, (const int32_t *)m->gid, (const int32_t *)m->pid,
-                       (const GroupParams *)m->d_groups, m->grid, R);
-  if (R.enabled) hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->bodies.size());
+  if (det) {
+    if (int rc = det2_p2g(m, R)) return rc;
+    if (R.enabled) det2_rows_apply(m);
+  } else {
+    if (m->n)
+      hipLaunchKernelGGL(mpm2d::k_p2g, pg, wg, 0, m->stream, m->P, m->n, (const float *)m->x, m->v, (const float *)m->F,
+                         (const float *)m->B, (const float *)m->aux, (const int32_t *)m->gid, (const int32_t *)m->pid,
+                         (const GroupParams *)m->d_groups, m->grid, R);
+    if (R.enabled) hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->bodies.size());
+  }
   if (R.enabled && m->ls_collision) {
     if (int rc = rigid2_ls_collision(m)) return rc;
   }
   hipLaunchKernelGGL(mpm2d::k_grid, gg, wg, 0, m->stream, m->P, m->LS, m->grid);
-  if (m->n)
+  if (det && R.enabled) {  // (without bodies k_g2p adds nothing across particles: the default launch is kept)
+    hipLaunchKernelGGL(mpm2d::k2d_g2p, pg, wg, 0, m->stream, m->P, m->LS, (const uint32_t *)(m->det.start + nodes), (const uint32_t *)m->det.idx,
+                       m->x, m->v, m->F, m->B, m->aux, (const int32_t *)m->gid, m->pid, (const GroupParams *)m->d_groups,
+                       (const float *)m->grid, m->n_dead, R, (int)m->bodies.size(), m->det.rows);
+    det2_rows_apply(m);
+  } else if (m->n) {
     hipLaunchKernelGGL(mpm2d::k_g2p, pg, wg, 0, m->stream, m->P, m->LS, m->n, m->x, m->v, m->F, m->B, m->aux, (const int32_t *)m->gid,
                        m->pid, (const GroupParams *)m->d_groups, (const float *)m->grid, m->n_dead, R);
+    if (R.enabled) hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->bodies.size());
+  }
   if (R.enabled) {
-    hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->bodies.size());
     if (int rc = rigid2_advect(m)) return rc;
   }
   HIPCHK2D(m, hipGetLastError());

@@ -54,6 +54,8 @@ class Simulation2D:
         self.verbose_bgeo = bool(cfg.get("verbose_bgeo", False))  # src/visualize.cpp:22
         self.frame_directory = cfg.get("frame_directory")  # injected by the python driver, async_mpm.py:49
         self.frame_count = 0
+        # bitwise reproducible runs (include/mpmhip.h: mpmhip2d_config.deterministic): cell sort + gather P2G instead of float atomics
+        self.deterministic = bool(cfg.get("deterministic", False))
         return self
 
     def _check(self, rc):
@@ -78,6 +80,7 @@ class Simulation2D:
         self._capacity = max(self.max_particles, int((self._n_added + extra) * 1.5) + 1024)
         c.max_particles = self._capacity
         c.device = int(cfg.get("device", 0))
+        c.deterministic = int(self.deterministic)
         ctx = C.c_void_p()
         rc = self._L.mpmhip2d_create(C.byref(c), C.byref(ctx))
         if rc != 0:
@@ -205,6 +208,19 @@ class Simulation2D:
 
     def synchronize(self):
         self.get_num_particles()
+
+    def set_deterministic(self, on=True):
+        """config key `deterministic` of a live simulation, from the next substep on (include/mpmhip.h: mpmhip2d_set_deterministic)"""
+        self.deterministic = bool(on)
+        if self._ctx is not None:
+            self._check(self._L.mpmhip2d_set_deterministic(self._ctx, int(self.deterministic)))
+
+    def upload_ids(self, ids):
+        """creation ids of the resident slots, in slot order (include/mpmhip.h: mpmhip2d_upload_ids): a scene added in another
+        order keeps its particles' names, which is what the deterministic mode orders a cell by"""
+        self._ensure_ctx()
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        self._check(self._L.mpmhip2d_upload_ids(self._ctx, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32))))
 
     def get_current_time(self):
         return self._L.mpmhip2d_current_time(self._ctx) if self._ctx is not None else 0.0
