@@ -113,6 +113,27 @@ class MPM<3> {
                                         shapes1.data(), friction), ctx_);
   }
 
+  // sampled level set (what taichi's LevelSet is: an array of phi on a lattice; include/mpmhip.h: mpmhip_set_levelset_sdf).
+  // phi: res[0] * res[1] * res[2] values, the last axis fastest, world units, negative inside the solid.  It replaces the shapes.
+  void set_levelset_sdf(const VectorI &lattice_res, const Vector &origin, real spacing, const std::vector<float> &phi, real friction) {
+    set_levelset_sdf(lattice_res, origin, spacing, 0.0f, 1.0f, phi, std::vector<float>(), friction);
+  }
+  // ... two key frames of one lattice, blended like the shapes' key frames above (phi1 empty: static)
+  void set_levelset_sdf(const VectorI &lattice_res, const Vector &origin, real spacing, real t0, real t1, const std::vector<float> &phi0,
+                        const std::vector<float> &phi1, real friction) {
+    mpmhip_sdf_desc d;
+    size_t count = 1;
+    for (int k = 0; k < 3; k++) {
+      d.res[k] = lattice_res[k];
+      d.origin[k] = origin[k];
+      count *= (size_t)(lattice_res[k] > 0 ? lattice_res[k] : 0);
+    }
+    d.spacing = spacing;
+    if (phi0.size() != count || (!phi1.empty() && phi1.size() != count))
+      throw std::runtime_error("set_levelset_sdf: the arrays must hold res[0] * res[1] * res[2] samples");
+    check(mpmhip_set_levelset_sdf(ctx_, &d, phi0.data(), phi1.empty() ? nullptr : phi1.data(), t0, t1, friction), ctx_);
+  }
+
   // --- MPM<dim>::add_particles (src/mpm.cpp:77-270).  Sampling: the built-in benchmark generator
   // ("benchmark" = 125 | 8000, :149-186), a lattice "cube_lo"/"cube_hi" in cells, or explicit arrays through
   // the overload below.  Returns "" (the reference returns a rigid-body id only for type "rigid").

@@ -169,6 +169,37 @@ int mpmhip_set_dirichlet(mpmhip_ctx *ctx, int32_t enabled);
 int mpmhip_set_levelset_keyframes(mpmhip_ctx *ctx, float t0, float t1, int32_t n0, const mpmhip_shape *shapes0,
                                   int32_t n1, const mpmhip_shape *shapes1, float friction);
 
+/* Sampled level set: a signed-distance field on a regular lattice instead of shapes — boundaries of any form (the reference's
+ * LevelSet IS a sampled array, taichi core; add_plane / add_sphere / add_cuboid only fill it and MPM<dim>::substep reads it
+ * through sample(), get_spatial_gradient(), get_temporal_derivative(): src/mpm.cpp:313-368, :414-426).  The taichi core is not
+ * vendored, so the sampling rules are this library's own:
+ *   lattice   res[k] >= 2 samples per axis, sample (0, 0, 0) at `origin`, one `spacing` > 0 (world units, independent of the
+ *             simulation's delta_x); arrays in C order [i][j][k] (k fastest), fp32, WORLD units, negative inside the solid.  The
+ *             library keeps its own device copy (4 res[0] res[1] res[2] bytes per key frame).
+ *   phi       trilinear interpolation in the cell that holds the point, returned in grid units.  A point outside
+ *             [origin, origin + (res - 1) spacing] on any axis has NO level set there: nothing is extrapolated.
+ *   gradient  trilinear interpolation of the eight samples' central-difference gradients (one-sided on the array's faces),
+ *             normalised; a length below 1e-10 gives the zero vector.
+ *   phi1      NULL: static.  Else a second key frame on the same lattice: phi = lerp(phi0, phi1), the normal is the normalised lerp
+ *             of the two unit gradients, d phi / dt = (phi1 - phi0) / (t1 - t0) — mpmhip_set_levelset_keyframes for samples.
+ * One level set at a time: a sampled set replaces the shapes and shapes replace a sampled set.  friction as above;
+ * particle_collision and mpmhip_delete_particles_inside_level_set work with it.  A call with the lattice size of the installed set
+ * reuses the device memory (the per-frame update of a dynamic level set allocates nothing).
+ * Out of scope: the 2D solver (mpmhip2d_set_levelset takes shapes only), meshes -> SDF, the reference's add_slope, and
+ * rigid_body_levelset_collision with a sampled set (refused with MPMHIP_EINVAL, here and in mpmhip_set_rigid_levelset_collision).
+ * Tiled jobs and the asynchronous stepper go through the same per-ctx call and substep; they are not tested with it. */
+typedef struct {
+  int32_t res[3];
+  float origin[3];
+  float spacing;
+} mpmhip_sdf_desc;
+int mpmhip_set_levelset_sdf(mpmhip_ctx *ctx, const mpmhip_sdf_desc *desc, const float *phi0, const float *phi1 /* NULL = static */,
+                            float t0, float t1, float friction);
+/* the DEVICE's level-set evaluation (whatever is installed: a sampled set or shapes) at n host-given points at time t:
+ * phi [n] in grid units, grad [n][3] the unit gradient, dphidt [n], hit [n] = 0 where there is no level set (then the rest is 0) */
+int mpmhip_debug_levelset_sample(mpmhip_ctx *ctx, int64_t n, const float *pos /* [n][3] */, float t, float *phi, float *grad,
+                                 float *dphidt, int32_t *hit);
+
 /* A ctx holds at most MPMHIP_MAX_GROUPS groups (k_g2p mirrors the whole group table in LDS). */
 #define MPMHIP_MAX_GROUPS 64
 /* particles — replaces MPM<3>::add_particles (src/mpm.cpp:77-270) with caller-generated samples.
@@ -220,7 +251,7 @@ int mpmhip_snapshot_load(mpmhip_ctx *ctx, const void *src, size_t size);
 int mpmhip_calculate_energy(mpmhip_ctx *ctx, double *kinetic, double *potential);
 
 /* replaces general_action "delete_particles_inside_level_set" (src/mpm.cpp:962-974): deletes every particle whose
- * level-set value at its position is negative (the level set last given to mpmhip_set_levelset[_shapes]);
+ * level-set value at its position is negative (the level set last given to mpmhip_set_levelset[_shapes | _sdf]);
  * *deleted = how many.  The next sort rebuilds the keys.  Synchronises. */
 int mpmhip_delete_particles_inside_level_set(mpmhip_ctx *ctx, int64_t *deleted);
 

@@ -84,7 +84,33 @@ __device__ __forceinline__ double node_block_ke(const float4 &acc, bool counted)
   return ke;
 }
 
-template <int MODE>
+// the boundary condition of a node against a SAMPLED level set (LS.sdf): same band, same friction_project (its form without fused
+// multiply-adds: the walks then agree bitwise whatever else differs between their kernels), same boundary velocity as the analytic
+// branch below it in both walks.  A lattice-aligned set takes the one-load path (mpm_math.h: sdf_node_in_band).
+__device__ __forceinline__ void sdf_node_bc(const Params &P, const LevelSetDev &LS, int gi, int gj, int gk, float v[3]) {
+  float phi, dphidt, nrm[3] = {0, 0, 0};
+  bool band;
+  if (LS.sdf.aligned) {  // kernel-uniform
+    band = sdf_node_in_band(LS.sdf, P.t, gi, gj, gk, P.idx, phi, nrm, dphidt);
+  } else {
+    const float xw[3] = {gi * P.dx, gj * P.dx, gk * P.dx};
+    int c[3];
+    float f[3];
+    band = sdf_locate(LS.sdf, xw, c, f);
+    if (band) {
+      phi = sdf_phi(LS.sdf, P.t, P.idx, c, f, &dphidt);
+      band = !(phi < -3.0f || 0.0f < phi);
+      if (band) sdf_normal(LS.sdf, P.t, c, f, nrm);
+    }
+  }
+  if (band) {
+    const float vb[3] = {-dphidt * nrm[0] * P.dx, -dphidt * nrm[1] * P.dx, -dphidt * nrm[2] * P.dx};  // (products only: nothing to fuse)
+    friction_project_exact(v, vb, nrm, LS.friction);
+  }
+}
+
+// SDF: the instantiation of mode 0 a ctx with a sampled level set launches (the others are the kernels they were)
+template <int MODE, bool SDF = false>
 __global__ __launch_bounds__(256) void k_grid_list(Params P, const Counters *__restrict__ cnt,
                                                    const uint32_t *__restrict__ nbr, const uint32_t *__restrict__ own_list,
                                                    const float4 *__restrict__ tiles, float4 *__restrict__ gridv,
@@ -157,7 +183,9 @@ __global__ __launch_bounds__(256) void k_grid_list(Params P, const Counters *__r
 #pragma unroll
       for (int k = 0; k < 3; k++) v[k] = fmaf(v[k], im, P.particle_gravity ? 0.0f : P.g[k] * P.dt);
     }
-    if (m != 0.0f && LS.n > 0) {  // src/mpm.cpp:313-368
+    if constexpr (SDF) {
+      if (m != 0.0f) sdf_node_bc(P, LS, gi, gj, gk, v);
+    } else if (m != 0.0f && LS.n > 0) {  // src/mpm.cpp:313-368
       const float xw[3] = {gi * P.dx, gj * P.dx, gk * P.dx};
       float phi, dphidt, nrm[3] = {0, 0, 0};
       levelset_eval(LS, P.t, xw, P.idx, phi, nrm, &dphidt);
@@ -174,7 +202,7 @@ __global__ __launch_bounds__(256) void k_grid_list(Params P, const Counters *__r
 }
 
 // ---- the walks of rounds 1-4 (see above)
-template <int MODE, bool PER_CAND>
+template <int MODE, bool PER_CAND, bool SDF = false>
 __global__ __launch_bounds__(256) void k_grid_blocks(Params P, const Counters *__restrict__ cnt,
                                               const uint32_t *__restrict__ act_blk,
                                               const uint32_t *__restrict__ bits,
@@ -314,7 +342,9 @@ __global__ __launch_bounds__(256) void k_grid_blocks(Params P, const Counters *_
 #pragma unroll
         for (int k = 0; k < 3; k++) v[k] = fmaf(v[k], im, P.particle_gravity ? 0.0f : P.g[k] * P.dt);
       }
-      if (m != 0.0f && LS.n > 0) {  // src/mpm.cpp:313-368
+      if constexpr (SDF) {
+        if (m != 0.0f) sdf_node_bc(P, LS, gi, gj, gk, v);
+      } else if (m != 0.0f && LS.n > 0) {  // src/mpm.cpp:313-368
         const float xw[3] = {gi * P.dx, gj * P.dx, gk * P.dx};
         float phi, dphidt, nrm[3] = {0, 0, 0};
         levelset_eval(LS, P.t, xw, P.idx, phi, nrm, &dphidt);

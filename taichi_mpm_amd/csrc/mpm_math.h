@@ -720,6 +720,18 @@ __device__ __forceinline__ void friction_project(float v[3], const float vb[3], 
 // frames blended linearly in time: phi = lerp, gradient = normalised lerp of the two gradients,
 // d phi / dt = (phi1 - phi0) / (t1 - t0), which gives the boundary velocity of src/mpm.cpp:340-342.
 struct ShapeDev { int type, inside_out; float p[6]; };  // type 0 plane {n, d}, 1 sphere, 2 cuboid
+// Sampled level set (mpmhip_set_levelset_sdf): phi in WORLD units on a regular lattice of res[0] x res[1] x res[2] samples, C order
+// (the last axis fastest), sample (0, 0, 0) at `origin`, one `spacing` for the three axes; phi1 != null: a second key frame on the
+// same lattice.  The sampler below is this library's design (the reference reads taichi's LevelSet class, which is not vendored).
+struct SdfDev {
+  const float *phi0, *phi1;
+  int res[3];
+  int aligned;     // the simulation's grid nodes coincide with samples: spacing == dx and origin = -off * dx (node g is sample g + off)
+  float origin[3];
+  float spacing, inv_spacing;
+  int off[3];
+  float t0, t1;    // times of the two key frames (phi1 != null)
+};
 struct LevelSetDev {
   int n;
   float friction;
@@ -730,6 +742,7 @@ struct LevelSetDev {
   int dirichlet;  // MPM<3>::apply_dirichlet_boundary_conditions (src/mpm.cpp:401-412): grid nodes above y = 0.525 are held at rest
   ShapeDev s[MPMHIP_MAX_SHAPES];
   ShapeDev s1[MPMHIP_MAX_SHAPES];
+  SdfDev sdf;  // sampled level set (sdf.phi0 != null: installed, and then n == 0 — one level set at a time)
 };
 
 __device__ __forceinline__ bool levelset_eval_key(const ShapeDev *S, int count, const float x[3], float idx, float &phi,
@@ -796,6 +809,177 @@ __device__ __forceinline__ bool levelset_eval(const LevelSetDev &L, float t, con
   const float inv = len < 1e-10f ? 0.0f : 1.0f / len;
   n[0] = g0 * inv; n[1] = g1 * inv; n[2] = g2 * inv;
   return true;
+}
+
+// ---- the sampled level set
+// No multiply-add of the sampler may be fused: every kernel that inlines it (both walks of the grid pass, the collision pass, the
+// deletion, the test entry) then computes the same bits for the same point, whatever its surroundings make the compiler prefer — the
+// walks agree bitwise and a particle is inside for one kernel exactly when it is for another — and tests/sdf_model.py reproduces
+// the device to the bit.
+#define SDF_NO_CONTRACT _Pragma("clang fp contract(off)")
+__device__ __forceinline__ float sdf_at(const SdfDev &S, const float *__restrict__ p, int i, int j, int k) {
+  return p[((size_t)i * S.res[1] + j) * S.res[2] + k];
+}
+// central-difference gradient of the sample (i, j, k), one-sided on the array's faces; d phi / d x, dimensionless
+__device__ __forceinline__ void sdf_sample_grad(const SdfDev &S, const float *__restrict__ p, int i, int j, int k, float g[3]) {
+  SDF_NO_CONTRACT
+  const int im = max(i - 1, 0), ip = min(i + 1, S.res[0] - 1), jm = max(j - 1, 0), jp = min(j + 1, S.res[1] - 1);
+  const int km = max(k - 1, 0), kp = min(k + 1, S.res[2] - 1);
+  g[0] = (sdf_at(S, p, ip, j, k) - sdf_at(S, p, im, j, k)) * ((ip - im == 2 ? 0.5f : 1.0f) * S.inv_spacing);
+  g[1] = (sdf_at(S, p, i, jp, k) - sdf_at(S, p, i, jm, k)) * ((jp - jm == 2 ? 0.5f : 1.0f) * S.inv_spacing);
+  g[2] = (sdf_at(S, p, i, j, kp) - sdf_at(S, p, i, j, km)) * ((kp - km == 2 ? 0.5f : 1.0f) * S.inv_spacing);
+}
+__device__ __forceinline__ float sdf_lerp(float a, float b, float f) {
+  SDF_NO_CONTRACT
+  return (1.0f - f) * a + f * b;
+}
+// the cell c (its lowest sample) that holds x and the position f in [0, 1]^3 inside it; false: x lies outside the lattice on some
+// axis — there is no level set there, nothing is extrapolated
+__device__ __forceinline__ bool sdf_locate(const SdfDev &S, const float x[3], int c[3], float f[3]) {
+  SDF_NO_CONTRACT
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float u = (x[k] - S.origin[k]) * S.inv_spacing;
+    in = in && u >= 0.0f && u <= (float)(S.res[k] - 1);  // (false for a NaN)
+    c[k] = min(max((int)u, 0), S.res[k] - 2);
+    f[k] = u - (float)c[k];
+  }
+  return in;
+}
+// trilinear interpolation of one key frame in the cell c: the last axis first, the first axis last
+__device__ __forceinline__ float sdf_phi_frame(const SdfDev &S, const float *__restrict__ p, const int c[3], const float f[3]) {
+  SDF_NO_CONTRACT
+  float a[2];
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    float b[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+      b[j] = sdf_lerp(sdf_at(S, p, c[0] + i, c[1] + j, c[2]), sdf_at(S, p, c[0] + i, c[1] + j, c[2] + 1), f[2]);
+    a[i] = sdf_lerp(b[0], b[1], f[1]);
+  }
+  return sdf_lerp(a[0], a[1], f[0]);
+}
+__device__ __forceinline__ void sdf_normalize(float g[3]) {
+  SDF_NO_CONTRACT
+  const float len = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+  const float inv = len < 1e-10f ? 0.0f : 1.0f / len;
+  g[0] *= inv; g[1] *= inv; g[2] *= inv;
+}
+// unit gradient of one key frame: the eight samples' central-difference gradients interpolated like phi, then normalised (second
+// order on curved surfaces; the derivative of the trilinear interpolant itself is first order)
+__device__ __forceinline__ void sdf_grad_frame(const SdfDev &S, const float *__restrict__ p, const int c[3], const float f[3],
+                                               float n[3]) {
+  SDF_NO_CONTRACT
+  float a[2][3];
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    float b[2][3];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      float g0[3], g1[3];
+      sdf_sample_grad(S, p, c[0] + i, c[1] + j, c[2], g0);
+      sdf_sample_grad(S, p, c[0] + i, c[1] + j, c[2] + 1, g1);
+#pragma unroll
+      for (int d = 0; d < 3; d++) b[j][d] = sdf_lerp(g0[d], g1[d], f[2]);
+    }
+#pragma unroll
+    for (int d = 0; d < 3; d++) a[i][d] = sdf_lerp(b[0][d], b[1][d], f[1]);
+  }
+#pragma unroll
+  for (int d = 0; d < 3; d++) n[d] = sdf_lerp(a[0][d], a[1][d], f[0]);
+  sdf_normalize(n);
+}
+// phi at time t in grid units (and d phi / dt) from the two frames' values in world units — the blend of levelset_eval
+__device__ __forceinline__ float sdf_blend_phi(const SdfDev &S, float t, float idx, float p0, float p1, float *dphidt) {
+  SDF_NO_CONTRACT
+  p0 *= idx; p1 *= idx;
+  const float a = (t - S.t0) / (S.t1 - S.t0);
+  if (dphidt) *dphidt = (p1 - p0) / (S.t1 - S.t0);
+  return (1.0f - a) * p0 + a * p1;
+}
+__device__ __forceinline__ void sdf_blend_normal(const SdfDev &S, float t, float n[3], const float n1[3]) {
+  SDF_NO_CONTRACT
+  const float a = (t - S.t0) / (S.t1 - S.t0);
+#pragma unroll
+  for (int d = 0; d < 3; d++) n[d] = n[d] * (1.0f - a) + n1[d] * a;
+  sdf_normalize(n);
+}
+// phi (grid units) in the located cell, and the unit normal there
+__device__ __forceinline__ float sdf_phi(const SdfDev &S, float t, float idx, const int c[3], const float f[3],
+                                         float *dphidt = nullptr) {
+  SDF_NO_CONTRACT
+  if (dphidt) *dphidt = 0.0f;
+  const float p0 = sdf_phi_frame(S, S.phi0, c, f);
+  if (!S.phi1) return p0 * idx;
+  return sdf_blend_phi(S, t, idx, p0, sdf_phi_frame(S, S.phi1, c, f), dphidt);
+}
+__device__ __forceinline__ void sdf_normal(const SdfDev &S, float t, const int c[3], const float f[3], float n[3]) {
+  SDF_NO_CONTRACT
+  sdf_grad_frame(S, S.phi0, c, f, n);
+  if (!S.phi1) return;
+  float n1[3];
+  sdf_grad_frame(S, S.phi1, c, f, n1);
+  sdf_blend_normal(S, t, n, n1);
+}
+// levelset_eval for a sampled set
+__device__ __forceinline__ bool sdf_eval(const SdfDev &S, float t, const float x[3], float idx, float &phi, float n[3],
+                                         float *dphidt = nullptr) {
+  SDF_NO_CONTRACT
+  if (dphidt) *dphidt = 0.0f;
+  int c[3];
+  float f[3];
+  if (!sdf_locate(S, x, c, f)) return false;
+  phi = sdf_phi(S, t, idx, c, f, dphidt);
+  sdf_normal(S, t, c, f, n);
+  return true;
+}
+// The grid pass at the node (gi, gj, gk) of a lattice-aligned set: one load per key frame, the band test -3 <= phi <= 0 first, and
+// only a node inside the band gathers its six neighbours.  Returns true when the node is in the band (phi, n, dphidt valid).  The
+// values are the ones sdf_eval gives at the node: with f = 0 (or 1) every interpolation returns its end point exactly.
+__device__ __forceinline__ bool sdf_node_in_band(const SdfDev &S, float t, int gi, int gj, int gk, float idx, float &phi, float n[3],
+                                                 float &dphidt) {
+  SDF_NO_CONTRACT
+  const int i = gi + S.off[0], j = gj + S.off[1], k = gk + S.off[2];
+  if ((unsigned)i >= (unsigned)S.res[0] || (unsigned)j >= (unsigned)S.res[1] || (unsigned)k >= (unsigned)S.res[2]) return false;
+  dphidt = 0.0f;
+  const float p0 = sdf_at(S, S.phi0, i, j, k);
+  phi = S.phi1 ? sdf_blend_phi(S, t, idx, p0, sdf_at(S, S.phi1, i, j, k), &dphidt) : p0 * idx;
+  if (phi < -3.0f || 0.0f < phi) return false;
+  sdf_sample_grad(S, S.phi0, i, j, k, n);
+  sdf_normalize(n);
+  if (S.phi1) {
+    float n1[3];
+    sdf_sample_grad(S, S.phi1, i, j, k, n1);
+    sdf_normalize(n1);
+    sdf_blend_normal(S, t, n, n1);
+  }
+  return true;
+}
+// friction_project with no multiply-add fused — the same expressions, for the grid pass against a sampled level set: its two walks
+// are separate kernels that must give the same bits, and what the compiler fuses depends on the code around (sdf_node_bc)
+__device__ __forceinline__ void friction_project_exact(float v[3], const float vb[3], const float n[3], float friction) {
+  SDF_NO_CONTRACT
+  if (friction == -1.0f) { v[0] = vb[0]; v[1] = vb[1]; v[2] = vb[2]; return; }
+  const bool slip = friction <= -2.0f;
+  if (slip) friction = -friction - 2.0f;
+  const float r0 = v[0] - vb[0], r1 = v[1] - vb[1], r2 = v[2] - vb[2];
+  const float nn = n[0] * r0 + n[1] * r1 + n[2] * r2;
+  const float t0 = r0 - nn * n[0], t1 = r1 - nn * n[1], t2 = r2 - nn * n[2];
+  const float tn = sqrtf(t0 * t0 + t1 * t1 + t2 * t2);
+  const float ts = fmaxf(tn + fminf(nn, 0.0f) * friction, 0.0f) / fmaxf(1e-30f, tn);
+  const float keep = slip ? 0.0f : fmaxf(0.0f, nn);
+  v[0] = ts * t0 + keep * n[0] + vb[0];
+  v[1] = ts * t1 + keep * n[1] + vb[1];
+  v[2] = ts * t2 + keep * n[2] + vb[2];
+}
+#undef SDF_NO_CONTRACT
+// whichever level set is installed
+__device__ __forceinline__ bool levelset_eval_any(const LevelSetDev &L, float t, const float x[3], float idx, float &phi,
+                                                  float n[3], float *dphidt = nullptr) {
+  if (L.sdf.phi0) return sdf_eval(L.sdf, t, x, idx, phi, n, dphidt);
+  return levelset_eval(L, t, x, idx, phi, n, dphidt);
 }
 
 // quadratic B-spline weights of MLSMPMFastKernel32 (src/transfer.cpp:168-186; src/kernel.h:126-130):

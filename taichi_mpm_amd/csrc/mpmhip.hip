@@ -82,6 +82,7 @@
 #include "k_g2p_packed.h"
 #include "k_rigid_transfer.h"
 #include "k_debug.h"
+#include "k_sdf.h"
 #include "k_bgeo.h"
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
@@ -193,6 +194,12 @@ struct mpmhip_ctx {
   // tiling
   LevelSetDev LS;
   LevelSetDev *d_LS = nullptr;  // device copy for k_g2p (k_grid takes it by value)
+  // sampled level set (mpmhip_set_levelset_sdf): this ctx's device copies of the key frames, [sdf_count] floats each; they live until
+  // the lattice changes, shapes replace the set, or the ctx goes (LS.sdf points at them while the set is installed)
+  float *d_sdf[2] = {nullptr, nullptr};
+  size_t sdf_count = 0;
+  int particle_collision_cfg = 0;  // the config's particle_collision.  P.particle_collision is 0 while a sampled set is installed:
+                                   // the G2P kernels then leave the push to k_sdf_collide (do_sdf_collide)
   Tiling T;
   DevBox *d_boxes = nullptr;
   uint32_t *d_counts = nullptr;
@@ -529,6 +536,7 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   memset(&c->LS, 0, sizeof c->LS);
   c->LS.particle_collision = cfg->particle_collision;
   P.particle_collision = cfg->particle_collision;
+  c->particle_collision_cfg = cfg->particle_collision;
   if (mpmhip_set_levelset(c, cfg->n_planes, &cfg->planes[0][0], cfg->friction) != MPMHIP_OK) return bail(MPMHIP_EINVAL);
   int kbits = 1;
   while ((1 << kbits) < maxnb) kbits++;
@@ -668,7 +676,7 @@ void mpmhip_destroy(mpmhip_ctx *c) {
   if (c->async.store.h_tbl_pin) hipHostFree(c->async.store.h_tbl_pin);
   { auto &S = c->async.store; hipFree(S.g); hipFree(S.w); hipFree(S.g2); hipFree(S.w2); hipFree(S.tag); hipFree(S.tag2); hipFree(S.id);
     hipFree(S.id2); hipFree(S.best); hipFree(S.d_scan); hipFree(S.d_tbl); hipFree(S.d_rank); hipFree(S.d_cnt); }
-  hipFree(c->cnt); hipFree(c->d_groups); hipFree(c->d_boxes); hipFree(c->d_LS); hipFree(c->d_counts); hipFree(c->d_bounds); if (c->h_pinned) hipHostFree(c->h_pinned); hipFree(c->d_energy); hipFree(c->d_energy_parts);
+  hipFree(c->cnt); hipFree(c->d_groups); hipFree(c->d_boxes); hipFree(c->d_LS); hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]); hipFree(c->d_counts); hipFree(c->d_bounds); if (c->h_pinned) hipHostFree(c->h_pinned); hipFree(c->d_energy); hipFree(c->d_energy_parts);
   { auto &R = c->rigid; hipFree(R.d_rb); hipFree(R.d_smp); hipFree(R.d_elems); hipFree(R.cdf.slot); hipFree(R.cdf.page_key); hipFree(R.cdf.mind);
     hipFree(R.cdf.tags); hipFree(R.cdf.rpage); hipFree(R.d_bnd); if (R.side) { hipStreamSynchronize(R.side); hipStreamDestroy(R.side); } if (R.ev_fork) hipEventDestroy(R.ev_fork); if (R.ev_join) hipEventDestroy(R.ev_join);
     hipFree(R.d_blk_rigid); hipFree(R.d_rigid_list); hipFree(R.d_counters); hipFree(R.d_joints); hipFree(R.d_imp_rows);
@@ -701,6 +709,14 @@ int mpmhip_set_dirichlet(mpmhip_ctx *c, int32_t enabled) {
   return MPMHIP_OK;
 }
 
+static void sdf_release(mpmhip_ctx *c) {
+  hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]);
+  c->d_sdf[0] = c->d_sdf[1] = nullptr;
+  c->sdf_count = 0;
+  memset(&c->LS.sdf, 0, sizeof c->LS.sdf);
+  c->P.particle_collision = c->particle_collision_cfg;
+}
+
 int mpmhip_set_levelset_shapes(mpmhip_ctx *c, int32_t n, const mpmhip_shape *shapes, float friction) {
   if (!c || n < 0 || n > MPMHIP_MAX_SHAPES || (n > 0 && !shapes)) return MPMHIP_EINVAL;
   for (int i = 0; i < n; i++) {
@@ -709,6 +725,11 @@ int mpmhip_set_levelset_shapes(mpmhip_ctx *c, int32_t n, const mpmhip_shape *sha
     if (shapes[i].type == 2)
       for (int k = 0; k < 3; k++)
         if (!(shapes[i].p[k] < shapes[i].p[3 + k])) return fail(c, MPMHIP_EINVAL, "shape %d: cuboid needs lo < hi", i);
+  }
+  if (c->LS.sdf.phi0) {  // shapes replace a sampled set: nothing of it survives
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    sdf_release(c);
   }
   c->LS.n = n;
   c->LS.friction = friction;
@@ -753,6 +774,80 @@ int mpmhip_set_levelset_keyframes(mpmhip_ctx *c, float t0, float t1, int32_t n0,
   }
   HIPCHK(c, hipMemcpy(c->d_LS, &c->LS, sizeof c->LS, hipMemcpyHostToDevice));
   return MPMHIP_OK;
+}
+
+// Sampled level set: see include/mpmhip.h.  The arrays are copied into device memory the ctx owns; a call with the lattice of the
+// installed set (the per-frame update of a dynamic level set) reuses that memory.
+int mpmhip_set_levelset_sdf(mpmhip_ctx *c, const mpmhip_sdf_desc *d, const float *phi0, const float *phi1, float t0, float t1,
+                            float friction) {
+  if (!c) return MPMHIP_EINVAL;
+  if (!d || !phi0) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: the lattice description and the first key frame are required");
+  if (c->in_substep) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf inside a substep");
+  size_t count = 1;
+  for (int k = 0; k < 3; k++) {
+    if (d->res[k] < 2) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: res[%d] = %d, at least 2 samples per axis are needed", k, d->res[k]);
+    if (!std::isfinite(d->origin[k])) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: origin[%d] is not finite", k);
+    count *= (size_t)d->res[k];
+  }
+  if (!(d->spacing > 0.0f) || !std::isfinite(d->spacing)) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: spacing must be a finite number > 0");
+  if (count > ((size_t)1 << 31)) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: more than 2^31 samples");
+  if (phi1 && !(t1 > t0)) return fail(c, MPMHIP_EINVAL, "key frame times must satisfy t0 < t1");
+  if (c->rigid.ls_collision)
+    return fail(c, MPMHIP_EINVAL, "rigid_body_levelset_collision is not supported with a sampled level set");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // (kernels in flight read the arrays)
+  if (count != c->sdf_count) {
+    hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]);
+    c->d_sdf[0] = c->d_sdf[1] = nullptr;
+    c->sdf_count = 0;
+    c->LS.sdf.phi0 = c->LS.sdf.phi1 = nullptr;
+    HIPCHK(c, dmalloc(&c->d_sdf[0], count));
+    c->sdf_count = count;
+  }
+  if (phi1 && !c->d_sdf[1]) HIPCHK(c, dmalloc(&c->d_sdf[1], count));
+  HIPCHK(c, hipMemcpy(c->d_sdf[0], phi0, sizeof(float) * count, hipMemcpyHostToDevice));
+  if (phi1) HIPCHK(c, hipMemcpy(c->d_sdf[1], phi1, sizeof(float) * count, hipMemcpyHostToDevice));
+  SdfDev &S = c->LS.sdf;
+  S.phi0 = c->d_sdf[0];
+  S.phi1 = phi1 ? c->d_sdf[1] : nullptr;
+  S.spacing = d->spacing; S.inv_spacing = 1.0f / d->spacing;
+  S.t0 = phi1 ? t0 : 0.0f; S.t1 = phi1 ? t1 : 1.0f;
+  // the one-load path of the grid pass: same spacing as the grid and the origin on a node (to 1e-4 of a cell)
+  S.aligned = d->spacing == c->P.dx;
+  for (int k = 0; k < 3; k++) {
+    S.res[k] = d->res[k]; S.origin[k] = d->origin[k];
+    const float o = d->origin[k] * c->P.idx, r = nearbyintf(o);
+    if (!(fabsf(o - r) <= 1e-4f) || fabsf(r) > 65536.0f) S.aligned = 0;
+    S.off[k] = S.aligned ? -(int)r : 0;
+  }
+  c->LS.n = 0; c->LS.dynamic = 0; c->LS.n1 = 0;  // the sampled set replaces the shapes
+  c->LS.friction = friction;
+  c->P.particle_collision = 0;
+  HIPCHK(c, hipMemcpy(c->d_LS, &c->LS, sizeof c->LS, hipMemcpyHostToDevice));
+  return MPMHIP_OK;
+}
+
+// the device's level-set evaluation at host-given points (tests): phi in grid units, the unit gradient, d phi / dt, hit = 0 where
+// there is no level set
+int mpmhip_debug_levelset_sample(mpmhip_ctx *c, int64_t n, const float *pos, float t, float *phi, float *grad, float *dphidt,
+                                 int32_t *hit) {
+  if (!c || n <= 0 || !pos || !phi || !grad || !dphidt || !hit) return MPMHIP_EINVAL;
+  HIPCHK(c, hipSetDevice(c->device));
+  float *dP, *dO;
+  HIPCHK(c, dmalloc(&dP, 3 * n));
+  if (hipError_t e = dmalloc(&dO, 6 * n); e != hipSuccess) { hipFree(dP); return fail(c, MPMHIP_EHIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
+  int rc = MPMHIP_OK;
+  if (hipMemcpy(dP, pos, sizeof(float) * 3 * n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, MPMHIP_EHIP, "hipMemcpy failed");
+  if (!rc) rc = run_debug(c, k_debug_levelset_sample, c->LS, t, c->P.idx, n, (const float *)dP, dO, dO + n, dO + 4 * n, reinterpret_cast<int32_t *>(dO + 5 * n));
+  if (!rc) {
+    hipError_t e = hipMemcpy(phi, dO, sizeof(float) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(grad, dO + n, sizeof(float) * 3 * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(dphidt, dO + 4 * n, sizeof(float) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(hit, dO + 5 * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(c, MPMHIP_EHIP, "hipMemcpy failed: %s", hipGetErrorString(e));
+  }
+  hipFree(dP); hipFree(dO);
+  return rc;
 }
 
 int mpmhip_set_levelset(mpmhip_ctx *c, int32_t n_planes, const float *planes, float friction) {
@@ -1254,7 +1349,8 @@ static int do_grid(mpmhip_ctx *c, int mode, int phase = 0) {
     if (n_own == 0) n_own = std::min<uint64_t>((uint64_t)c->P.max_blocks * 8u, 32768u);  // (before the first sort has reported)
     int wgs = (int)std::min<uint64_t>(8192u, std::max<uint64_t>(64u, (n_own + n_own / 8 + 3) / 4 + 8));
     if (c->grid_wgs > 0) wgs = c->grid_wgs;
-    hipLaunchKernelGGL(mode == 0 ? k_grid_list<0> : (mode == 4 ? k_grid_list<4> : k_grid_list<5>), dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, (const uint32_t *)c->nbr,
+    const bool sdf = mode == 0 && c->LS.sdf.phi0;  // sampled level set: the instantiation that reads it
+    hipLaunchKernelGGL(mode == 0 ? (sdf ? k_grid_list<0, true> : k_grid_list<0>) : (mode == 4 ? k_grid_list<4> : k_grid_list<5>), dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, (const uint32_t *)c->nbr,
                        (const uint32_t *)c->own_list, c->tiles, c->gridv, c->fat_slot, reinterpret_cast<double *>(c->dense), c->T,
                        c->d_boxes_cur, c->LS, phase);
     return launch_check(c, "grid");
@@ -1269,6 +1365,7 @@ static int do_grid(mpmhip_ctx *c, int mode, int phase = 0) {
                                      : (mode == 2 ? k_grid_blocks<2, false>
                                                   : (mode == 3 ? k_grid_blocks<3, false>
                                                                : (mode == 4 ? k_grid_blocks<4, false> : k_grid_blocks<5, false>))));
+  if (mode == 0 && c->LS.sdf.phi0) kern = per_cand ? k_grid_blocks<0, true, true> : k_grid_blocks<0, false, true>;
   int wgs = per_cand ? 16384 : 4096;
   if (c->grid_wgs > 0 && mode == 0) wgs = c->grid_wgs;
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, c->act_blk, c->bits, c->wprefix, c->tiles,
@@ -1361,6 +1458,14 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
   return launch_check(c, "g2p");
 }
 
+// particle_collision against a sampled level set (k_sdf.h): behind the LAST k_g2p launch of a substep, on the buffers it wrote
+static int do_sdf_collide(mpmhip_ctx *c) {
+  if (!c->LS.sdf.phi0 || !c->particle_collision_cfg || c->n_slots == 0) return MPMHIP_OK;
+  hipLaunchKernelGGL(k_sdf_collide, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const Counters *)c->cnt,
+                     (float4 *)c->rg2, (float4 *)c->rp2, c->key, c->blk_flag, c->cnt, c->LS.sdf);
+  return launch_check(c, "sdf_collide");
+}
+
 // behind the LAST k_g2p launch of a substep: the buffers it wrote become the current records
 static void swap_records(mpmhip_ctx *c) {
   std::swap(c->rg, c->rg2); std::swap(c->rp, c->rp2); std::swap(c->rb, c->rb2);
@@ -1395,7 +1500,7 @@ int mpmhip_g2p(mpmhip_ctx *c) {
   if (!c) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   int rc = need_sorted(c, "g2p");
-  if (rc || (rc = do_g2p(c))) return rc;
+  if (rc || (rc = do_g2p(c)) || (rc = do_sdf_collide(c))) return rc;
   swap_records(c);
   return MPMHIP_OK;
 }
@@ -1529,6 +1634,7 @@ int mpmhip_substep_end(mpmhip_ctx *c) {  // grid (+ halo sum), G2P
   if ((rc = do_grid(c, 0, ph))) return rc;
   if (ev && (lvl == 1 || lvl == 2)) HIPCHK(c, hipEventRecord(ev->e[4], c->stream));
   if ((rc = do_g2p(c, ph))) return rc;
+  if ((rc = do_sdf_collide(c))) return rc;
   if (ev && (lvl == 1 || lvl == 2 || lvl == 4)) HIPCHK(c, hipEventRecord(ev->e[5], c->stream));
   swap_records(c);
   if (rigid_active(c) && (rc = do_rigid_advect(c, c->P.dt))) return rc;  // src/mpm.cpp:570-572
@@ -1786,7 +1892,7 @@ int mpmhip_delete_particles_inside_level_set(mpmhip_ctx *c, int64_t *deleted) {
   if (!c || !deleted) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   *deleted = 0;
-  if (c->LS.n <= 0 || c->n_slots == 0) return MPMHIP_OK;
+  if ((c->LS.n <= 0 && !c->LS.sdf.phi0) || c->n_slots == 0) return MPMHIP_OK;
   if (int rc = ensure_b_current(c)) return rc;  // the recovery reads every live record: do it before some die
   Counters before, after;
   if (int rc = read_counters(c, before)) return rc;

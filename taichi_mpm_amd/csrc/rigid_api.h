@@ -288,6 +288,8 @@ static int do_rigid_pre_b(mpmhip_ctx *c) {
 
 int mpmhip_set_rigid_levelset_collision(mpmhip_ctx *c, int32_t enabled) {
   if (!c) return MPMHIP_EINVAL;
+  if (enabled && c->LS.sdf.phi0)
+    return fail(c, MPMHIP_EINVAL, "rigid_body_levelset_collision is not supported with a sampled level set");
   c->rigid.ls_collision = enabled != 0;
   return MPMHIP_OK;
 }

@@ -88,6 +88,100 @@ class LevelSet:
         return [(t_, io) + tuple(p[:4] if t_ == 1 else p) for t_, io, p in self.shapes if t_ != 0]
 
 
+def eval_shapes(shapes, pts):
+    """phi (world units, float64) of a LevelSet's shapes at the points pts (n, 3): min over the shapes, the formulas of
+    levelset_eval_key (csrc/mpm_math.h).  +inf where there is no shape."""
+    x = np.asarray(pts, np.float64).reshape(-1, 3)
+    phi = np.full(len(x), np.inf)
+    for t_, io, p in shapes:
+        p = np.asarray(p, np.float64)
+        if t_ == 0:
+            ph = x @ p[:3] + p[3]
+        elif t_ == 1:
+            ph = np.linalg.norm(x - p[:3], axis=1) - p[3]
+        else:
+            lo, hi = p[:3], p[3:6]
+            inside = np.all((lo <= x) & (x <= hi), axis=1)
+            ph = np.where(inside, -np.minimum(x - lo, hi - x).min(axis=1), np.linalg.norm(x - np.clip(x, lo, hi), axis=1))
+        if t_ != 0 and io:
+            ph = -ph
+        phi = np.minimum(phi, ph)
+    return phi
+
+
+class SampledLevelSet:
+    """A signed-distance field sampled on a regular lattice (include/mpmhip.h: mpmhip_set_levelset_sdf): boundaries of any shape.
+    `phi`: array of shape (res0, res1, res2), world units, negative inside the solid; sample (i, j, k) sits at
+    origin + (i, j, k) * spacing.  spacing=None: the cell size of the simulation it is given to.  Outside the lattice there is no
+    level set; one level set at a time, so a floor is baked into the array (from_levelset bakes any analytic LevelSet)."""
+
+    def __init__(self, phi, origin=(0.0, 0.0, 0.0), spacing=None, friction=-1.0):
+        a = np.asarray(phi)
+        if a.ndim != 3:
+            raise MPMError("SampledLevelSet: phi must have 3 axes, got shape %r" % (a.shape,))
+        if min(a.shape) < 2:
+            raise MPMError("SampledLevelSet: at least 2 samples per axis are needed, got shape %r" % (a.shape,))
+        a = np.ascontiguousarray(a, np.float32)
+        if not np.all(np.isfinite(a)):
+            raise MPMError("SampledLevelSet: phi holds non-finite values")
+        o = _vec3(origin, None)
+        if not np.all(np.isfinite(o)):
+            raise MPMError("SampledLevelSet: origin must be finite, got %r" % (o,))
+        if spacing is not None and not (np.isfinite(spacing) and float(spacing) > 0):
+            raise MPMError("SampledLevelSet: spacing must be a finite number > 0, got %r" % (spacing,))
+        self.phi, self.origin = a, o
+        self.spacing = None if spacing is None else float(spacing)
+        self.friction = float(friction)
+
+    @property
+    def res(self):
+        return self.phi.shape
+
+    def get_delta_x(self):
+        if self.spacing is None:
+            raise MPMError("this SampledLevelSet has no spacing yet: it takes the cell size of the simulation it is given to")
+        return self.spacing
+
+    def set_friction(self, f):
+        self.friction = float(f)
+        return self
+
+    def same_lattice(self, other):
+        return self.res == other.res and self.origin == other.origin and self.spacing == other.spacing
+
+    @staticmethod
+    def lattice_points(res, origin, spacing):
+        """(n, 3) float64 positions of the samples in the array's order"""
+        res = tuple(int(r) for r in res)
+        if len(res) != 3 or min(res) < 2:
+            raise MPMError("SampledLevelSet: res must be three numbers >= 2, got %r" % (res,))
+        if not (np.isfinite(spacing) and float(spacing) > 0):
+            raise MPMError("SampledLevelSet: spacing must be a finite number > 0, got %r" % (spacing,))
+        o = _vec3(origin, None)
+        ax = [o[k] + np.arange(res[k], dtype=np.float64) * float(spacing) for k in range(3)]
+        return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 3)
+
+    @classmethod
+    def from_function(cls, f, res, origin=(0.0, 0.0, 0.0), spacing=None, friction=-1.0):
+        """sample f, which maps an (n, 3) array of world positions to n values of phi"""
+        if spacing is None:
+            raise MPMError("SampledLevelSet.from_function needs the spacing of the lattice")
+        pts = cls.lattice_points(res, origin, spacing)
+        phi = np.empty(len(pts), np.float64)
+        for i in range(0, len(pts), 1 << 20):  # (chunks: f may build large temporaries)
+            phi[i:i + (1 << 20)] = np.asarray(f(pts[i:i + (1 << 20)]), np.float64).reshape(-1)
+        return cls(phi.reshape(tuple(int(r) for r in res)), origin, spacing, friction)
+
+    @classmethod
+    def from_levelset(cls, ls, res, origin=(0.0, 0.0, 0.0), spacing=None):
+        """bake an analytic LevelSet (its friction travels along)"""
+        if not ls.shapes:
+            raise MPMError("SampledLevelSet.from_levelset: the LevelSet has no shapes")
+        if spacing is None:
+            spacing = ls.delta_x
+        return cls.from_function(lambda x: eval_shapes(ls.shapes, x), res, origin, spacing, ls.friction)
+
+
 class DynamicLevelSet:
     """taichi's DynamicLevelSet as the python driver builds it every frame (scripts/async/async_mpm.py:119-127):
     `initialize(t0, t1, levelset(t0), levelset(t1))`; the two key frames are blended linearly in time on the device
@@ -99,6 +193,11 @@ class DynamicLevelSet:
     def initialize(self, t0, t1, levelset0, levelset1):
         if not float(t1) > float(t0):
             raise MPMError("DynamicLevelSet needs t0 < t1")
+        s0, s1 = isinstance(levelset0, SampledLevelSet), isinstance(levelset1, SampledLevelSet)
+        if s0 != s1:
+            raise MPMError("DynamicLevelSet: a sampled and an analytic key frame cannot be mixed")
+        if s0 and not levelset0.same_lattice(levelset1):
+            raise MPMError("DynamicLevelSet: the two sampled key frames must share one lattice (res, origin, spacing)")
         self.t0, self.t1, self.levelset0, self.levelset1 = float(t0), float(t1), levelset0, levelset1
         return self
 
@@ -505,7 +604,7 @@ class Simulation3D:
 
     # ---------------------------------------------------------------- level set
     def set_levelset(self, levelset):
-        """Simulation::set_levelset: a LevelSet (static) or a DynamicLevelSet (two key frames)"""
+        """Simulation::set_levelset: a LevelSet or SampledLevelSet (static) or a DynamicLevelSet (two key frames of one kind)"""
         self._levelset = levelset
         if self._ctx is not None:
             self._apply_levelset()
@@ -526,10 +625,41 @@ class Simulation3D:
             l0, l1 = ls.levelset0, ls.levelset1
             # key frame times are relative to the ctx clock (a re-created ctx restarts it at 0)
             off = getattr(self, "_time_offset", 0.0)
+            if isinstance(l0, SampledLevelSet):
+                self._set_sdf(l0, l1, ls.t0 - off, ls.t1 - off)
+                return
             self._check(self._L.mpmhip_set_levelset_keyframes(self._ctx, ls.t0 - off, ls.t1 - off, len(l0.shapes), self._shape_array(l0),
                                                               len(l1.shapes), self._shape_array(l1), l0.friction))
             return
+        if isinstance(ls, SampledLevelSet):
+            self._set_sdf(ls, None, 0.0, 1.0)
+            return
         self._check(self._L.mpmhip_set_levelset_shapes(self._ctx, len(ls.shapes), self._shape_array(ls), ls.friction))
+
+    def _set_sdf(self, l0, l1, t0, t1):
+        if self.rigid_body_levelset_collision:
+            raise MPMError("rigid_body_levelset_collision is not supported with a sampled level set")
+        d = _lib.SdfDesc()
+        d.res[:] = l0.res
+        d.origin[:] = l0.origin
+        d.spacing = l0.spacing if l0.spacing is not None else self.delta_x
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.mpmhip_set_levelset_sdf(self._ctx, C.byref(d), l0.phi.ctypes.data_as(fp),
+                                                    l1.phi.ctypes.data_as(fp) if l1 is not None else None, t0, t1, l0.friction))
+
+    def sample_levelset(self, positions, t=None):
+        """the device's evaluation of the installed level set (sampled or analytic) at positions (n, 3):
+        (phi in grid units, unit gradient, d phi / dt, hit) — hit is False where there is no level set"""
+        self._ensure_ctx()
+        x = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n = len(x)
+        phi, grad, dphidt, hit = np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        if n:
+            fp = C.POINTER(C.c_float)
+            t = self.get_current_time() - getattr(self, "_time_offset", 0.0) if t is None else float(t)
+            self._check(self._L.mpmhip_debug_levelset_sample(self._ctx, n, x.ctypes.data_as(fp), t, phi.ctypes.data_as(fp), grad.ctypes.data_as(fp),
+                                                             dphidt.ctypes.data_as(fp), hit.ctypes.data_as(C.POINTER(C.c_int32))))
+        return phi, grad, dphidt, hit.astype(bool)
 
     # ---------------------------------------------------------------- stepping
     def _check_script(self):
