@@ -134,6 +134,27 @@ class MPM<3> {
     check(mpmhip_set_levelset_sdf(ctx_, &d, phi0.data(), phi1.empty() ? nullptr : phi1.data(), t0, t1, friction), ctx_);
   }
 
+  // sampled level set from a closed triangle mesh, voxelised on the device (include/mpmhip.h: mpmhip_set_levelset_mesh).
+  // tri: 9 floats per triangle, world units.  band (world units, +inf allowed): phi is exact within it and +-band beyond.
+  void set_levelset_mesh(const VectorI &lattice_res, const Vector &origin, real spacing, const std::vector<float> &tri, real band,
+                         real friction) {
+    set_levelset_mesh(lattice_res, origin, spacing, 0.0f, 1.0f, tri, std::vector<float>(), band, friction);
+  }
+  // ... two key frames on one lattice (tri1 empty: static)
+  void set_levelset_mesh(const VectorI &lattice_res, const Vector &origin, real spacing, real t0, real t1, const std::vector<float> &tri0,
+                         const std::vector<float> &tri1, real band, real friction) {
+    mpmhip_sdf_desc d;
+    for (int k = 0; k < 3; k++) {
+      d.res[k] = lattice_res[k];
+      d.origin[k] = origin[k];
+    }
+    d.spacing = spacing;
+    if (tri0.empty() || tri0.size() % 9 != 0 || tri1.size() % 9 != 0)
+      throw std::runtime_error("set_levelset_mesh: a mesh is 9 floats per triangle, at least one triangle");
+    check(mpmhip_set_levelset_mesh(ctx_, &d, (int32_t)(tri0.size() / 9), tri0.data(), (int32_t)(tri1.size() / 9),
+                                   tri1.empty() ? nullptr : tri1.data(), t0, t1, band, friction), ctx_);
+  }
+
   // --- MPM<dim>::add_particles (src/mpm.cpp:77-270).  Sampling: the built-in benchmark generator
   // ("benchmark" = 125 | 8000, :149-186), a lattice "cube_lo"/"cube_hi" in cells, or explicit arrays through
   // the overload below.  Returns "" (the reference returns a rigid-body id only for type "rigid").

@@ -185,7 +185,8 @@ int mpmhip_set_levelset_keyframes(mpmhip_ctx *ctx, float t0, float t1, int32_t n
  * One level set at a time: a sampled set replaces the shapes and shapes replace a sampled set.  friction as above;
  * particle_collision and mpmhip_delete_particles_inside_level_set work with it.  A call with the lattice size of the installed set
  * reuses the device memory (the per-frame update of a dynamic level set allocates nothing).
- * Out of scope: the 2D solver (mpmhip2d_set_levelset takes shapes only), meshes -> SDF, the reference's add_slope, and
+ * Out of scope: the 2D solver (mpmhip2d_set_levelset takes shapes only), the reference's add_slope, open or self-intersecting
+ * meshes (closed triangle meshes are voxelised on the device: mpmhip_set_levelset_mesh below), and
  * rigid_body_levelset_collision with a sampled set (refused with MPMHIP_EINVAL, here and in mpmhip_set_rigid_levelset_collision).
  * Tiled jobs and the asynchronous stepper go through the same per-ctx call and substep; they are not tested with it. */
 typedef struct {
@@ -199,6 +200,52 @@ int mpmhip_set_levelset_sdf(mpmhip_ctx *ctx, const mpmhip_sdf_desc *desc, const 
  * phi [n] in grid units, grad [n][3] the unit gradient, dphidt [n], hit [n] = 0 where there is no level set (then the rest is 0) */
 int mpmhip_debug_levelset_sample(mpmhip_ctx *ctx, int64_t n, const float *pos /* [n][3] */, float t, float *phi, float *grad,
                                  float *dphidt, int32_t *hit);
+
+/* Triangle mesh -> sampled level set, voxelised on the device (the reference's scenes give bowls, cutters and wheels as .obj
+ * files; its LevelSet is filled from a mesh by the taichi core, which is not vendored, so the rules are this library's own).
+ * Input: n_tri triangles, float [n_tri][3][3] in world units; a lattice as above; band > 0 in world units, +inf allowed.
+ * Output per sample: phi = s * min(d, band), fp32, world units, C order.  Sample (i, j, k) sits at fl(origin + fl(index * spacing))
+ * per axis, in fp32.
+ *   d      the Euclidean distance to the nearest triangle: the exact closest point of each triangle by its regions (three
+ *          vertices, three edges, the face), evaluated in fp32.  A triangle's vertices are first put in lexicographic order, so its
+ *          orientation and vertex order do not reach any number.  Triangles of zero area (cross product exactly 0) are skipped.
+ *   s      -1 iff the ray from the sample towards +k (the array's fastest axis) crosses an odd number of triangles, else +1:
+ *          independent of the triangles' orientation and order.  Column (x, y) lies in a triangle's xy-projection iff the ray from
+ *          (x, y) towards +x crosses an odd number of its three projected edges.  An edge is crossed iff exactly one end point has
+ *          y' > y (half-open: an end point AT y counts as below) and the edge function, taken from the lower end point in fp64 on
+ *          differences of the fp32 inputs (differences and products exact, the sign of the result exact), is > 0: a point ON an
+ *          edge does not cross it.  The decision depends on the edge and the column only, so the two triangles sharing an edge
+ *          always agree and every column of a closed mesh crosses it an even number of times, however vertices, edges and faces
+ *          line up with the lattice.  A projection of zero area contributes nothing.  The crossing height is interpolated in fp64
+ *          and a sample is below it iff crossing > the sample's own height.
+ *   closed a column with an ODD total of crossings means the mesh is not closed: the call fails with MPMHIP_EINVAL, the message
+ *          says how many columns were odd, nothing is installed and no output array is written.  (An even column proves nothing: a
+ *          hole seen exactly edge-on from +k crosses no column.  Open and self-intersecting meshes are out of scope beyond this.)
+ *   band   finite: the field is exact wherever d < band and exactly +-band elsewhere (bitwise the +inf result where that is inside
+ *          the band).  What the consumers need: the grid pass reads -3 <= phi <= 0 grid units, plus one interpolation cell, plus
+ *          the central-difference neighbours, so band >= 3 delta_x + 2 spacing gives the grid pass the bits an unclamped field
+ *          gives.  Where the field is clamped the sampled normal is the zero vector: particle_collision does not push a particle
+ *          that is deeper inside than the band.
+ * The result is a pure function of the triangle SET and the lattice: two runs, a shuffled list, reversed orientations give the same
+ * bits (minimum and parity are order-free; no float atomics).  MPMHIP_EINVAL for: a non-finite vertex, n_tri <= 0 (or > 2^26),
+ * band <= 0 or NaN, a lattice mpmhip_set_levelset_sdf refuses, res[2] > 8191, a mesh of zero-area triangles only.
+ *
+ * mpmhip_mesh_to_sdf: no ctx, voxelises on `device` into the host array phi_out [res0 * res1 * res2] (replaces a point-to-mesh
+ * distance written in numpy in front of SampledLevelSet; a cached result goes back in through mpmhip_set_levelset_sdf).  Errors:
+ * mpmhip_last_error(NULL), as for mpmhip_create. */
+int mpmhip_mesh_to_sdf(int32_t device, const mpmhip_sdf_desc *desc, int32_t n_tri, const float *tri /* [n_tri][3][3] */, float band,
+                       float *phi_out);
+/* mpmhip_set_levelset_sdf with the key frames given as meshes (replaces host voxelisation + the upload of the arrays, twice per
+ * frame for a moving boundary): voxelises on the ctx's stream straight into the ctx's device arrays and installs the set exactly as
+ * mpmhip_set_levelset_sdf does — the same refusals (inside a substep, with rigid_body_levelset_collision), the same reuse of the
+ * device memory for an unchanged lattice, the same aligned / one-load decision.  tri1 == NULL: static (n_tri1, t0, t1 ignored).
+ * The triangle and list buffers are kept between calls too; no lattice-sized host array exists at any point.  Both meshes are
+ * judged before the installed level set is touched: a refused call leaves it in force. */
+int mpmhip_set_levelset_mesh(mpmhip_ctx *ctx, const mpmhip_sdf_desc *desc, int32_t n_tri0, const float *tri0, int32_t n_tri1,
+                             const float *tri1 /* NULL = static */, float t0, float t1, float band, float friction);
+/* reads back key frame `frame` (0, or 1 of a two-frame set) of the installed sampled level set, however it was installed:
+ * sdf_count floats in C order, world units; capacity = room in dst, in floats.  For caching a voxelisation and for tests. */
+int mpmhip_download_levelset_sdf(mpmhip_ctx *ctx, int32_t frame, float *dst, int64_t capacity);
 
 /* A ctx holds at most MPMHIP_MAX_GROUPS groups (k_g2p mirrors the whole group table in LDS). */
 #define MPMHIP_MAX_GROUPS 64

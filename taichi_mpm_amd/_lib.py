@@ -157,7 +157,7 @@ def build_variant(name, extra_flags):
 
 _lib = None
 
-_SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create", "mpmhip_destroy", "mpmhip_last_error", "mpmhip_set_stream", "mpmhip_set_deterministic", "mpmhip_set_levelset", "mpmhip_set_rigid_levelset_collision", "mpmhip_set_dirichlet", "mpmhip2d_set_dirichlet", "mpmhip_set_levelset_shapes", "mpmhip_set_levelset_keyframes", "mpmhip_set_levelset_sdf", "mpmhip_debug_levelset_sample",
+_SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create", "mpmhip_destroy", "mpmhip_last_error", "mpmhip_set_stream", "mpmhip_set_deterministic", "mpmhip_set_levelset", "mpmhip_set_rigid_levelset_collision", "mpmhip_set_dirichlet", "mpmhip2d_set_dirichlet", "mpmhip_set_levelset_shapes", "mpmhip_set_levelset_keyframes", "mpmhip_set_levelset_sdf", "mpmhip_debug_levelset_sample", "mpmhip_mesh_to_sdf", "mpmhip_set_levelset_mesh", "mpmhip_download_levelset_sdf",
             "mpmhip_add_group", "mpmhip_add_particles", "mpmhip_num_particles", "mpmhip_download",
             "mpmhip_upload", "mpmhip_substep", "mpmhip_run_substeps", "mpmhip_step", "mpmhip_current_time",
             "mpmhip_synchronize", "mpmhip_sort", "mpmhip_p2g", "mpmhip_grid_update", "mpmhip_g2p",
@@ -233,6 +233,9 @@ def load():
     L.mpmhip_set_levelset_keyframes.argtypes = [vp, C.c_float, C.c_float, C.c_int32, P(Shape), C.c_int32, P(Shape), C.c_float]
     L.mpmhip_set_levelset_sdf.argtypes = [vp, P(SdfDesc), fp, fp, C.c_float, C.c_float, C.c_float]
     L.mpmhip_debug_levelset_sample.argtypes = [vp, C.c_int64, fp, C.c_float, fp, fp, fp, P(C.c_int32)]
+    L.mpmhip_mesh_to_sdf.argtypes = [C.c_int32, P(SdfDesc), C.c_int32, fp, C.c_float, fp]
+    L.mpmhip_set_levelset_mesh.argtypes = [vp, P(SdfDesc), C.c_int32, fp, C.c_int32, fp, C.c_float, C.c_float, C.c_float, C.c_float]
+    L.mpmhip_download_levelset_sdf.argtypes = [vp, C.c_int32, fp, C.c_int64]
     L.mpmhip_add_group.argtypes = [vp, C.c_int32, fp]
     L.mpmhip_add_particles.argtypes = [vp, C.c_int32, C.c_int64, fp, fp, fp, fp, fp]
     L.mpmhip_num_particles.argtypes = [vp]

@@ -83,6 +83,7 @@
 #include "k_rigid_transfer.h"
 #include "k_debug.h"
 #include "k_sdf.h"
+#include "k_mesh_sdf.h"
 #include "k_bgeo.h"
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
@@ -198,6 +199,7 @@ struct mpmhip_ctx {
   // the lattice changes, shapes replace the set, or the ctx goes (LS.sdf points at them while the set is installed)
   float *d_sdf[2] = {nullptr, nullptr};
   size_t sdf_count = 0;
+  MeshSdfWork mesh_work[2];  // mpmhip_set_levelset_mesh: the voxeliser's buffers per key frame, kept between calls
   int particle_collision_cfg = 0;  // the config's particle_collision.  P.particle_collision is 0 while a sampled set is installed:
                                    // the G2P kernels then leave the push to k_sdf_collide (do_sdf_collide)
   Tiling T;
@@ -676,7 +678,7 @@ void mpmhip_destroy(mpmhip_ctx *c) {
   if (c->async.store.h_tbl_pin) hipHostFree(c->async.store.h_tbl_pin);
   { auto &S = c->async.store; hipFree(S.g); hipFree(S.w); hipFree(S.g2); hipFree(S.w2); hipFree(S.tag); hipFree(S.tag2); hipFree(S.id);
     hipFree(S.id2); hipFree(S.best); hipFree(S.d_scan); hipFree(S.d_tbl); hipFree(S.d_rank); hipFree(S.d_cnt); }
-  hipFree(c->cnt); hipFree(c->d_groups); hipFree(c->d_boxes); hipFree(c->d_LS); hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]); hipFree(c->d_counts); hipFree(c->d_bounds); if (c->h_pinned) hipHostFree(c->h_pinned); hipFree(c->d_energy); hipFree(c->d_energy_parts);
+  hipFree(c->cnt); hipFree(c->d_groups); hipFree(c->d_boxes); hipFree(c->d_LS); hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]); msdf_free(c->mesh_work[0]); msdf_free(c->mesh_work[1]); hipFree(c->d_counts); hipFree(c->d_bounds); if (c->h_pinned) hipHostFree(c->h_pinned); hipFree(c->d_energy); hipFree(c->d_energy_parts);
   { auto &R = c->rigid; hipFree(R.d_rb); hipFree(R.d_smp); hipFree(R.d_elems); hipFree(R.cdf.slot); hipFree(R.cdf.page_key); hipFree(R.cdf.mind);
     hipFree(R.cdf.tags); hipFree(R.cdf.rpage); hipFree(R.d_bnd); if (R.side) { hipStreamSynchronize(R.side); hipStreamDestroy(R.side); } if (R.ev_fork) hipEventDestroy(R.ev_fork); if (R.ev_join) hipEventDestroy(R.ev_join);
     hipFree(R.d_blk_rigid); hipFree(R.d_rigid_list); hipFree(R.d_counters); hipFree(R.d_joints); hipFree(R.d_imp_rows);
@@ -776,6 +778,44 @@ int mpmhip_set_levelset_keyframes(mpmhip_ctx *c, float t0, float t1, int32_t n0,
   return MPMHIP_OK;
 }
 
+// device arrays for a sampled set of d's lattice: a lattice of the installed set's size keeps its memory.  The stream must be idle
+// (kernels in flight read the arrays).
+static int sdf_reserve(mpmhip_ctx *c, const mpmhip_sdf_desc *d, bool two) {
+  const size_t count = (size_t)d->res[0] * d->res[1] * d->res[2];
+  if (count != c->sdf_count) {
+    hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]);
+    c->d_sdf[0] = c->d_sdf[1] = nullptr;
+    c->sdf_count = 0;
+    c->LS.sdf.phi0 = c->LS.sdf.phi1 = nullptr;
+    HIPCHK(c, dmalloc(&c->d_sdf[0], count));
+    c->sdf_count = count;
+  }
+  if (two && !c->d_sdf[1]) HIPCHK(c, dmalloc(&c->d_sdf[1], count));
+  return MPMHIP_OK;
+}
+
+// c->d_sdf[0 / 1] hold the key frames: make them the ctx's level set
+static int sdf_install(mpmhip_ctx *c, const mpmhip_sdf_desc *d, bool two, float t0, float t1, float friction) {
+  SdfDev &S = c->LS.sdf;
+  S.phi0 = c->d_sdf[0];
+  S.phi1 = two ? c->d_sdf[1] : nullptr;
+  S.spacing = d->spacing; S.inv_spacing = 1.0f / d->spacing;
+  S.t0 = two ? t0 : 0.0f; S.t1 = two ? t1 : 1.0f;
+  // the one-load path of the grid pass: same spacing as the grid and the origin on a node (to 1e-4 of a cell)
+  S.aligned = d->spacing == c->P.dx;
+  for (int k = 0; k < 3; k++) {
+    S.res[k] = d->res[k]; S.origin[k] = d->origin[k];
+    const float o = d->origin[k] * c->P.idx, r = nearbyintf(o);
+    if (!(fabsf(o - r) <= 1e-4f) || fabsf(r) > 65536.0f) S.aligned = 0;
+    S.off[k] = S.aligned ? -(int)r : 0;
+  }
+  c->LS.n = 0; c->LS.dynamic = 0; c->LS.n1 = 0;  // the sampled set replaces the shapes
+  c->LS.friction = friction;
+  c->P.particle_collision = 0;
+  HIPCHK(c, hipMemcpy(c->d_LS, &c->LS, sizeof c->LS, hipMemcpyHostToDevice));
+  return MPMHIP_OK;
+}
+
 // Sampled level set: see include/mpmhip.h.  The arrays are copied into device memory the ctx owns; a call with the lattice of the
 // installed set (the per-frame update of a dynamic level set) reuses that memory.
 int mpmhip_set_levelset_sdf(mpmhip_ctx *c, const mpmhip_sdf_desc *d, const float *phi0, const float *phi1, float t0, float t1,
@@ -796,35 +836,10 @@ int mpmhip_set_levelset_sdf(mpmhip_ctx *c, const mpmhip_sdf_desc *d, const float
     return fail(c, MPMHIP_EINVAL, "rigid_body_levelset_collision is not supported with a sampled level set");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // (kernels in flight read the arrays)
-  if (count != c->sdf_count) {
-    hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]);
-    c->d_sdf[0] = c->d_sdf[1] = nullptr;
-    c->sdf_count = 0;
-    c->LS.sdf.phi0 = c->LS.sdf.phi1 = nullptr;
-    HIPCHK(c, dmalloc(&c->d_sdf[0], count));
-    c->sdf_count = count;
-  }
-  if (phi1 && !c->d_sdf[1]) HIPCHK(c, dmalloc(&c->d_sdf[1], count));
+  if (int rc = sdf_reserve(c, d, phi1 != nullptr)) return rc;
   HIPCHK(c, hipMemcpy(c->d_sdf[0], phi0, sizeof(float) * count, hipMemcpyHostToDevice));
   if (phi1) HIPCHK(c, hipMemcpy(c->d_sdf[1], phi1, sizeof(float) * count, hipMemcpyHostToDevice));
-  SdfDev &S = c->LS.sdf;
-  S.phi0 = c->d_sdf[0];
-  S.phi1 = phi1 ? c->d_sdf[1] : nullptr;
-  S.spacing = d->spacing; S.inv_spacing = 1.0f / d->spacing;
-  S.t0 = phi1 ? t0 : 0.0f; S.t1 = phi1 ? t1 : 1.0f;
-  // the one-load path of the grid pass: same spacing as the grid and the origin on a node (to 1e-4 of a cell)
-  S.aligned = d->spacing == c->P.dx;
-  for (int k = 0; k < 3; k++) {
-    S.res[k] = d->res[k]; S.origin[k] = d->origin[k];
-    const float o = d->origin[k] * c->P.idx, r = nearbyintf(o);
-    if (!(fabsf(o - r) <= 1e-4f) || fabsf(r) > 65536.0f) S.aligned = 0;
-    S.off[k] = S.aligned ? -(int)r : 0;
-  }
-  c->LS.n = 0; c->LS.dynamic = 0; c->LS.n1 = 0;  // the sampled set replaces the shapes
-  c->LS.friction = friction;
-  c->P.particle_collision = 0;
-  HIPCHK(c, hipMemcpy(c->d_LS, &c->LS, sizeof c->LS, hipMemcpyHostToDevice));
-  return MPMHIP_OK;
+  return sdf_install(c, d, phi1 != nullptr, t0, t1, friction);
 }
 
 // the device's level-set evaluation at host-given points (tests): phi in grid units, the unit gradient, d phi / dt, hit = 0 where
@@ -1478,6 +1493,7 @@ static int need_sorted(mpmhip_ctx *c, const char *who) {
 }
 
 #include "rigid_api.h"
+#include "mesh_sdf_api.h"
 
 int mpmhip_sort(mpmhip_ctx *c) {
   if (!c) return MPMHIP_EINVAL;

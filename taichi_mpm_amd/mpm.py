@@ -182,6 +182,93 @@ class SampledLevelSet:
         return cls.from_function(lambda x: eval_shapes(ls.shapes, x), res, origin, spacing, ls.friction)
 
 
+    @classmethod
+    def from_mesh(cls, mesh, res, origin=(0.0, 0.0, 0.0), spacing=None, band=None, friction=-1.0, device=0):
+        """voxelise a closed triangle mesh on the GPU (include/mpmhip.h: mpmhip_mesh_to_sdf).  mesh: an (n, 3, 3) array or the path
+        of a Wavefront .obj file; band (world units, +inf allowed): phi is exact within it and +-band beyond, None = 8 * spacing."""
+        m = MeshLevelSet(mesh, res, origin, spacing, band, friction)
+        if m.spacing is None:
+            raise MPMError("SampledLevelSet.from_mesh needs the spacing of the lattice")
+        L = _lib.load()
+        phi = np.empty(m.res, np.float32)
+        fp = C.POINTER(C.c_float)
+        d = m.desc(m.spacing)
+        if L.mpmhip_mesh_to_sdf(int(device), C.byref(d), len(m.triangles), m.triangles.ctypes.data_as(fp), m.band_for(m.spacing), phi.ctypes.data_as(fp)) != 0:
+            raise MPMError(L.mpmhip_last_error(None).decode())
+        return cls(phi, m.origin, m.spacing, friction)
+
+
+def _triangles(mesh, who):
+    if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
+        mesh = load_obj_triangles(mesh)
+    a = np.asarray(mesh)
+    if a.ndim != 3 or a.shape[1:] != (3, 3) or len(a) == 0:
+        raise MPMError("%s: the mesh must be an (n, 3, 3) array of triangles with n >= 1, got shape %r" % (who, a.shape))
+    a = np.ascontiguousarray(a, np.float32)
+    if not np.all(np.isfinite(a)):
+        raise MPMError("%s: the mesh holds non-finite vertices" % who)
+    return a
+
+
+class MeshLevelSet:
+    """A closed triangle mesh as a level set (include/mpmhip.h: mpmhip_set_levelset_mesh): it holds only the triangles and the
+    lattice (res, origin, spacing) they are voxelised on — on the device, straight into the simulation's own arrays, when it is given
+    to set_levelset, to DynamicLevelSet.initialize (two of them on one lattice) or returned by the update_levelset generator.
+    mesh: an (n, 3, 3) array or the path of a Wavefront .obj file.  spacing=None: the cell size of the simulation it is given to.
+    band (world units, +inf allowed): phi is exact within it and +-band beyond; None = 8 * spacing."""
+
+    def __init__(self, mesh, res, origin=(0.0, 0.0, 0.0), spacing=None, band=None, friction=-1.0):
+        self.triangles = _triangles(mesh, "MeshLevelSet")
+        try:
+            res = tuple(int(r) for r in res)
+        except TypeError:
+            res = ()
+        if len(res) != 3 or min(res) < 2:
+            raise MPMError("MeshLevelSet: res must be three numbers >= 2, got %r" % (res,))
+        o = _vec3(origin, None)
+        if not np.all(np.isfinite(o)):
+            raise MPMError("MeshLevelSet: origin must be finite, got %r" % (o,))
+        if spacing is not None and not (np.isfinite(spacing) and float(spacing) > 0):
+            raise MPMError("MeshLevelSet: spacing must be a finite number > 0, got %r" % (spacing,))
+        if band is not None and not float(band) > 0:
+            raise MPMError("MeshLevelSet: band must be > 0 (+inf is allowed), got %r" % (band,))
+        self.res, self.origin = res, o
+        self.spacing = None if spacing is None else float(spacing)
+        self.band = None if band is None else float(band)
+        self.friction = float(friction)
+
+    def get_delta_x(self):
+        if self.spacing is None:
+            raise MPMError("this MeshLevelSet has no spacing yet: it takes the cell size of the simulation it is given to")
+        return self.spacing
+
+    def set_friction(self, f):
+        self.friction = float(f)
+        return self
+
+    def same_lattice(self, other):
+        return self.res == other.res and self.origin == other.origin and self.spacing == other.spacing and self.band == other.band
+
+    def band_for(self, spacing):
+        return 8.0 * spacing if self.band is None else self.band
+
+    def desc(self, spacing):
+        d = _lib.SdfDesc()
+        d.res[:] = self.res
+        d.origin[:] = self.origin
+        d.spacing = spacing
+        return d
+
+    def with_transform(self, rotation=None, translation=(0.0, 0.0, 0.0)):
+        """a copy on the same lattice whose vertices are x -> rotation @ x + translation (rotation: a 3x3 matrix, None = identity)"""
+        R = np.eye(3) if rotation is None else np.asarray(rotation, np.float64)
+        if R.shape != (3, 3) or not np.all(np.isfinite(R)):
+            raise MPMError("MeshLevelSet.with_transform: rotation must be a finite 3x3 matrix")
+        t = np.asarray(_vec3(translation, None), np.float64)
+        moved = self.triangles.astype(np.float64) @ R.T + t
+        return MeshLevelSet(moved, self.res, self.origin, self.spacing, self.band, self.friction)
+
+
 class DynamicLevelSet:
     """taichi's DynamicLevelSet as the python driver builds it every frame (scripts/async/async_mpm.py:119-127):
     `initialize(t0, t1, levelset(t0), levelset(t1))`; the two key frames are blended linearly in time on the device
@@ -194,6 +281,11 @@ class DynamicLevelSet:
         if not float(t1) > float(t0):
             raise MPMError("DynamicLevelSet needs t0 < t1")
         s0, s1 = isinstance(levelset0, SampledLevelSet), isinstance(levelset1, SampledLevelSet)
+        m0, m1 = isinstance(levelset0, MeshLevelSet), isinstance(levelset1, MeshLevelSet)
+        if m0 != m1:
+            raise MPMError("DynamicLevelSet: a mesh key frame cannot be mixed with an analytic or an array key frame")
+        if m0 and not levelset0.same_lattice(levelset1):
+            raise MPMError("DynamicLevelSet: the two mesh key frames must share one lattice (res, origin, spacing) and band")
         if s0 != s1:
             raise MPMError("DynamicLevelSet: a sampled and an analytic key frame cannot be mixed")
         if s0 and not levelset0.same_lattice(levelset1):
@@ -604,7 +696,8 @@ class Simulation3D:
 
     # ---------------------------------------------------------------- level set
     def set_levelset(self, levelset):
-        """Simulation::set_levelset: a LevelSet or SampledLevelSet (static) or a DynamicLevelSet (two key frames of one kind)"""
+        """Simulation::set_levelset: a LevelSet, SampledLevelSet or MeshLevelSet (static) or a DynamicLevelSet (two key frames of one
+        kind)"""
         self._levelset = levelset
         if self._ctx is not None:
             self._apply_levelset()
@@ -628,11 +721,17 @@ class Simulation3D:
             if isinstance(l0, SampledLevelSet):
                 self._set_sdf(l0, l1, ls.t0 - off, ls.t1 - off)
                 return
+            if isinstance(l0, MeshLevelSet):
+                self._set_mesh(l0, l1, ls.t0 - off, ls.t1 - off)
+                return
             self._check(self._L.mpmhip_set_levelset_keyframes(self._ctx, ls.t0 - off, ls.t1 - off, len(l0.shapes), self._shape_array(l0),
                                                               len(l1.shapes), self._shape_array(l1), l0.friction))
             return
         if isinstance(ls, SampledLevelSet):
             self._set_sdf(ls, None, 0.0, 1.0)
+            return
+        if isinstance(ls, MeshLevelSet):
+            self._set_mesh(ls, None, 0.0, 1.0)
             return
         self._check(self._L.mpmhip_set_levelset_shapes(self._ctx, len(ls.shapes), self._shape_array(ls), ls.friction))
 
@@ -646,6 +745,30 @@ class Simulation3D:
         fp = C.POINTER(C.c_float)
         self._check(self._L.mpmhip_set_levelset_sdf(self._ctx, C.byref(d), l0.phi.ctypes.data_as(fp),
                                                     l1.phi.ctypes.data_as(fp) if l1 is not None else None, t0, t1, l0.friction))
+
+    def _set_mesh(self, l0, l1, t0, t1):
+        if self.rigid_body_levelset_collision:
+            raise MPMError("rigid_body_levelset_collision is not supported with a sampled level set")
+        spacing = l0.spacing if l0.spacing is not None else self.delta_x
+        d = l0.desc(spacing)
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.mpmhip_set_levelset_mesh(self._ctx, C.byref(d), len(l0.triangles), l0.triangles.ctypes.data_as(fp),
+                                                     len(l1.triangles) if l1 is not None else 0,
+                                                     l1.triangles.ctypes.data_as(fp) if l1 is not None else None, t0, t1,
+                                                     l0.band_for(spacing), l0.friction))
+
+    def download_levelset_sdf(self, frame=0):
+        """key frame `frame` of the installed sampled level set (given as arrays or voxelised from a mesh) as a
+        (res0, res1, res2) float32 array in world units, and the lattice: (phi, origin, spacing)"""
+        self._ensure_ctx()
+        ls = self._levelset
+        if isinstance(ls, DynamicLevelSet):
+            ls = ls.levelset0
+        if not isinstance(ls, (SampledLevelSet, MeshLevelSet)):
+            raise MPMError("download_levelset_sdf: no sampled level set is installed")
+        phi = np.empty(tuple(ls.res), np.float32)
+        self._check(self._L.mpmhip_download_levelset_sdf(self._ctx, int(frame), phi.ctypes.data_as(C.POINTER(C.c_float)), phi.size))
+        return phi, ls.origin, ls.spacing if ls.spacing is not None else self.delta_x
 
     def sample_levelset(self, positions, t=None):
         """the device's evaluation of the installed level set (sampled or analytic) at positions (n, 3):
