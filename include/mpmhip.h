@@ -723,6 +723,10 @@ int mpmhip_debug_scan_grid(int32_t n_cus, int32_t per_cu, int32_t env_request, u
  * 2 fully shuffled.  Reads exactly (64 + 4) n bytes per launch: the yardstick rocprofv3's FETCH_SIZE is calibrated
  * against for this access width (profiles/calibrate_fetch.py). */
 int mpmhip_debug_gather_bandwidth(mpmhip_ctx *ctx, int64_t n_records, int32_t mode, int32_t iters, double *gb_per_s);
+/* device and pinned arrays this process's objects hold right now (arrays, not bytes; every ctx, 2D object and mpm88 object
+ * together; the halo arena of a tiled ctx is not counted).  An object gives back what it took when the number after its destroy
+ * is the number before its create.  No device call. */
+int64_t mpmhip_debug_live_buffers(void);
 
 /* debug/parity helpers running the device math on host arrays (n items each) */
 int mpmhip_debug_svd3(mpmhip_ctx *ctx, int64_t n, const float *F, float *U, float *S, float *V);

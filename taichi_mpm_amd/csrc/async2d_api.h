@@ -13,9 +13,9 @@ static int a2_grow_particles(mpmhip2d_ctx *m, int64_t need) {
   const size_t cap = (size_t)need + (size_t)need / 2 + 1024, keep = (size_t)m->n;
   hipError_t e = hipSuccess;
   auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  A(regrow(&m->x, 2 * keep, 2 * cap, false)); A(regrow(&m->v, 2 * keep, 2 * cap, false)); A(regrow(&m->F, 4 * keep, 4 * cap, false));
-  A(regrow(&m->B, 4 * keep, 4 * cap, false)); A(regrow(&m->aux, keep, cap, false)); A(regrow(&m->gid, keep, cap, false));
-  A(regrow(&m->pid, keep, cap, false));
+  A(m->x.regrow(2 * keep, 2 * cap, false)); A(m->v.regrow(2 * keep, 2 * cap, false)); A(m->F.regrow(4 * keep, 4 * cap, false));
+  A(m->B.regrow(4 * keep, 4 * cap, false)); A(m->aux.regrow(keep, cap, false)); A(m->gid.regrow(keep, cap, false));
+  A(m->pid.regrow(keep, cap, false));
   if (e != hipSuccess) return fail2d(m, MPMHIP_ENOMEM, std::string("growing the particle arrays failed: ") + hipGetErrorString(e));
   m->cap = (int64_t)cap;
   return MPMHIP_OK;
@@ -26,8 +26,8 @@ static int a2_grow_particles_any(mpmhip2d_ctx *m, int64_t need) {
   const size_t keep = (size_t)m->n;
   if (int rc = a2_grow_particles(m, need)) return rc;
   if (m->rigid_enabled) {
-    hipError_t e = regrow(&m->d_states, keep, (size_t)m->cap, true);
-    if (e == hipSuccess) e = regrow(&m->d_bnd, keep, (size_t)m->cap, true);
+    hipError_t e = m->d_states.regrow(keep, (size_t)m->cap, true);
+    if (e == hipSuccess) e = m->d_bnd.regrow(keep, (size_t)m->cap, true);
     if (e != hipSuccess) return fail2d(m, MPMHIP_ENOMEM, std::string("growing the particle arrays failed: ") + hipGetErrorString(e));
   }
   return MPMHIP_OK;
@@ -37,12 +37,11 @@ static int a2_store_reserve(mpmhip2d_ctx *m, uint32_t need) {  // room for `need
   if (need <= A.cap) return MPMHIP_OK;
   HIPCHK2D(m, hipStreamSynchronize(m->stream));
   const uint32_t cap = std::max<uint32_t>(need + need / 2, 4096), keep = std::min(A.size_ub, A.cap);
-  hipError_t e = regrow(&A.rec, (size_t)keep * 4, (size_t)cap * 4, false);
-  if (e == hipSuccess) e = regrow(&A.tag, (size_t)keep, (size_t)cap, false);
+  hipError_t e = A.rec.regrow((size_t)keep * 4, (size_t)cap * 4, false);
+  if (e == hipSuccess) e = A.tag.regrow((size_t)keep, (size_t)cap, false);
   // (kernels walk [0, upper bound of the size): every tag behind the containers in use says FREE)
   if (e == hipSuccess) e = hipMemset(A.tag + keep, 0xFF, sizeof(uint32_t) * (size_t)(cap - keep));
-  (void)hipFree(A.rec2); (void)hipFree(A.tag2);
-  A.rec2 = nullptr; A.tag2 = nullptr;  // (the compaction targets are re-allocated when a compaction runs)
+  A.rec2.reset(); A.tag2.reset();  // (the compaction targets are re-allocated when a compaction runs)
   if (e != hipSuccess) return fail2d(m, MPMHIP_ENOMEM, std::string("async store: growing failed: ") + hipGetErrorString(e));
   A.cap = cap;
   return MPMHIP_OK;
@@ -61,8 +60,7 @@ static int a2_best_reserve(mpmhip2d_ctx *m) {  // one dedup word per creation id
   auto &A = m->async;
   if ((int64_t)m->next_pid <= A.best_cap) return MPMHIP_OK;
   const size_t cap = (size_t)m->next_pid + (size_t)m->next_pid / 2 + 1024;
-  (void)hipFree(A.best); A.best = nullptr;
-  HIPCHK2D(m, dmalloc(&A.best, cap));
+  HIPCHK2D(m, A.best.alloc(cap));
   HIPCHK2D(m, hipMemsetAsync(A.best, 0xFF, sizeof(unsigned long long) * cap, m->stream));
   A.best_cap = (int64_t)cap;
   return MPMHIP_OK;
@@ -90,15 +88,14 @@ static int a2_compact(mpmhip2d_ctx *m) {
   auto &A = m->async;
   if (A.size == 0) return MPMHIP_OK;
   if (!A.rec2) {
-    hipError_t e = dmalloc(&A.rec2, (size_t)A.cap * 4);
-    if (e == hipSuccess) e = dmalloc(&A.tag2, (size_t)A.cap);
+    hipError_t e = A.rec2.alloc((size_t)A.cap * 4);
+    if (e == hipSuccess) e = A.tag2.alloc((size_t)A.cap);
     if (e != hipSuccess) return fail2d(m, MPMHIP_ENOMEM, std::string("async store: compaction buffers: ") + hipGetErrorString(e));
   }
   HIPCHK2D(m, hipMemsetAsync(A.tag2, 0xFF, sizeof(uint32_t) * (size_t)A.cap, m->stream));
   const uint32_t nchunks = (A.size + 1023) / 1024;
   if (nchunks + 1 > A.scan_cap) {
-    (void)hipFree(A.d_scan); A.d_scan = nullptr;
-    HIPCHK2D(m, dmalloc(&A.d_scan, (size_t)nchunks + 1024));
+    HIPCHK2D(m, A.d_scan.alloc((size_t)nchunks + 1024));
     HIPCHK2D(m, hipMemsetAsync(A.d_scan, 0, sizeof(unsigned long long) * ((size_t)nchunks + 1024), m->stream));
     A.scan_cap = nchunks + 1024;
   }
@@ -134,14 +131,17 @@ int mpmhip2d_async_begin(mpmhip2d_ctx *m, const mpmhip_async_config *cfg) {
   A.sched_enable(2, m->P.res, *cfg);
   A.sched_begin();
   const size_t nblk = A.nblk();
-  a2_free(m);
-  HIPCHK2D(m, dmalloc(&A.d_tab, 3 * nblk));
-  HIPCHK2D(m, dmalloc(&A.d_tbl, nblk));
-  HIPCHK2D(m, dmalloc(&A.d_rank, nblk));
-  HIPCHK2D(m, dmalloc(&A.d_cnt, 1));
-  HIPCHK2D(m, hipHostMalloc((void **)&A.h_tab, sizeof(uint32_t) * 3 * nblk, hipHostMallocDefault));
-  HIPCHK2D(m, hipHostMalloc((void **)&A.h_tbl_pin, 4 * nblk, hipHostMallocDefault));
-  HIPCHK2D(m, hipHostMalloc((void **)&A.h_cnt, sizeof(AsyncCounters), hipHostMallocDefault));
+  // a second begin starts from an empty store: the arrays sized by the counters reset below go, the others are replaced here
+  A.rec.reset(); A.rec2.reset(); A.tag.reset(); A.tag2.reset(); A.d_blk_of.reset(); A.best.reset(); A.d_scan.reset();
+  A.blk_of_cap = 0;  // (the next load_pools must allocate d_blk_of again)
+  A.resident = false;
+  HIPCHK2D(m, A.d_tab.alloc(3 * nblk));
+  HIPCHK2D(m, A.d_tbl.alloc(nblk));
+  HIPCHK2D(m, A.d_rank.alloc(nblk));
+  HIPCHK2D(m, A.d_cnt.alloc(1));
+  HIPCHK2D(m, A.h_tab.alloc(3 * nblk));
+  HIPCHK2D(m, A.h_tbl_pin.alloc(4 * nblk));
+  HIPCHK2D(m, A.h_cnt.alloc(1));
   HIPCHK2D(m, hipMemcpy(A.d_rank, A.rank_of.data(), sizeof(uint32_t) * nblk, hipMemcpyHostToDevice));
   HIPCHK2D(m, hipMemset(A.d_cnt, 0, sizeof(AsyncCounters)));
   A.cap = A.size = A.size_ub = A.live = 0;
@@ -312,8 +312,7 @@ int64_t mpmhip2d_async_load_pools(mpmhip2d_ctx *m) {
   if (int rc = a2_settle(m)) return rc;
   if (int rc = a2_grow_particles(m, (int64_t)A.live)) return rc;
   if (A.blk_of_cap < m->cap) {
-    (void)hipFree(A.d_blk_of); A.d_blk_of = nullptr;
-    HIPCHK2D(m, dmalloc(&A.d_blk_of, (size_t)m->cap));
+    HIPCHK2D(m, A.d_blk_of.alloc((size_t)m->cap));
     A.blk_of_cap = m->cap;
   }
   hipLaunchKernelGGL(mpm2d::k2a_load, dim3(a2_grid(A.size)), dim3(256), 0, m->stream, A.size, (const uint32_t *)A.tag, (const float4 *)A.rec,

@@ -15,12 +15,11 @@ static int async_store_reserve(mpmhip_ctx *c, uint32_t need) {  // room for `nee
   const uint32_t cap = std::max<uint32_t>(need + need / 2, 4096), keep = std::min(S.size_ub, S.cap);
   hipError_t e = hipSuccess;
   auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  A(regrow(&S.g, (size_t)keep * 4, (size_t)cap * 4, false)); A(regrow(&S.w, (size_t)keep * 4, (size_t)cap * 4, false));
-  A(regrow(&S.tag, (size_t)keep, (size_t)cap, false)); A(regrow(&S.id, (size_t)keep, (size_t)cap, false));
+  A(S.g.regrow((size_t)keep * 4, (size_t)cap * 4, false)); A(S.w.regrow((size_t)keep * 4, (size_t)cap * 4, false));
+  A(S.tag.regrow((size_t)keep, (size_t)cap, false)); A(S.id.regrow((size_t)keep, (size_t)cap, false));
   // (kernels walk [0, upper bound of the size): every tag behind the containers in use says FREE)
   if (e == hipSuccess) A(hipMemset(S.tag + keep, 0xFF, sizeof(uint32_t) * (size_t)(cap - keep)));
-  (void)hipFree(S.g2); (void)hipFree(S.w2); (void)hipFree(S.tag2); (void)hipFree(S.id2);
-  S.g2 = S.w2 = nullptr; S.tag2 = nullptr; S.id2 = nullptr;  // (the compaction targets are re-allocated when a compaction runs)
+  S.g2.reset(); S.w2.reset(); S.tag2.reset(); S.id2.reset();  // (the compaction targets are re-allocated when a compaction runs)
   if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "async store: growing to %u containers failed: %s", cap, hipGetErrorString(e));
   S.cap = cap;
   return MPMHIP_OK;
@@ -35,9 +34,7 @@ static int async_upload_tbl(mpmhip_ctx *c) {
   const size_t nblk = A.tbl.size();
   if (S.pin_cap < nblk) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (S.h_tbl_pin) (void)hipHostFree(S.h_tbl_pin);
-    S.h_tbl_pin = nullptr;
-    HIPCHK(c, hipHostMalloc((void **)&S.h_tbl_pin, 4 * nblk, hipHostMallocDefault));
+    HIPCHK(c, S.h_tbl_pin.alloc(4 * nblk));
     S.pin_cap = nblk;
   }
   uint8_t *img = S.h_tbl_pin + (size_t)(S.pin_next++ & 3) * S.pin_cap;
@@ -49,8 +46,7 @@ static int async_best_reserve(mpmhip_ctx *c) {  // one dedup word per creation i
   auto &S = c->async.store;
   if ((int64_t)c->next_pid <= S.best_cap) return MPMHIP_OK;
   const size_t cap = (size_t)c->next_pid + (size_t)c->next_pid / 2 + 1024;
-  (void)hipFree(S.best); S.best = nullptr;
-  HIPCHK(c, dmalloc(&S.best, cap));
+  HIPCHK(c, S.best.alloc(cap));
   HIPCHK(c, hipMemsetAsync(S.best, 0xFF, sizeof(unsigned long long) * cap, c->stream));
   S.best_cap = (int64_t)cap;
   return MPMHIP_OK;
@@ -98,14 +94,13 @@ static int async_compact(mpmhip_ctx *c) {
   if (!S.g2) {
     hipError_t e = hipSuccess;
     auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    A(dmalloc(&S.g2, (size_t)S.cap * 4)); A(dmalloc(&S.w2, (size_t)S.cap * 4)); A(dmalloc(&S.tag2, (size_t)S.cap)); A(dmalloc(&S.id2, (size_t)S.cap));
+    A(S.g2.alloc((size_t)S.cap * 4)); A(S.w2.alloc((size_t)S.cap * 4)); A(S.tag2.alloc((size_t)S.cap)); A(S.id2.alloc((size_t)S.cap));
     if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "async store: compaction buffers: %s", hipGetErrorString(e));
   }
   HIPCHK(c, hipMemsetAsync(S.tag2, 0xFF, sizeof(uint32_t) * (size_t)S.cap, c->stream));
   const uint32_t nchunks = (S.size + 1023) / 1024;
   if (nchunks + 1 > S.scan_cap) {
-    (void)hipFree(S.d_scan); S.d_scan = nullptr;
-    HIPCHK(c, dmalloc(&S.d_scan, (size_t)nchunks + 1024));
+    HIPCHK(c, S.d_scan.alloc((size_t)nchunks + 1024));
     HIPCHK(c, hipMemsetAsync(S.d_scan, 0, sizeof(unsigned long long) * ((size_t)nchunks + 1024), c->stream));
     S.scan_cap = nchunks + 1024;
   }
@@ -147,11 +142,9 @@ int mpmhip_async_begin(mpmhip_ctx *c, const mpmhip_async_config *cfg) {
   A.sched_begin();  // block times, the reference's block order, cached_neighbours
   const size_t nblk = A.nblk();
   HIPCHK(c, hipSetDevice(c->device));
-  hipFree(S.d_tbl); hipFree(S.d_rank); hipFree(S.d_cnt);
-  S.d_tbl = nullptr; S.d_rank = nullptr; S.d_cnt = nullptr;
-  HIPCHK(c, dmalloc(&S.d_tbl, nblk));
-  HIPCHK(c, dmalloc(&S.d_rank, nblk));
-  HIPCHK(c, dmalloc(&S.d_cnt, 1));
+  HIPCHK(c, S.d_tbl.alloc(nblk));
+  HIPCHK(c, S.d_rank.alloc(nblk));
+  HIPCHK(c, S.d_cnt.alloc(1));
   HIPCHK(c, hipMemcpy(S.d_rank, A.rank_of.data(), sizeof(uint32_t) * nblk, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemset(S.d_cnt, 0, sizeof(AsyncCounters)));
   S.size = S.size_ub = S.live = 0;
@@ -173,8 +166,8 @@ int mpmhip_async_pool_particles(mpmhip_ctx *c) {
   if (int rc = async_settle(c)) return rc;
   if (int rc = ensure_b_current(c)) return rc;
   if (int rc = async_store_reserve(c, S.size + (uint32_t)c->n_slots)) return rc;
-  hipLaunchKernelGGL(k_async_file, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg,
-                     (const float4 *)c->rp, (const float4 *)c->rb, (const uint8_t *)S.d_tbl, 1, A.nb[0], A.nb[1], A.nb[2], S.cap,
+  hipLaunchKernelGGL(k_async_file, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(),
+                     (const float4 *)c->rp.get(), (const float4 *)c->rb.get(), (const uint8_t *)S.d_tbl, 1, A.nb[0], A.nb[1], A.nb[2], S.cap,
                      S.g, S.w, S.tag, S.id, S.d_cnt);
   if (int rc = launch_check(c, "async_file")) return rc;
   AsyncCounters h;
@@ -228,7 +221,7 @@ static int async_advance(mpmhip_ctx *c, int64_t limit) {
                      (const int32_t *)S.id, (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best);
   hipLaunchKernelGGL(k_async_gather, dim3(as_grid(S.size_ub)), dim3(256), 0, c->stream, S.size_ub, S.tag, (const int32_t *)S.id,
                      (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best, (const float4 *)S.g, (const float4 *)S.w,
-                     (const GroupParams *)c->d_groups, (float4 *)c->rg, (float4 *)c->rp, (float4 *)c->rb, S.d_cnt);
+                     (const GroupParams *)c->d_groups, (float4 *)c->rg.get(), (float4 *)c->rp.get(), (float4 *)c->rb.get(), S.d_cnt);
   if (int rc = launch_check(c, "async_gather")) return rc;
   AsyncCounters h;
   if (int rc = async_counters(c, h, true)) return rc;  // the one read-back of an advance (also settles the previous one's appends)
@@ -255,8 +248,8 @@ static int async_advance(mpmhip_ctx *c, int64_t limit) {
   if (n_work) {
     if (int rc = async_compact_if_needed(c, n_work)) return rc;
     if (int rc = async_store_reserve(c, S.size + n_work)) return rc;
-    hipLaunchKernelGGL(k_async_file, dim3(particle_grid(n_work)), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg,
-                       (const float4 *)c->rp, (const float4 *)c->rb, (const uint8_t *)S.d_tbl, 0, A.nb[0], A.nb[1], A.nb[2], S.cap,
+    hipLaunchKernelGGL(k_async_file, dim3(particle_grid(n_work)), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(),
+                       (const float4 *)c->rp.get(), (const float4 *)c->rb.get(), (const uint8_t *)S.d_tbl, 0, A.nb[0], A.nb[1], A.nb[2], S.cap,
                        S.g, S.w, S.tag, S.id, S.d_cnt);
     S.size_ub = S.size + n_work;  // (the exact size comes with the next read-back)
   }
@@ -345,28 +338,22 @@ int64_t mpmhip_async_download_pools(mpmhip_ctx *c, int64_t capacity, float *rows
   if (!A.resident) return fail(c, MPMHIP_EINVAL, "mpmhip_async_begin first");
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = async_settle(c)) return rc;
-  float *d_rows = nullptr;
-  uint32_t *d_blk = nullptr;
+  DevBuf<float> d_rows;
+  DevBuf<uint32_t> d_blk;
   const size_t m = std::max<size_t>(S.size, 1);
-  HIPCHK(c, dmalloc(&d_rows, m * 27));
-  hipError_t e = dmalloc(&d_blk, m);
-  if (e != hipSuccess) { (void)hipFree(d_rows); return fail(c, MPMHIP_ENOMEM, "async download: %s", hipGetErrorString(e)); }
+  HIPCHK(c, d_rows.alloc(m * 27));
+  HIPCHK(c, d_blk.alloc(m));
   hipLaunchKernelGGL(k_async_export, dim3(as_grid(S.size)), dim3(256), 0, c->stream, S.size, (const uint32_t *)S.tag, (const float4 *)S.g,
                      (const float4 *)S.w, d_rows, d_blk, S.d_cnt);
   AsyncCounters h;
-  int rc = launch_check(c, "async_export");
-  if (!rc) rc = async_counters(c, h, true);
-  int64_t n = rc ? rc : (int64_t)h.n_work;
-  if (!rc && rows && block) {
-    if (capacity < n) { rc = fail(c, MPMHIP_ECAPACITY, "async download: %lld containers, room for %lld", (long long)n, (long long)capacity); n = rc; }
-    else if (n) {
-      e = hipMemcpy(rows, d_rows, sizeof(float) * 27 * (size_t)n, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(block, d_blk, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) n = fail(c, MPMHIP_EHIP, "async download: %s", hipGetErrorString(e));
-      c->host_particle_bytes += (int64_t)n * 27 * 4;
-    }
-  }
-  (void)hipFree(d_rows); (void)hipFree(d_blk);
+  if (int rc = launch_check(c, "async_export")) return rc;
+  if (int rc = async_counters(c, h, true)) return rc;
+  const int64_t n = (int64_t)h.n_work;
+  if (!rows || !block || !n) return n;
+  if (capacity < n) return fail(c, MPMHIP_ECAPACITY, "async download: %lld containers, room for %lld", (long long)n, (long long)capacity);
+  HIPCHK(c, hipMemcpy(rows, d_rows, sizeof(float) * 27 * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(block, d_blk, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  c->host_particle_bytes += n * 27 * 4;
   return n;
 }
 
@@ -389,7 +376,7 @@ int mpmhip_async_load_pools(mpmhip_ctx *c) {
   std::fill(A.tbl.begin(), A.tbl.end(), (uint8_t)AT_POOL1);
   if (int rc = async_upload_tbl(c)) return rc;
   hipLaunchKernelGGL(k_async_load, dim3(as_grid(S.size)), dim3(256), 0, c->stream, S.size, (const uint32_t *)S.tag, (const float4 *)S.g,
-                     (const float4 *)S.w, (const GroupParams *)c->d_groups, (float4 *)c->rg, (float4 *)c->rp, (float4 *)c->rb,
+                     (const float4 *)S.w, (const GroupParams *)c->d_groups, (float4 *)c->rg.get(), (float4 *)c->rp.get(), (float4 *)c->rb.get(),
                      A.d_blk_of, S.d_cnt);
   if (int rc = launch_check(c, "async_load")) return rc;
   AsyncCounters h;

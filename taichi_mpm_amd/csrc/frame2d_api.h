@@ -292,9 +292,9 @@ static int snap2d_load(mpmhip2d_ctx *m, const void *src, size_t size) {
     HIPCHK2D(m, get_dev(m->d_rb, sizeof(mpm2d::Rigid2) * (size_t)h.n_bodies));
     memcpy(&m->joints, arr, sizeof m->joints); arr += sizeof m->joints;
     if (m->joints.n < 0 || m->joints.n > mpm2d::MAX_JOINTS2) { m->joints.n = 0; return fail2d(m, MPMHIP_EINVAL, "snapshot joint table inconsistent"); }
-    (void)hipFree(m->d_smp_rank); m->d_smp_rank = nullptr; m->n_ranked = 0;
+    m->d_smp_rank.reset(); m->n_ranked = 0;
     if (h.n_ranked) {
-      HIPCHK2D(m, dmalloc(&m->d_smp_rank, (size_t)m->h_smp.size() + m->h_smp.size() / 4 + 1024));
+      HIPCHK2D(m, m->d_smp_rank.alloc((size_t)m->h_smp.size() + m->h_smp.size() / 4 + 1024));
       HIPCHK2D(m, get_dev(m->d_smp_rank, sizeof(uint32_t) * h.n_ranked));
       m->n_ranked = h.n_ranked;
     }

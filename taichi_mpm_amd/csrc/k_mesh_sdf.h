@@ -271,24 +271,18 @@ __global__ __launch_bounds__(256) void k_msdf_distance(MeshLattice L, float band
 // ------------------------------------------------------------------------------------------------ host side: the work buffers
 // One voxelisation's device buffers; a ctx keeps one per key frame and every call reuses what is large enough.
 struct MeshSdfWork {
-  float *d_tri = nullptr;    // [n_tri][3][3], vertices in lexicographic order behind k_msdf_prep
-  float4 *d_rec = nullptr;   // [n_tri][4]
+  DevBuf<float> d_tri;    // [n_tri][3][3], vertices in lexicographic order behind k_msdf_prep
+  DevBuf<float4> d_rec;   // [n_tri][4]
   size_t tri_cap = 0;
-  uint32_t *d_cnt2 = nullptr, *d_off2 = nullptr, *d_cnt3 = nullptr, *d_off3 = nullptr;
+  DevBuf<uint32_t> d_cnt2, d_off2, d_cnt3, d_off3;
   size_t tiles2_cap = 0, tiles3_cap = 0;
-  uint32_t *d_list2 = nullptr, *d_list3 = nullptr;
+  DevBuf<uint32_t> d_list2, d_list3;
   size_t list2_cap = 0, list3_cap = 0;
-  uint32_t *d_sign = nullptr;  // [res0][res1][words]
+  DevBuf<uint32_t> d_sign;  // [res0][res1][words]
   size_t sign_cap = 0;
-  uint32_t *d_flags = nullptr;  // MSDF_F_*
+  DevBuf<uint32_t> d_flags;  // MSDF_F_*
   uint32_t n_tri = 0;
   bool lists3 = false;  // this voxelisation has 3D lists (else every tile reads every record)
 };
-
-inline void msdf_free(MeshSdfWork &W) {
-  (void)hipFree(W.d_tri); (void)hipFree(W.d_rec); (void)hipFree(W.d_cnt2); (void)hipFree(W.d_off2); (void)hipFree(W.d_cnt3);
-  (void)hipFree(W.d_off3); (void)hipFree(W.d_list2); (void)hipFree(W.d_list3); (void)hipFree(W.d_sign); (void)hipFree(W.d_flags);
-  W = MeshSdfWork();
-}
 
 }  // namespace mpm

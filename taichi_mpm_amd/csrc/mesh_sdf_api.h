@@ -3,18 +3,16 @@
 // lists, column parity) and, once msdf_verdict has read the flags, msdf_distance into the destination array.
 #pragma once
 
-extern "C++" {  // (mpmhip.hip includes this inside its extern "C" block; the helpers below include a template)
+extern "C++" {  // (mpmhip.hip includes this inside its extern "C" block)
 namespace {
 
 constexpr uint32_t MSDF_MAX_TRI = 1u << 26;
 constexpr unsigned long long MSDF_MAX_LIST3 = 1ull << 27;  // entries (512 MB); above it the tiles read every record instead
 
-template <typename T>
-int msdf_reserve(mpmhip_ctx *c, T **p, size_t &cap, size_t count) {
-  if (count <= cap && *p) return MPMHIP_OK;
-  (void)hipFree(*p);
-  *p = nullptr; cap = 0;
-  if (dmalloc(p, count) != hipSuccess) return fail(c, MPMHIP_ENOMEM, "mesh voxeliser: device allocation of %zu bytes failed", count * sizeof(T));
+int msdf_reserve(mpmhip_ctx *c, DevBuf<uint32_t> &p, size_t &cap, size_t count) {
+  if (count <= cap && p) return MPMHIP_OK;
+  cap = 0;
+  if (p.alloc(count) != hipSuccess) return fail(c, MPMHIP_ENOMEM, "mesh voxeliser: device allocation of %zu bytes failed", count * sizeof(uint32_t));
   cap = count;
   return MPMHIP_OK;
 }
@@ -47,27 +45,26 @@ int msdf_stage(mpmhip_ctx *c, MeshSdfWork &W, hipStream_t stream, const MeshLatt
   const size_t cols = (size_t)L.res[0] * L.res[1];
   int rc;
   if (n_tri > W.tri_cap || !W.d_tri) {
-    (void)hipFree(W.d_tri); (void)hipFree(W.d_rec);
-    W.d_tri = nullptr; W.d_rec = nullptr; W.tri_cap = 0;
-    if (dmalloc(&W.d_tri, (size_t)n_tri * 9) != hipSuccess || dmalloc(&W.d_rec, (size_t)n_tri * 4) != hipSuccess)
+    W.tri_cap = 0;
+    if (W.d_tri.alloc((size_t)n_tri * 9) != hipSuccess || W.d_rec.alloc((size_t)n_tri * 4) != hipSuccess)
       return fail(c, MPMHIP_ENOMEM, "mesh voxeliser: device allocation for %u triangles failed", n_tri);
     W.tri_cap = n_tri;
   }
   if (tiles2 > W.tiles2_cap) {
     size_t cap = W.tiles2_cap;
-    if ((rc = msdf_reserve(c, &W.d_cnt2, cap, tiles2))) return rc;
-    if ((rc = msdf_reserve(c, &W.d_off2, W.tiles2_cap, tiles2 + 1))) return rc;
+    if ((rc = msdf_reserve(c, W.d_cnt2, cap, tiles2))) return rc;
+    if ((rc = msdf_reserve(c, W.d_off2, W.tiles2_cap, tiles2 + 1))) return rc;
     W.tiles2_cap = tiles2;
   }
   W.lists3 = std::isfinite(band);
   if (W.lists3 && tiles3 > W.tiles3_cap) {
     size_t cap = W.tiles3_cap;
-    if ((rc = msdf_reserve(c, &W.d_cnt3, cap, tiles3))) return rc;
-    if ((rc = msdf_reserve(c, &W.d_off3, W.tiles3_cap, tiles3 + 1))) return rc;
+    if ((rc = msdf_reserve(c, W.d_cnt3, cap, tiles3))) return rc;
+    if ((rc = msdf_reserve(c, W.d_off3, W.tiles3_cap, tiles3 + 1))) return rc;
     W.tiles3_cap = tiles3;
   }
-  if ((rc = msdf_reserve(c, &W.d_sign, W.sign_cap, cols * (size_t)L.words))) return rc;
-  if (!W.d_flags) HIPCHK(c, dmalloc(&W.d_flags, (size_t)MSDF_F_WORDS));
+  if ((rc = msdf_reserve(c, W.d_sign, W.sign_cap, cols * (size_t)L.words))) return rc;
+  if (!W.d_flags) HIPCHK(c, W.d_flags.alloc((size_t)MSDF_F_WORDS));
   W.n_tri = n_tri;
   HIPCHK(c, hipMemcpyAsync(W.d_tri, tri, sizeof(float) * 9 * n_tri, hipMemcpyHostToDevice, stream));
   HIPCHK(c, hipMemsetAsync(W.d_flags, 0, sizeof(uint32_t) * MSDF_F_WORDS, stream));
@@ -87,8 +84,8 @@ int msdf_stage(mpmhip_ctx *c, MeshSdfWork &W, hipStream_t stream, const MeshLatt
   if (fl[MSDF_F_TOTAL2] >= 0x80000000u) return fail(c, MPMHIP_EINVAL, "mesh voxeliser: the column lists would hold more than 2^31 entries");
   const unsigned long long total3 = ((unsigned long long)fl[MSDF_F_TOTAL3_HI] << 32) | fl[MSDF_F_TOTAL3_LO];
   if (W.lists3 && total3 > MSDF_MAX_LIST3) W.lists3 = false;  // a superset of every list is as good: all records
-  if ((rc = msdf_reserve(c, &W.d_list2, W.list2_cap, (size_t)fl[MSDF_F_TOTAL2] + 1))) return rc;
-  if (W.lists3 && (rc = msdf_reserve(c, &W.d_list3, W.list3_cap, (size_t)total3 + 1))) return rc;
+  if ((rc = msdf_reserve(c, W.d_list2, W.list2_cap, (size_t)fl[MSDF_F_TOTAL2] + 1))) return rc;
+  if (W.lists3 && (rc = msdf_reserve(c, W.d_list3, W.list3_cap, (size_t)total3 + 1))) return rc;
   hipLaunchKernelGGL(k_msdf_bin<true>, tgrid, dim3(256), 0, stream, L, band, n_tri, (const float *)W.d_tri, (const float4 *)W.d_rec, W.d_cnt2,
                      (const uint32_t *)W.d_off2, W.d_list2, W.lists3 ? W.d_cnt3 : nullptr, (const uint32_t *)W.d_off3, W.d_list3);
   hipLaunchKernelGGL(k_msdf_parity, dim3((uint32_t)tiles2), dim3(64), sizeof(uint32_t) * 64 * (size_t)L.words, stream, L, (const float *)W.d_tri,
@@ -127,18 +124,13 @@ int mpmhip_mesh_to_sdf(int32_t device, const mpmhip_sdf_desc *d, int32_t n_tri, 
   HIPCHK(nullptr, hipSetDevice(device));
   const size_t count = (size_t)L.res[0] * L.res[1] * L.res[2];
   MeshSdfWork W;
-  float *d_phi = nullptr;
-  int rc = msdf_stage(nullptr, W, nullptr, L, (uint32_t)n_tri, tri, band);
-  if (!rc) rc = msdf_verdict(nullptr, W, nullptr, "mesh_to_sdf", "");
-  if (!rc && dmalloc(&d_phi, count) != hipSuccess) rc = fail(nullptr, MPMHIP_ENOMEM, "mesh_to_sdf: device allocation of %zu bytes failed", count * 4);
-  if (!rc) rc = msdf_distance(nullptr, W, nullptr, L, band, d_phi);
-  if (!rc) {
-    const hipError_t e = hipMemcpy(phi_out, d_phi, sizeof(float) * count, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(nullptr, MPMHIP_EHIP, "mesh_to_sdf: %s", hipGetErrorString(e));
-  }
-  (void)hipFree(d_phi);
-  msdf_free(W);
-  return rc;
+  DevBuf<float> d_phi;
+  if (int rc = msdf_stage(nullptr, W, nullptr, L, (uint32_t)n_tri, tri, band)) return rc;
+  if (int rc = msdf_verdict(nullptr, W, nullptr, "mesh_to_sdf", "")) return rc;
+  if (d_phi.alloc(count) != hipSuccess) return fail(nullptr, MPMHIP_ENOMEM, "mesh_to_sdf: device allocation of %zu bytes failed", count * 4);
+  if (int rc = msdf_distance(nullptr, W, nullptr, L, band, d_phi)) return rc;
+  HIPCHK(nullptr, hipMemcpy(phi_out, d_phi, sizeof(float) * count, hipMemcpyDeviceToHost));
+  return MPMHIP_OK;
 }
 
 // triangles -> the ctx's own sampled level set: mpmhip_set_levelset_sdf without the host arrays (include/mpmhip.h)

@@ -3,6 +3,8 @@
 //   mpm_common.h (records, parameter blocks, Morton keys)   mpm_math.h (3x3 math, constitutive models, level set)
 //   k_sort.h  k_p2g.h  k_grid.h  k_g2p.h  k_tiling.h  k_particles.h  k_debug.h
 //   k_bgeo.h (.bgeo frame rows)   k_mpm88.h (the 2D dense-grid demo, its own small object)
+// host_mem.h: DevBuf / PinnedBuf, the owners of every device and pinned array of the objects below (a new array needs a field and
+// its allocation, nothing else); what a kernel takes by value keeps raw pointers into them.
 //
 // One substep (reference: MPM<3>::substep, src/mpm.cpp:452-575):
 //
@@ -71,6 +73,7 @@
 #include <rccl/rccl.h>  // types and prototypes only (tiled_api.h): librccl is dlopen'ed, this library does not link it
 
 
+#include "host_mem.h"
 #include "mpm_common.h"
 #include "k_sort.h"
 #include "k_particles.h"
@@ -128,25 +131,25 @@ struct mpmhip_ctx {
   int64_t cap = 0;
   int64_t n_slots = 0;  // slots in use (live + deleted)
   int32_t next_pid = 0;
-  RecG *rg = nullptr, *rg2 = nullptr;
-  RecP *rp = nullptr, *rp2 = nullptr;
-  float *rb = nullptr, *rb2 = nullptr;
-  uint32_t *key = nullptr, *rank = nullptr, *perm = nullptr;
+  DevBuf<RecG> rg, rg2;
+  DevBuf<RecP> rp, rp2;
+  DevBuf<float> rb, rb2;
+  DevBuf<uint32_t> key, rank, perm;
   // blocks
   uint32_t NB = 0;
-  uint8_t *blk_flag = nullptr;
-  uint32_t *bits = nullptr, *wprefix = nullptr, *act_blk = nullptr, *act_start = nullptr;
-  uint32_t *cell_cnt = nullptr, *cell_start = nullptr, *fat_slot = nullptr;
+  DevBuf<uint8_t> blk_flag;
+  DevBuf<uint32_t> bits, wprefix, act_blk, act_start;
+  DevBuf<uint32_t> cell_cnt, cell_start, fat_slot;
   bool sort_keyed = false;
   bool deterministic = false;  // mpmhip_config.deterministic (env MPMHIP_DETERMINISTIC): in-cell order by creation id behind every sort (do_sort)
-  uint32_t *cellcnt_key = nullptr;  // [64 NB] cell counters indexed by KEY (Morton block << 6 | cell): the two-launch front of the sort (do_sort); nullptr on grids beyond 2^21 blocks
-  uint32_t *nbr = nullptr, *own_list = nullptr;  // k_cell_table -> k_grid: 32-word neighbour row per active block, list of owned (block, candidate) pairs
+  DevBuf<uint32_t> cellcnt_key;  // [64 NB] cell counters indexed by KEY (Morton block << 6 | cell): the two-launch front of the sort (do_sort); nullptr on grids beyond 2^21 blocks
+  DevBuf<uint32_t> nbr, own_list;  // k_cell_table -> k_grid: 32-word neighbour row per active block, list of owned (block, candidate) pairs
   FillStats *d_stats = nullptr;  // device address of the pinned page's statistics words (h_pinned + FILL_STATS_WORD): k_cell_table stores there
   int grid_walk = -1;            // walk of the substep's grid pass (k_grid.h): 2 owner list, 0 per block / per (block, candidate) as until round 4,
                                  // -1 by size and tiling (env MPMHIP_GRID_WALK: A/B)
   bool list_valid = false;       // the last sort built neighbour rows + owner list (do_sort -> do_grid)
   int grid_wgs = 0;              // workgroups of the grid pass; 0: from the last sort's owner count (env MPMHIP_GRID_WGS)
-  unsigned long long *scan_slots = nullptr;  // [256] k_block_table + [ct_grid] k_cell_table: {epoch, chunk sum}
+  DevBuf<unsigned long long> scan_slots;  // [256] k_block_table + [ct_grid] k_cell_table: {epoch, chunk sum}
   uint32_t list_clear_epoch = 0;  // sort epoch at which the scan words of the list form of k_cell_table were last zeroed (do_sort)
   uint32_t sort_epoch = 0, bt_slots = 0, ct_slots = 0;  // scan_slots: [bt_slots] k_block_table | [ct_slots] k_cell_table_plain | [ct_slots] k_cell_table
   uint32_t scan_grid = 256;  // workgroups of the single-pass scan kernels: three eighths of what the device keeps resident (the lowest
@@ -154,14 +157,14 @@ struct mpmhip_ctx {
   std::map<const void *, uint32_t> scan_limits;  // kernel -> three eighths of its resident workgroups
   int scan_grid_env = 0;
   uint32_t rank_wgs_cap = 4096u;  // workgroups of the rank role (k_rank / k_sort_front): MPMHIP_RANK_WGS (tuning)
-  float4 *tiles = nullptr, *gridv = nullptr, *dense = nullptr;
-  Counters *cnt = nullptr;
+  DevBuf<float4> tiles, gridv, dense;
+  DevBuf<Counters> cnt;
   std::vector<GroupParams> groups;
-  GroupParams *d_groups = nullptr;
+  DevBuf<GroupParams> d_groups;
   int groups_cap = G2P_LDS_GROUPS;  // k_g2p mirrors the whole table in LDS
   bool sorted = false;        // perm / cell_start describe the current positions
   bool keys_valid = false;    // key[] + block flags describe the current positions (set by k_g2p)
-  uint32_t *pidc = nullptr;   // creation id per slot beside key[] (Params::pidc points here while the deterministic mode is on)
+  DevBuf<uint32_t> pidc;      // creation id per slot beside key[] (Params::pidc points here while the deterministic mode is on)
   int cell_order_wgs = 24;    // env MPMHIP_CELL_ORDER_WGS: workgroups per CU of k_cell_order_blocks' launch
   int cell_order_form = 1;    // env MPMHIP_CELL_ORDER: 1 k_cell_order_blocks (a wave per block through LDS), 0 k_cell_order (a lane per cell)
   bool pidc_valid = false;    // ... and was written together with the current key[] (every key writer does while Params::pidc is set)
@@ -174,7 +177,7 @@ struct mpmhip_ctx {
   int n_cus = 256;            // compute units of the device
   int g2p_packed = -1;        // k_g2p_packed instead of k_g2p: -1 by size (from 2 M slots on; no rigid bodies, no tiling), 0 never, 1 wherever it
                               // applies (env MPMHIP_G2P_PACKED)
-  uint32_t *chunk_blk = nullptr;  // per 256 positions of the sorted index: the block holding the first (k_cell_table -> k_g2p_packed)
+  DevBuf<uint32_t> chunk_blk;  // per 256 positions of the sorted index: the block holding the first (k_cell_table -> k_g2p_packed)
   int rigid_wgs = 2048;       // workgroups of k_p2g_rigid (one per wave slot of the device), twice those of k_g2p_rigid (env MPMHIP_RIGID_WGS: tuning)
   uint32_t rank_runs_mul = 3; // k_rank takes its LDS-hash path when runs * this > slots (env MPMHIP_RANK_RUNS_MUL: tuning)
   int ct_blocks = 0;          // blocks per chunk of k_cell_table: 0 by size, 16, 32, 64 (env MPMHIP_CT_BLOCKS: tuning)
@@ -194,53 +197,53 @@ struct mpmhip_ctx {
   Ev *cur_ev = nullptr;  // events of the substep between substep_begin and substep_end
   // tiling
   LevelSetDev LS;
-  LevelSetDev *d_LS = nullptr;  // device copy for k_g2p (k_grid takes it by value)
+  DevBuf<LevelSetDev> d_LS;  // device copy for k_g2p (k_grid takes it by value)
   // sampled level set (mpmhip_set_levelset_sdf): this ctx's device copies of the key frames, [sdf_count] floats each; they live until
   // the lattice changes, shapes replace the set, or the ctx goes (LS.sdf points at them while the set is installed)
-  float *d_sdf[2] = {nullptr, nullptr};
+  DevBuf<float> d_sdf[2];
   size_t sdf_count = 0;
   MeshSdfWork mesh_work[2];  // mpmhip_set_levelset_mesh: the voxeliser's buffers per key frame, kept between calls
   int particle_collision_cfg = 0;  // the config's particle_collision.  P.particle_collision is 0 while a sampled set is installed:
                                    // the G2P kernels then leave the push to k_sdf_collide (do_sdf_collide)
   Tiling T;
-  DevBox *d_boxes = nullptr;
-  uint32_t *d_counts = nullptr;
-  int *d_bounds = nullptr;
-  uint32_t *h_pinned = nullptr;  // 64 KiB of pinned host memory for small readbacks (counters, migration table)
+  DevBuf<DevBox> d_boxes;
+  DevBuf<uint32_t> d_counts;
+  DevBuf<int> d_bounds;
+  PinnedBuf<uint32_t> h_pinned;  // 64 KiB of pinned host memory for small readbacks (counters, migration table)
   static constexpr int FILL_STATS_WORD = 16368;  // word offset of the block-fill statistics in that page (do_sort, g2p_is_packed)
-  double *d_energy = nullptr;
-  double *d_energy_parts = nullptr;  // deterministic mode: [8 energy_parts_cap + POT_WAVES] the partial sums of calculate_energy (energy_end_det)
+  DevBuf<double> d_energy;
+  DevBuf<double> d_energy_parts;  // deterministic mode: [8 energy_parts_cap + POT_WAVES] the partial sums of calculate_energy (energy_end_det)
   size_t energy_parts_cap = 0;
   int counts_cap = 0;
   bool compact_requested = false;
   bool in_substep = false;
   struct AsyncState : AsyncSched {  // the block scheduler (async_sched.h) + what this ctx keeps on the device for it
     bool enabled = false, limits_valid = false;
-    uint32_t *d_tab = nullptr, *d_blk_of = nullptr;
-    int32_t *d_blk_limits = nullptr, *d_particle_limits = nullptr;
+    DevBuf<uint32_t> d_tab, d_blk_of;
+    DevBuf<int32_t> d_blk_limits, d_particle_limits;
     int64_t blk_of_cap = 0;
     // the resident stepper (async_api.h): the device store of pool / backup containers
     bool resident = false, pending_counters = false;
     bool records_are_view = false;  // the ctx's records are copies of the pools (mpmhip_async_load_pools), not new particles
     double prof_ms[6] = {0, 0, 0, 0, 0, 0};
-    uint32_t *h_tab = nullptr;
+    PinnedBuf<uint32_t> h_tab;
     size_t h_tab_cap = 0;
     bool profile_sync = false;
     struct Store {
       uint32_t cap = 0, size = 0, live = 0;   // containers allocated / in use incl. freed ones / not freed (as of the last read-back)
       uint32_t size_ub = 0;                   // upper bound of the size now (launch bound: tags behind the size say FREE)
-      float4 *g = nullptr, *w = nullptr, *g2 = nullptr, *w2 = nullptr;
-      uint32_t *tag = nullptr, *tag2 = nullptr;
-      int32_t *id = nullptr, *id2 = nullptr;
-      unsigned long long *best = nullptr, *d_scan = nullptr;
+      DevBuf<float4> g, w, g2, w2;
+      DevBuf<uint32_t> tag, tag2;
+      DevBuf<int32_t> id, id2;
+      DevBuf<unsigned long long> best, d_scan;
       int64_t best_cap = 0;
       uint32_t scan_cap = 0, scan_epoch = 0;
-      uint8_t *d_tbl = nullptr;
-      uint8_t *h_tbl_pin = nullptr;  // four pinned images of the action table (async_upload_tbl)
+      DevBuf<uint8_t> d_tbl;
+      PinnedBuf<uint8_t> h_tbl_pin;  // four pinned images of the action table (async_upload_tbl)
       size_t pin_cap = 0;
       uint32_t pin_next = 0;
-      uint32_t *d_rank = nullptr;
-      AsyncCounters *d_cnt = nullptr;
+      DevBuf<uint32_t> d_rank;
+      DevBuf<AsyncCounters> d_cnt;
       int64_t compactions = 0;
     } store;
   } async;
@@ -255,36 +258,38 @@ struct mpmhip_ctx {
   struct RigidState {
     bool enabled = false;
     std::vector<HostRigid> bodies;
-    RigidBodyDev *d_rb = nullptr;
-    RigidSample *d_smp = nullptr;
-    float *d_elems = nullptr;
+    DevBuf<RigidBodyDev> d_rb;
+    DevBuf<RigidSample> d_smp;
+    DevBuf<float> d_elems;
     uint32_t n_smp = 0;
     std::vector<RigidSample> h_smp;
     std::vector<int32_t> h_smp_id;  // creation id of every boundary particle (they share the material particles' counter)
     std::vector<float> h_elems;
-    CdfDev cdf{};
-    BndRec *d_bnd = nullptr;
-    uint8_t *d_blk_rigid = nullptr;
+    CdfDev cdf{};  // what the kernels take by value: slot / page_key / mind / tags / rpage point into the five arrays below (rigid_enable)
+    DevBuf<uint32_t> cdf_slot, cdf_page_key, cdf_tags, cdf_rpage;
+    DevBuf<unsigned long long> cdf_mind;
+    DevBuf<BndRec> d_bnd;
+    DevBuf<uint8_t> d_blk_rigid;
     hipStream_t side = nullptr;          // the colour-aware transfer kernels run here, next to the plain ones on the ctx stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int concurrent = 7;                  // which pairs run side by side: 1 P2G, 2 G2P, 4 rasterisation | sort (env MPMHIP_RIGID_CONCURRENT; 0: one stream)
-    uint32_t *d_rigid_list = nullptr;  // [max_blocks + 1] the flagged blocks as a list; its length is d_counters[CDF_POOLS + 1]
-    float *d_imp_rows = nullptr;       // deterministic mode only: [imp_rows_cap][IMP_ROW] per flagged block its impulse sums (k_rigid.h)
+    DevBuf<uint32_t> d_rigid_list;  // [max_blocks + 1] the flagged blocks as a list; its length is d_counters[CDF_POOLS + 1]
+    DevBuf<float> d_imp_rows;       // deterministic mode only: [imp_rows_cap][IMP_ROW] per flagged block its impulse sums (k_rigid.h)
     size_t imp_rows_cap = 0;
-    uint32_t *d_counters = nullptr;  // [0, CDF_POOLS) pages handed out per sub-pool, [CDF_POOLS] cutting_counter
+    DevBuf<uint32_t> d_counters;  // [0, CDF_POOLS) pages handed out per sub-pool, [CDF_POOLS] cutting_counter
     uint32_t max_pages = 0;
     uint32_t gather_epoch = 0;  // stamps the boundary records of the particles the last gather_cdf visited
     size_t rpage_words = 0;
     float penalty = 0.0f, pushing_force = 20000.0f;  // MPM::initialize defaults, src/mpm.cpp:35,40
     bool ls_collision = false;       // config key rigid_body_levelset_collision (src/mpm.cpp:535-538)
-    uint32_t *d_smp_rank = nullptr;  // position of every boundary particle in the reference's sorted particle list (among the boundary particles)
+    DevBuf<uint32_t> d_smp_rank;  // position of every boundary particle in the reference's sorted particle list (among the boundary particles)
     uint32_t n_ranked = 0, ls_cap = 0;
-    unsigned long long *d_ls_keys[2] = {nullptr, nullptr};
-    uint32_t *d_ls_vals[2] = {nullptr, nullptr};
-    void *d_ls_tmp = nullptr;
+    DevBuf<unsigned long long> d_ls_keys[2];
+    DevBuf<uint32_t> d_ls_vals[2];
+    DevBuf<uint8_t> d_ls_tmp;
     size_t ls_tmp_bytes = 0;
     std::vector<JointDev> joints;    // MPM::articulations, in the order they were added
-    JointDev *d_joints = nullptr;
+    DevBuf<JointDev> d_joints;
     int joint_iterations = 100;      // 'articulation_iterations' (src/mpm.h:279-280)
   } rigid;
   bool overlap = false;        // mpmhip_set_overlap: split tiled substeps into boundary / interior work
@@ -315,16 +320,18 @@ struct mpmhip_ctx {
     std::vector<int> halo_peers, all_ranks;
     uint64_t total = 0, halo_cap = 0, inbox_cap = 0;
     size_t arena_bytes = 0, table_bytes = 0, recv_bytes = 0, mig_send_cap = 0;
-    char *arena = nullptr;
+    char *arena = nullptr;  // raw on purpose: one of two allocation calls, mapped by other processes; released in tn_free
     uint8_t handle[MPMHIP_IPC_HANDLE_BYTES] = {};  // the arena's IPC handle, made once per arena (mpmhip_tiled_ipc_handle)
     bool handle_valid = false;
-    uint32_t *flags = nullptr, *table[2] = {nullptr, nullptr}, *row = nullptr, *d_done = nullptr;
-    float4 *send = nullptr, *recv[2] = {nullptr, nullptr}, *inbox = nullptr, *mig_send = nullptr;
-    DevBox *d_boxes[2] = {nullptr, nullptr};
-    int *d_halo_idx = nullptr, *d_all_idx = nullptr;
+    uint32_t *flags = nullptr, *table[2] = {nullptr, nullptr};             // views into the arena
+    float4 *recv[2] = {nullptr, nullptr}, *inbox = nullptr;  // ditto
+    DevBuf<uint32_t> row, d_done;
+    DevBuf<float4> send, mig_send;
+    DevBuf<DevBox> d_boxes[2];
+    DevBuf<int> d_halo_idx, d_all_idx;
     std::vector<Peer> peers;
     uint32_t epoch = 0, mig_epoch = 0, red_epoch = 0;
-    double *d_red = nullptr;  // this rank's row of a reduction (+ room for the all-reduced row)
+    DevBuf<double> d_red;  // this rank's row of a reduction (+ room for the all-reduced row)
     unsigned long long timeout_ticks = 2000000000ull;  // of the 100 MHz wall clock
     void *comm = nullptr;  // ncclComm_t
     int comm_rank = 0, comm_world = 1;
@@ -351,23 +358,6 @@ static int fail(mpmhip_ctx *c, int code, const char *fmt, ...) {
     hipError_t e_ = (call);                                                                  \
     if (e_ != hipSuccess) return fail((c), MPMHIP_EHIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
-
-template <typename T>
-static hipError_t dmalloc(T **p, size_t count) { return hipMalloc((void **)p, count * sizeof(T)); }
-
-// new array of `count` elements holding the first `keep` elements of *p (the rest zero-filled when `zero`); *p is freed
-template <typename T>
-static hipError_t regrow(T **p, size_t keep, size_t count, bool zero) {
-  T *q = nullptr;
-  hipError_t e = hipMalloc((void **)&q, count * sizeof(T));
-  if (e != hipSuccess) return e;
-  if (zero) e = hipMemset(q, 0, count * sizeof(T));
-  if (e == hipSuccess && keep && *p) e = hipMemcpy(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice);
-  if (e != hipSuccess) { (void)hipFree(q); return e; }
-  (void)hipFree(*p);
-  *p = q;
-  return hipSuccess;
-}
 
 static int particle_grid(int64_t n) {
   int64_t b = (n + 255) / 256;
@@ -445,14 +435,12 @@ static int bgeo_order(mpmhip_ctx *c, std::vector<uint32_t> &order, std::vector<i
   order.clear();
   const size_t ns = (size_t)c->n_slots;
   if (!ns) return MPMHIP_OK;
-  int32_t *d_ids = nullptr;
-  HIPCHK(c, dmalloc(&d_ids, ns));
+  DevBuf<int32_t> d_ids;
+  HIPCHK(c, d_ids.alloc(ns));
   hipLaunchKernelGGL(k_bgeo_ids, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const RecG *)c->rg, d_ids);
   std::vector<int32_t> ids(ns);
-  hipError_t e = hipMemcpyAsync(ids.data(), d_ids, ns * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_ids);
-  HIPCHK(c, e);
+  HIPCHK(c, hipMemcpyAsync(ids.data(), d_ids, ns * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   order.reserve(ns);
   bool ascending = true;
   int32_t last = -1, max_id = -1;
@@ -557,47 +545,47 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
   A(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;
-  A(dmalloc(&c->rg, (size_t)c->cap));
-  A(dmalloc(&c->rp, (size_t)c->cap));
-  A(dmalloc(&c->rb, (size_t)c->cap * BW));
-  A(dmalloc(&c->rg2, (size_t)c->cap));  // k_g2p writes the updated records here, at their sorted positions; the two sets swap
-  A(dmalloc(&c->rp2, (size_t)c->cap));
-  A(dmalloc(&c->rb2, (size_t)c->cap * BW));
-  A(dmalloc(&c->key, (size_t)c->cap));
-  A(dmalloc(&c->pidc, (size_t)c->cap));
-  A(dmalloc(&c->rank, (size_t)c->cap));
-  A(dmalloc(&c->perm, (size_t)c->cap));
-  A(dmalloc(&c->chunk_blk, (size_t)c->cap / 256 + 2));
-  A(dmalloc(&c->bits, (size_t)P.nbw));
-  A(dmalloc(&c->blk_flag, (size_t)P.nbw * 32));
-  A(dmalloc(&c->wprefix, (size_t)P.nbw));
-  A(dmalloc(&c->fat_slot, (size_t)c->NB));
-  A(dmalloc(&c->act_blk, (size_t)mb + 1));
-  A(dmalloc(&c->act_start, (size_t)mb + 2));
-  A(dmalloc(&c->cell_cnt, (size_t)mb * BC));
-  A(dmalloc(&c->cell_start, (size_t)mb * BC + 1));
+  A(c->rg.alloc((size_t)c->cap));
+  A(c->rp.alloc((size_t)c->cap));
+  A(c->rb.alloc((size_t)c->cap * BW));
+  A(c->rg2.alloc((size_t)c->cap));  // k_g2p writes the updated records here, at their sorted positions; the two sets swap
+  A(c->rp2.alloc((size_t)c->cap));
+  A(c->rb2.alloc((size_t)c->cap * BW));
+  A(c->key.alloc((size_t)c->cap));
+  A(c->pidc.alloc((size_t)c->cap));
+  A(c->rank.alloc((size_t)c->cap));
+  A(c->perm.alloc((size_t)c->cap));
+  A(c->chunk_blk.alloc((size_t)c->cap / 256 + 2));
+  A(c->bits.alloc((size_t)P.nbw));
+  A(c->blk_flag.alloc((size_t)P.nbw * 32));
+  A(c->wprefix.alloc((size_t)P.nbw));
+  A(c->fat_slot.alloc((size_t)c->NB));
+  A(c->act_blk.alloc((size_t)mb + 1));
+  A(c->act_start.alloc((size_t)mb + 2));
+  A(c->cell_cnt.alloc((size_t)mb * BC));
+  A(c->cell_start.alloc((size_t)mb * BC + 1));
   // key-indexed cell counters (256 B per block of the WHOLE block space: 67 MB at 128^3, 537 MB at 256^3..508^3): with them the ranks
   // need no block table and share a launch with it (k_sort_front); grids of 2^24 blocks (res > 508) keep the four-launch sort
   const bool sort_v1 = getenv("MPMHIP_SORT_V1") && atoi(getenv("MPMHIP_SORT_V1")) != 0;  // (A/B and tests: the four launches)
   c->sort_keyed = c->NB <= (1u << 21) && !sort_v1;  // (the table itself is allocated behind every other buffer, below)
-  A(dmalloc(&c->nbr, (size_t)mb * 32));
-  A(dmalloc(&c->own_list, (size_t)mb * 8));
+  A(c->nbr.alloc((size_t)mb * 32));
+  A(c->own_list.alloc((size_t)mb * 8));
   c->bt_slots = (P.nbw + 255) / 256;
   c->ct_slots = (uint32_t)(((size_t)mb + 15) / 16 + 1);  // k_cell_table chunks are >= 16 blocks
   const size_t n_slots64 = c->bt_slots + 2 * (size_t)c->ct_slots;
-  A(dmalloc(&c->scan_slots, n_slots64));
-  A(dmalloc(&c->tiles, (size_t)mb * TN));
-  A(dmalloc(&c->gridv, (size_t)mb * 8 * BC));
-  A(dmalloc(&c->cnt, 1));
-  A(dmalloc(&c->d_LS, 1));
-  A(hipHostMalloc((void **)&c->h_pinned, 65536, hipHostMallocDefault));
+  A(c->scan_slots.alloc(n_slots64));
+  A(c->tiles.alloc((size_t)mb * TN));
+  A(c->gridv.alloc((size_t)mb * 8 * BC));
+  A(c->cnt.alloc(1));
+  A(c->d_LS.alloc(1));
+  A(c->h_pinned.alloc(65536 / sizeof(uint32_t)));
   if (e == hipSuccess && c->h_pinned) memset(c->h_pinned, 0, 65536);
   if (e == hipSuccess) {
     void *dp = nullptr;
     A(hipHostGetDevicePointer(&dp, c->h_pinned, 0));
     c->d_stats = reinterpret_cast<FillStats *>(reinterpret_cast<uint32_t *>(dp) + mpmhip_ctx::FILL_STATS_WORD);
   }
-  A(dmalloc(&c->d_groups, (size_t)c->groups_cap));
+  A(c->d_groups.alloc((size_t)c->groups_cap));
   if (e == hipSuccess && c->sort_keyed) {
     // (an optimisation's table, 256 B per block of the whole block space: 67 MB at 128^3, 537 MB from 256^3 to 508^3.  A device that
     // cannot spare it keeps the four-launch sort instead of failing the create — or a later mpmhip_reserve, a tiled arena, the next
@@ -605,9 +593,8 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
     size_t free_b = 0, total_b = 0;
     const size_t table_b = (size_t)c->NB * BC * sizeof(uint32_t);
     const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && table_b <= free_b / 8;
-    if (!room || dmalloc(&c->cellcnt_key, (size_t)c->NB * BC) != hipSuccess) {
+    if (!room || c->cellcnt_key.alloc((size_t)c->NB * BC) != hipSuccess) {
       (void)hipGetLastError();
-      c->cellcnt_key = nullptr;
       c->sort_keyed = false;
     }
   }
@@ -669,23 +656,10 @@ void mpmhip_destroy(mpmhip_ctx *c) {
   if (c->own_stream) hipStreamSynchronize(c->own_stream);
   for (auto &ev : c->ev_pool)
     for (int k = 0; k <= PH_COUNT; k++) hipEventDestroy(ev.e[k]);
-  hipFree(c->rg); hipFree(c->rp); hipFree(c->rb); hipFree(c->rg2); hipFree(c->rp2); hipFree(c->rb2);
-  hipFree(c->key); hipFree(c->pidc); hipFree(c->rank); hipFree(c->perm); hipFree(c->chunk_blk); hipFree(c->blk_flag); hipFree(c->bits); hipFree(c->wprefix);
-  hipFree(c->fat_slot); hipFree(c->act_blk); hipFree(c->act_start); hipFree(c->cell_cnt);
-  hipFree(c->cell_start); hipFree(c->cellcnt_key); hipFree(c->nbr); hipFree(c->own_list); hipFree(c->scan_slots); hipFree(c->tiles); hipFree(c->gridv); hipFree(c->dense);
-  hipFree(c->async.d_tab); hipFree(c->async.d_blk_of); hipFree(c->async.d_blk_limits); hipFree(c->async.d_particle_limits);
-  if (c->async.h_tab) hipHostFree(c->async.h_tab);
-  if (c->async.store.h_tbl_pin) hipHostFree(c->async.store.h_tbl_pin);
-  { auto &S = c->async.store; hipFree(S.g); hipFree(S.w); hipFree(S.g2); hipFree(S.w2); hipFree(S.tag); hipFree(S.tag2); hipFree(S.id);
-    hipFree(S.id2); hipFree(S.best); hipFree(S.d_scan); hipFree(S.d_tbl); hipFree(S.d_rank); hipFree(S.d_cnt); }
-  hipFree(c->cnt); hipFree(c->d_groups); hipFree(c->d_boxes); hipFree(c->d_LS); hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]); msdf_free(c->mesh_work[0]); msdf_free(c->mesh_work[1]); hipFree(c->d_counts); hipFree(c->d_bounds); if (c->h_pinned) hipHostFree(c->h_pinned); hipFree(c->d_energy); hipFree(c->d_energy_parts);
-  { auto &R = c->rigid; hipFree(R.d_rb); hipFree(R.d_smp); hipFree(R.d_elems); hipFree(R.cdf.slot); hipFree(R.cdf.page_key); hipFree(R.cdf.mind);
-    hipFree(R.cdf.tags); hipFree(R.cdf.rpage); hipFree(R.d_bnd); if (R.side) { hipStreamSynchronize(R.side); hipStreamDestroy(R.side); } if (R.ev_fork) hipEventDestroy(R.ev_fork); if (R.ev_join) hipEventDestroy(R.ev_join);
-    hipFree(R.d_blk_rigid); hipFree(R.d_rigid_list); hipFree(R.d_counters); hipFree(R.d_joints); hipFree(R.d_imp_rows);
-    hipFree(R.d_smp_rank); hipFree(R.d_ls_keys[0]); hipFree(R.d_ls_keys[1]); hipFree(R.d_ls_vals[0]); hipFree(R.d_ls_vals[1]); hipFree(R.d_ls_tmp); }
+  { auto &R = c->rigid; if (R.side) { hipStreamSynchronize(R.side); hipStreamDestroy(R.side); } if (R.ev_fork) hipEventDestroy(R.ev_fork); if (R.ev_join) hipEventDestroy(R.ev_join); }
   tn_free(c);
   if (c->own_stream) hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // (the members free their arrays on the device set above)
 }
 
 int mpmhip_set_stream(mpmhip_ctx *c, void *s) {
@@ -712,8 +686,7 @@ int mpmhip_set_dirichlet(mpmhip_ctx *c, int32_t enabled) {
 }
 
 static void sdf_release(mpmhip_ctx *c) {
-  hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]);
-  c->d_sdf[0] = c->d_sdf[1] = nullptr;
+  c->d_sdf[0].reset(); c->d_sdf[1].reset();
   c->sdf_count = 0;
   memset(&c->LS.sdf, 0, sizeof c->LS.sdf);
   c->P.particle_collision = c->particle_collision_cfg;
@@ -783,14 +756,13 @@ int mpmhip_set_levelset_keyframes(mpmhip_ctx *c, float t0, float t1, int32_t n0,
 static int sdf_reserve(mpmhip_ctx *c, const mpmhip_sdf_desc *d, bool two) {
   const size_t count = (size_t)d->res[0] * d->res[1] * d->res[2];
   if (count != c->sdf_count) {
-    hipFree(c->d_sdf[0]); hipFree(c->d_sdf[1]);
-    c->d_sdf[0] = c->d_sdf[1] = nullptr;
+    c->d_sdf[0].reset(); c->d_sdf[1].reset();
     c->sdf_count = 0;
     c->LS.sdf.phi0 = c->LS.sdf.phi1 = nullptr;
-    HIPCHK(c, dmalloc(&c->d_sdf[0], count));
+    HIPCHK(c, c->d_sdf[0].alloc(count));
     c->sdf_count = count;
   }
-  if (two && !c->d_sdf[1]) HIPCHK(c, dmalloc(&c->d_sdf[1], count));
+  if (two && !c->d_sdf[1]) HIPCHK(c, c->d_sdf[1].alloc(count));
   return MPMHIP_OK;
 }
 
@@ -848,12 +820,12 @@ int mpmhip_debug_levelset_sample(mpmhip_ctx *c, int64_t n, const float *pos, flo
                                  int32_t *hit) {
   if (!c || n <= 0 || !pos || !phi || !grad || !dphidt || !hit) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  float *dP, *dO;
-  HIPCHK(c, dmalloc(&dP, 3 * n));
-  if (hipError_t e = dmalloc(&dO, 6 * n); e != hipSuccess) { hipFree(dP); return fail(c, MPMHIP_EHIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
+  DevBuf<float> dP, dO;
+  HIPCHK(c, dP.alloc(3 * n));
+  if (hipError_t e = dO.alloc(6 * n); e != hipSuccess) return fail(c, MPMHIP_EHIP, "hipMalloc failed: %s", hipGetErrorString(e));
   int rc = MPMHIP_OK;
   if (hipMemcpy(dP, pos, sizeof(float) * 3 * n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, MPMHIP_EHIP, "hipMemcpy failed");
-  if (!rc) rc = run_debug(c, k_debug_levelset_sample, c->LS, t, c->P.idx, n, (const float *)dP, dO, dO + n, dO + 4 * n, reinterpret_cast<int32_t *>(dO + 5 * n));
+  if (!rc) rc = run_debug(c, k_debug_levelset_sample, c->LS, t, c->P.idx, n, (const float *)dP, dO.get(), dO + n, dO + 4 * n, reinterpret_cast<int32_t *>(dO + 5 * n));
   if (!rc) {
     hipError_t e = hipMemcpy(phi, dO, sizeof(float) * n, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(grad, dO + n, sizeof(float) * 3 * n, hipMemcpyDeviceToHost);
@@ -861,7 +833,6 @@ int mpmhip_debug_levelset_sample(mpmhip_ctx *c, int64_t n, const float *pos, flo
     if (e == hipSuccess) e = hipMemcpy(hit, dO + 5 * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(c, MPMHIP_EHIP, "hipMemcpy failed: %s", hipGetErrorString(e));
   }
-  hipFree(dP); hipFree(dO);
   return rc;
 }
 
@@ -907,7 +878,7 @@ static int invalidate_keys(mpmhip_ctx *c) {
 // synchronise and read the device counters; reports the sticky capacity error
 static int read_counters(mpmhip_ctx *c, Counters &h) {
   // through the ctx's pinned page: an "async" copy into pageable memory is staged and costs ~50 us more
-  Counters *pin = reinterpret_cast<Counters *>(c->h_pinned);
+  Counters *pin = reinterpret_cast<Counters *>(c->h_pinned.get());
   HIPCHK(c, hipMemcpyAsync(pin, c->cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   h = *pin;
@@ -1239,11 +1210,11 @@ static int do_sort(mpmhip_ctx *c) {
     if (c->cell_order_form == 0) {  // (A/B: one lane per cell over the whole table)
       const int cg = (int)std::min<uint64_t>(8192u, ((uint64_t)P.max_blocks * BC + 255) / 256);
       hipLaunchKernelGGL((compact ? k_cell_order<true> : k_cell_order<false>), dim3(cg), dim3(256), 0, st, P, (const Counters *)c->cnt,
-                         (const uint32_t *)c->cell_start, (const uint32_t *)c->perm, (const float4 *)c->rg, c->rank);
+                         (const uint32_t *)c->cell_start, (const uint32_t *)c->perm, (const float4 *)c->rg.get(), c->rank);
     } else {  // one wave per active block through LDS: 7 workgroups per CU resident (22 KiB each), a few blocks per wave
       const int cg = (int)std::min<uint64_t>((uint64_t)c->n_cus * (uint64_t)c->cell_order_wgs, ((uint64_t)P.max_blocks + 3) / 4);
       hipLaunchKernelGGL((compact ? k_cell_order_blocks<true> : k_cell_order_blocks<false>), dim3(std::max(1, cg)), dim3(256), 0, st, P,
-                         (const Counters *)c->cnt, (const uint32_t *)c->cell_start, (const uint32_t *)c->perm, (const float4 *)c->rg, c->rank);
+                         (const Counters *)c->cnt, (const uint32_t *)c->cell_start, (const uint32_t *)c->perm, (const float4 *)c->rg.get(), c->rank);
     }
     std::swap(c->perm, c->rank);
   }
@@ -1270,8 +1241,8 @@ static int do_sort(mpmhip_ctx *c) {
 // Needs the live count on the host, hence one synchronisation: keep reorder_interval large.
 static int do_reorder(mpmhip_ctx *c) {
   const int pg = particle_grid(c->n_slots * 4);
-  hipLaunchKernelGGL(k_gather_records, dim3(pg), dim3(256), 0, c->stream, c->cnt, c->perm, (const float4 *)c->rg,
-                     (const float4 *)c->rp, (const float4 *)c->rb, (float4 *)c->rg2, (float4 *)c->rp2, (float4 *)c->rb2);
+  hipLaunchKernelGGL(k_gather_records, dim3(pg), dim3(256), 0, c->stream, c->cnt, c->perm, (const float4 *)c->rg.get(),
+                     (const float4 *)c->rp.get(), (const float4 *)c->rb.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(), (float4 *)c->rb2.get());
   hipLaunchKernelGGL(k_identity_perm, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->cnt, c->perm);
   int rc = launch_check(c, "reorder");
   if (rc) return rc;
@@ -1337,21 +1308,23 @@ static int do_p2g(mpmhip_ctx *c, int phase = 0) {
   hipStream_t rs = c->stream;
   if (rigid) { if (int rc = rigid_fork(c, &rs, 1)) return rc; }
   hipLaunchKernelGGL(rigid ? k_p2g<true> : k_p2g<false>, dim3(c->p2g_wgs), dim3(64), 0, c->stream, c->P,
-                     (const float4 *)c->rp, c->cnt, c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, c->T, phase,
+                     (const float4 *)c->rp.get(), c->cnt, c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, c->T, phase,
                      rigid ? (const uint8_t *)c->rigid.d_blk_rigid : (const uint8_t *)nullptr);
   if (rigid) {  // blocks near a body (block_op_rigid), then RigidBody::apply_tmp_velocity (src/transfer.cpp:578-580)
     // (deterministic mode: the all-material form with the impulse rows, summed by do_rigid_apply_tmp)
     auto rk = c->deterministic ? k_p2g_rigid<MAT_ALL | MAT_DET>
                                : one_material(material_mask(c), k_p2g_rigid<MAT_ALL>, [](auto m) { return k_p2g_rigid<m.value>; });
     if (c->deterministic) { if (int rc = rigid_imp_rows(c)) return rc; }
-    hipLaunchKernelGGL(rk, dim3(c->rigid_wgs), dim3(64), 0, rs, c->P, (const float4 *)c->rp, (const float4 *)c->rg, c->cnt,
+    hipLaunchKernelGGL(rk, dim3(c->rigid_wgs), dim3(64), 0, rs, c->P, (const float4 *)c->rp.get(), (const float4 *)c->rg.get(), c->cnt,
                        c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, rigid_xfer(c));
     if (int rc = rigid_join(c, rs)) return rc;
     if (int rc = do_rigid_apply_tmp(c)) return rc;
   }
   return launch_check(c, "p2g");
 }
-static int do_grid(mpmhip_ctx *c, int mode, int phase = 0) {
+// dense: what the kernels' `dense` argument points at; nullptr: the ctx's staging array of the dense views (modes 1-3; unused in mode 0)
+static int do_grid(mpmhip_ctx *c, int mode, int phase = 0, float4 *dense = nullptr) {
+  if (!dense) dense = c->dense;
   c->P.t = c->t;  // this->current_t of the substep in flight (src/mpm.cpp:532-533)
   c->LS.dirichlet = c->dirichlet ? 1 : 0;
   // mode 0 (the substep's pass) and mode 4 (energy) walk the owner list when the last sort built one (do_sort: small problems and
@@ -1366,7 +1339,7 @@ static int do_grid(mpmhip_ctx *c, int mode, int phase = 0) {
     if (c->grid_wgs > 0) wgs = c->grid_wgs;
     const bool sdf = mode == 0 && c->LS.sdf.phi0;  // sampled level set: the instantiation that reads it
     hipLaunchKernelGGL(mode == 0 ? (sdf ? k_grid_list<0, true> : k_grid_list<0>) : (mode == 4 ? k_grid_list<4> : k_grid_list<5>), dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, (const uint32_t *)c->nbr,
-                       (const uint32_t *)c->own_list, c->tiles, c->gridv, c->fat_slot, reinterpret_cast<double *>(c->dense), c->T,
+                       (const uint32_t *)c->own_list, c->tiles, c->gridv, c->fat_slot, reinterpret_cast<double *>(dense), c->T,
                        c->d_boxes_cur, c->LS, phase);
     return launch_check(c, "grid");
   }
@@ -1384,7 +1357,7 @@ static int do_grid(mpmhip_ctx *c, int mode, int phase = 0) {
   int wgs = per_cand ? 16384 : 4096;
   if (c->grid_wgs > 0 && mode == 0) wgs = c->grid_wgs;
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, c->act_blk, c->bits, c->wprefix, c->tiles,
-                     c->gridv, c->fat_slot, c->dense, c->T, c->d_boxes_cur, c->LS, phase);
+                     c->gridv, c->fat_slot, dense, c->T, c->d_boxes_cur, c->LS, phase);
   return launch_check(c, "grid");
 }
 // which G2P kernel the plain blocks of the next substep get (bench.py names the kernel of its roofline after it).  By size and by
@@ -1438,8 +1411,8 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
     // the partly filled last round — 4 096 workgroups are 5.33 rounds of 768.  At C3, lattice / after impact: 3 072 -> 287 / 336 us,
     // 4 096 -> 287 / 352, 6 144 -> 291 / 343, 2 304 -> 296 / 346, 1 536 -> 292 / 350, 768 -> 304 / 350 (profiles/r04_u_g2p_wgs.txt)
     const int wgs = c->g2p_wgs > 0 ? c->g2p_wgs : (c->n_slots < (2 << 20) ? 768 : 12 * c->n_cus);
-    hipLaunchKernelGGL(pk, dim3(wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg, (float4 *)c->rg2, (float4 *)c->rp2,
-                       (float4 *)c->rb2, c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
+    hipLaunchKernelGGL(pk, dim3(wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(),
+                       (float4 *)c->rb2.get(), c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
                        c->blk_flag, (const LevelSetDev *)c->d_LS, (const uint32_t *)c->chunk_blk);
     c->sorted = false; c->keys_valid = true; c->affine_valid = true;
     c->pidc_valid = c->P.pidc != nullptr;
@@ -1452,15 +1425,15 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
   // workgroups per CU = 768) walking ~6 chunks each WITH the record prefetch beats one chunk per workgroup: 51.9 -> 46.1 us at
   // 1 M particles (profiles/r04_b_knobs.txt; 512 and 1 024 are slower again)
   const int g2p_wgs = c->g2p_wgs > 0 ? c->g2p_wgs : (c->n_slots < (2 << 20) ? 768 : 4096);
-  hipLaunchKernelGGL(kern, dim3(g2p_wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg, (float4 *)c->rg2, (float4 *)c->rp2,
-                     (float4 *)c->rb2, c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
+  hipLaunchKernelGGL(kern, dim3(g2p_wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(),
+                     (float4 *)c->rb2.get(), c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
                      c->blk_flag, (const LevelSetDev *)c->d_LS, phase_box(c->T), phase);
   if (rigid) {
     auto rk = c->deterministic ? k_g2p_rigid<MAT_ALL | MAT_DET>
                                : one_material(mask, k_g2p_rigid<MAT_ALL>, [](auto m) { return k_g2p_rigid<m.value>; });
     if (c->deterministic) { if (int rc = rigid_imp_rows(c)) return rc; }
-    hipLaunchKernelGGL(rk, dim3(c->rigid_wgs / 2), dim3(256), 0, rs, c->P, (const float4 *)c->rg, (float4 *)c->rg2, (float4 *)c->rp2,
-                       (float4 *)c->rb2, c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
+    hipLaunchKernelGGL(rk, dim3(c->rigid_wgs / 2), dim3(256), 0, rs, c->P, (const float4 *)c->rg.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(),
+                       (float4 *)c->rb2.get(), c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
                        c->blk_flag, (const LevelSetDev *)c->d_LS, rigid_xfer(c));
     if (int rc = rigid_join(c, rs)) return rc;
     if (int rc = do_rigid_apply_tmp(c)) return rc;
@@ -1477,7 +1450,7 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
 static int do_sdf_collide(mpmhip_ctx *c) {
   if (!c->LS.sdf.phi0 || !c->particle_collision_cfg || c->n_slots == 0) return MPMHIP_OK;
   hipLaunchKernelGGL(k_sdf_collide, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const Counters *)c->cnt,
-                     (float4 *)c->rg2, (float4 *)c->rp2, c->key, c->blk_flag, c->cnt, c->LS.sdf);
+                     (float4 *)c->rg2.get(), (float4 *)c->rp2.get(), c->key, c->blk_flag, c->cnt, c->LS.sdf);
   return launch_check(c, "sdf_collide");
 }
 
@@ -1731,7 +1704,7 @@ int mpmhip_synchronize(mpmhip_ctx *c) {
 static int ensure_dense(mpmhip_ctx *c, size_t &nodes) {
   nodes = (size_t)(c->P.res[0] + 1) * (c->P.res[1] + 1) * (c->P.res[2] + 1);
   if (!c->dense) {
-    if (dmalloc(&c->dense, nodes) != hipSuccess) return fail(c, MPMHIP_ENOMEM, "dense grid staging allocation failed");
+    if (c->dense.alloc(nodes) != hipSuccess) return fail(c, MPMHIP_ENOMEM, "dense grid staging allocation failed");
   }
   return MPMHIP_OK;
 }
@@ -1958,25 +1931,20 @@ int mpmhip_bgeo_encode(mpmhip_ctx *c, int32_t verbose, void *dst, size_t capacit
   uint8_t *mat_dst = out;
   if (with_rigid) { mat_rows.resize(mat_bytes); mat_dst = mat_rows.data(); }
   if (nm) {
-    uint32_t *d_order = nullptr, *d_rows = nullptr;
-    hipError_t e = dmalloc(&d_order, (size_t)nm);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_rows, mat_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_order, order.data(), (size_t)nm * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-      const dim3 grid(particle_grid(nm)), wg(256);
-      if (verbose)
-        hipLaunchKernelGGL(k_bgeo_rows<true>, grid, wg, 0, c->stream, nm, (const uint32_t *)d_order, (const RecG *)c->rg,
-                           (const RecP *)c->rp, (const float *)c->rb, (const GroupParams *)c->d_groups, (const int32_t *)limits, d_rows);
-      else
-        hipLaunchKernelGGL(k_bgeo_rows<false>, grid, wg, 0, c->stream, nm, (const uint32_t *)d_order, (const RecG *)c->rg,
-                           (const RecP *)c->rp, (const float *)c->rb, (const GroupParams *)c->d_groups, (const int32_t *)limits, d_rows);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(mat_dst, d_rows, mat_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_order);
-    (void)hipFree(d_rows);
-    HIPCHK(c, e);
+    DevBuf<uint32_t> d_order, d_rows;
+    HIPCHK(c, d_order.alloc((size_t)nm));
+    HIPCHK(c, d_rows.alloc((size_t)nm * W));
+    HIPCHK(c, hipMemcpyAsync(d_order, order.data(), (size_t)nm * 4, hipMemcpyHostToDevice, c->stream));
+    const dim3 grid(particle_grid(nm)), wg(256);
+    if (verbose)
+      hipLaunchKernelGGL(k_bgeo_rows<true>, grid, wg, 0, c->stream, nm, (const uint32_t *)d_order, (const RecG *)c->rg,
+                         (const RecP *)c->rp, (const float *)c->rb, (const GroupParams *)c->d_groups, (const int32_t *)limits, d_rows);
+    else
+      hipLaunchKernelGGL(k_bgeo_rows<false>, grid, wg, 0, c->stream, nm, (const uint32_t *)d_order, (const RecG *)c->rg,
+                         (const RecP *)c->rp, (const float *)c->rb, (const GroupParams *)c->d_groups, (const int32_t *)limits, d_rows);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(mat_dst, d_rows, mat_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   if (with_rigid) {
     // rows of the boundary particles (RigidBoundaryParticle, src/boundary_particle.h): position = anchor point, type = 1,
@@ -2070,16 +2038,13 @@ static int energy_end_det(mpmhip_ctx *c) {
   const size_t mb = c->P.max_blocks;
   if (c->energy_parts_cap < mb) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_energy_parts); c->d_energy_parts = nullptr; c->energy_parts_cap = 0;
-    HIPCHK(c, dmalloc(&c->d_energy_parts, mb * 8 + POT_WAVES));
+    c->energy_parts_cap = 0;
+    HIPCHK(c, c->d_energy_parts.alloc(mb * 8 + POT_WAVES));
     c->energy_parts_cap = mb;
   }
   double *kin = c->d_energy_parts, *pot = c->d_energy_parts + 8 * mb, *acc = c->d_energy;
   HIPCHK(c, hipMemsetAsync(kin, 0, 8 * mb * sizeof(double), c->stream));  // (node blocks no walk visits: not owned, not in phase)
-  float4 *const dense_saved = c->dense;
-  c->dense = reinterpret_cast<float4 *>(kin);  // k_grid<5> stores into its `dense` argument
-  int rc = do_grid(c, 5);
-  c->dense = dense_saved;
+  int rc = do_grid(c, 5, 0, reinterpret_cast<float4 *>(kin));  // k_grid<5> stores into its `dense` argument
   if (rc) return rc;
   const uint32_t *n_active = &c->cnt->n_active;
   hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(1024), 0, c->stream, (const double *)kin, n_active, (uint32_t)mb, 8u, acc);
@@ -2090,16 +2055,12 @@ static int energy_end_det(mpmhip_ctx *c) {
 }
 static int energy_end(mpmhip_ctx *c, double out[3]) {
   int rc;
-  if (!c->d_energy) HIPCHK(c, dmalloc(&c->d_energy, 4));
+  if (!c->d_energy) HIPCHK(c, c->d_energy.alloc(4));
   HIPCHK(c, hipMemsetAsync(c->d_energy, 0, 4 * sizeof(double), c->stream));
   if (c->deterministic) {
     if ((rc = energy_end_det(c))) return rc;
   } else {
-    float4 *const dense_saved = c->dense;
-    c->dense = reinterpret_cast<float4 *>(c->d_energy);  // k_grid<4> accumulates into its `dense` argument
-    rc = do_grid(c, 4);
-    c->dense = dense_saved;
-    if (rc) return rc;
+    if ((rc = do_grid(c, 4, 0, reinterpret_cast<float4 *>(c->d_energy.get())))) return rc;  // k_grid<4> accumulates into its `dense` argument
     hipLaunchKernelGGL(k_potential_energy, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const RecG *)c->rg,
                        (const GroupParams *)c->d_groups, c->d_energy + 1);
     if ((rc = launch_check(c, "potential_energy"))) return rc;
@@ -2242,7 +2203,7 @@ int mpmhip_set_halo(mpmhip_ctx *c, int32_t n, const mpmhip_halo_box *boxes) {
     if (off >= (1ull << 31)) return fail(c, MPMHIP_EINVAL, "halo boxes too large");
   }
   if (empty_interior) for (int a = 0; a < 3; a++) T.int_hi[a] = T.int_lo[a];
-  if (!c->d_boxes) HIPCHK(c, dmalloc(&c->d_boxes, (size_t)MPMHIP_MAX_HALO_BOXES));
+  if (!c->d_boxes) HIPCHK(c, c->d_boxes.alloc((size_t)MPMHIP_MAX_HALO_BOXES));
   HIPCHK(c, hipMemcpy(c->d_boxes, hb.data(), sizeof(DevBox) * n, hipMemcpyHostToDevice));
   c->d_boxes_cur = c->d_boxes;
   T.n_boxes = n; T.box_nodes = (uint32_t)off; T.box_blocks = boff;
@@ -2260,9 +2221,7 @@ static int ensure_counts(mpmhip_ctx *c, int world) {
   if (!c->T.enabled) return fail(c, MPMHIP_EINVAL, "no partition set");
   if (world != c->T.dims[0] * c->T.dims[1] * c->T.dims[2]) return fail(c, MPMHIP_EINVAL, "world=%d does not match the partition", world);
   if (c->counts_cap < world) {
-    hipFree(c->d_counts);
-    c->d_counts = nullptr;
-    HIPCHK(c, dmalloc(&c->d_counts, (size_t)world + 8));  // + the 6 bounds and the speed of mpmhip_migration_scan + one word of the native data plane
+    HIPCHK(c, c->d_counts.alloc((size_t)world + 8));  // + the 6 bounds and the speed of mpmhip_migration_scan + one word of the native data plane
     c->counts_cap = world;
   }
   return MPMHIP_OK;
@@ -2281,8 +2240,8 @@ int mpmhip_migration_scan(mpmhip_ctx *c, int32_t world, int64_t *counts, int32_t
   hipLaunchKernelGGL(k_scan_init, dim3((world + 8 + 255) / 256), dim3(256), 0, c->stream, c->d_counts, world, 0u);
   int grid = particle_grid(c->n_slots);
   if (grid > 128) grid = 128;  // few workgroups: 6 same-address atomics each for the bounds
-  hipLaunchKernelGGL(k_leaver_count, dim3(grid), dim3(256), 0, c->stream, c->P, c->T, (const float4 *)c->rg,
-                     (const float4 *)c->rp, c->d_counts, reinterpret_cast<int *>(c->d_counts + world), c->cnt);
+  hipLaunchKernelGGL(k_leaver_count, dim3(grid), dim3(256), 0, c->stream, c->P, c->T, (const float4 *)c->rg.get(),
+                     (const float4 *)c->rp.get(), c->d_counts, reinterpret_cast<int *>(c->d_counts + world), c->cnt);
   if ((rc = launch_check(c, "leaver_count"))) return rc;
   uint32_t *h = c->h_pinned + sizeof(Counters) / 4;  // behind the counters read_counters() fetches
   HIPCHK(c, hipMemcpyAsync(h, c->d_counts, sizeof(uint32_t) * ((size_t)world + 7), hipMemcpyDeviceToHost, c->stream));
@@ -2315,8 +2274,8 @@ int mpmhip_export_leavers(mpmhip_ctx *c, int32_t world, const int64_t *counts, v
   uint32_t *pin = c->h_pinned + 1024;  // stays untouched until the next migration: no synchronisation needed
   memcpy(pin, cur.data(), sizeof(uint32_t) * world);
   HIPCHK(c, hipMemcpyAsync(c->d_counts, pin, sizeof(uint32_t) * world, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_leaver_pack, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, c->T, (float4 *)c->rg,
-                     (const float4 *)c->rp, (const float4 *)c->rb, c->key, c->d_counts, (float4 *)dev_records, c->cnt);
+  hipLaunchKernelGGL(k_leaver_pack, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, c->T, (float4 *)c->rg.get(),
+                     (const float4 *)c->rp.get(), (const float4 *)c->rb.get(), c->key, c->d_counts, (float4 *)dev_records, c->cnt);
   return launch_check(c, "leaver_pack");
 }
 
@@ -2329,7 +2288,7 @@ int mpmhip_import_particles(mpmhip_ctx *c, int64_t n, const void *dev_records) {
     return fail(c, MPMHIP_ECAPACITY, "particle capacity exceeded on import: %lld + %lld > %lld (request_compaction or a larger max_particles)",
                 (long long)c->n_slots, (long long)n, (long long)c->cap);
   hipLaunchKernelGGL(k_import, dim3(particle_grid(n)), dim3(256), 0, c->stream, c->P, (uint32_t)n, (uint32_t)c->n_slots,
-                     (const float4 *)dev_records, (float4 *)c->rg, (float4 *)c->rp, (float4 *)c->rb, c->key, c->blk_flag,
+                     (const float4 *)dev_records, (float4 *)c->rg.get(), (float4 *)c->rp.get(), (float4 *)c->rb.get(), c->key, c->blk_flag,
                      c->cnt);
   c->n_slots += n;
   c->P.n_slots = (uint32_t)c->n_slots;
@@ -2340,7 +2299,7 @@ int mpmhip_import_particles(mpmhip_ctx *c, int64_t n, const void *dev_records) {
 int mpmhip_active_bounds(mpmhip_ctx *c, int32_t lo[3], int32_t hi[3]) {
   if (!c || !lo || !hi) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->d_bounds) HIPCHK(c, dmalloc(&c->d_bounds, 6));
+  if (!c->d_bounds) HIPCHK(c, c->d_bounds.alloc(6));
   const int init[6] = {1 << 30, 1 << 30, 1 << 30, -1, -1, -1};
   int h[6];
   HIPCHK(c, hipMemcpyAsync(c->d_bounds, init, sizeof init, hipMemcpyHostToDevice, c->stream));
@@ -2375,13 +2334,13 @@ int mpmhip_reserve(mpmhip_ctx *c, int64_t max_particles) {
   const size_t n = (size_t)c->n_slots, cap = (size_t)max_particles;
   hipError_t e = hipSuccess;
   auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  A(regrow(&c->rg, n, cap, false)); A(regrow(&c->rp, n, cap, false)); A(regrow(&c->rb, n * BW, cap * BW, true));
-  A(regrow(&c->rg2, 0, cap, false)); A(regrow(&c->rp2, 0, cap, false)); A(regrow(&c->rb2, 0, cap * BW, false));
-  A(regrow(&c->key, 0, cap, false)); A(regrow(&c->pidc, 0, cap, false)); A(regrow(&c->rank, 0, cap, false)); A(regrow(&c->perm, 0, cap, false)); A(regrow(&c->chunk_blk, 0, cap / 256 + 2, false));
-  if (c->rigid.d_bnd) A(regrow(&c->rigid.d_bnd, n, cap, true));
+  A(c->rg.regrow(n, cap, false)); A(c->rp.regrow(n, cap, false)); A(c->rb.regrow(n * BW, cap * BW, true));
+  A(c->rg2.regrow(0, cap, false)); A(c->rp2.regrow(0, cap, false)); A(c->rb2.regrow(0, cap * BW, false));
+  A(c->key.regrow(0, cap, false)); A(c->pidc.regrow(0, cap, false)); A(c->rank.regrow(0, cap, false)); A(c->perm.regrow(0, cap, false)); A(c->chunk_blk.regrow(0, cap / 256 + 2, false));
+  if (c->rigid.d_bnd) A(c->rigid.d_bnd.regrow(n, cap, true));
   if (c->async.d_blk_of) {  // (re-allocated at the size of the ctx by the next update_dt_limits)
-    (void)hipFree(c->async.d_blk_of); (void)hipFree(c->async.d_particle_limits);
-    c->async.d_blk_of = nullptr; c->async.d_particle_limits = nullptr; c->async.blk_of_cap = 0; c->async.limits_valid = false;
+    c->async.d_blk_of.reset(); c->async.d_particle_limits.reset();
+    c->async.blk_of_cap = 0; c->async.limits_valid = false;
   }
   if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "growing the particle arrays to %lld failed: %s", (long long)max_particles, hipGetErrorString(e));
   c->cap = max_particles;
@@ -2393,15 +2352,15 @@ int mpmhip_reserve(mpmhip_ctx *c, int64_t max_particles) {
     if (mb > (int64_t)c->NB) mb = c->NB;
     if ((uint32_t)mb > c->P.max_blocks) {
       const size_t m = (size_t)mb;
-      A(regrow(&c->act_blk, 0, m + 1, false)); A(regrow(&c->act_start, 0, m + 2, true));
-      A(regrow(&c->cell_cnt, 0, m * BC, true)); A(regrow(&c->cell_start, 0, m * BC + 1, true));
-      A(regrow(&c->nbr, 0, m * 32, false)); A(regrow(&c->own_list, 0, m * 8, false));
+      A(c->act_blk.regrow(0, m + 1, false)); A(c->act_start.regrow(0, m + 2, true));
+      A(c->cell_cnt.regrow(0, m * BC, true)); A(c->cell_start.regrow(0, m * BC + 1, true));
+      A(c->nbr.regrow(0, m * 32, false)); A(c->own_list.regrow(0, m * 8, false));
       c->ct_slots = (uint32_t)((m + 15) / 16 + 1);
-      A(regrow(&c->scan_slots, 0, c->bt_slots + 2 * (size_t)c->ct_slots, true));  // (epoch 0 is never used)
+      A(c->scan_slots.regrow(0, c->bt_slots + 2 * (size_t)c->ct_slots, true));  // (epoch 0 is never used)
       c->list_clear_epoch = c->sort_epoch;
-      A(regrow(&c->tiles, 0, m * TN, false)); A(regrow(&c->gridv, 0, m * 8 * BC, false));
-      if (c->rigid.d_blk_rigid) { A(regrow(&c->rigid.d_blk_rigid, 0, m + 1, true)); A(regrow(&c->rigid.d_rigid_list, 0, m + 1, false)); }
-      if (c->rigid.d_imp_rows) { A(regrow(&c->rigid.d_imp_rows, 0, m * IMP_ROW, false)); c->rigid.imp_rows_cap = m; }
+      A(c->tiles.regrow(0, m * TN, false)); A(c->gridv.regrow(0, m * 8 * BC, false));
+      if (c->rigid.d_blk_rigid) { A(c->rigid.d_blk_rigid.regrow(0, m + 1, true)); A(c->rigid.d_rigid_list.regrow(0, m + 1, false)); }
+      if (c->rigid.d_imp_rows) { A(c->rigid.d_imp_rows.regrow(0, m * IMP_ROW, false)); c->rigid.imp_rows_cap = m; }
       if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "growing the block table to %lld failed: %s", (long long)mb, hipGetErrorString(e));
       c->P.max_blocks = (uint32_t)mb;
       HIPCHK(c, hipMemset(c->fat_slot, 0, sizeof(uint32_t) * (size_t)c->NB));  // slots of the old grid array
@@ -2418,15 +2377,16 @@ int mpmhip_debug_scan_grid(int32_t n_cus, int32_t per_cu, int32_t env_request, u
   *resident = scan_resident_set(n_cus, per_cu);
   return MPMHIP_OK;
 }
+int64_t mpmhip_debug_live_buffers(void) { return hostmem::g_live_buffers.load(std::memory_order_relaxed); }
 int mpmhip_debug_g2p_is_packed(const mpmhip_ctx *c) { return c ? (g2p_is_packed(c, 0) ? 1 : 0) : MPMHIP_EINVAL; }
 int mpmhip_debug_copy_bandwidth(mpmhip_ctx *c, size_t bytes, int32_t iters, double *gb_per_s) {
   if (!c || !gb_per_s || iters <= 0 || bytes < 16) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = bytes / 16;
-  float4 *a = nullptr, *b = nullptr;
+  DevBuf<float4> a, b;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = dmalloc(&a, n);
-  if (e == hipSuccess) e = dmalloc(&b, n);
+  hipError_t e = a.alloc(n);
+  if (e == hipSuccess) e = b.alloc(n);
   if (e == hipSuccess) e = hipMemsetAsync(a, 0, n * 16, c->stream);
   if (e == hipSuccess) e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -2451,8 +2411,6 @@ int mpmhip_debug_copy_bandwidth(mpmhip_ctx *c, size_t bytes, int32_t iters, doub
       }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(a);
-  (void)hipFree(b);
   HIPCHK(c, e);
   *gb_per_s = best;
   return MPMHIP_OK;
@@ -2463,13 +2421,13 @@ int mpmhip_debug_copy_bandwidth(mpmhip_ctx *c, size_t bytes, int32_t iters, doub
 int mpmhip_debug_gather_bandwidth(mpmhip_ctx *c, int64_t n, int32_t mode, int32_t iters, double *gb_per_s) {
   if (!c || !gb_per_s || iters <= 0 || n < 1024 || (n & (n - 1)) || n > (1ll << 30) || mode < 0 || mode > 2) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  float4 *rec = nullptr, *out = nullptr;
-  uint32_t *idx = nullptr;
+  DevBuf<float4> rec, out;
+  DevBuf<uint32_t> idx;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   const int grid = 256 * 16;
-  hipError_t e = dmalloc(&rec, (size_t)n * 4);
-  if (e == hipSuccess) e = dmalloc(&idx, (size_t)n);
-  if (e == hipSuccess) e = dmalloc(&out, (size_t)grid * 4);
+  hipError_t e = rec.alloc((size_t)n * 4);
+  if (e == hipSuccess) e = idx.alloc((size_t)n);
+  if (e == hipSuccess) e = out.alloc((size_t)grid * 4);
   if (e == hipSuccess) e = hipMemsetAsync(rec, 0, (size_t)n * 64, c->stream);
   if (e == hipSuccess) e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -2489,7 +2447,6 @@ int mpmhip_debug_gather_bandwidth(mpmhip_ctx *c, int64_t n, int32_t mode, int32_
   }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(rec); (void)hipFree(idx); (void)hipFree(out);
   HIPCHK(c, e);
   *gb_per_s = best;
   return MPMHIP_OK;
@@ -2500,7 +2457,7 @@ struct mpmhip_mpm88 {
   mpm88::Params P{};
   int device = 0;
   int64_t n = 0, cap = 0;
-  float *x = nullptr, *v = nullptr, *F = nullptr, *C = nullptr, *Jp = nullptr, *grid = nullptr;
+  DevBuf<float> x, v, F, C, Jp, grid;
   hipStream_t stream = nullptr;
   std::string err;
 };
@@ -2532,7 +2489,7 @@ int mpmhip_mpm88_create(int32_t n_grid, float dt, int32_t plastic, int32_t devic
   m->P.mass = 1.0f; m->P.vol = 1.0f; m->P.plastic = plastic ? 1 : 0;
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = dmalloc(&m->grid, (size_t)3 * (n_grid + 1) * (n_grid + 1));
+  if (e == hipSuccess) e = m->grid.alloc((size_t)3 * (n_grid + 1) * (n_grid + 1));
   if (e != hipSuccess) {
     const int rc = fail88(nullptr, MPMHIP_EHIP, std::string("mpm88 create: ") + hipGetErrorString(e));
     mpmhip_mpm88_destroy(m);
@@ -2546,7 +2503,6 @@ void mpmhip_mpm88_destroy(mpmhip_mpm88 *m) {
   if (!m) return;
   hipSetDevice(m->device);
   if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
-  hipFree(m->x); hipFree(m->v); hipFree(m->F); hipFree(m->C); hipFree(m->Jp); hipFree(m->grid);
   delete m;
 }
 
@@ -2560,15 +2516,9 @@ int mpmhip_mpm88_add(mpmhip_mpm88 *m, int64_t n, const float *x, const float *v,
   const int64_t total = m->n + n;
   if (total > m->cap) {  // grow: new arrays, old contents copied over
     const int64_t cap = std::max<int64_t>(total, 2 * m->cap);
-    float **arrs[5] = {&m->x, &m->v, &m->F, &m->C, &m->Jp};
+    DevBuf<float> *arrs[5] = {&m->x, &m->v, &m->F, &m->C, &m->Jp};
     const int width[5] = {2, 2, 4, 4, 1};
-    for (int a = 0; a < 5; a++) {
-      float *fresh = nullptr;
-      HIPCHK88(m, dmalloc(&fresh, (size_t)cap * width[a]));
-      if (m->n) HIPCHK88(m, hipMemcpy(fresh, *arrs[a], sizeof(float) * m->n * width[a], hipMemcpyDeviceToDevice));
-      (void)hipFree(*arrs[a]);
-      *arrs[a] = fresh;
-    }
+    for (int a = 0; a < 5; a++) HIPCHK88(m, arrs[a]->regrow((size_t)m->n * width[a], (size_t)cap * width[a], false));
     m->cap = cap;
   }
   std::vector<float> h;
@@ -2642,10 +2592,8 @@ int mpmhip_async_enable(mpmhip_ctx *c, const mpmhip_async_config *cfg) {
   auto &A = c->async;
   A.sched_enable(3, c->P.res, *cfg);
   const size_t nblk = A.nblk();
-  hipFree(A.d_tab); hipFree(A.d_blk_limits);
-  A.d_tab = nullptr; A.d_blk_limits = nullptr;
-  HIPCHK(c, dmalloc(&A.d_tab, 3 * nblk));
-  HIPCHK(c, dmalloc(&A.d_blk_limits, 3 * nblk));
+  HIPCHK(c, A.d_tab.alloc(3 * nblk));
+  HIPCHK(c, A.d_blk_limits.alloc(3 * nblk));
   A.enabled = true; A.limits_valid = false;
   return MPMHIP_OK;
 }
@@ -2653,10 +2601,8 @@ int mpmhip_async_enable(mpmhip_ctx *c, const mpmhip_async_config *cfg) {
 static int async_ensure_particle_arrays(mpmhip_ctx *c) {
   auto &A = c->async;
   if (A.blk_of_cap < c->cap) {
-    hipFree(A.d_blk_of); hipFree(A.d_particle_limits);
-    A.d_blk_of = nullptr; A.d_particle_limits = nullptr;
-    HIPCHK(c, dmalloc(&A.d_blk_of, (size_t)c->cap));
-    HIPCHK(c, dmalloc(&A.d_particle_limits, 3 * (size_t)c->cap));
+    HIPCHK(c, A.d_blk_of.alloc((size_t)c->cap));
+    HIPCHK(c, A.d_particle_limits.alloc(3 * (size_t)c->cap));
     A.blk_of_cap = c->cap;
   }
   return MPMHIP_OK;
@@ -2679,9 +2625,7 @@ static int async_limits_from_table(mpmhip_ctx *c) {
   auto &A = c->async;
   const size_t nblk = A.strength.size();
   if (A.h_tab_cap < 3 * nblk) {  // pinned staging (a copy into pageable memory is staged by the runtime: ~50 us more)
-    if (A.h_tab) (void)hipHostFree(A.h_tab);
-    A.h_tab = nullptr;
-    HIPCHK(c, hipHostMalloc((void **)&A.h_tab, sizeof(uint32_t) * 3 * nblk, hipHostMallocDefault));
+    HIPCHK(c, A.h_tab.alloc(3 * nblk));
     A.h_tab_cap = 3 * nblk;
   }
   HIPCHK(c, hipMemcpyAsync(A.h_tab, A.d_tab, sizeof(uint32_t) * 3 * nblk, hipMemcpyDeviceToHost, c->stream));
@@ -2770,14 +2714,13 @@ int mpmhip_debug_allowed_dt(mpmhip_ctx *c, int32_t material, const float params[
   memset(&g, 0, sizeof g);
   memcpy(g.p, params, sizeof g.p);
   g.type = material;
-  float *dF, *dA, *dV, *dO;
-  HIPCHK(c, dmalloc(&dF, 9 * n)); HIPCHK(c, dmalloc(&dA, n)); HIPCHK(c, dmalloc(&dV, 3 * n)); HIPCHK(c, dmalloc(&dO, n));
+  DevBuf<float> dF, dA, dV, dO;
+  HIPCHK(c, dF.alloc(9 * n)); HIPCHK(c, dA.alloc(n)); HIPCHK(c, dV.alloc(3 * n)); HIPCHK(c, dO.alloc(n));
   HIPCHK(c, hipMemcpy(dF, F, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dA, aux, sizeof(float) * n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dV, v, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-  int rc = run_debug(c, k_debug_allowed_dt, g, n, (const float *)dF, (const float *)dA, (const float *)dV, dx, dO);
+  int rc = run_debug(c, k_debug_allowed_dt, g, n, (const float *)dF, (const float *)dA, (const float *)dV, dx, dO.get());
   if (!rc) HIPCHK(c, hipMemcpy(out, dO, sizeof(float) * n, hipMemcpyDeviceToHost));
-  hipFree(dF); hipFree(dA); hipFree(dV); hipFree(dO);
   return rc;
 }
 
@@ -2789,10 +2732,10 @@ struct mpmhip2d_ctx {
   LevelSetDev LS{};
   int device = 0;
   int64_t n = 0, cap = 0;
-  float *x = nullptr, *v = nullptr, *F = nullptr, *B = nullptr, *aux = nullptr, *grid = nullptr;
-  int32_t *gid = nullptr, *pid = nullptr;
-  unsigned int *n_dead = nullptr;
-  GroupParams *d_groups = nullptr;
+  DevBuf<float> x, v, F, B, aux, grid;
+  DevBuf<int32_t> gid, pid;
+  DevBuf<unsigned int> n_dead;
+  DevBuf<GroupParams> d_groups;
   std::vector<GroupParams> groups;
   int32_t next_pid = 0;
   float t = 0.0f, request_t = 0.0f;
@@ -2805,18 +2748,19 @@ struct mpmhip2d_ctx {
   std::vector<mpm2d::Sample2> h_smp;
   std::vector<int32_t> h_smp_id;  // creation id of every boundary particle (they share the material particles' counter)
   std::vector<float> h_elems;
-  mpm2d::Rigid2 *d_rb = nullptr;
-  mpm2d::Sample2 *d_smp = nullptr;
-  float *d_elems = nullptr;
-  unsigned long long *d_mind = nullptr;
-  uint32_t *d_tags = nullptr, *d_states = nullptr;
-  mpm2d::Bnd2 *d_bnd = nullptr;
+  DevBuf<mpm2d::Rigid2> d_rb;
+  DevBuf<mpm2d::Sample2> d_smp;
+  DevBuf<float> d_elems;
+  DevBuf<unsigned long long> d_mind;
+  DevBuf<uint32_t> d_tags, d_states;
+  DevBuf<mpm2d::Bnd2> d_bnd;
   float penalty = 0.0f, pushing_force = 20000.0f;
   // rigid_body_levelset_collision: the boundary particles' order (see k2_ls_keys)
   bool ls_collision = false;
-  uint32_t *d_smp_rank = nullptr, *d_ls_vals[2] = {nullptr, nullptr}, n_ranked = 0, ls_cap = 0;
-  unsigned long long *d_ls_keys[2] = {nullptr, nullptr};
-  void *d_ls_tmp = nullptr;
+  DevBuf<uint32_t> d_smp_rank, d_ls_vals[2];
+  uint32_t n_ranked = 0, ls_cap = 0;
+  DevBuf<unsigned long long> d_ls_keys[2];
+  DevBuf<uint8_t> d_ls_tmp;
   size_t ls_tmp_bytes = 0;
   mpm2d::Joints2 joints{};     // MPM<2>::articulations ('rotation' joints)
   int joint_iterations = 100;  // 'articulation_iterations'
@@ -2826,12 +2770,12 @@ struct mpmhip2d_ctx {
   struct Det2 {
     bool on = false;
     int64_t cap = 0;                 // particles the per-particle arrays hold
-    uint32_t *count = nullptr, *start = nullptr;   // [nodes + 1]; start[nodes] = live particles
-    uint32_t *off = nullptr, *unordered = nullptr, *idx = nullptr;
-    int32_t *key = nullptr;
-    float4 *rec = nullptr;           // [3 cap]
-    float *rows = nullptr;           // [ceil(cap / 256)][DET_ROW]; entries behind 3 * bodies are never written nor read
-    void *scan_tmp = nullptr;
+    DevBuf<uint32_t> count, start;   // [nodes + 1]; start[nodes] = live particles
+    DevBuf<uint32_t> off, unordered, idx;
+    DevBuf<int32_t> key;
+    DevBuf<float4> rec;              // [3 cap]
+    DevBuf<float> rows;              // [ceil(cap / 256)][DET_ROW]; entries behind 3 * bodies are never written nor read
+    DevBuf<uint8_t> scan_tmp;
     size_t scan_bytes = 0;
   } det;
   // AsyncMPM<2> (async2d_api.h): the block scheduler + the device store of pool / backup containers (k_async2d.h)
@@ -2839,36 +2783,25 @@ struct mpmhip2d_ctx {
     bool resident = false, pending_counters = false;
     bool view = false;  // the particle arrays are copies of the pools (mpmhip2d_async_load_pools), not new particles
     uint32_t cap = 0, size = 0, live = 0, size_ub = 0;  // containers allocated / in use incl. freed ones / not freed / upper bound now
-    float4 *rec = nullptr, *rec2 = nullptr;
-    uint32_t *tag = nullptr, *tag2 = nullptr, *d_tab = nullptr, *d_rank = nullptr, *d_blk_of = nullptr, *h_tab = nullptr;
-    unsigned long long *best = nullptr, *d_scan = nullptr;
+    DevBuf<float4> rec, rec2;
+    DevBuf<uint32_t> tag, tag2, d_tab, d_rank, d_blk_of;
+    PinnedBuf<uint32_t> h_tab;
+    DevBuf<unsigned long long> best, d_scan;
     int64_t best_cap = 0, blk_of_cap = 0, compactions = 0;
     uint32_t scan_cap = 0, scan_epoch = 0, pin_next = 0;
-    uint8_t *d_tbl = nullptr, *h_tbl_pin = nullptr;
-    AsyncCounters *d_cnt = nullptr, *h_cnt = nullptr;
+    DevBuf<uint8_t> d_tbl;
+    PinnedBuf<uint8_t> h_tbl_pin;
+    DevBuf<AsyncCounters> d_cnt;
+    PinnedBuf<AsyncCounters> h_cnt;
   } async;
 };
-static void a2_free(mpmhip2d_ctx *m) {
-  auto &A = m->async;
-  hipFree(A.rec); hipFree(A.rec2); hipFree(A.tag); hipFree(A.tag2); hipFree(A.d_tab); hipFree(A.d_rank); hipFree(A.d_blk_of);
-  hipFree(A.best); hipFree(A.d_scan); hipFree(A.d_tbl); hipFree(A.d_cnt);
-  if (A.h_tab) hipHostFree(A.h_tab);
-  if (A.h_tbl_pin) hipHostFree(A.h_tbl_pin);
-  if (A.h_cnt) hipHostFree(A.h_cnt);
-  A.rec = A.rec2 = nullptr; A.tag = A.tag2 = A.d_tab = A.d_rank = A.d_blk_of = A.h_tab = nullptr;
-  A.best = A.d_scan = nullptr; A.d_tbl = A.h_tbl_pin = nullptr; A.d_cnt = A.h_cnt = nullptr;
-  A.blk_of_cap = 0;  // (d_blk_of is gone: the next load_pools must allocate it again)
-  A.resident = false;
-}
 static int a2_drop_view(mpmhip2d_ctx *m);
 static int a2_grow_particles(mpmhip2d_ctx *m, int64_t need);
 int mpmhip2d_async_step(mpmhip2d_ctx *m, float dt);
-static void det2_free(mpmhip2d_ctx *m) {
-  auto &D = m->det;
-  hipFree(D.count); hipFree(D.start); hipFree(D.off); hipFree(D.unordered); hipFree(D.idx); hipFree(D.key); hipFree(D.rec); hipFree(D.rows);
-  hipFree(D.scan_tmp);
-  D.count = D.start = D.off = D.unordered = D.idx = nullptr; D.key = nullptr; D.rec = nullptr; D.rows = nullptr; D.scan_tmp = nullptr;
-  D.cap = 0; D.scan_bytes = 0;
+static void det2_free(mpmhip2d_ctx *m) {  // a failed det2_reserve leaves nothing half-allocated
+  const bool on = m->det.on;
+  m->det = mpmhip2d_ctx::Det2();
+  m->det.on = on;
 }
 static thread_local std::string g_2d_create_error;
 static int fail2d(mpmhip2d_ctx *m, int code, const std::string &msg) {
@@ -2911,9 +2844,9 @@ int mpmhip2d_create(const mpmhip2d_config *cfg, mpmhip2d_ctx **out) {
   hipError_t e = hipSetDevice(m->device);
   auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
   A(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-  A(dmalloc(&m->x, 2 * c)); A(dmalloc(&m->v, 2 * c)); A(dmalloc(&m->F, 4 * c)); A(dmalloc(&m->B, 4 * c)); A(dmalloc(&m->aux, c));
-  A(dmalloc(&m->gid, c)); A(dmalloc(&m->pid, c)); A(dmalloc(&m->grid, 3 * nodes)); A(dmalloc(&m->n_dead, 1));
-  A(dmalloc(&m->d_groups, (size_t)MPMHIP_MAX_GROUPS));
+  A(m->x.alloc(2 * c)); A(m->v.alloc(2 * c)); A(m->F.alloc(4 * c)); A(m->B.alloc(4 * c)); A(m->aux.alloc(c));
+  A(m->gid.alloc(c)); A(m->pid.alloc(c)); A(m->grid.alloc(3 * nodes)); A(m->n_dead.alloc(1));
+  A(m->d_groups.alloc((size_t)MPMHIP_MAX_GROUPS));
   if (e == hipSuccess) e = hipMemset(m->n_dead, 0, sizeof(unsigned int));
   if (e != hipSuccess) {
     const int rc = fail2d(nullptr, MPMHIP_ENOMEM, std::string("mpmhip2d_create: ") + hipGetErrorString(e));
@@ -2928,14 +2861,7 @@ void mpmhip2d_destroy(mpmhip2d_ctx *m) {
   if (!m) return;
   hipSetDevice(m->device);
   if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
-  hipFree(m->x); hipFree(m->v); hipFree(m->F); hipFree(m->B); hipFree(m->aux); hipFree(m->gid); hipFree(m->pid); hipFree(m->grid);
-  hipFree(m->n_dead); hipFree(m->d_groups);
-  det2_free(m);
-  hipFree(m->d_rb); hipFree(m->d_smp); hipFree(m->d_elems); hipFree(m->d_mind); hipFree(m->d_tags); hipFree(m->d_states); hipFree(m->d_bnd);
-  a2_free(m);
-  hipFree(m->d_smp_rank); hipFree(m->d_ls_tmp);
-  for (int k = 0; k < 2; k++) { hipFree(m->d_ls_keys[k]); hipFree(m->d_ls_vals[k]); }
-  delete m;
+  delete m;  // (the members free their arrays on the device set above)
 }
 
 // level set in the plane: the shapes of mpmhip_shape with z ignored (plane = line n.x + d, sphere = disc, cuboid = box with
@@ -3054,13 +2980,12 @@ static int rigid2_ls_collision(mpmhip2d_ctx *m) {
   const uint32_t n = (uint32_t)m->h_smp.size();
   if (n == 0 || m->LS.n == 0) return MPMHIP_OK;
   if (m->ls_cap < n) {
-    for (int k = 0; k < 2; k++) { (void)hipFree(m->d_ls_keys[k]); (void)hipFree(m->d_ls_vals[k]); m->d_ls_keys[k] = nullptr; m->d_ls_vals[k] = nullptr; }
-    (void)hipFree(m->d_ls_tmp); m->d_ls_tmp = nullptr; m->ls_tmp_bytes = 0;
+    m->ls_tmp_bytes = 0;
     const size_t cap = (size_t)n + n / 4 + 1024;
-    for (int k = 0; k < 2; k++) { HIPCHK2D(m, dmalloc(&m->d_ls_keys[k], cap)); HIPCHK2D(m, dmalloc(&m->d_ls_vals[k], cap)); }
+    for (int k = 0; k < 2; k++) { HIPCHK2D(m, m->d_ls_keys[k].alloc(cap)); HIPCHK2D(m, m->d_ls_vals[k].alloc(cap)); }
     size_t bytes = 0;
-    HIPCHK2D(m, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, m->d_ls_keys[0], m->d_ls_keys[1], m->d_ls_vals[0], m->d_ls_vals[1], (int)cap, 0, 64, m->stream));
-    HIPCHK2D(m, hipMalloc(&m->d_ls_tmp, bytes));
+    HIPCHK2D(m, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, m->d_ls_keys[0].get(), m->d_ls_keys[1].get(), m->d_ls_vals[0].get(), m->d_ls_vals[1].get(), (int)cap, 0, 64, m->stream));
+    HIPCHK2D(m, m->d_ls_tmp.alloc(bytes));
     m->ls_tmp_bytes = bytes;
     m->ls_cap = (uint32_t)cap;
   }
@@ -3069,15 +2994,14 @@ static int rigid2_ls_collision(mpmhip2d_ctx *m) {
     HIPCHK2D(m, hipStreamSynchronize(m->stream));
     if (m->n_ranked) HIPCHK2D(m, hipMemcpy(rk.data(), m->d_smp_rank, sizeof(uint32_t) * m->n_ranked, hipMemcpyDeviceToHost));
     for (uint32_t s = m->n_ranked; s < n; s++) rk[s] = s;
-    (void)hipFree(m->d_smp_rank); m->d_smp_rank = nullptr;
-    HIPCHK2D(m, dmalloc(&m->d_smp_rank, (size_t)n + n / 4 + 1024));
+    HIPCHK2D(m, m->d_smp_rank.alloc((size_t)n + n / 4 + 1024));
     HIPCHK2D(m, hipMemcpy(m->d_smp_rank, rk.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     m->n_ranked = n;
   }
   hipLaunchKernelGGL(mpm2d::k2_ls_keys, dim3((n + 255) / 256), dim3(256), 0, m->stream, m->P.idx, (const mpm2d::Rigid2 *)m->d_rb,
                      (const mpm2d::Sample2 *)m->d_smp, n, (const uint32_t *)m->d_smp_rank, m->d_ls_keys[0], m->d_ls_vals[0]);
   size_t bytes = m->ls_tmp_bytes;
-  HIPCHK2D(m, hipcub::DeviceRadixSort::SortPairs(m->d_ls_tmp, bytes, m->d_ls_keys[0], m->d_ls_keys[1], m->d_ls_vals[0], m->d_ls_vals[1], (int)n, 0, 64, m->stream));
+  HIPCHK2D(m, hipcub::DeviceRadixSort::SortPairs(m->d_ls_tmp, bytes, m->d_ls_keys[0].get(), m->d_ls_keys[1].get(), m->d_ls_vals[0].get(), m->d_ls_vals[1].get(), (int)n, 0, 64, m->stream));
   mpm2d::Restitution2 rest;
   memset(&rest, 0, sizeof rest);
   for (size_t b = 1; b < m->bodies.size(); b++) rest.e[b] = m->bodies[b].cfg.restitution;
@@ -3142,19 +3066,18 @@ static int det2_reserve(mpmhip2d_ctx *m) {
   hipError_t e = hipSuccess;
   auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
   if (!D.count) {
-    A(dmalloc(&D.count, nodes + 1)); A(dmalloc(&D.start, nodes + 1));
+    A(D.count.alloc(nodes + 1)); A(D.start.alloc(nodes + 1));
     size_t bytes = 0;
-    A(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, D.count, D.start, (int)(nodes + 1), m->stream));
-    if (e == hipSuccess) A(hipMalloc(&D.scan_tmp, std::max<size_t>(bytes, 16)));
+    A(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, D.count.get(), D.start.get(), (int)(nodes + 1), m->stream));
+    A(D.scan_tmp.alloc(std::max<size_t>(bytes, 16)));
     D.scan_bytes = bytes;
   }
   if (e == hipSuccess && D.cap < m->cap) {
     HIPCHK2D(m, hipStreamSynchronize(m->stream));
-    hipFree(D.off); hipFree(D.unordered); hipFree(D.idx); hipFree(D.key); hipFree(D.rec); hipFree(D.rows);
-    D.off = D.unordered = D.idx = nullptr; D.key = nullptr; D.rec = nullptr; D.rows = nullptr; D.cap = 0;
+    D.cap = 0;
     const size_t c = (size_t)m->cap;
-    A(dmalloc(&D.off, c)); A(dmalloc(&D.unordered, c)); A(dmalloc(&D.idx, c)); A(dmalloc(&D.key, c)); A(dmalloc(&D.rec, 3 * c));
-    A(dmalloc(&D.rows, ((c + 255) / 256) * (size_t)mpm2d::DET_ROW));
+    A(D.off.alloc(c)); A(D.unordered.alloc(c)); A(D.idx.alloc(c)); A(D.key.alloc(c)); A(D.rec.alloc(3 * c));
+    A(D.rows.alloc(((c + 255) / 256) * (size_t)mpm2d::DET_ROW));
     if (e == hipSuccess) D.cap = m->cap;
   }
   if (e != hipSuccess) {
@@ -3173,7 +3096,7 @@ static int det2_p2g(mpmhip2d_ctx *m, const mpm2d::RigidArgs2 &R) {
   hipLaunchKernelGGL(mpm2d::k2d_count, pg, wg, 0, m->stream, m->P, m->n, (const float *)m->x, (const float *)m->v, m->pid, D.key, D.off, D.count,
                      m->n_dead);
   size_t bytes = D.scan_bytes;
-  HIPCHK2D(m, hipcub::DeviceScan::ExclusiveSum(D.scan_tmp, bytes, D.count, D.start, (int)(nodes + 1), m->stream));
+  HIPCHK2D(m, hipcub::DeviceScan::ExclusiveSum(D.scan_tmp, bytes, D.count.get(), D.start.get(), (int)(nodes + 1), m->stream));
   hipLaunchKernelGGL(mpm2d::k2d_fill, pg, wg, 0, m->stream, m->n, (const int32_t *)D.key, (const uint32_t *)D.off, (const uint32_t *)D.start,
                      D.unordered);
   hipLaunchKernelGGL(mpm2d::k2d_order, pg, wg, 0, m->stream, m->n, (const int32_t *)D.key, (const int32_t *)m->pid, (const uint32_t *)D.start,
@@ -3275,8 +3198,8 @@ int mpmhip2d_add_rigid_body(mpmhip2d_ctx *m, const mpmhip2d_rigid_config *cfg, i
   if (!m->rigid_enabled) {
     hipError_t e = hipSuccess;
     auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    A(dmalloc(&m->d_rb, (size_t)mpm2d::MAX_RIGID2)); A(dmalloc(&m->d_mind, nodes)); A(dmalloc(&m->d_tags, nodes));
-    A(dmalloc(&m->d_states, (size_t)m->cap)); A(dmalloc(&m->d_bnd, (size_t)m->cap));
+    A(m->d_rb.alloc((size_t)mpm2d::MAX_RIGID2)); A(m->d_mind.alloc(nodes)); A(m->d_tags.alloc(nodes));
+    A(m->d_states.alloc((size_t)m->cap)); A(m->d_bnd.alloc((size_t)m->cap));
     if (e != hipSuccess) return fail2d(m, MPMHIP_ENOMEM, std::string("rigid coupling: ") + hipGetErrorString(e));
     HIPCHK2D(m, hipMemset(m->d_rb, 0, sizeof(mpm2d::Rigid2) * mpm2d::MAX_RIGID2));
     HIPCHK2D(m, hipMemset(m->d_states, 0, sizeof(uint32_t) * (size_t)m->cap));
@@ -3348,10 +3271,8 @@ int mpmhip2d_add_rigid_body(mpmhip2d_ctx *m, const mpmhip2d_rigid_config *cfg, i
   }
   m->next_pid += allocated;  // boundary particles take creation ids from the same counter (src/particle_allocator.h:68-74)
   m->h_elems.insert(m->h_elems.end(), seg.begin(), seg.end());
-  (void)hipFree(m->d_smp); (void)hipFree(m->d_elems);
-  m->d_smp = nullptr; m->d_elems = nullptr;
-  HIPCHK2D(m, dmalloc(&m->d_smp, std::max<size_t>(m->h_smp.size(), 1)));
-  HIPCHK2D(m, dmalloc(&m->d_elems, std::max<size_t>(m->h_elems.size(), 4)));
+  HIPCHK2D(m, m->d_smp.alloc(std::max<size_t>(m->h_smp.size(), 1)));
+  HIPCHK2D(m, m->d_elems.alloc(std::max<size_t>(m->h_elems.size(), 4)));
   if (!m->h_smp.empty()) HIPCHK2D(m, hipMemcpy(m->d_smp, m->h_smp.data(), sizeof(mpm2d::Sample2) * m->h_smp.size(), hipMemcpyHostToDevice));
   HIPCHK2D(m, hipMemcpy(m->d_elems, m->h_elems.data(), sizeof(float) * m->h_elems.size(), hipMemcpyHostToDevice));
   HIPCHK2D(m, hipMemcpy(m->d_rb + body, &D, sizeof D, hipMemcpyHostToDevice));
@@ -3418,14 +3339,12 @@ int64_t mpmhip2d_rigid_get_samples(mpmhip2d_ctx *m, int32_t id, int64_t cap, flo
   const uint32_t ns = (uint32_t)m->h_smp.size();
   std::vector<float> w((size_t)ns * 2);
   if (ns && pos) {
-    float *d = nullptr;
-    HIPCHK2D(m, dmalloc(&d, (size_t)ns * 2));
+    DevBuf<float> d;
+    HIPCHK2D(m, d.alloc((size_t)ns * 2));
     hipLaunchKernelGGL(mpm2d::k2_sample_positions, dim3((ns + 255) / 256), dim3(256), 0, m->stream, (const mpm2d::Rigid2 *)m->d_rb,
                        (const mpm2d::Sample2 *)m->d_smp, ns, d);
-    hipError_t e = hipMemcpyAsync(w.data(), d, sizeof(float) * w.size(), hipMemcpyDeviceToHost, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    (void)hipFree(d);
-    HIPCHK2D(m, e);
+    HIPCHK2D(m, hipMemcpyAsync(w.data(), d, sizeof(float) * w.size(), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK2D(m, hipStreamSynchronize(m->stream));
   }
   int64_t n = 0;
   for (size_t s = 0; s < m->h_smp.size(); s++) {
@@ -3561,18 +3480,16 @@ int mpmhip_debug_cond_census(mpmhip_ctx *c, double out[MPMHIP_COND_CENSUS_WORDS]
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "cond_census inside a substep");
   constexpr int W = 8 + COND_BINS;
   static_assert(W == MPMHIP_COND_CENSUS_WORDS, "census layout");
-  unsigned long long *d = nullptr;
-  HIPCHK(c, dmalloc(&d, (size_t)W));
-  hipError_t e = hipMemsetAsync(d, 0, sizeof(unsigned long long) * W, c->stream);
+  DevBuf<unsigned long long> d;
+  HIPCHK(c, d.alloc((size_t)W));
+  HIPCHK(c, hipMemsetAsync(d, 0, sizeof(unsigned long long) * W, c->stream));
   std::vector<unsigned long long> h((size_t)W);
-  if (e == hipSuccess && c->n_slots > 0) {
-    hipLaunchKernelGGL(k_cond_census, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg, d);
-    e = hipGetLastError();
+  if (c->n_slots > 0) {
+    hipLaunchKernelGGL(k_cond_census, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(), d);
+    HIPCHK(c, hipGetLastError());
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  HIPCHK(c, e);
+  HIPCHK(c, hipMemcpyAsync(h.data(), d, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < W; i++) out[i] = (double)h[i];
   const uint32_t bits = (uint32_t)h[4];
   float mx;
@@ -3584,16 +3501,15 @@ int mpmhip_debug_cond_census(mpmhip_ctx *c, double out[MPMHIP_COND_CENSUS_WORDS]
 int mpmhip_debug_svd3(mpmhip_ctx *c, int64_t n, const float *F, float *U, float *S, float *V) {
   if (!c || n <= 0) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  float *dF, *dU, *dS, *dV;
-  HIPCHK(c, dmalloc(&dF, 9 * n)); HIPCHK(c, dmalloc(&dU, 9 * n)); HIPCHK(c, dmalloc(&dS, 3 * n)); HIPCHK(c, dmalloc(&dV, 9 * n));
+  DevBuf<float> dF, dU, dS, dV;
+  HIPCHK(c, dF.alloc(9 * n)); HIPCHK(c, dU.alloc(9 * n)); HIPCHK(c, dS.alloc(3 * n)); HIPCHK(c, dV.alloc(9 * n));
   HIPCHK(c, hipMemcpy(dF, F, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
-  int rc = run_debug(c, k_debug_svd, n, (const float *)dF, dU, dS, dV);
+  int rc = run_debug(c, k_debug_svd, n, (const float *)dF, dU.get(), dS.get(), dV.get());
   if (!rc) {
     HIPCHK(c, hipMemcpy(U, dU, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(S, dS, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(V, dV, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
   }
-  hipFree(dF); hipFree(dU); hipFree(dS); hipFree(dV);
   return rc;
 }
 
@@ -3612,13 +3528,12 @@ int mpmhip_debug_force(mpmhip_ctx *c, int32_t material, const float params[MPMHI
   GroupParams g;
   int rc = make_group(c, material, params, g);
   if (rc) return rc;
-  float *dF, *dA, *dO;
-  HIPCHK(c, dmalloc(&dF, 9 * n)); HIPCHK(c, dmalloc(&dA, n)); HIPCHK(c, dmalloc(&dO, 9 * n));
+  DevBuf<float> dF, dA, dO;
+  HIPCHK(c, dF.alloc(9 * n)); HIPCHK(c, dA.alloc(n)); HIPCHK(c, dO.alloc(9 * n));
   HIPCHK(c, hipMemcpy(dF, F, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dA, aux, sizeof(float) * n, hipMemcpyHostToDevice));
-  rc = run_debug(c, k_debug_force, g, n, (const float *)dF, (const float *)dA, dO);
+  rc = run_debug(c, k_debug_force, g, n, (const float *)dF, (const float *)dA, dO.get());
   if (!rc) HIPCHK(c, hipMemcpy(out, dO, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
-  hipFree(dF); hipFree(dA); hipFree(dO);
   return rc;
 }
 
@@ -3629,19 +3544,18 @@ int mpmhip_debug_plasticity(mpmhip_ctx *c, int32_t material, const float params[
   GroupParams g;
   int rc = make_group(c, material, params, g);
   if (rc) return rc;
-  float *dC, *dF, *dA, *dO = nullptr;
-  HIPCHK(c, dmalloc(&dC, 9 * n)); HIPCHK(c, dmalloc(&dF, 9 * n)); HIPCHK(c, dmalloc(&dA, n));
-  if (next_force) HIPCHK(c, dmalloc(&dO, 9 * n));
+  DevBuf<float> dC, dF, dA, dO;
+  HIPCHK(c, dC.alloc(9 * n)); HIPCHK(c, dF.alloc(9 * n)); HIPCHK(c, dA.alloc(n));
+  if (next_force) HIPCHK(c, dO.alloc(9 * n));
   HIPCHK(c, hipMemcpy(dC, cdg, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dF, F, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dA, aux, sizeof(float) * n, hipMemcpyHostToDevice));
-  rc = run_debug(c, k_debug_plasticity, g, n, (const float *)dC, dF, dA, dO);
+  rc = run_debug(c, k_debug_plasticity, g, n, (const float *)dC, dF.get(), dA.get(), dO.get());
   if (!rc) {
     HIPCHK(c, hipMemcpy(F, dF, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(aux, dA, sizeof(float) * n, hipMemcpyDeviceToHost));
     if (next_force) HIPCHK(c, hipMemcpy(next_force, dO, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
   }
-  hipFree(dC); hipFree(dF); hipFree(dA); hipFree(dO);
   return rc;
 }
 

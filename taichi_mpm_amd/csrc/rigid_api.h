@@ -94,19 +94,20 @@ static int rigid_enable(mpmhip_ctx *c) {
   R.max_pages = (R.max_pages + CDF_POOLS - 1) / CDF_POOLS * CDF_POOLS;
   const int rpd[3] = {c->P.res[0] / 4 + 2, c->P.res[1] / 4 + 2, c->P.res[2] / 8 + 2};
   R.rpage_words = ((size_t)rpd[0] * rpd[1] * rpd[2] + 31) / 32;
-  A(dmalloc(&R.d_rb, (size_t)MAX_RIGID));
-  A(dmalloc(&R.d_joints, (size_t)MAX_JOINTS));
-  A(dmalloc(&R.cdf.slot, (size_t)c->NB));
-  A(dmalloc(&R.cdf.page_key, (size_t)R.max_pages));
-  A(dmalloc(&R.cdf.mind, (size_t)R.max_pages * 64));
-  A(dmalloc(&R.cdf.tags, (size_t)R.max_pages * 64));
-  A(dmalloc(&R.d_counters, (size_t)CDF_POOLS + 4));  // [0, CDF_POOLS) pages handed out per sub-pool, [CDF_POOLS] cutting_counter,
+  A(R.d_rb.alloc((size_t)MAX_RIGID));
+  A(R.d_joints.alloc((size_t)MAX_JOINTS));
+  A(R.cdf_slot.alloc((size_t)c->NB));
+  A(R.cdf_page_key.alloc((size_t)R.max_pages));
+  A(R.cdf_mind.alloc((size_t)R.max_pages * 64));
+  A(R.cdf_tags.alloc((size_t)R.max_pages * 64));
+  A(R.d_counters.alloc((size_t)CDF_POOLS + 4));  // [0, CDF_POOLS) pages handed out per sub-pool, [CDF_POOLS] cutting_counter,
                                                     // [CDF_POOLS + 1] length of d_rigid_list
-  A(dmalloc(&R.cdf.rpage, R.rpage_words));
-  A(dmalloc(&R.d_bnd, (size_t)c->cap));
-  A(dmalloc(&R.d_blk_rigid, (size_t)c->P.max_blocks + 1));
-  A(dmalloc(&R.d_rigid_list, (size_t)c->P.max_blocks + 1));
+  A(R.cdf_rpage.alloc(R.rpage_words));
+  A(R.d_bnd.alloc((size_t)c->cap));
+  A(R.d_blk_rigid.alloc((size_t)c->P.max_blocks + 1));
+  A(R.d_rigid_list.alloc((size_t)c->P.max_blocks + 1));
   if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "rigid coupling: device allocation failed: %s", hipGetErrorString(e));
+  R.cdf.slot = R.cdf_slot; R.cdf.page_key = R.cdf_page_key; R.cdf.mind = R.cdf_mind; R.cdf.tags = R.cdf_tags; R.cdf.rpage = R.cdf_rpage;
   R.cdf.n_pages = R.d_counters; R.cdf.error = &c->cnt->error;
   R.cdf.nb_axis = 1 << c->P.kbits;
   R.cdf.max_pages = R.max_pages;
@@ -142,7 +143,7 @@ static RigidXfer rigid_xfer(mpmhip_ctx *c) {
   RigidXfer X;
   X.C = c->rigid.cdf; X.rb = c->rigid.d_rb; X.bnd = c->rigid.d_bnd; X.imp_rows = c->rigid.d_imp_rows;
   X.rigid_list = c->rigid.d_rigid_list; X.n_rigid = c->rigid.d_counters + CDF_POOLS + 1;
-  X.rp_in = (const float4 *)c->rp;
+  X.rp_in = (const float4 *)c->rp.get();
   X.penalty = c->rigid.penalty; X.pushing_force = c->rigid.pushing_force;
   return X;
 }
@@ -181,8 +182,8 @@ static int rigid_imp_rows(mpmhip_ctx *c) {
   if (R.d_imp_rows && R.imp_rows_cap >= c->P.max_blocks) return MPMHIP_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (R.side) HIPCHK(c, hipStreamSynchronize(R.side));
-  (void)hipFree(R.d_imp_rows); R.d_imp_rows = nullptr; R.imp_rows_cap = 0;
-  HIPCHK(c, dmalloc(&R.d_imp_rows, (size_t)c->P.max_blocks * IMP_ROW));
+  R.imp_rows_cap = 0;
+  HIPCHK(c, R.d_imp_rows.alloc((size_t)c->P.max_blocks * IMP_ROW));
   R.imp_rows_cap = c->P.max_blocks;
   return MPMHIP_OK;
 }
@@ -202,13 +203,12 @@ static int do_rigid_ls_collision(mpmhip_ctx *c) {
   const uint32_t n = R.n_smp;
   if (n == 0 || c->LS.n == 0) return MPMHIP_OK;
   if (R.ls_cap < n) {
-    for (int k = 0; k < 2; k++) { (void)hipFree(R.d_ls_keys[k]); (void)hipFree(R.d_ls_vals[k]); R.d_ls_keys[k] = nullptr; R.d_ls_vals[k] = nullptr; }
-    (void)hipFree(R.d_ls_tmp); R.d_ls_tmp = nullptr; R.ls_tmp_bytes = 0;
+    R.ls_tmp_bytes = 0;
     const size_t cap = (size_t)n + n / 4 + 1024;
-    for (int k = 0; k < 2; k++) { HIPCHK(c, dmalloc(&R.d_ls_keys[k], cap)); HIPCHK(c, dmalloc(&R.d_ls_vals[k], cap)); }
+    for (int k = 0; k < 2; k++) { HIPCHK(c, R.d_ls_keys[k].alloc(cap)); HIPCHK(c, R.d_ls_vals[k].alloc(cap)); }
     size_t bytes = 0;
-    HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, R.d_ls_keys[0], R.d_ls_keys[1], R.d_ls_vals[0], R.d_ls_vals[1], (int)cap, 0, 64, c->stream));
-    HIPCHK(c, hipMalloc(&R.d_ls_tmp, bytes));
+    HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, R.d_ls_keys[0].get(), R.d_ls_keys[1].get(), R.d_ls_vals[0].get(), R.d_ls_vals[1].get(), (int)cap, 0, 64, c->stream));
+    HIPCHK(c, R.d_ls_tmp.alloc(bytes));
     R.ls_tmp_bytes = bytes;
     R.ls_cap = (uint32_t)cap;
   }
@@ -219,8 +219,7 @@ static int do_rigid_ls_collision(mpmhip_ctx *c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (R.n_ranked) HIPCHK(c, hipMemcpy(rk.data(), R.d_smp_rank, sizeof(uint32_t) * R.n_ranked, hipMemcpyDeviceToHost));
     for (uint32_t s = R.n_ranked; s < n; s++) rk[s] = s;
-    (void)hipFree(R.d_smp_rank); R.d_smp_rank = nullptr;
-    HIPCHK(c, dmalloc(&R.d_smp_rank, (size_t)n + n / 4 + 1024));
+    HIPCHK(c, R.d_smp_rank.alloc((size_t)n + n / 4 + 1024));
     HIPCHK(c, hipMemcpy(R.d_smp_rank, rk.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     R.n_ranked = n;
   }
@@ -228,7 +227,7 @@ static int do_rigid_ls_collision(mpmhip_ctx *c) {
   hipLaunchKernelGGL(k_rigid_ls_keys, dim3(particle_grid(n)), dim3(256), 0, c->stream, c->P, (const RigidBodyDev *)R.d_rb,
                      (const RigidSample *)R.d_smp, n, (const uint32_t *)R.d_smp_rank, R.d_ls_keys[0], R.d_ls_vals[0]);
   size_t bytes = R.ls_tmp_bytes;
-  HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(R.d_ls_tmp, bytes, R.d_ls_keys[0], R.d_ls_keys[1], R.d_ls_vals[0], R.d_ls_vals[1], (int)n, 0, 64, c->stream));
+  HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(R.d_ls_tmp, bytes, R.d_ls_keys[0].get(), R.d_ls_keys[1].get(), R.d_ls_vals[0].get(), R.d_ls_vals[1].get(), (int)n, 0, 64, c->stream));
   RigidRestitution rest;
   memset(&rest, 0, sizeof rest);
   for (size_t b = 1; b < R.bodies.size(); b++) rest.e[b] = R.bodies[b].cfg.restitution;
@@ -388,10 +387,8 @@ int mpmhip_add_rigid_body(mpmhip_ctx *c, const mpmhip_rigid_config *cfg, int64_t
   B.first_elem = (int64_t)elem0; B.n_elems = n_triangles;
   R.h_elems.insert(R.h_elems.end(), tri.begin(), tri.end());
   // (re)upload samples and elements
-  (void)hipFree(R.d_smp); (void)hipFree(R.d_elems);
-  R.d_smp = nullptr; R.d_elems = nullptr;
-  HIPCHK(c, dmalloc(&R.d_smp, std::max<size_t>(R.h_smp.size(), 1)));
-  HIPCHK(c, dmalloc(&R.d_elems, std::max<size_t>(R.h_elems.size(), 9)));
+  HIPCHK(c, R.d_smp.alloc(std::max<size_t>(R.h_smp.size(), 1)));
+  HIPCHK(c, R.d_elems.alloc(std::max<size_t>(R.h_elems.size(), 9)));
   if (!R.h_smp.empty()) HIPCHK(c, hipMemcpy(R.d_smp, R.h_smp.data(), sizeof(RigidSample) * R.h_smp.size(), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(R.d_elems, R.h_elems.data(), sizeof(float) * R.h_elems.size(), hipMemcpyHostToDevice));
   R.n_smp = (uint32_t)R.h_smp.size();
@@ -440,14 +437,12 @@ int64_t mpmhip_rigid_get_samples(mpmhip_ctx *c, int32_t id, int64_t cap, float *
   auto &R = c->rigid;
   std::vector<float> w((size_t)R.n_smp * 3);
   if (R.n_smp && pos) {
-    float *d = nullptr;
-    HIPCHK(c, dmalloc(&d, (size_t)R.n_smp * 3));
+    DevBuf<float> d;
+    HIPCHK(c, d.alloc((size_t)R.n_smp * 3));
     hipLaunchKernelGGL(k_rigid_sample_positions, dim3(particle_grid(R.n_smp)), dim3(256), 0, c->stream, (const RigidBodyDev *)R.d_rb,
                        (const RigidSample *)R.d_smp, R.n_smp, d);
-    hipError_t e = hipMemcpyAsync(w.data(), d, sizeof(float) * w.size(), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    HIPCHK(c, e);
+    HIPCHK(c, hipMemcpyAsync(w.data(), d, sizeof(float) * w.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   int64_t n = 0;
   for (size_t s = 0; s < R.h_smp.size(); s++) {
@@ -556,20 +551,16 @@ int mpmhip_download_cdf(mpmhip_ctx *c, uint32_t *states, float *distance) {
   memset(states, 0, nodes * 4);
   memset(distance, 0, nodes * 4);
   if (!c->rigid.enabled) return MPMHIP_OK;
-  uint32_t *ds = nullptr;
-  float *dd = nullptr;
-  HIPCHK(c, dmalloc(&ds, nodes));
-  hipError_t e = dmalloc(&dd, nodes);
-  if (e == hipSuccess) e = hipMemsetAsync(ds, 0, nodes * 4, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(dd, 0, nodes * 4, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_cdf_dense, dim3(1024), dim3(256), 0, c->stream, c->P, c->rigid.cdf, ds, dd);
-    e = hipMemcpyAsync(states, ds, nodes * 4, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(distance, dd, nodes * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(ds); (void)hipFree(dd);
-  HIPCHK(c, e);
+  DevBuf<uint32_t> ds;
+  DevBuf<float> dd;
+  HIPCHK(c, ds.alloc(nodes));
+  HIPCHK(c, dd.alloc(nodes));
+  HIPCHK(c, hipMemsetAsync(ds, 0, nodes * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(dd, 0, nodes * 4, c->stream));
+  hipLaunchKernelGGL(k_cdf_dense, dim3(1024), dim3(256), 0, c->stream, c->P, c->rigid.cdf, ds, dd);
+  HIPCHK(c, hipMemcpyAsync(states, ds, nodes * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(distance, dd, nodes * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return MPMHIP_OK;
 }
 // what gather_cdf left for every live particle, in slot order (like mpmhip_download): boundary_normal 3, boundary_distance,

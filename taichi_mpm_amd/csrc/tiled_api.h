@@ -318,7 +318,7 @@ int tn_mig_a(mpmhip_ctx *c) {
                      (uint32_t)std::min<uint64_t>(N.inbox_cap, 0xFFFFFFFFull));
   int grid = particle_grid(c->n_slots);
   if (grid > 128) grid = 128;
-  hipLaunchKernelGGL(k_leaver_count, dim3(grid), dim3(256), 0, c->stream, c->P, c->T, (const float4 *)c->rg, (const float4 *)c->rp,
+  hipLaunchKernelGGL(k_leaver_count, dim3(grid), dim3(256), 0, c->stream, c->P, c->T, (const float4 *)c->rg.get(), (const float4 *)c->rp.get(),
                      c->d_counts, reinterpret_cast<int *>(c->d_counts + world), c->cnt);
   if ((rc = launch_check(c, "leaver_count"))) return rc;
   uint32_t *table = N.table[N.mig_epoch & 1];
@@ -377,10 +377,8 @@ int tn_mig_b(mpmhip_ctx *c) {
   if (total == 0) return MPMHIP_OK;
   // records: grouped by destination in mig_send (k_leaver_pack), then one message per destination
   if ((size_t)M.n_out > N.mig_send_cap) {
-    if (N.mig_send) (void)hipFree(N.mig_send);
-    N.mig_send = nullptr;
     N.mig_send_cap = (size_t)M.n_out + (size_t)M.n_out / 2 + 4096;
-    HIPCHK(c, dmalloc(&N.mig_send, N.mig_send_cap * 11));
+    HIPCHK(c, N.mig_send.alloc(N.mig_send_cap * 11));
   }
   for (int s = 0; s < world; s++) {  // every rank sees every inbox: all refuse together, BEFORE anybody writes beyond one
     int64_t arriving = 0;
@@ -560,7 +558,7 @@ int tn_reduce_put(mpmhip_ctx *c, const double *vals, int n, int op) {
   const int par = (int)(N.red_epoch & 1u);
   for (int p = 0; p < N.world; p++) {
     const auto &P = N.peers[p];
-    L.src[p] = reinterpret_cast<const uint32_t *>(N.d_red);
+    L.src[p] = reinterpret_cast<const uint32_t *>(N.d_red.get());
     L.dst[p] = reinterpret_cast<uint32_t *>(P.red[par] + (size_t)c->T.rank * TN_RED_N);
     L.flag[p] = P.flags + 3 * TN_MAX_WORLD + c->T.rank;
     L.words[p] = 2u * (uint32_t)TN_RED_N;
@@ -611,6 +609,16 @@ int tn_energy(mpmhip_ctx *c, double out[3]) {
   return tn_reduce_finish(c, out, 3, MPMHIP_REDUCE_SUM);
 }
 
+// the arena, with the mappings of the peers' arenas
+void tn_drop_arena(mpmhip_ctx::TiledNative &N) {
+  for (auto &p : N.peers)
+    if (p.ipc_base) (void)hipIpcCloseMemHandle(p.ipc_base);
+  N.peers.clear();
+  (void)hipFree(N.arena);  // the one array the host layer frees by hand (TiledNative::arena)
+  N.arena = nullptr;
+  N.handle_valid = false;
+}
+
 // keep_ipc (an IPC job set up again, mpmhip_tiled_setup): the arena, its handle and the mappings of the peers' arenas stay in the
 // ctx for the new set-up to take over or release.  Freeing an exported arena and exporting / opening a fresh one in the same
 // processes is not reliable in the HIP runtime: a re-wired two-rank job then waited in vain for its peer's epochs, or the export
@@ -618,20 +626,7 @@ int tn_energy(mpmhip_ctx *c, double out[3]) {
 void tn_release(mpmhip_ctx *c, bool keep_ipc) {
   auto &N = c->tn;
   keep_ipc = keep_ipc && N.wire == MPMHIP_WIRE_IPC && N.arena;
-  if (!keep_ipc) {
-    for (auto &p : N.peers)
-      if (p.ipc_base) (void)hipIpcCloseMemHandle(p.ipc_base);
-    N.peers.clear();
-    if (N.arena) (void)hipFree(N.arena);
-  }
-  if (N.send) (void)hipFree(N.send);
-  if (N.mig_send) (void)hipFree(N.mig_send);
-  if (N.row) (void)hipFree(N.row);
-  for (int k = 0; k < 2; k++) if (N.d_boxes[k]) (void)hipFree(N.d_boxes[k]);
-  if (N.d_halo_idx) (void)hipFree(N.d_halo_idx);
-  if (N.d_all_idx) (void)hipFree(N.d_all_idx);
-  if (N.d_done) (void)hipFree(N.d_done);
-  if (N.d_red) (void)hipFree(N.d_red);
+  if (!keep_ipc) tn_drop_arena(N);
   if (N.side) { (void)hipStreamSynchronize(N.side); (void)hipStreamDestroy(N.side); }
   if (N.ev_a) (void)hipEventDestroy(N.ev_a);
   if (N.ev_b) (void)hipEventDestroy(N.ev_b);
@@ -645,7 +640,7 @@ void tn_release(mpmhip_ctx *c, bool keep_ipc) {
     memcpy(kept.handle, N.handle, sizeof kept.handle);
     kept.handle_valid = N.handle_valid;
   }
-  N = std::move(kept);
+  N = std::move(kept);  // (releases this set-up's own arrays)
 }
 
 void tn_free(mpmhip_ctx *c) { tn_release(c, false); }
@@ -699,13 +694,12 @@ int mpmhip_comm_selftest(mpmhip_ctx *c) {
   RcclApi *R = rccl_api();
   HIPCHK(c, hipSetDevice(c->device));
   const int world = N.comm_world, me = N.comm_rank, n = 1024;
-  uint32_t *d = nullptr;
-  HIPCHK(c, dmalloc(&d, (size_t)n * (world + 3)));
+  DevBuf<uint32_t> d;
+  HIPCHK(c, d.alloc((size_t)n * (world + 3)));
   std::vector<uint32_t> h((size_t)n * (world + 3));
   for (int i = 0; i < n; i++) h[i] = (uint32_t)(me * 1000003 + i);
   hipError_t e = hipMemcpy(d, h.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice);
-  auto bail = [&](int code) { (void)hipFree(d); return code; };
-  if (e != hipSuccess) return bail(fail(c, MPMHIP_EHIP, "selftest upload: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return fail(c, MPMHIP_EHIP, "selftest upload: %s", hipGetErrorString(e));
   uint32_t *gathered = d + n, *ring = d + (size_t)n * (world + 1), *ring_out = ring + n;
   ncclResult_t r = R->AllGather(d, gathered, n, ncclUint32, (ncclComm_t)N.comm, c->stream);
   const int next = (me + 1) % world, prev = (me + world - 1) % world;
@@ -715,21 +709,21 @@ int mpmhip_comm_selftest(mpmhip_ctx *c) {
   if (r == ncclSuccess) r = R->GroupEnd();
   // all-reduce (sum) of the first 8 words as uint32: word i becomes sum over ranks of (rank * 1000003 + i), into ring_out
   if (r == ncclSuccess) r = R->AllReduce(d, ring_out, 8, ncclUint32, ncclSum, (ncclComm_t)N.comm, c->stream);
-  if (r != ncclSuccess) return bail(fail(c, MPMHIP_EHIP, "selftest: %s", R->GetErrorString(r)));
+  if (r != ncclSuccess) return fail(c, MPMHIP_EHIP, "selftest: %s", R->GetErrorString(r));
   e = hipMemcpyAsync(h.data(), d, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return bail(fail(c, MPMHIP_EHIP, "selftest read-back: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return fail(c, MPMHIP_EHIP, "selftest read-back: %s", hipGetErrorString(e));
   for (int s = 0; s < world; s++)
     for (int i = 0; i < n; i++)
-      if (h[(size_t)n * (1 + s) + i] != (uint32_t)(s * 1000003 + i)) return bail(fail(c, MPMHIP_EHIP, "selftest: all-gather delivered wrong data (rank %d, word %d)", s, i));
+      if (h[(size_t)n * (1 + s) + i] != (uint32_t)(s * 1000003 + i)) return fail(c, MPMHIP_EHIP, "selftest: all-gather delivered wrong data (rank %d, word %d)", s, i);
   for (int i = 0; i < n; i++)
-    if (h[(size_t)n * (world + 1) + i] != (uint32_t)(prev * 1000003 + i)) return bail(fail(c, MPMHIP_EHIP, "selftest: send / receive delivered wrong data (word %d)", i));
+    if (h[(size_t)n * (world + 1) + i] != (uint32_t)(prev * 1000003 + i)) return fail(c, MPMHIP_EHIP, "selftest: send / receive delivered wrong data (word %d)", i);
   for (int i = 0; i < 8; i++) {
     uint32_t want = 0;
     for (int s = 0; s < world; s++) want += (uint32_t)(s * 1000003 + i);
-    if (h[(size_t)n * (world + 2) + i] != want) return bail(fail(c, MPMHIP_EHIP, "selftest: all-reduce delivered wrong data (word %d)", i));
+    if (h[(size_t)n * (world + 2) + i] != want) return fail(c, MPMHIP_EHIP, "selftest: all-reduce delivered wrong data (word %d)", i);
   }
-  return bail(MPMHIP_OK);
+  return MPMHIP_OK;
 }
 
 int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int32_t *cuts_x, const int32_t *cuts_y, const int32_t *cuts_z) {
@@ -785,14 +779,7 @@ int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int3
   const size_t recv_bytes = ((sizeof(float4) * N.halo_cap + 255) / 256) * 256;
   N.arena_bytes = TN_FLAG_BYTES + TN_RED_BYTES + 2 * table_bytes + 2 * recv_bytes + sizeof(float4) * 11 * N.inbox_cap;
   const bool peer_wire = N.wire == MPMHIP_WIRE_IPC || N.wire == MPMHIP_WIRE_LOCAL;
-  if (N.arena && (kept_bytes != N.arena_bytes || N.peers.size() != (size_t)N.world)) {
-    for (auto &p : N.peers)
-      if (p.ipc_base) (void)hipIpcCloseMemHandle(p.ipc_base);
-    N.peers.clear();
-    (void)hipFree(N.arena);
-    N.arena = nullptr;
-    N.handle_valid = false;
-  }
+  if (N.arena && (kept_bytes != N.arena_bytes || N.peers.size() != (size_t)N.world)) tn_drop_arena(N);
   std::vector<mpmhip_ctx::TiledNative::Peer> mapped;  // (the kept mappings of the peers' arenas)
   mapped.swap(N.peers);
   hipError_t e = hipSuccess;
@@ -821,14 +808,14 @@ int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int3
       N.peers[p].ipc_base = mapped[p].ipc_base;
       memcpy(N.peers[p].handle, mapped[p].handle, sizeof mapped[p].handle);
     }
-  if (!peer_wire || N.loop_rccl) HIPCHK(c, dmalloc(&N.send, (size_t)N.halo_cap));
-  HIPCHK(c, dmalloc(&N.row, (size_t)TN_ROW));
+  if (!peer_wire || N.loop_rccl) HIPCHK(c, N.send.alloc((size_t)N.halo_cap));
+  HIPCHK(c, N.row.alloc((size_t)TN_ROW));
   HIPCHK(c, hipMemset(N.row, 0, sizeof(uint32_t) * TN_ROW));
-  for (int k = 0; k < 2; k++) HIPCHK(c, dmalloc(&N.d_boxes[k], (size_t)MPMHIP_MAX_HALO_BOXES));
-  HIPCHK(c, dmalloc(&N.d_halo_idx, (size_t)MPMHIP_MAX_HALO_BOXES));
-  HIPCHK(c, dmalloc(&N.d_all_idx, (size_t)TN_MAX_WORLD));
-  HIPCHK(c, dmalloc(&N.d_red, (size_t)TN_RED_N * (TN_MAX_WORLD + 1)));
-  HIPCHK(c, dmalloc(&N.d_done, (size_t)TN_MAX_WORLD + 1));
+  for (int k = 0; k < 2; k++) HIPCHK(c, N.d_boxes[k].alloc((size_t)MPMHIP_MAX_HALO_BOXES));
+  HIPCHK(c, N.d_halo_idx.alloc((size_t)MPMHIP_MAX_HALO_BOXES));
+  HIPCHK(c, N.d_all_idx.alloc((size_t)TN_MAX_WORLD));
+  HIPCHK(c, N.d_red.alloc((size_t)TN_RED_N * (TN_MAX_WORLD + 1)));
+  HIPCHK(c, N.d_done.alloc((size_t)TN_MAX_WORLD + 1));
   HIPCHK(c, hipMemset(N.d_done, 0, sizeof(uint32_t) * (TN_MAX_WORLD + 1)));
   N.all_ranks.resize((size_t)N.world);
   for (int r = 0; r < N.world; r++) N.all_ranks[r] = r;
@@ -870,17 +857,14 @@ int mpmhip_tiled_ipc_connect(mpmhip_ctx *c, const uint8_t *handles) {
     uint8_t mine[MPMHIP_IPC_HANDLE_BYTES];
     int rc = mpmhip_tiled_ipc_handle(c, mine);
     if (rc) return rc;
-    uint8_t *d = nullptr;
-    HIPCHK(c, dmalloc(&d, (size_t)MPMHIP_IPC_HANDLE_BYTES * (N.world + 1)));
-    hipError_t e = hipMemcpy(d, mine, sizeof mine, hipMemcpyHostToDevice);
-    ncclResult_t r = ncclSuccess;
-    if (e == hipSuccess) r = rccl_api()->AllGather(d, d + MPMHIP_IPC_HANDLE_BYTES, MPMHIP_IPC_HANDLE_BYTES, ncclUint8, (ncclComm_t)N.comm, c->stream);
-    gathered.resize((size_t)MPMHIP_IPC_HANDLE_BYTES * N.world);
-    if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(gathered.data(), d + MPMHIP_IPC_HANDLE_BYTES, gathered.size(), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && r == ncclSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
+    DevBuf<uint8_t> d;
+    HIPCHK(c, d.alloc((size_t)MPMHIP_IPC_HANDLE_BYTES * (N.world + 1)));
+    HIPCHK(c, hipMemcpy(d, mine, sizeof mine, hipMemcpyHostToDevice));
+    const ncclResult_t r = rccl_api()->AllGather(d, d + MPMHIP_IPC_HANDLE_BYTES, MPMHIP_IPC_HANDLE_BYTES, ncclUint8, (ncclComm_t)N.comm, c->stream);
     if (r != ncclSuccess) return fail(c, MPMHIP_EHIP, "all-gather of the IPC handles: %s", rccl_api()->GetErrorString(r));
-    HIPCHK(c, e);
+    gathered.resize((size_t)MPMHIP_IPC_HANDLE_BYTES * N.world);
+    HIPCHK(c, hipMemcpyAsync(gathered.data(), d + MPMHIP_IPC_HANDLE_BYTES, gathered.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     handles = gathered.data();
   }
   const size_t table_bytes = N.table_bytes, recv_bytes = N.recv_bytes;
@@ -1101,7 +1085,7 @@ static int tn_totals_local(mpmhip_ctx *c, double v[8]) {
   Counters h;
   HIPCHK(c, hipSetDevice(c->device));
   // (the error word is read as it is: read_counters would turn a set bit into this rank's failure before the others have seen it)
-  Counters *pin = reinterpret_cast<Counters *>(c->h_pinned);
+  Counters *pin = reinterpret_cast<Counters *>(c->h_pinned.get());
   HIPCHK(c, hipMemcpyAsync(pin, c->cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   h = *pin;
