@@ -121,12 +121,7 @@ static int async_drop_view(mpmhip_ctx *c) {
   auto &A = c->async;
   if (!A.resident || !A.records_are_view) return MPMHIP_OK;
   A.records_are_view = false;
-  c->n_slots = 0; c->P.n_slots = 0;
-  const uint32_t zero = 0;
-  HIPCHK(c, hipMemcpy(&c->cnt->n_dead, &zero, sizeof zero, hipMemcpyHostToDevice));
-  c->affine_valid = false; c->b_stale = false;
-  c->keys_valid = true;
-  return invalidate_keys(c);
+  return drop_records(c, DEAD_ZERO_SYNC);
 }
 
 // AsyncMPM<dim>::initialize (src/async/async_mpm.cpp:13-55) on top of mpmhip_async_enable: the pools become device-resident
@@ -172,12 +167,7 @@ int mpmhip_async_pool_particles(mpmhip_ctx *c) {
   if (int rc = launch_check(c, "async_file")) return rc;
   AsyncCounters h;
   if (int rc = async_counters(c, h, true)) return rc;
-  c->n_slots = 0; c->P.n_slots = 0;  // (creation ids keep counting: next_pid stays)
-  const uint32_t zero = 0;
-  HIPCHK(c, hipMemcpy(&c->cnt->n_dead, &zero, sizeof zero, hipMemcpyHostToDevice));
-  c->affine_valid = false; c->b_stale = false;
-  c->keys_valid = true;
-  return invalidate_keys(c);
+  return drop_records(c, DEAD_ZERO_SYNC);  // (creation ids keep counting: next_pid stays)
 }
 
 // AsyncMPM<dim>::update_dt_limits (src/async/async_mpm.cpp:90-253) over the resident pools
@@ -229,13 +219,10 @@ static int async_advance(mpmhip_ctx *c, int64_t limit) {
   if ((int64_t)n_work > c->cap) return fail(c, MPMHIP_ECAPACITY, "async: a working set of %u particles exceeds the ctx capacity %lld", n_work, (long long)c->cap);
   A.update_counter += n_work;
   // ONE ordinary substep of the working set with this level's dt (:327-329; step() sets base_delta_t / current_t, :405-408)
-  c->n_slots = n_work; c->P.n_slots = n_work;
-  HIPCHK(c, hipMemsetAsync(&c->cnt->n_dead, 0, sizeof(uint32_t), c->stream));
+  if (int rc = drop_records(c, DEAD_ZERO_ON_STREAM)) return rc;  // the gather replaced the records by the working set
+  set_slots(c, n_work);
   c->P.dt = A.cfg.unit_delta_t * (float)limit;
   c->t = A.cfg.unit_delta_t * (float)t;
-  c->affine_valid = false; c->b_stale = false;
-  c->keys_valid = true;
-  if (int rc = invalidate_keys(c)) return rc;
   if (n_work) {
     AsTimer sub(A.prof_ms[3]);
     if (int rc = mpmhip_substep(c)) return rc;
@@ -286,7 +273,7 @@ int mpmhip_async_step(mpmhip_ctx *c, float dt) {
     A.finish_round();
   } while (A.current_t < A.request_t);
   if (int rc = async_settle(c)) return rc;
-  c->n_slots = 0; c->P.n_slots = 0;  // the records held the last working set: the state is in the pools
+  set_slots(c, 0);  // the records held the last working set: the state is in the pools
   c->t = A.current_t;
   A.step_counter++;
   return MPMHIP_OK;
@@ -381,14 +368,10 @@ int mpmhip_async_load_pools(mpmhip_ctx *c) {
   if (int rc = launch_check(c, "async_load")) return rc;
   AsyncCounters h;
   if (int rc = async_counters(c, h, true)) return rc;
-  c->n_slots = h.n_work; c->P.n_slots = h.n_work;
+  if (int rc = drop_records(c, DEAD_ZERO_SYNC)) return rc;  // k_async_load replaced the records by the view
+  set_slots(c, h.n_work);
   A.records_are_view = true;
-  const uint32_t zero = 0;
-  HIPCHK(c, hipMemcpy(&c->cnt->n_dead, &zero, sizeof zero, hipMemcpyHostToDevice));
   c->P.dt = c->cfg.dt;  // (the P2G matrices are rebuilt for the configured base step if anybody runs a synchronous substep)
-  c->affine_valid = false; c->b_stale = false;
-  c->keys_valid = true;
-  if (int rc = invalidate_keys(c)) return rc;
   // the frame's `limit` attribute: the limits of the container's POOL block
   if (c->n_slots) {
     std::vector<int32_t> lim(3 * nblk);
@@ -537,9 +520,7 @@ int mpmhip_async_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
   A.request_t = h.request_t; A.current_t = h.current_t;
   A.limits_version++;  // (the neighbour lists are rebuilt from the loaded limits at the next update)
   c->next_pid = h.next_pid;
-  c->n_slots = 0; c->P.n_slots = 0;
   c->t = A.current_t;
-  c->affine_valid = false; c->b_stale = false;
-  c->keys_valid = true;
-  return invalidate_keys(c);
+  // (the one drop that leaves n_dead alone: a count left by the last working set stays until the next advance zeroes it)
+  return drop_records(c, DEAD_KEEP);
 }

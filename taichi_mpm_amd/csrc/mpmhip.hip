@@ -5,6 +5,8 @@
 //   k_bgeo.h (.bgeo frame rows)   k_mpm88.h (the 2D dense-grid demo, its own small object)
 // host_mem.h: DevBuf / PinnedBuf, the owners of every device and pinned array of the objects below (a new array needs a field and
 // its allocation, nothing else); what a kernel takes by value keeps raw pointers into them.
+// record_state.h: RecordState, the owner of the ctx's validity flags (which arrays describe the current particles); the host code
+// changes them through its named transitions only.
 //
 // One substep (reference: MPM<3>::substep, src/mpm.cpp:452-575):
 //
@@ -74,6 +76,7 @@
 
 
 #include "host_mem.h"
+#include "record_state.h"
 #include "mpm_common.h"
 #include "k_sort.h"
 #include "k_particles.h"
@@ -162,16 +165,10 @@ struct mpmhip_ctx {
   std::vector<GroupParams> groups;
   DevBuf<GroupParams> d_groups;
   int groups_cap = G2P_LDS_GROUPS;  // k_g2p mirrors the whole table in LDS
-  bool sorted = false;        // perm / cell_start describe the current positions
-  bool keys_valid = false;    // key[] + block flags describe the current positions (set by k_g2p)
+  RecordState rec;            // which arrays describe the current particles (record_state.h)
   DevBuf<uint32_t> pidc;      // creation id per slot beside key[] (Params::pidc points here while the deterministic mode is on)
   int cell_order_wgs = 24;    // env MPMHIP_CELL_ORDER_WGS: workgroups per CU of k_cell_order_blocks' launch
   int cell_order_form = 1;    // env MPMHIP_CELL_ORDER: 1 k_cell_order_blocks (a wave per block through LDS), 0 k_cell_order (a lane per cell)
-  bool pidc_valid = false;    // ... and was written together with the current key[] (every key writer does while Params::pidc is set)
-  bool affine_valid = false;  // RecP.A matches (F, aux, apic_b)
-  bool b_stale = false;       // discard_apic_b: the side array is behind RecP.A (k_g2p did not write it)
-  bool ordered = false;       // the records lie in the order of the last sort (k_g2p wrote them at their sorted positions)
-  bool compact = false;       // ... and the live ones occupy exactly [0, cnt->n_sorted): n_slots may shrink to that
   int p2g_wgs = 16384;        // workgroups of k_p2g (env MPMHIP_P2G_WGS)
   int g2p_wgs = 0;            // workgroups of k_g2p; 0: by size (env MPMHIP_G2P_WGS pins it)
   int n_cus = 256;            // compute units of the device
@@ -342,6 +339,13 @@ struct mpmhip_ctx {
   } tn;
 };
 namespace { void tn_free(mpmhip_ctx *c); void tn_begin_substep(mpmhip_ctx *c); }
+
+// what Params mirrors of the ctx: the slot count, and the id cache beside key[] while the deterministic mode is on
+static void set_slots(mpmhip_ctx *c, int64_t n) {
+  c->n_slots = n;
+  c->P.n_slots = (uint32_t)n;
+}
+static void sync_pidc(mpmhip_ctx *c) { c->P.pidc = c->deterministic ? c->pidc.get() : nullptr; }
 
 static int fail(mpmhip_ctx *c, int code, const char *fmt, ...) {
   char buf[512];
@@ -603,7 +607,7 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
          (long long)c->cap, (long long)mb);
     return bail(MPMHIP_ENOMEM);
   }
-  P.pidc = c->deterministic ? c->pidc : nullptr;
+  sync_pidc(c);
   A(hipMemset(c->bits, 0, sizeof(uint32_t) * P.nbw));
   A(hipMemset(c->blk_flag, 0, (size_t)P.nbw * 32));
   A(hipMemset(c->cell_cnt, 0, sizeof(uint32_t) * (size_t)mb * BC));
@@ -674,8 +678,8 @@ int mpmhip_set_deterministic(mpmhip_ctx *c, int32_t enabled) {
   if (!c) return MPMHIP_EINVAL;
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "set_deterministic inside a substep");
   c->deterministic = enabled != 0;
-  c->P.pidc = c->deterministic ? c->pidc : nullptr;  // (the key writers keep the ids beside the keys from now on; until a G2P has, k_cell_order reads the records)
-  c->pidc_valid = false;
+  sync_pidc(c);  // (the key writers keep the ids beside the keys from now on; until a G2P has, k_cell_order reads the records)
+  c->rec.id_cache_dropped();
   return MPMHIP_OK;
 }
 
@@ -864,15 +868,21 @@ int mpmhip_add_group(mpmhip_ctx *c, int32_t material, const float params[MPMHIP_
 // The particle positions changed behind k_g2p's back (uploads, new particles, deletions): key[] and the block flags
 // G2P wrote for the OLD positions must not leak into the next sort — k_build_keys only ORs new flags on top, so stale
 // ones would turn into phantom active blocks (empty tiles, inflated n_active, spurious capacity errors).
-static int invalidate_keys(mpmhip_ctx *c) {
-  c->sorted = false;
-  c->ordered = c->compact = false;
-  c->pidc_valid = false;
-  if (c->keys_valid) {
-    c->keys_valid = false;
-    HIPCHK(c, hipMemsetAsync(c->blk_flag, 0, (size_t)c->P.nbw * 32, c->stream));
-  }
+static int clear_block_flags(mpmhip_ctx *c, bool needed) {  // `needed`: what a RecordState transition returned
+  if (needed) HIPCHK(c, hipMemsetAsync(c->blk_flag, 0, (size_t)c->P.nbw * 32, c->stream));
   return MPMHIP_OK;
+}
+static int invalidate_keys(mpmhip_ctx *c) { return clear_block_flags(c, c->rec.positions_changed()); }
+
+// Every record of the ctx is dropped (the caller may put others in their place: set_slots): no slots, no deleted ones, no array
+// that describes them.  n_dead is zeroed by a blocking copy, or on the ctx stream between the async stepper's launches.
+enum DeadCount { DEAD_ZERO_SYNC, DEAD_ZERO_ON_STREAM, DEAD_KEEP };
+static int drop_records(mpmhip_ctx *c, DeadCount dead) {
+  set_slots(c, 0);
+  const uint32_t zero = 0;
+  if (dead == DEAD_ZERO_SYNC) HIPCHK(c, hipMemcpy(&c->cnt->n_dead, &zero, sizeof zero, hipMemcpyHostToDevice));
+  if (dead == DEAD_ZERO_ON_STREAM) HIPCHK(c, hipMemsetAsync(&c->cnt->n_dead, 0, sizeof(uint32_t), c->stream));
+  return clear_block_flags(c, c->rec.records_dropped());
 }
 
 // synchronise and read the device counters; reports the sticky capacity error
@@ -882,12 +892,11 @@ static int read_counters(mpmhip_ctx *c, Counters &h) {
   HIPCHK(c, hipMemcpyAsync(pin, c->cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   h = *pin;
-  if (c->compact && !c->sorted && !c->in_substep && (int64_t)h.n_sorted < c->n_slots) {
+  if (c->rec.compact() && !c->rec.sorted() && !c->in_substep && (int64_t)h.n_sorted < c->n_slots) {
     // k_g2p left the live records in [0, n_sorted): the slots behind are all dead (particles deleted in earlier substeps)
     const uint32_t tail = (uint32_t)(c->n_slots - (int64_t)h.n_sorted);
     h.n_dead = h.n_dead >= tail ? h.n_dead - tail : 0u;
-    c->n_slots = h.n_sorted;
-    c->P.n_slots = h.n_sorted;
+    set_slots(c, h.n_sorted);
     HIPCHK(c, hipMemcpy(&c->cnt->n_dead, &h.n_dead, sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   if (h.error & 1u)
@@ -911,14 +920,14 @@ static int read_counters(mpmhip_ctx *c, Counters &h) {
 
 // discard_apic_b: bring the apic_b side array up to date from RecP.A before anybody reads it or invalidates A
 static int ensure_b_current(mpmhip_ctx *c) {
-  if (!c->b_stale) return MPMHIP_OK;
-  if (!c->affine_valid) return fail(c, MPMHIP_EINVAL, "internal: apic_b is stale and the affine matrices are invalid");
+  if (!c->rec.b_stale()) return MPMHIP_OK;
+  if (!c->rec.affine_valid()) return fail(c, MPMHIP_EINVAL, "internal: apic_b is stale and the affine matrices are invalid");
   hipLaunchKernelGGL(k_recover_b, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const RecG *)c->rg,
                      (const RecP *)c->rp, c->rb, (const GroupParams *)c->d_groups);
   int rc = launch_check(c, "recover_b");
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->b_stale = false;
+  c->rec.b_recovered();
   return MPMHIP_OK;
 }
 
@@ -963,10 +972,8 @@ int mpmhip_add_particles(mpmhip_ctx *c, int32_t group, int64_t n, const float *x
   HIPCHK(c, hipMemcpy(c->rg + c->n_slots, hg.data(), sizeof(RecG) * n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->rp + c->n_slots, hp.data(), sizeof(RecP) * n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->rb + (size_t)c->n_slots * BW, hb.data(), sizeof(float) * n * BW, hipMemcpyHostToDevice));
-  c->n_slots += n;
-  c->P.n_slots = (uint32_t)c->n_slots;
-  c->affine_valid = false;
-  return invalidate_keys(c);
+  set_slots(c, c->n_slots + n);
+  return clear_block_flags(c, c->rec.particles_appended());
 }
 
 // drop every particle (groups, level set and configuration stay): the asynchronous stepper reloads the working set of
@@ -976,12 +983,8 @@ int mpmhip_clear_particles(mpmhip_ctx *c) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "clear_particles inside a substep");
-  c->n_slots = 0; c->P.n_slots = 0; c->next_pid = 0;
-  c->affine_valid = false; c->b_stale = false;
-  const uint32_t zero = 0;
-  HIPCHK(c, hipMemcpy(&c->cnt->n_dead, &zero, sizeof zero, hipMemcpyHostToDevice));
-  c->keys_valid = true;  // force the flag array to be cleared
-  return invalidate_keys(c);
+  c->next_pid = 0;
+  return drop_records(c, DEAD_ZERO_SYNC);
 }
 // base_delta_t / current_t of the next substeps (AsyncMPM<dim>::step sets both per advance, src/async/async_mpm.cpp:405-408)
 int mpmhip_set_dt(mpmhip_ctx *c, float dt) {
@@ -989,7 +992,7 @@ int mpmhip_set_dt(mpmhip_ctx *c, float dt) {
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "set_dt inside a substep");
   if (int rc = ensure_b_current(c)) return rc;  // the stored P2G matrices carry the old dt: they are rebuilt from apic_b
   c->P.dt = dt;
-  c->affine_valid = false;
+  c->rec.affine_inputs_changed();
   return MPMHIP_OK;
 }
 int mpmhip_set_time(mpmhip_ctx *c, double t) {
@@ -1104,7 +1107,8 @@ int mpmhip_upload(mpmhip_ctx *c, int32_t field, const void *src, int64_t n) {
   HIPCHK(c, hipMemcpy(c->rb, hb.data(), sizeof(float) * ns * BW, hipMemcpyHostToDevice));
   if (field == MPMHIP_F_X || field == MPMHIP_F_V)
     if (int rc = invalidate_keys(c)) return rc;
-  if (field == MPMHIP_F_B || field == MPMHIP_F_F || field == MPMHIP_F_AUX) c->affine_valid = false;
+  if (field == MPMHIP_F_B || field == MPMHIP_F_F || field == MPMHIP_F_AUX) c->rec.affine_inputs_changed();
+  if (field == MPMHIP_F_ID) c->rec.ids_changed(c->deterministic);
   return MPMHIP_OK;
 }
 
@@ -1143,10 +1147,10 @@ static int do_sort(mpmhip_ctx *c) {
   Params &P = c->P;
   hipStream_t st = c->stream;
   const int pg = particle_grid(c->n_slots);
-  if (!c->keys_valid) {
-    hipLaunchKernelGGL(k_build_keys, dim3(pg), dim3(256), 0, st, P, c->rg, c->rp, c->cnt, c->key, c->blk_flag);
-    c->pidc_valid = P.pidc != nullptr;
-  }
+  const bool build_keys = !c->rec.keys_valid();
+  if (build_keys) hipLaunchKernelGGL(k_build_keys, dim3(pg), dim3(256), 0, st, P, c->rg, c->rp, c->cnt, c->key, c->blk_flag);
+  // pidc[] holds the ids of the current key[]: k_build_keys wrote both just now, or the last G2P did
+  const bool ids_cached = P.pidc && (build_keys || c->rec.pidc_valid());
   // blocks per chunk of k_cell_table: few blocks -> finer chunks (shorter chains, more workgroups).  16 below 2 M slots, 64 from 6 M on
   // (16 costs 10 us at 8 M: its 1 100 chunks no longer fit the scans' resident grid), 32 in between — a rank of a 2-brick job
   // holds 4 M particles in 8 788 blocks: 17.4 us with 64 (as long as the whole 8 M problem takes: the kernel is a latency chain)
@@ -1206,14 +1210,13 @@ static int do_sort(mpmhip_ctx *c) {
   if (c->deterministic) {
     // every cell's entries in ascending creation id (k_sort.h: k_cell_order); rank[] is idle until the next sort: the ordered index goes
     // there and then IS the index
-    const bool compact = c->pidc_valid && P.pidc;
     if (c->cell_order_form == 0) {  // (A/B: one lane per cell over the whole table)
       const int cg = (int)std::min<uint64_t>(8192u, ((uint64_t)P.max_blocks * BC + 255) / 256);
-      hipLaunchKernelGGL((compact ? k_cell_order<true> : k_cell_order<false>), dim3(cg), dim3(256), 0, st, P, (const Counters *)c->cnt,
+      hipLaunchKernelGGL((ids_cached ? k_cell_order<true> : k_cell_order<false>), dim3(cg), dim3(256), 0, st, P, (const Counters *)c->cnt,
                          (const uint32_t *)c->cell_start, (const uint32_t *)c->perm, (const float4 *)c->rg.get(), c->rank);
     } else {  // one wave per active block through LDS: 7 workgroups per CU resident (22 KiB each), a few blocks per wave
       const int cg = (int)std::min<uint64_t>((uint64_t)c->n_cus * (uint64_t)c->cell_order_wgs, ((uint64_t)P.max_blocks + 3) / 4);
-      hipLaunchKernelGGL((compact ? k_cell_order_blocks<true> : k_cell_order_blocks<false>), dim3(std::max(1, cg)), dim3(256), 0, st, P,
+      hipLaunchKernelGGL((ids_cached ? k_cell_order_blocks<true> : k_cell_order_blocks<false>), dim3(std::max(1, cg)), dim3(256), 0, st, P,
                          (const Counters *)c->cnt, (const uint32_t *)c->cell_start, (const uint32_t *)c->perm, (const float4 *)c->rg.get(), c->rank);
     }
     std::swap(c->perm, c->rank);
@@ -1221,16 +1224,14 @@ static int do_sort(mpmhip_ctx *c) {
   // (k_cell_table's last chunk stores (live particles, active blocks, owner entries) of this sort straight into the pinned page,
   // never waited for: the host picks the G2P walk by how full the blocks are (g2p_is_packed) and sizes the grid pass's launch
   // from numbers that may be a few substeps old)
-  c->sorted = true;
-  c->keys_valid = false;  // key[] now holds k_rank's packed (rank, cell index) words
-  c->pidc_valid = false;
+  c->rec.sort_done();  // (key[] now holds k_rank's packed (rank, cell index) words)
   int rc = launch_check(c, "sort");
   if (rc) return rc;
   // sort_allocator (src/mpm.cpp:752-768, every reorder_interval substeps :811-813): needed here only for records that
   // did not come out of k_g2p (fresh uploads, arrivals of a migration) — k_g2p itself leaves the records in sorted order
   // every substep, so a running simulation never pays for a separate reorder (nor for its host synchronisation)
   // (not for the working sets of the resident asynchronous stepper: they live for ONE substep)
-  if ((c->reorder_interval > 0 && !c->ordered && !c->async.resident) || c->compact_requested) {
+  if ((c->reorder_interval > 0 && !c->rec.ordered() && !c->async.resident) || c->compact_requested) {
     c->compact_requested = false;
     return do_reorder(c);
   }
@@ -1249,9 +1250,8 @@ static int do_reorder(mpmhip_ctx *c) {
   Counters h;
   if ((rc = read_counters(c, h))) return rc;
   std::swap(c->rg, c->rg2); std::swap(c->rp, c->rp2); std::swap(c->rb, c->rb2);
-  c->ordered = true;
-  c->n_slots = h.n_sorted;
-  c->P.n_slots = h.n_sorted;
+  c->rec.reordered();
+  set_slots(c, h.n_sorted);
   const uint32_t zero = 0;
   HIPCHK(c, hipMemcpy(&c->cnt->n_dead, &zero, sizeof zero, hipMemcpyHostToDevice));
   return MPMHIP_OK;
@@ -1295,10 +1295,10 @@ static int do_rigid_apply_tmp(mpmhip_ctx *c);
 static int rigid_imp_rows(mpmhip_ctx *c);
 
 static int do_p2g(mpmhip_ctx *c, int phase = 0) {
-  if (!c->affine_valid) {
+  if (!c->rec.affine_valid()) {
     hipLaunchKernelGGL(k_affine, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, c->rg, c->rp, c->rb,
                        c->d_groups);
-    c->affine_valid = true;
+    c->rec.affine_rebuilt();
   }
   // one wavefront per block (all 27 nodes, all particles) measured fastest at 256^3 / 8 M: 0.187 ms against
   // 0.237 (two waves splitting the nodes) and 0.225 (two waves splitting the particles).  Splitting the particles does
@@ -1414,9 +1414,7 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
     hipLaunchKernelGGL(pk, dim3(wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(),
                        (float4 *)c->rb2.get(), c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
                        c->blk_flag, (const LevelSetDev *)c->d_LS, (const uint32_t *)c->chunk_blk);
-    c->sorted = false; c->keys_valid = true; c->affine_valid = true;
-    c->pidc_valid = c->P.pidc != nullptr;
-    if (!c->P.store_b) c->b_stale = true;
+    c->rec.g2p_done(sb, c->P.pidc != nullptr);
     return launch_check(c, "g2p_packed");
   }
   hipStream_t rs = c->stream;
@@ -1438,11 +1436,7 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
     if (int rc = rigid_join(c, rs)) return rc;
     if (int rc = do_rigid_apply_tmp(c)) return rc;
   }
-  c->sorted = false;       // positions moved
-  c->keys_valid = true;    // ... and their keys / block flags are ready for the next sort
-  c->pidc_valid = c->P.pidc != nullptr;
-  c->affine_valid = true;  // A was produced together with F
-  if (!c->P.store_b) c->b_stale = true;
+  c->rec.g2p_done(sb, c->P.pidc != nullptr);
   return launch_check(c, "g2p");
 }
 
@@ -1457,11 +1451,11 @@ static int do_sdf_collide(mpmhip_ctx *c) {
 // behind the LAST k_g2p launch of a substep: the buffers it wrote become the current records
 static void swap_records(mpmhip_ctx *c) {
   std::swap(c->rg, c->rg2); std::swap(c->rp, c->rp2); std::swap(c->rb, c->rb2);
-  c->ordered = c->compact = true;
+  c->rec.records_swapped();
 }
 
 static int need_sorted(mpmhip_ctx *c, const char *who) {
-  if (!c->sorted) return fail(c, MPMHIP_EINVAL, "%s needs sorted particles: call mpmhip_sort first", who);
+  if (!c->rec.sorted()) return fail(c, MPMHIP_EINVAL, "%s needs sorted particles: call mpmhip_sort first", who);
   return MPMHIP_OK;
 }
 
@@ -1771,9 +1765,9 @@ int mpmhip_snapshot_save(mpmhip_ctx *c, void *dst, size_t cap) {
   Counters hc;
   int rc = read_counters(c, hc);
   if (rc) return rc;
-  if (!c->affine_valid) {  // make A current first (fresh uploads), so that the blob is self-consistent
+  if (!c->rec.affine_valid()) {  // make A current first (fresh uploads), so that the blob is self-consistent
     hipLaunchKernelGGL(k_affine, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, c->rg, c->rp, c->rb, c->d_groups);
-    c->affine_valid = true;
+    c->rec.affine_rebuilt();
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   SnapHeader h;
@@ -1781,7 +1775,7 @@ int mpmhip_snapshot_save(mpmhip_ctx *c, void *dst, size_t cap) {
   memcpy(h.magic, "MPMHIP01", 8);
   h.abi = MPMHIP_ABI_VERSION; h.n_groups = (uint32_t)c->groups.size();
   h.n_slots = c->n_slots; h.substeps = c->substeps; h.next_pid = c->next_pid;
-  h.b_stale = c->b_stale; h.store_b = c->P.store_b;
+  h.b_stale = c->rec.b_stale(); h.store_b = c->P.store_b;
   for (int k = 0; k < 3; k++) h.res[k] = c->P.res[k];
   h.t = c->t; h.request_t = c->request_t; h.dx = c->P.dx; h.dt = c->P.dt; h.n_dead = hc.n_dead;
   char *p = (char *)dst;
@@ -1851,19 +1845,16 @@ int mpmhip_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
     HIPCHK(c, hipMemcpy(c->rp, p, sizeof(RecP) * n, hipMemcpyHostToDevice)); p += sizeof(RecP) * n;
     HIPCHK(c, hipMemcpy(c->rb, p, sizeof(float) * BW * n, hipMemcpyHostToDevice));
   }
-  c->n_slots = h.n_slots; c->P.n_slots = (uint32_t)h.n_slots;
+  set_slots(c, h.n_slots);
   c->substeps = h.substeps; c->next_pid = h.next_pid;
   c->t = h.t; c->request_t = h.request_t;
   // A travels in the records; apic_b is current only if the saving ctx kept it up to date
-  c->affine_valid = true;
-  c->b_stale = h.b_stale != 0 || (h.store_b == 0);
-  if (c->P.store_b && c->b_stale) {  // this ctx keeps apic_b: rebuild it from A once
+  // (keys and block flags are rebuilt by the next sort)
+  if (int rc = clear_block_flags(c, c->rec.snapshot_loaded(h.b_stale != 0 || h.store_b == 0))) return rc;
+  if (c->P.store_b && c->rec.b_stale()) {  // this ctx keeps apic_b: rebuild it from A once
     int rc = ensure_b_current(c);
     if (rc) return rc;
   }
-  c->sorted = c->keys_valid = false;  // keys and block flags are rebuilt by the next sort
-  c->ordered = c->compact = false;
-  HIPCHK(c, hipMemset(c->blk_flag, 0, (size_t)c->P.nbw * 32));
   Counters hc;
   memset(&hc, 0, sizeof hc);
   hc.n_dead = h.n_dead;
@@ -2283,16 +2274,15 @@ int mpmhip_import_particles(mpmhip_ctx *c, int64_t n, const void *dev_records) {
   if (!c || n < 0 || (n > 0 && !dev_records)) return MPMHIP_EINVAL;
   if (n == 0) return MPMHIP_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->in_substep || c->sorted) return fail(c, MPMHIP_EINVAL, "import_particles between sort and G2P");
+  if (c->in_substep || c->rec.sorted()) return fail(c, MPMHIP_EINVAL, "import_particles between sort and G2P");
   if (c->n_slots + n > c->cap)
     return fail(c, MPMHIP_ECAPACITY, "particle capacity exceeded on import: %lld + %lld > %lld (request_compaction or a larger max_particles)",
                 (long long)c->n_slots, (long long)n, (long long)c->cap);
   hipLaunchKernelGGL(k_import, dim3(particle_grid(n)), dim3(256), 0, c->stream, c->P, (uint32_t)n, (uint32_t)c->n_slots,
                      (const float4 *)dev_records, (float4 *)c->rg.get(), (float4 *)c->rp.get(), (float4 *)c->rb.get(), c->key, c->blk_flag,
                      c->cnt);
-  c->n_slots += n;
-  c->P.n_slots = (uint32_t)c->n_slots;
-  c->compact = false;  // live records now also sit behind the range k_g2p compacted
+  set_slots(c, c->n_slots + n);
+  c->rec.records_imported();
   return launch_check(c, "import");
 }
 
@@ -2345,8 +2335,8 @@ int mpmhip_reserve(mpmhip_ctx *c, int64_t max_particles) {
   if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "growing the particle arrays to %lld failed: %s", (long long)max_particles, hipGetErrorString(e));
   c->cap = max_particles;
   c->cfg.max_particles = max_particles;
-  c->P.pidc = c->deterministic ? c->pidc : nullptr;
-  c->pidc_valid = false;
+  sync_pidc(c);
+  if (int rc = clear_block_flags(c, c->rec.index_dropped())) return rc;  // (the next sort rebuilds keys from the records)
   if (c->cfg.max_blocks <= 0) {  // auto-sized block table: same rule as mpmhip_create
     int64_t mb = c->cap / 48 + 4096;
     if (mb > (int64_t)c->NB) mb = c->NB;
@@ -2366,8 +2356,7 @@ int mpmhip_reserve(mpmhip_ctx *c, int64_t max_particles) {
       HIPCHK(c, hipMemset(c->fat_slot, 0, sizeof(uint32_t) * (size_t)c->NB));  // slots of the old grid array
     }
   }
-  c->keys_valid = true;  // (forces invalidate_keys to clear the block flags: the next sort rebuilds keys from the records)
-  return invalidate_keys(c);
+  return MPMHIP_OK;
 }
 
 // the launch bound of the chained scans as a function of what the occupancy API answered (no device needed: scan_grid_for)

@@ -241,3 +241,44 @@ def test_rccl_exchange_path_preflight_on_one_gpu_gives_the_bits_of_the_local_wir
     assert np.array_equal(got["id"], want["id"]) and len(got["id"]) > 1000
     for f in FIELDS + ("B",):
         assert np.array_equal(got[f], want[f]), (f, float(np.abs(got[f] - want[f]).max()))
+
+
+def test_ids_uploaded_in_mid_run_give_the_bits_of_a_fresh_ctx(tm, tmp_path):
+    """upload(F_ID) behind a G2P: the G2P left key[] and the id cache beside it ready for the next sort, and the cache now holds the
+    OLD ids (csrc/record_state.h: ids_changed drops it).  ctx A runs 3 substeps, saves a snapshot, uploads max_id - id — every
+    cell's order reverses — and runs 5 more; a fresh ctx B loads that snapshot (no keys, no cache: the next sort builds both from
+    the records), gets the same ids and runs the same 5.  8 particles per cell, so the in-cell order reaches the sums: every field
+    agrees bit for bit exactly when A's next sort orders the cells by the ids it was given."""
+    from taichi_mpm_amd.mpm import F_ID
+    x = lattice_cube(RES, 9, 23, DX, jitter=0.25, seed=80)  # 14^3 cells x 8 = 21 952 particles
+    s = make_state(x, "sand", DX, perturb_F=0.03, seed=81, vel_scale=6.0)
+
+    def sim_():
+        sim = tm.create_simulation3("mpm").initialize(dict(res=(RES,) * 3, delta_x=DX, base_delta_t=DT, deterministic=True))
+        ls = tm.mpm.LevelSet(friction=0.4)
+        for p in PLANES:
+            ls.add_plane(p[:3], d=p[3])
+        sim.set_levelset(ls)
+        return sim
+
+    def reverse_ids_and_run(sim):
+        ids = sim.get_particles(sort_by_id=False)["id"]  # (slot order: what upload takes)
+        assert len(ids) == s.n
+        sim.upload(F_ID, (ids.max() - ids).astype(np.int32))
+        sim.run_substeps(5)
+        out = sim.get_particles()
+        sim.close()
+        return out
+
+    path = str(tmp_path / "mid_run.snap")
+    a = sim_()
+    a.add_particles(dict(type="sand", positions=s.x, velocities=s.v, F=s.F, B=s.B, aux=s.aux, params=s.gparams[0]))
+    a.run_substeps(3)
+    a.save_snapshot(path)
+    a = reverse_ids_and_run(a)
+    b = sim_()
+    b.load_snapshot(path)
+    b = reverse_ids_and_run(b)
+    assert np.array_equal(a["id"], b["id"]) and np.array_equal(a["id"], np.arange(s.n))
+    for f in FIELDS + ("B",):
+        assert np.array_equal(a[f], b[f]), (f, float(np.abs(a[f] - b[f]).max()))
