@@ -287,6 +287,35 @@ class MPM<3> {
     return "";
   }
 
+  // --- add_particles(density_tex=...) with the reference's default sampler, the periodic Poisson-disk tile (src/mpm.cpp:205-251;
+  // include/mpmhip.h: mpmhip_seed_particles): the region — where the shapes' level set is negative — is filled on the device.
+  // Keys: ppc (8), initial_velocity, pd_source, delta_t (1e-3), initial_dg, density and the material keys.  Returns the number
+  // of particles added.
+  int64_t add_particles_region(const Config &config, const std::vector<mpmhip_shape> &shapes) {
+    if (shapes.size() > (size_t)MPMHIP_MAX_SHAPES) throw std::runtime_error("add_particles_region: too many shapes");
+    mpmhip_seed_desc d{};
+    d.n_shapes = (int32_t)shapes.size();
+    std::copy(shapes.begin(), shapes.end(), d.shapes);
+    return seed(config, d);
+  }
+  // ... the region as a sampled field: phi holds res[0] * res[1] * res[2] values, the last axis fastest, world units
+  int64_t add_particles_region(const Config &config, const VectorI &lattice_res, const Vector &origin, real spacing,
+                               const std::vector<float> &phi) {
+    mpmhip_sdf_desc l;
+    size_t count = 1;
+    for (int k = 0; k < 3; k++) {
+      l.res[k] = lattice_res[k];
+      l.origin[k] = origin[k];
+      count *= (size_t)(lattice_res[k] > 0 ? lattice_res[k] : 0);
+    }
+    l.spacing = spacing;
+    if (phi.size() != count) throw std::runtime_error("add_particles_region: the array must hold res[0] * res[1] * res[2] samples");
+    mpmhip_seed_desc d{};
+    d.sdf = &l;
+    d.phi = phi.data();
+    return seed(config, d);
+  }
+
   // --- time stepping
   virtual void step(real dt) { check(mpmhip_step(ctx_, dt), ctx_); frame++; }  // src/mpm.cpp:428-439 (dt < 0: one substep)
   void substep() { check(mpmhip_substep(ctx_), ctx_); }              // :452-575
@@ -414,6 +443,33 @@ class MPM<3> {
             x.push_back((j + 0.5f + ((s & 2) ? 0.25f : -0.25f)) * delta_x);
             x.push_back((k + 0.5f + ((s & 4) ? 0.25f : -0.25f)) * delta_x);
           }
+  }
+  // the group of a seeding call (vol = dx^3 / ppc, mass = vol * density: create_particle(coord, maximum, config), :134-135) and
+  // the call; a ctx that is too small is grown once and the call repeated
+  int64_t seed(const Config &config, mpmhip_seed_desc &d) {
+    const std::string type = config.get("type", "");
+    const float ppc = config.get("ppc", config.get("maximum", 8.0f));
+    if (!(ppc > 0)) throw std::runtime_error("add_particles_region: ppc must be > 0");
+    const float vol = delta_x * delta_x * delta_x / ppc;
+    const float mass = vol * config.get("density", 400.0f);
+    const ParticleType t = create_particle_type(type, config, mass, vol);
+    const int gid = mpmhip_add_group(ctx_, t.material, t.params);
+    check(gid, ctx_);
+    types_.push_back(t);
+    d.ppc = ppc;
+    const Vector v0 = config.get_vec("initial_velocity", Vector(0.0f, 0.0f, 0.0f));
+    for (int k = 0; k < 3; k++) d.velocity[k] = v0[k];
+    d.source = config.get("pd_source", false);
+    d.source_delta_t = config.get("delta_t", 1e-3f);  // src/mpm.cpp:224
+    d.initial_dg = t.initial_dg;
+    int64_t n = 0;
+    int rc = mpmhip_seed_particles(ctx_, gid, &d, &n);
+    if (rc == MPMHIP_ECAPACITY) {
+      check(mpmhip_reserve(ctx_, (mpmhip_num_slots(ctx_) + n) * 5 / 4), ctx_);
+      rc = mpmhip_seed_particles(ctx_, gid, &d, &n);
+    }
+    check(rc, ctx_);
+    return n;
   }
   static void check(int rc, const mpmhip_ctx *c) {
     if (rc < 0) throw std::runtime_error(std::string("libmpmhip error ") + std::to_string(rc) + ": " + mpmhip_last_error(c));

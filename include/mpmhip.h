@@ -254,6 +254,54 @@ int mpmhip_download_levelset_sdf(mpmhip_ctx *ctx, int32_t frame, float *dst, int
 int mpmhip_add_group(mpmhip_ctx *ctx, int32_t material, const float params[MPMHIP_NPARAM]);
 int mpmhip_add_particles(mpmhip_ctx *ctx, int32_t group, int64_t n, const float *x, const float *v,
                          const float *F, const float *B, const float *aux);
+
+/* Seeding on the device — replaces the reference's default fill, add_particles(density_tex=...) with pd / pd_periodic
+ * (PoissonDiskSampler<3>::sample_from_periodic_data and, with pd_source, sample_from_source: src/poisson_disk_sampler.h:157-252,
+ * src/mpm.cpp:205-251): a fixed periodic blue-noise tile is scaled to the wanted spacing, repeated over the region's bounding box,
+ * and the points inside the region become particles.  No particle record passes through host memory
+ * (mpmhip_host_particle_bytes does not change).
+ *
+ * The tile: mpmhip_poisson_tile writes min(count, capacity) points, 3 floats each, to `out` (NULL allowed) and returns the count.
+ * Bridson's algorithm in the periodic box [-20, 20)^3, minimum distance 1, 30 attempts per active point, the first point at the
+ * centre (write_periodic_data, :255-324), generated once per process in integer arithmetic: the same bytes on every machine.
+ *
+ * The region is "where this level set is negative", independent of the ctx's boundary level set (which is not touched):
+ *   sdf == NULL   the first n_shapes of `shapes` (phi = min over the shapes, as mpmhip_set_levelset_shapes);
+ *   sdf != NULL   a sampled field phi [res0 res1 res2] on the lattice *sdf (host array, uploaded by the call; the rules of
+ *                 mpmhip_set_levelset_sdf: trilinear, a point outside the lattice is not in the region).
+ * All arithmetic is fp32, in this order, nothing contracted (tests/seed_model.py restates it to the bit):
+ *   get ready   over the cell centres fl((i + 0.5) dx) of the grid: min / max per axis of the centres inside the region;
+ *               min_corner = min - dx, max_corner = max + dx; no centre inside: MPMHIP_EINVAL "region is empty".
+ *               min_distance = (float)cbrt(dx^3 / ppc * 13 / 18) (in double), region_size = fl(40 min_distance),
+ *               replicas per axis = ceil((max_corner - min_corner) / region_size).
+ *   candidates  c = i * n_replicas + r pairs tile point i with replica r (the replica index in C order, (ind0, ind1, ind2));
+ *               q = fl(tile_i * min_distance);  position = fl(fl(q + min_corner) + fl(region_size * (ind + 0.5))).
+ *               source = 1 (an emitter called before every frame): q = fl(q + fl(velocity * current_t)), wrapped into the period
+ *               q -= fl(floor(fl(fl(q / region_size) + 0.5)) * region_size) — the tile drifts with the jet.
+ *   acceptance  inside the region and not within 7 cells of a wall (MPM::near_boundary, src/mpm.h:269-276: X = fl(x * fl(1 / dx)),
+ *               min X < 7 or max (X - res) > -7).  source = 1: and position + advection is NOT inside, advection =
+ *               velocity * d + 0.5 * gravity * (d + base_delta_t) * d with d = source_delta_t (src/mpm.cpp:222-227): only the shell
+ *               the jet vacates within d is filled.
+ *   order       the survivors are appended in ascending c with creation ids next_id + rank (the reference's order).
+ *   records     velocity as given, F = initial_dg * I, B = 0, aux the material default, mass from the group row.
+ * *n_added = the number of new particles.  If they do not fit the ctx, nothing is written, *n_added is the number needed and the
+ * call returns MPMHIP_ECAPACITY: mpmhip_reserve and call again.  MPMHIP_EINVAL with a message: inside a substep, on a tiled ctx,
+ * an unknown group, ppc <= 0, a lattice mpmhip_set_levelset_sdf would refuse, more than 2^31 candidates.
+ * Out of scope: the 2D solver, pd_packed, non-uniform densities, pd = False, point_cloud. */
+typedef struct {
+  int32_t n_shapes;
+  mpmhip_shape shapes[MPMHIP_MAX_SHAPES];
+  const mpmhip_sdf_desc *sdf; /* NULL: the region is given by the shapes */
+  const float *phi;
+  float ppc;                  /* particles per cell the spacing is chosen for (> 0) */
+  float velocity[3];
+  int32_t source;             /* 0 fill, 1 emitter shell */
+  float source_delta_t;
+  float initial_dg;
+  int32_t reserved;
+} mpmhip_seed_desc;
+int64_t mpmhip_poisson_tile(float *out, int64_t capacity);
+int mpmhip_seed_particles(mpmhip_ctx *ctx, int32_t group, const mpmhip_seed_desc *desc, int64_t *n_added);
 int64_t mpmhip_num_particles(mpmhip_ctx *ctx); /* synchronises; <0 on error */
 int mpmhip_download(mpmhip_ctx *ctx, int32_t field, void *dst, int64_t n_capacity); /* returns n written */
 int mpmhip_upload(mpmhip_ctx *ctx, int32_t field, const void *src, int64_t n);

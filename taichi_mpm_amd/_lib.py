@@ -46,6 +46,13 @@ class SdfDesc(C.Structure):
     _fields_ = [("res", C.c_int32 * 3), ("origin", C.c_float * 3), ("spacing", C.c_float)]
 
 
+class SeedDesc(C.Structure):
+    """mirror of mpmhip_seed_desc"""
+    _fields_ = [("n_shapes", C.c_int32), ("shapes", Shape * MAX_SHAPES), ("sdf", C.POINTER(SdfDesc)), ("phi", C.POINTER(C.c_float)),
+                ("ppc", C.c_float), ("velocity", C.c_float * 3), ("source", C.c_int32), ("source_delta_t", C.c_float),
+                ("initial_dg", C.c_float), ("reserved", C.c_int32)]
+
+
 class AsyncConfig(C.Structure):
     """mirror of mpmhip_async_config"""
     _fields_ = [("unit_delta_t", C.c_float), ("max_units", C.c_int64), ("cfl_dt_mul", C.c_float), ("strength_dt_mul", C.c_float),
@@ -158,7 +165,7 @@ def build_variant(name, extra_flags):
 _lib = None
 
 _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create", "mpmhip_destroy", "mpmhip_last_error", "mpmhip_set_stream", "mpmhip_set_deterministic", "mpmhip_set_levelset", "mpmhip_set_rigid_levelset_collision", "mpmhip_set_dirichlet", "mpmhip2d_set_dirichlet", "mpmhip_set_levelset_shapes", "mpmhip_set_levelset_keyframes", "mpmhip_set_levelset_sdf", "mpmhip_debug_levelset_sample", "mpmhip_mesh_to_sdf", "mpmhip_set_levelset_mesh", "mpmhip_download_levelset_sdf",
-            "mpmhip_add_group", "mpmhip_add_particles", "mpmhip_num_particles", "mpmhip_download",
+            "mpmhip_add_group", "mpmhip_add_particles", "mpmhip_poisson_tile", "mpmhip_seed_particles", "mpmhip_num_particles", "mpmhip_download",
             "mpmhip_upload", "mpmhip_substep", "mpmhip_run_substeps", "mpmhip_step", "mpmhip_current_time",
             "mpmhip_synchronize", "mpmhip_sort", "mpmhip_p2g", "mpmhip_grid_update", "mpmhip_g2p",
             "mpmhip_download_grid", "mpmhip_upload_grid", "mpmhip_calculate_energy", "mpmhip_snapshot_size", "mpmhip_snapshot_save", "mpmhip_snapshot_load", "mpmhip_delete_particles_inside_level_set", "mpmhip_bgeo_size", "mpmhip_bgeo_encode", "mpmhip_write_bgeo", "mpmhip_set_profiling", "mpmhip_profile",
@@ -238,6 +245,9 @@ def load():
     L.mpmhip_download_levelset_sdf.argtypes = [vp, C.c_int32, fp, C.c_int64]
     L.mpmhip_add_group.argtypes = [vp, C.c_int32, fp]
     L.mpmhip_add_particles.argtypes = [vp, C.c_int32, C.c_int64, fp, fp, fp, fp, fp]
+    L.mpmhip_poisson_tile.argtypes = [fp, C.c_int64]
+    L.mpmhip_poisson_tile.restype = C.c_int64
+    L.mpmhip_seed_particles.argtypes = [vp, C.c_int32, P(SeedDesc), P(C.c_int64)]
     L.mpmhip_num_particles.argtypes = [vp]
     L.mpmhip_num_particles.restype = C.c_int64
     L.mpmhip_download.argtypes = [vp, C.c_int32, vp, C.c_int64]

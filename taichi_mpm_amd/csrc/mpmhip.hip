@@ -2,6 +2,7 @@
 // the host side of the ctx.  The kernels live next to this file, one header per phase:
 //   mpm_common.h (records, parameter blocks, Morton keys)   mpm_math.h (3x3 math, constitutive models, level set)
 //   k_sort.h  k_p2g.h  k_grid.h  k_g2p.h  k_tiling.h  k_particles.h  k_debug.h
+//   k_seed.h (particle seeding from the periodic Poisson-disk tile, poisson_tile.h)
 //   k_bgeo.h (.bgeo frame rows)   k_mpm88.h (the 2D dense-grid demo, its own small object)
 // host_mem.h: DevBuf / PinnedBuf, the owners of every device and pinned array of the objects below (a new array needs a field and
 // its allocation, nothing else); what a kernel takes by value keeps raw pointers into them.
@@ -90,6 +91,8 @@
 #include "k_debug.h"
 #include "k_sdf.h"
 #include "k_mesh_sdf.h"
+#include "k_seed.h"
+#include "poisson_tile.h"
 #include "k_bgeo.h"
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
@@ -199,6 +202,7 @@ struct mpmhip_ctx {
   // the lattice changes, shapes replace the set, or the ctx goes (LS.sdf points at them while the set is installed)
   DevBuf<float> d_sdf[2];
   size_t sdf_count = 0;
+  SeedWork seed;            // mpmhip_seed_particles: the tile and the work buffers, kept between calls (seed_api.h)
   MeshSdfWork mesh_work[2];  // mpmhip_set_levelset_mesh: the voxeliser's buffers per key frame, kept between calls
   int particle_collision_cfg = 0;  // the config's particle_collision.  P.particle_collision is 0 while a sampled set is installed:
                                    // the G2P kernels then leave the push to k_sdf_collide (do_sdf_collide)
@@ -2693,6 +2697,7 @@ int mpmhip_async_set_time_int(mpmhip_ctx *c, int64_t t_int) {
 }
 
 #include "async_api.h"
+#include "seed_api.h"
 
 int mpmhip_debug_allowed_dt(mpmhip_ctx *c, int32_t material, const float params[MPMHIP_NPARAM], int64_t n, const float *F,
                             const float *aux, const float *v, float dx, float *out) {

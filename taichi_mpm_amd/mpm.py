@@ -10,9 +10,10 @@ Two layers, as in the reference:
     `set_levelset`, `step`, `simulate`.
 
 Configs are flat dicts (reference: taichi `Config`, string->string; `P(**kwargs)`).  Errors raise `MPMError`
-(reference: TC_ASSERT / TC_ERROR abort).  Scene tooling the hot path does not need (textures, Poisson-disk sampling,
-rendering) is out of scope: `add_particles` takes explicit `positions=` or the built-in `benchmark=` generator
-(src/mpm.cpp:149-186) or a `cube=(lo, hi)` lattice; `type='rigid'` takes `mesh=` triangles or `mesh_fn='file.obj'`
+(reference: TC_ASSERT / TC_ERROR abort).  Scene tooling the hot path does not need (textures, point clouds,
+rendering) is out of scope: `add_particles` takes explicit `positions=`, the built-in `benchmark=` generator
+(src/mpm.cpp:149-186), a `cube=(lo, hi)` lattice, or `region=` — a level set filled on the device from the reference's periodic
+Poisson-disk tile (its default for density_tex; include/mpmhip.h: mpmhip_seed_particles); `type='rigid'` takes `mesh=` triangles or `mesh_fn='file.obj'`
 (CPIC rigid bodies, `add_rigid_body`), joints come through `general_action(action='add_articulation', ...)`.
 """
 import ctypes as C
@@ -519,8 +520,10 @@ class Simulation3D:
             x = lattice_cube(0, int(cfg["cube_cells"]), dx) + (np.asarray(cfg["cube_lo"], np.float64) * dx).astype(np.float32)
         elif "positions" in cfg:
             x = np.ascontiguousarray(cfg["positions"], np.float32).reshape(-1, 3)
+        elif "region" in cfg:
+            return self._seed_region(cfg, ptype, maximum)
         else:
-            raise MPMError("add_particles needs one of: benchmark=, cube=(lo,hi), positions= "
+            raise MPMError("add_particles needs one of: benchmark=, cube=(lo,hi), positions=, region= "
                            "(density_tex / point_cloud sampling is scene tooling outside this build)")
         keep = ~self._near_boundary(x.astype(np.float64))  # "particle out of box or near boundary. Ignored."
         x = x[keep]
@@ -552,6 +555,75 @@ class Simulation3D:
         else:
             self._staged.append((gi, (x, v0, F, B, aux)))
         self._n_added += n
+        return ""
+
+    def _seed_desc(self, cfg, ptype, ppc):
+        """the mpmhip_seed_desc of an add_particles(region=...) config, and the objects its pointers need alive"""
+        region, dx = cfg["region"], self.delta_x
+        if not (np.isfinite(ppc) and ppc > 0):
+            raise MPMError("add_particles(region=): ppc must be a finite number > 0, got %r" % (ppc,))
+        for k in ("velocities", "F", "B", "aux", "pd_packed", "point_cloud"):
+            if k in cfg and cfg[k] is not False:
+                raise MPMError("add_particles(region=) does not take %r" % k)
+        if not cfg.get("pd", True) or not cfg.get("pd_periodic", True):
+            raise MPMError("add_particles(region=) implements the periodic Poisson-disk tile only (pd and pd_periodic must stay True)")
+        if initial_aux(ptype, **cfg) != initial_aux(ptype):
+            raise MPMError("add_particles(region=) gives every particle the material's default state")
+        d = _lib.SeedDesc()
+        keep = []
+        if isinstance(region, MeshLevelSet):
+            region = SampledLevelSet.from_mesh(region.triangles, region.res, region.origin, region.spacing or dx, region.band,
+                                               device=self.device)
+        if isinstance(region, SampledLevelSet):
+            sd = _lib.SdfDesc()
+            sd.res[:] = region.res
+            sd.origin[:] = region.origin
+            sd.spacing = dx if region.spacing is None else region.spacing
+            keep += [sd, region.phi]
+            d.sdf = C.pointer(sd)
+            d.phi = region.phi.ctypes.data_as(C.POINTER(C.c_float))
+        elif isinstance(region, LevelSet):
+            d.n_shapes = len(region.shapes)
+            for i, (t_, io, p) in enumerate(region.shapes):
+                d.shapes[i].type, d.shapes[i].inside_out = t_, io
+                d.shapes[i].p[:] = p
+        else:
+            raise MPMError("add_particles(region=) takes a LevelSet, a SampledLevelSet or a MeshLevelSet, got %r" % type(region).__name__)
+        d.ppc = ppc
+        d.velocity[:] = _vec3(cfg.get("initial_velocity"), (0, 0, 0))
+        d.source = int(bool(cfg.get("pd_source", False)))
+        d.source_delta_t = float(cfg.get("delta_t", 1e-3))  # src/mpm.cpp:224
+        d.initial_dg = float(cfg.get("initial_dg", 1.0))  # src/particles.h:120
+        return d, keep
+
+    def _seed_region(self, cfg, ptype, ppc):
+        """add_particles(region=...): the reference's default fill, add_particles(density_tex=...) with the periodic Poisson-disk
+        tile (src/mpm.cpp:205-251), on the device (include/mpmhip.h: mpmhip_seed_particles).  region: a LevelSet (where its shapes
+        are negative), a SampledLevelSet, or a MeshLevelSet (voxelised through SampledLevelSet.from_mesh).  Keys: ppc (8),
+        initial_velocity, pd_source, delta_t (1e-3), initial_dg, density and the material keys."""
+        dx = self.delta_x
+        d, keep = self._seed_desc(cfg, ptype, ppc)
+        vol = dx ** 3 / ppc  # create_particle(coord, maximum, config), src/mpm.cpp:134-135
+        mass = vol * float(cfg.get("density", 400.0))
+        params, mat = group_params(ptype, mass, vol, **{k: v for k, v in cfg.items() if isinstance(v, (int, float))})
+        if "params" in cfg:
+            params = np.ascontiguousarray(cfg["params"], np.float32).reshape(16).copy()
+        self._ensure_ctx()  # (a call before the ctx exists creates it)
+        # an emitter calls before every frame with one material: its particles share a group row (a ctx holds 64 of them)
+        gi = next((i for i, (m_, p_) in enumerate(self._groups) if m_ == mat and p_.tobytes() == params.tobytes()), len(self._groups))
+        if gi == len(self._groups):
+            self._groups.append((mat, params))
+            self._check(self._L.mpmhip_add_group(self._ctx, mat, params.ctypes.data_as(C.POINTER(C.c_float))))
+        n = C.c_int64(0)
+        rc = self._L.mpmhip_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+        if rc == -4:  # MPMHIP_ECAPACITY: n is what the call needs; nothing was written
+            need = int(self._L.mpmhip_num_slots(self._ctx)) + n.value
+            cap = max(int(need * 1.25), self.max_particles)
+            self._check(self._L.mpmhip_reserve(self._ctx, cap))
+            self._capacity = cap
+            rc = self._L.mpmhip_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+        self._check(rc)
+        self._n_added += n.value
         return ""
 
     # ---------------------------------------------------------------- CPIC rigid bodies

@@ -1,0 +1,159 @@
+"""numpy model of mpmhip_seed_particles (include/mpmhip.h; csrc/k_seed.h, csrc/seed_api.h) — the yardstick of the seeding tests.
+It restates, in fp32 and in the device's order of operations, PoissonDiskSampler<3>::sample_from_periodic_data and
+sample_from_source (src/poisson_disk_sampler.h:157-252) behind get_ready (:34-69):
+
+  get ready   cell centres ((i + 0.5) * dx); box of the centres inside the region; min_corner = min - dx, max_corner = max + dx;
+              min_distance = float32(cbrt(dx^3 / ppc * 13 / 18)) (double); region_size = 40 * min_distance;
+              replicas per axis = ceil((max_corner - min_corner) / region_size)
+  candidates  c = i * n_replicas + r (r: the replica index in C order);  q = tile_i * min_distance
+              [source: q += velocity * current_t;  q -= floor(q / region_size + 0.5) * region_size]
+              position = (q + min_corner) + region_size * (ind + 0.5)
+  acceptance  inside the region, not within 7 cells of a wall (X = x * (1 / dx): min X < 7 or max (X - res) > -7)
+              [source: and position + advection NOT inside; advection = v * d + ((0.5 * g) * (d + base_dt)) * d]
+  order       survivors in ascending c, creation ids first_id + rank
+
+The tile comes from the library (mpmhip_poisson_tile: host code, no GPU).  A sampled region is evaluated by tests/sdf_model.py, which
+reproduces the device's sampler to the bit; shapes are evaluated here in fp32 with the formulas of levelset_eval_key, where the
+device's compiler may contract a multiply and an add: a shape test sets candidates with |phi| below a margin aside."""
+import ctypes as C
+
+import numpy as np
+
+from tests.sdf_model import SdfModel
+
+F = np.float32
+
+
+def load_tile():
+    import taichi_mpm_amd as tm
+    L = tm.load()
+    n = int(L.mpmhip_poisson_tile(None, 0))
+    out = np.empty((n, 3), F)
+    assert L.mpmhip_poisson_tile(out.ctypes.data_as(C.POINTER(C.c_float)), n) == n
+    return out
+
+
+class SampledRegion:
+    """where the trilinear interpolant of phi (world units) is negative; outside the lattice: not in the region"""
+
+    def __init__(self, phi, origin, spacing, dx):
+        self.m = SdfModel(phi, origin, spacing, dx)
+
+    def phi(self, x):
+        """grid units; +inf outside the lattice"""
+        hit, c, f = self.m.locate(x)
+        p = self.m._phi_frame(self.m.phi0, c, f)
+        return np.where(hit, (p * self.m.idx).astype(F), F(np.inf)), hit & (p < 0)
+
+    def inside(self, x):
+        return self.phi(x)[1]
+
+
+class ShapeRegion:
+    """where min over the shapes of phi is negative (levelset_eval_key, csrc/mpm_math.h), fp32"""
+
+    def __init__(self, shapes, dx):
+        self.shapes = [(int(t), int(io), np.asarray(p, F)) for t, io, p in shapes]
+        self.idx = F(1.0) / F(dx)
+
+    def phi(self, x):
+        x = np.asarray(x, F).reshape(-1, 3)
+        phi = np.full(len(x), F(1e30), F)
+        for t, io, q in self.shapes:
+            if t == 0:
+                ph = x[:, 0] * q[0] + x[:, 1] * q[1] + x[:, 2] * q[2] + q[3]
+            elif t == 1:
+                d = x - q[None, :3]
+                ph = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]) - q[3]
+            else:
+                lo, hi = q[None, :3], q[None, 3:6]
+                ins = np.all((lo <= x) & (x <= hi), axis=1)
+                depth = np.minimum(x - lo, hi - x).min(axis=1)
+                d = x - np.minimum(np.maximum(x, lo), hi)
+                out = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+                ph = np.where(ins, -depth, out)
+            if t != 0 and io:
+                ph = -ph
+            ph = (ph.astype(F) * self.idx).astype(F)
+            phi = np.minimum(phi, ph)
+        return phi, phi < 0
+
+    def inside(self, x):
+        return self.phi(x)[1]
+
+
+class SeedModel:
+    def __init__(self, res, dx, region, ppc=8.0, velocity=(0.0, 0.0, 0.0), source=False, delta_t=1e-3, current_t=0.0,
+                 gravity=(0.0, -10.0, 0.0), base_dt=1e-4, tile=None):
+        self.res = np.array([res] * 3 if np.isscalar(res) else res, np.int64)
+        self.dx, self.idx = F(dx), F(1.0) / F(dx)
+        self.region = region
+        self.tile = load_tile() if tile is None else np.asarray(tile, F)
+        self.source = bool(source)
+        self.velocity = np.asarray(velocity, F)
+        self.offset = (self.velocity * F(current_t)).astype(F)
+        d, g = F(delta_t), np.asarray(gravity, F)
+        self.advection = ((self.velocity * d).astype(F) + (((F(0.5) * g).astype(F) * F(d + F(base_dt))).astype(F) * d).astype(F)).astype(F)
+        self._get_ready(float(F(ppc)))
+
+    def _get_ready(self, ppc):
+        ax = [((np.arange(r).astype(F) + F(0.5)) * self.dx).astype(F) for r in self.res]
+        lo, hi = [None] * 3, [None] * 3
+        any_inside = np.zeros([len(a) for a in ax], bool)
+        for i in range(len(ax[0])):  # (slabs: the sampled model builds large temporaries)
+            pts = np.stack(np.meshgrid(ax[0][i:i + 1], ax[1], ax[2], indexing="ij"), axis=-1).reshape(-1, 3)
+            any_inside[i] = self.region.inside(pts).reshape(len(ax[1]), len(ax[2]))
+        self.empty = not any_inside.any()
+        if self.empty:
+            return
+        idx = np.argwhere(any_inside)
+        lo, hi = idx.min(axis=0), idx.max(axis=0)
+        self.min_corner = np.array([ax[k][lo[k]] - self.dx for k in range(3)], F)
+        self.max_corner = np.array([ax[k][hi[k]] + self.dx for k in range(3)], F)
+        dx = float(self.dx)
+        self.min_distance = F(np.cbrt(dx * dx * dx / ppc * 13.0 / 18.0))
+        self.region_size = F(F(40.0) * self.min_distance)
+        self.nrep = np.maximum(1, np.ceil(((self.max_corner - self.min_corner).astype(F) / self.region_size).astype(F)).astype(np.int64))
+        self.n_rep = int(np.prod(self.nrep))
+        self.n_cand = self.n_rep * len(self.tile)
+
+    def near_boundary(self, x):
+        X = (x * self.idx).astype(F)
+        return (X.min(axis=1) < F(7.0)) | ((X - self.res.astype(F)[None, :]).astype(F).max(axis=1) > F(-7.0))
+
+    def positions(self, lo=0, hi=None):
+        """positions of the candidates c = i * n_replicas + r for the tile points lo <= i < hi, (n, 3) fp32 in the order of c"""
+        q = (self.tile[lo:hi] * self.min_distance).astype(F)
+        rs = self.region_size
+        if self.source:
+            q = (q + self.offset[None, :]).astype(F)
+            w = np.floor(((q / rs).astype(F) + F(0.5)).astype(F)).astype(F)
+            q = (q - (w * rs).astype(F)).astype(F)
+        a = (q + self.min_corner[None, :]).astype(F)
+        ind = np.stack(np.meshgrid(*[np.arange(n) for n in self.nrep], indexing="ij"), axis=-1).reshape(-1, 3)
+        b = (rs * (ind.astype(F) + F(0.5)).astype(F)).astype(F)
+        return (a[:, None, :] + b[None, :, :]).astype(F).reshape(-1, 3)
+
+    def run(self, margin=None, chunk=4096):
+        """-> dict(x (n, 3) fp32 survivors in order, c their candidate numbers, n_cand, unsure: candidate numbers with
+        |phi| < margin (grid units) at the position — or, source mode, at the advected position — when a margin is given)"""
+        xs, cs, unsure = [], [], []
+        for lo in range(0, len(self.tile), chunk):
+            x = self.positions(lo, lo + chunk)
+            c = lo * self.n_rep + np.arange(len(x), dtype=np.int64)
+            phi, ins = self.region.phi(x)
+            keep = ins & ~self.near_boundary(x)
+            near = np.abs(phi) < F(margin) if margin is not None else None
+            if self.source:
+                phi2, ins2 = self.region.phi((x + self.advection[None, :]).astype(F))
+                keep &= ~ins2
+                if margin is not None:
+                    near |= np.abs(phi2) < F(margin)
+            xs.append(x[keep])
+            cs.append(c[keep])
+            if margin is not None:
+                unsure.append(c[near])
+        out = dict(x=np.concatenate(xs), c=np.concatenate(cs), n_cand=self.n_cand)
+        if margin is not None:
+            out["unsure"] = np.concatenate(unsure)
+        return out
