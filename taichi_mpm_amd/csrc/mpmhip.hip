@@ -8,6 +8,9 @@
 // its allocation, nothing else); what a kernel takes by value keeps raw pointers into them.
 // record_state.h: RecordState, the owner of the ctx's validity flags (which arrays describe the current particles); the host code
 // changes them through its named transitions only.
+// launch_plan.h: Knobs (the tuning switches of the substep path, from the environment), Facts and the pure plan_sort / plan_p2g /
+// plan_grid / plan_g2p: which kernel instantiation a phase launches and with how many workgroups.  do_sort / do_p2g / do_grid /
+// do_g2p compute their plan, map it to a kernel pointer and launch; they decide nothing themselves.
 //
 // One substep (reference: MPM<3>::substep, src/mpm.cpp:452-575):
 //
@@ -78,6 +81,7 @@
 
 #include "host_mem.h"
 #include "record_state.h"
+#include "launch_plan.h"
 #include "mpm_common.h"
 #include "k_sort.h"
 #include "k_particles.h"
@@ -123,6 +127,68 @@ static K one_material(uint32_t mask, K fallback, Pick pick) {
   return one_material<SKIP>(mask, fallback, pick, std::make_integer_sequence<int, 32>());
 }
 
+// ---- a launch plan (launch_plan.h) -> the kernel it names: one function per kernel family, the only places that spell instantiations out
+// k_cell_table (neighbour rows + owner list) / k_cell_table_plain at the plan's chunk size, on the key-indexed or the per-block counters
+template <class K> static K by_chunk(int ct, K k16, K k32, K k64) { return ct == 16 ? k16 : (ct == 32 ? k32 : k64); }
+static auto cell_table_kernel(const lp::SortPlan &p) {
+  return p.keyed ? by_chunk(p.ct, k_cell_table<16, true>, k_cell_table<32, true>, k_cell_table<64, true>)
+                 : by_chunk(p.ct, k_cell_table<16, false>, k_cell_table<32, false>, k_cell_table<64, false>);
+}
+static auto cell_table_plain_kernel(const lp::SortPlan &p) {
+  return p.keyed ? by_chunk(p.ct, k_cell_table_plain<16, true>, k_cell_table_plain<32, true>, k_cell_table_plain<64, true>)
+                 : by_chunk(p.ct, k_cell_table_plain<16, false>, k_cell_table_plain<32, false>, k_cell_table_plain<64, false>);
+}
+// the colour-aware transfer kernels of a plan's material set (deterministic mode: the all-material form with the impulse rows, summed
+// by do_rigid_apply_tmp)
+static auto rigid_p2g_kernel(lp::MatSet m) {
+  if (m.kind == lp::MatSet::ALL_DET) return k_p2g_rigid<MAT_ALL | MAT_DET>;
+  return one_material(m.kind == lp::MatSet::ONE ? m.bit : 0u, k_p2g_rigid<MAT_ALL>, [](auto b) { return k_p2g_rigid<b.value>; });
+}
+static auto rigid_g2p_kernel(lp::MatSet m) {
+  if (m.kind == lp::MatSet::ALL_DET) return k_g2p_rigid<MAT_ALL | MAT_DET>;
+  return one_material(m.kind == lp::MatSet::ONE ? m.bit : 0u, k_g2p_rigid<MAT_ALL>, [](auto b) { return k_g2p_rigid<b.value>; });
+}
+// the grid pass's kernels: the owner-list walk (modes 0, 4, 5) and the walks per block / per (block, candidate) (every mode)
+static auto grid_list_kernel(const lp::GridPlan &p, int mode) {
+  return mode == 0 ? (p.sampled ? k_grid_list<0, true> : k_grid_list<0>) : (mode == 4 ? k_grid_list<4> : k_grid_list<5>);
+}
+static auto grid_blocks_kernel(const lp::GridPlan &p, int mode) {
+  if (mode == 0) {
+    if (p.walk == lp::GridWalk::PER_CAND) return p.sampled ? k_grid_blocks<0, true, true> : k_grid_blocks<0, true>;
+    return p.sampled ? k_grid_blocks<0, false, true> : k_grid_blocks<0, false>;
+  }
+  return mode == 1 ? k_grid_blocks<1, false>
+                   : (mode == 2 ? k_grid_blocks<2, false>
+                                : (mode == 3 ? k_grid_blocks<3, false> : (mode == 4 ? k_grid_blocks<4, false> : k_grid_blocks<5, false>)));
+}
+// k_g2p of a plan's material set (launch_plan.h: plan_g2p).
+// __launch_bounds__(256, 2) only PERMITS 256 VGPRs; what decides the speed is whether the allocation stays <= 168, i.e.
+// whether THREE workgroups fit a CU's register file (512 per SIMD lane): 168 VGPRs 0.303 ms, 180 VGPRs 0.347 ms on the same
+// box (profiles/r03_b_ab_vgpr.txt).  Forcing the bound (256, 3) makes the ALL-material kernel spill (its scratch reloads
+// wait on the prefetched records: vmcnt is shared and in-order) and costs the others 3 % (profiles/r03_h_ab_refactor.txt),
+// so the budget is met by specialising instead and guarded by tests/test_kernel_budget_cpu.py:
+// the kernel is instantiated per material SET (k_g2p.h: MATS): one material in the whole ctx (the benchmark configurations,
+// most scene scripts) -> the kernel that carries only that material's constitutive code (sand: 2 833 instructions and 153
+// VGPRs against 5 552 / 180 for all eight); no visco group -> the set without it (161 VGPRs: visco, with two eigen-solves
+// and a matrix exponential, is what pushes the full kernel over the budget).
+template <bool STORE_B, bool RIGID>
+static auto g2p_kernel_of(lp::MatSet m) {
+  constexpr uint32_t NO_VISCO = MAT_ALL & ~(1u << MPMHIP_VISCO);
+  auto kern = m.kind == lp::MatSet::ALL ? k_g2p<256, 2, true, STORE_B, RIGID> : k_g2p<256, G2P_MIN_WAVES, true, STORE_B, RIGID, NO_VISCO>;
+  if constexpr (!STORE_B)  // (the one-material kernels exist only without apic_b)
+    if (m.kind == lp::MatSet::ONE) kern = one_material(m.bit, kern, [](auto b) { return k_g2p<256, G2P_MIN_WAVES, true, false, RIGID, b.value>; });
+  return kern;
+}
+static auto g2p_kernel(const lp::G2PPlan &p) {
+  return p.store_b ? (p.rigid ? g2p_kernel_of<true, true>(p.mats) : g2p_kernel_of<true, false>(p.mats))
+                   : (p.rigid ? g2p_kernel_of<false, true>(p.mats) : g2p_kernel_of<false, false>(p.mats));
+}
+// k_g2p_packed: one-material instantiations only, none for visco (launch_plan.h: plan_g2p picks the walk for no other ctx)
+static auto g2p_packed_kernel(const lp::G2PPlan &p) {
+  decltype(&k_g2p_packed<256, G2P_MIN_WAVES, false, 1u << MPMHIP_SAND>) none = nullptr;
+  return one_material<1u << MPMHIP_VISCO>(p.mats.bit, none, [](auto b) { return k_g2p_packed<256, G2P_MIN_WAVES, false, b.value>; });
+}
+
 static thread_local std::string g_create_error;
 
 enum { PH_SORT = 0, PH_P2G = 1, PH_EXCH = 2, PH_GRID = 3, PH_G2P = 4, PH_COUNT = 5 };
@@ -146,23 +212,18 @@ struct mpmhip_ctx {
   DevBuf<uint8_t> blk_flag;
   DevBuf<uint32_t> bits, wprefix, act_blk, act_start;
   DevBuf<uint32_t> cell_cnt, cell_start, fat_slot;
-  bool sort_keyed = false;
   bool deterministic = false;  // mpmhip_config.deterministic (env MPMHIP_DETERMINISTIC): in-cell order by creation id behind every sort (do_sort)
   DevBuf<uint32_t> cellcnt_key;  // [64 NB] cell counters indexed by KEY (Morton block << 6 | cell): the two-launch front of the sort (do_sort); nullptr on grids beyond 2^21 blocks
   DevBuf<uint32_t> nbr, own_list;  // k_cell_table -> k_grid: 32-word neighbour row per active block, list of owned (block, candidate) pairs
   FillStats *d_stats = nullptr;  // device address of the pinned page's statistics words (h_pinned + FILL_STATS_WORD): k_cell_table stores there
-  int grid_walk = -1;            // walk of the substep's grid pass (k_grid.h): 2 owner list, 0 per block / per (block, candidate) as until round 4,
-                                 // -1 by size and tiling (env MPMHIP_GRID_WALK: A/B)
+  lp::Knobs knobs;               // the tuning switches of the substep path (launch_plan.h), read from the environment by mpmhip_create
   bool list_valid = false;       // the last sort built neighbour rows + owner list (do_sort -> do_grid)
-  int grid_wgs = 0;              // workgroups of the grid pass; 0: from the last sort's owner count (env MPMHIP_GRID_WGS)
   DevBuf<unsigned long long> scan_slots;  // [256] k_block_table + [ct_grid] k_cell_table: {epoch, chunk sum}
   uint32_t list_clear_epoch = 0;  // sort epoch at which the scan words of the list form of k_cell_table were last zeroed (do_sort)
   uint32_t sort_epoch = 0, bt_slots = 0, ct_slots = 0;  // scan_slots: [bt_slots] k_block_table | [ct_slots] k_cell_table_plain | [ct_slots] k_cell_table
   uint32_t scan_grid = 256;  // workgroups of the single-pass scan kernels: three eighths of what the device keeps resident (the lowest
                              // of the plain kernels; scan_limit() answers per kernel)
   std::map<const void *, uint32_t> scan_limits;  // kernel -> three eighths of its resident workgroups
-  int scan_grid_env = 0;
-  uint32_t rank_wgs_cap = 4096u;  // workgroups of the rank role (k_rank / k_sort_front): MPMHIP_RANK_WGS (tuning)
   DevBuf<float4> tiles, gridv, dense;
   DevBuf<Counters> cnt;
   std::vector<GroupParams> groups;
@@ -170,17 +231,8 @@ struct mpmhip_ctx {
   int groups_cap = G2P_LDS_GROUPS;  // k_g2p mirrors the whole table in LDS
   RecordState rec;            // which arrays describe the current particles (record_state.h)
   DevBuf<uint32_t> pidc;      // creation id per slot beside key[] (Params::pidc points here while the deterministic mode is on)
-  int cell_order_wgs = 24;    // env MPMHIP_CELL_ORDER_WGS: workgroups per CU of k_cell_order_blocks' launch
-  int cell_order_form = 1;    // env MPMHIP_CELL_ORDER: 1 k_cell_order_blocks (a wave per block through LDS), 0 k_cell_order (a lane per cell)
-  int p2g_wgs = 16384;        // workgroups of k_p2g (env MPMHIP_P2G_WGS)
-  int g2p_wgs = 0;            // workgroups of k_g2p; 0: by size (env MPMHIP_G2P_WGS pins it)
   int n_cus = 256;            // compute units of the device
-  int g2p_packed = -1;        // k_g2p_packed instead of k_g2p: -1 by size (from 2 M slots on; no rigid bodies, no tiling), 0 never, 1 wherever it
-                              // applies (env MPMHIP_G2P_PACKED)
   DevBuf<uint32_t> chunk_blk;  // per 256 positions of the sorted index: the block holding the first (k_cell_table -> k_g2p_packed)
-  int rigid_wgs = 2048;       // workgroups of k_p2g_rigid (one per wave slot of the device), twice those of k_g2p_rigid (env MPMHIP_RIGID_WGS: tuning)
-  uint32_t rank_runs_mul = 3; // k_rank takes its LDS-hash path when runs * this > slots (env MPMHIP_RANK_RUNS_MUL: tuning)
-  int ct_blocks = 0;          // blocks per chunk of k_cell_table: 0 by size, 16, 32, 64 (env MPMHIP_CT_BLOCKS: tuning)
   int reorder_interval = 0;   // physical reorder every this many substeps (0 = never); env MPMHIP_REORDER_INTERVAL
   float t = 0.0f, request_t = 0.0f;  // `real` accumulators, as in the reference (src/mpm.h:99, mpm.cpp:573)
   int64_t substeps = 0;
@@ -211,7 +263,7 @@ struct mpmhip_ctx {
   DevBuf<uint32_t> d_counts;
   DevBuf<int> d_bounds;
   PinnedBuf<uint32_t> h_pinned;  // 64 KiB of pinned host memory for small readbacks (counters, migration table)
-  static constexpr int FILL_STATS_WORD = 16368;  // word offset of the block-fill statistics in that page (do_sort, g2p_is_packed)
+  static constexpr int FILL_STATS_WORD = 16368;  // word offset of the block-fill statistics in that page (do_sort, facts)
   DevBuf<double> d_energy;
   DevBuf<double> d_energy_parts;  // deterministic mode: [8 energy_parts_cap + POT_WAVES] the partial sums of calculate_energy (energy_end_det)
   size_t energy_parts_cap = 0;
@@ -273,7 +325,6 @@ struct mpmhip_ctx {
     DevBuf<uint8_t> d_blk_rigid;
     hipStream_t side = nullptr;          // the colour-aware transfer kernels run here, next to the plain ones on the ctx stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int concurrent = 7;                  // which pairs run side by side: 1 P2G, 2 G2P, 4 rasterisation | sort (env MPMHIP_RIGID_CONCURRENT; 0: one stream)
     DevBuf<uint32_t> d_rigid_list;  // [max_blocks + 1] the flagged blocks as a list; its length is d_counters[CDF_POOLS + 1]
     DevBuf<float> d_imp_rows;       // deterministic mode only: [imp_rows_cap][IMP_ROW] per flagged block its impulse sums (k_rigid.h)
     size_t imp_rows_cap = 0;
@@ -476,7 +527,6 @@ static int bgeo_order(mpmhip_ctx *c, std::vector<uint32_t> &order, std::vector<i
 extern "C" {
 
 static uint32_t scan_limit(mpmhip_ctx *c, const void *kernel);   // (defined with do_sort, below)
-static uint32_t scan_resident_set(int n_cus, int per_cu);
 
 uint32_t mpmhip_abi_version(void) { return MPMHIP_ABI_VERSION; }
 
@@ -498,21 +548,11 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   if (!c) return fail(nullptr, MPMHIP_ENOMEM, "host allocation failed");
   c->cfg = *cfg;
   c->device = cfg->device;
-  if (const char *e = getenv("MPMHIP_G2P_WGS")) c->g2p_wgs = atoi(e) > 0 ? atoi(e) : 0;
-  if (const char *e = getenv("MPMHIP_RIGID_CONCURRENT")) c->rigid.concurrent = atoi(e);
-  if (const char *e = getenv("MPMHIP_RIGID_WGS")) c->rigid_wgs = atoi(e) > 1 ? atoi(e) : 2048;
-  if (const char *e = getenv("MPMHIP_RANK_RUNS_MUL")) c->rank_runs_mul = (uint32_t)atoi(e);
-  if (const char *e = getenv("MPMHIP_CT_BLOCKS")) c->ct_blocks = atoi(e);
-  if (const char *e = getenv("MPMHIP_G2P_PACKED")) c->g2p_packed = atoi(e);
-  if (const char *e = getenv("MPMHIP_P2G_WGS")) c->p2g_wgs = atoi(e) > 0 ? atoi(e) : 16384;
-  if (const char *e = getenv("MPMHIP_GRID_WALK")) c->grid_walk = atoi(e);
-  if (const char *e = getenv("MPMHIP_GRID_WGS")) c->grid_wgs = atoi(e) > 0 ? atoi(e) : 0;
+  c->knobs = lp::Knobs::from_env();
   c->reorder_interval = cfg->reorder_interval;
   if (const char *e = getenv("MPMHIP_REORDER_INTERVAL")) c->reorder_interval = atoi(e);
   c->deterministic = cfg->deterministic != 0;
   if (const char *e = getenv("MPMHIP_DETERMINISTIC")) c->deterministic = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_CELL_ORDER")) c->cell_order_form = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_CELL_ORDER_WGS")) c->cell_order_wgs = std::max(1, atoi(e));
   auto bail = [&](int code) { g_create_error = c->err; mpmhip_destroy(c); return code; };
   if (hipSetDevice(c->device) != hipSuccess) { fail(c, MPMHIP_EHIP, "hipSetDevice failed"); return bail(MPMHIP_EHIP); }
   Params &P = c->P;
@@ -574,8 +614,8 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   A(c->cell_start.alloc((size_t)mb * BC + 1));
   // key-indexed cell counters (256 B per block of the WHOLE block space: 67 MB at 128^3, 537 MB at 256^3..508^3): with them the ranks
   // need no block table and share a launch with it (k_sort_front); grids of 2^24 blocks (res > 508) keep the four-launch sort
-  const bool sort_v1 = getenv("MPMHIP_SORT_V1") && atoi(getenv("MPMHIP_SORT_V1")) != 0;  // (A/B and tests: the four launches)
-  c->sort_keyed = c->NB <= (1u << 21) && !sort_v1;  // (the table itself is allocated behind every other buffer, below)
+  // (MPMHIP_SORT_V1, A/B and tests: the four launches)
+  const bool want_keyed = c->NB <= lp::KEYED_MAX_BLOCK_SPACE && !c->knobs.sort_v1;  // (the table itself is allocated behind every other buffer, below)
   A(c->nbr.alloc((size_t)mb * 32));
   A(c->own_list.alloc((size_t)mb * 8));
   c->bt_slots = (P.nbw + 255) / 256;
@@ -594,17 +634,14 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
     c->d_stats = reinterpret_cast<FillStats *>(reinterpret_cast<uint32_t *>(dp) + mpmhip_ctx::FILL_STATS_WORD);
   }
   A(c->d_groups.alloc((size_t)c->groups_cap));
-  if (e == hipSuccess && c->sort_keyed) {
+  if (e == hipSuccess && want_keyed) {
     // (an optimisation's table, 256 B per block of the whole block space: 67 MB at 128^3, 537 MB from 256^3 to 508^3.  A device that
     // cannot spare it keeps the four-launch sort instead of failing the create — or a later mpmhip_reserve, a tiled arena, the next
     // rank sharing the device: the table is only taken while it is at most an eighth of what is free NOW, behind every other buffer)
     size_t free_b = 0, total_b = 0;
     const size_t table_b = (size_t)c->NB * BC * sizeof(uint32_t);
     const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && table_b <= free_b / 8;
-    if (!room || c->cellcnt_key.alloc((size_t)c->NB * BC) != hipSuccess) {
-      (void)hipGetLastError();
-      c->sort_keyed = false;
-    }
+    if (!room || c->cellcnt_key.alloc((size_t)c->NB * BC) != hipSuccess) (void)hipGetLastError();
   }
   if (e != hipSuccess) {
     fail(c, MPMHIP_ENOMEM, "device allocation failed: %s (max_particles=%lld, max_blocks=%lld)", hipGetErrorString(e),
@@ -627,8 +664,6 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
     int cus = 0;
     A(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     if (cus > 0) c->n_cus = cus;
-    if (const char *e = getenv("MPMHIP_SCAN_GRID")) c->scan_grid_env = atoi(e);  // (tuning)
-    if (const char *e = getenv("MPMHIP_RANK_WGS")) c->rank_wgs_cap = (uint32_t)std::max(1, atoi(e));  // (tuning)
   }
   A(hipDeviceSynchronize());
   if (e != hipSuccess) { fail(c, MPMHIP_EHIP, "device init failed: %s", hipGetErrorString(e)); return bail(MPMHIP_EHIP); }
@@ -647,9 +682,9 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
         fail(c, MPMHIP_EHIP, "the occupancy query of a chained-scan kernel failed: its launch cannot be sized safely");
         return bail(MPMHIP_EHIP);
       }
-      if (scan_limit(c, k) > scan_resident_set(c->n_cus, per_cu)) {
+      if (scan_limit(c, k) > lp::scan_resident_set(c->n_cus, per_cu)) {
         fail(c, MPMHIP_EINVAL, "a chained scan would be launched with %u workgroups, the device keeps %u resident (MPMHIP_SCAN_GRID=%d?)",
-             scan_limit(c, k), scan_resident_set(c->n_cus, per_cu), c->scan_grid_env);
+             scan_limit(c, k), lp::scan_resident_set(c->n_cus, per_cu), c->knobs.scan_grid);
         return bail(MPMHIP_EINVAL);
       }
     }
@@ -1120,34 +1155,40 @@ int mpmhip_upload(mpmhip_ctx *c, int32_t field, const void *src, int64_t n) {
 static int do_reorder(mpmhip_ctx *c);
 
 static inline bool rigid_active(const mpmhip_ctx *c);
-// workgroups a single-pass scan kernel may be launched with: three eighths of what the device keeps resident of THAT kernel (a
-// quarter until round 4: after impact C3 has 21 k active blocks = 335 chunks of k_cell_table, and with 256 workgroups 79 of them
-// took a second chunk behind their first — sort 98 -> 88 us, profiles/r04_l_scan_grid.txt); the margin is for kernels of a second
-// stream (CPIC) beside the scans.  Per kernel since round 5: the list forms of k_cell_table hold fewer workgroups per CU than the
-// plain ones, and the lowest of all of them would cost the plain ones their grid.
-// The arithmetic of that bound, host-only (tests/test_host_cpu.py drives it through mpmhip_debug_scan_grid).  `per_cu` = what the
-// occupancy API answers for the kernel at 256 threads.  That answer can be one workgroup per CU HIGH (MI355X guide: 256-thread blocks
-// are admitted up to min(API, 8, ...) per CU, one fewer than the API says at 81..112 SGPRs), so the set that is certainly resident is
-// min(per_cu, 8) - 1 per CU (at least 1).  Three eighths of the API's number lies inside it for every per_cu (3/8 p <= p - 1 from
-// p = 2 on; p = 1: a third of the CUs), a request from the environment is cut to half the API's number AND to that set.
-static uint32_t scan_resident_set(int n_cus, int per_cu) { return (uint32_t)(std::max(1, n_cus) * std::max(1, std::min(per_cu, 8) - 1)); }
-static uint32_t scan_grid_for(int n_cus, int per_cu, int env_request) {
-  per_cu = std::max(1, per_cu);
-  int lim = std::max(1, std::max(1, n_cus) * per_cu * 3 / 8);
-  if (env_request > 0) lim = std::max(1, std::min(env_request, std::max(1, n_cus) * per_cu / 2));
-  return std::min<uint32_t>((uint32_t)lim, scan_resident_set(n_cus, per_cu));
+// bit t set = some particle group of the ctx is of material type t
+static uint32_t material_mask(const mpmhip_ctx *c) {
+  uint32_t mask = 0;
+  for (const GroupParams &g : c->groups) mask |= 1u << (g.type & 31);
+  return mask;
 }
+static_assert(lp::RANK_BATCH == RANK_BATCH && lp::BC == BC && lp::MAT_ALL == MAT_ALL, "launch_plan.h: copies of the device-side constants");
+// what the launch plans depend on (launch_plan.h).  The fill statistics are {live particles, active blocks, owner entries} of a
+// recent sort: k_cell_table's last chunk stores them straight into the pinned page, never waited for, so they may be a few
+// substeps old ({0, 0, 0} before the first sort has reported)
+static lp::Facts facts(const mpmhip_ctx *c) {
+  const volatile FillStats *fs = reinterpret_cast<const volatile FillStats *>(c->h_pinned + mpmhip_ctx::FILL_STATS_WORD);
+  lp::Facts f;
+  f.n_slots = c->n_slots; f.max_blocks = c->P.max_blocks; f.nbw = c->P.nbw; f.n_cus = c->n_cus;
+  f.mask = material_mask(c);
+  f.n_live = fs->n_live; f.n_act = fs->n_active; f.n_own = fs->n_own;
+  f.keyed_table = c->cellcnt_key != nullptr; f.tiled = c->T.enabled != 0; f.has_boxes = c->T.n_boxes > 0;
+  f.rigid = rigid_active(c); f.deterministic = c->deterministic; f.store_b = c->P.store_b != 0;
+  f.sampled_levelset = c->LS.sdf.phi0 != nullptr; f.has_chunk_blk = c->chunk_blk != nullptr;
+  return f;
+}
+// workgroups a chained-scan kernel may be launched with (launch_plan.h: scan_grid_for), per kernel: asked of the occupancy API once
 static uint32_t scan_limit(mpmhip_ctx *c, const void *kernel) {
   const void *key = kernel;
   auto it = c->scan_limits.find(key);
   if (it != c->scan_limits.end()) return it->second;
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-  const uint32_t lim = scan_grid_for(c->n_cus, per_cu, c->scan_grid_env);
+  const uint32_t lim = lp::scan_grid_for(c->n_cus, per_cu, c->knobs.scan_grid);
   c->scan_limits[key] = lim;
   return lim;
 }
 static int do_sort(mpmhip_ctx *c) {
+  const lp::SortPlan plan = lp::plan_sort(c->knobs, facts(c));
   Params &P = c->P;
   hipStream_t st = c->stream;
   const int pg = particle_grid(c->n_slots);
@@ -1155,58 +1196,45 @@ static int do_sort(mpmhip_ctx *c) {
   if (build_keys) hipLaunchKernelGGL(k_build_keys, dim3(pg), dim3(256), 0, st, P, c->rg, c->rp, c->cnt, c->key, c->blk_flag);
   // pidc[] holds the ids of the current key[]: k_build_keys wrote both just now, or the last G2P did
   const bool ids_cached = P.pidc && (build_keys || c->rec.pidc_valid());
-  // blocks per chunk of k_cell_table: few blocks -> finer chunks (shorter chains, more workgroups).  16 below 2 M slots, 64 from 6 M on
-  // (16 costs 10 us at 8 M: its 1 100 chunks no longer fit the scans' resident grid), 32 in between — a rank of a 2-brick job
-  // holds 4 M particles in 8 788 blocks: 17.4 us with 64 (as long as the whole 8 M problem takes: the kernel is a latency chain)
-  // With the key-indexed counters (k_sort_front) 16 is the best or within 3 us of it at every size (profiles/r05_s_ct_blocks.txt: a rank
-  // of 4 M 47.5 -> 44 us, C3 after impact 89.6 -> 86.5, the lattice 67.3 -> 64.2 where 32 gives 61.5): the plain table of that form keeps
-  // 1 100..1 340 chunks resident in one round.
-  const bool keyed = c->sort_keyed && c->cellcnt_key != nullptr;
-  const int ct = (c->ct_blocks == 16 || c->ct_blocks == 32 || c->ct_blocks == 64) ? c->ct_blocks
-                 : (keyed || c->n_slots < (2 << 20) ? 16 : (c->n_slots < (6 << 20) ? 32 : 64));
-  const uint32_t bt_chunks = (P.nbw + 255) / 256, ct_chunks = (P.max_blocks + ct - 1) / ct;
-  // Owner list of the grid pass (k_sort.h, k_grid.h): below 2 M slots it takes the pass from 17 to 7.5 us (1 M particles) for 2..3 us
-  // in k_rank + k_cell_table; a tiled ctx always builds it (the per-block walk with the halo-box code in it thrashes the instruction
-  // cache: 31 -> 19 us at 4 M particles per rank); an untiled ctx of 2 M slots and more does not — there the pass is bound by its
-  // 180 MB of tile reads either way (30.4 against 30.5 us at 8 M) and the rows cost the sort 8 us (profiles/r05_e_*_census.txt).
-  c->list_valid = c->grid_walk == 2 || (c->grid_walk < 0 && (c->T.enabled || c->n_slots < (2 << 20)));
-  uint32_t *const nbr = c->list_valid ? c->nbr : nullptr;
+  c->list_valid = plan.build_list;
+  uint32_t *const nbr = plan.build_list ? c->nbr : nullptr;
   uint32_t epoch = ++c->sort_epoch;
   if ((epoch & 0x7FFFFFu) == 0u) epoch = ++c->sort_epoch;  // (k_cell_table's scan words keep 23 bits of it; 0 = never published)
   // (single-pass scans: never more workgroups than are resident at once, see k_sort.h)
-  const uint32_t rank_wgs = std::max(1u, std::min<uint32_t>((P.n_slots + RANK_BATCH - 1) / RANK_BATCH, c->rank_wgs_cap));
-  const uint32_t bt_wgs = std::min(bt_chunks, keyed ? scan_limit(c, (const void *)k_sort_front) : scan_limit(c, (const void *)k_block_table));
-  if (keyed) {
+  uint32_t *counters = c->cell_cnt;
+  if (plan.keyed) {
     // block table and in-cell ranks in ONE launch (k_sort_front): the ranks count into key-indexed counters and need no table
-    hipLaunchKernelGGL(k_sort_front, dim3(bt_wgs + rank_wgs), dim3(256), 0, st, P, c->blk_flag, c->bits, c->wprefix, c->act_blk, c->cnt,
+    const uint32_t bt_wgs = std::min(plan.bt_chunks, scan_limit(c, (const void *)k_sort_front));
+    hipLaunchKernelGGL(k_sort_front, dim3(bt_wgs + plan.rank_wgs), dim3(256), 0, st, P, c->blk_flag, c->bits, c->wprefix, c->act_blk, c->cnt,
                        c->scan_slots, epoch, bt_wgs, c->key, c->rank, c->cellcnt_key);
+    counters = c->cellcnt_key;
   } else {
+    const uint32_t bt_wgs = std::min(plan.bt_chunks, scan_limit(c, (const void *)k_block_table));
     hipLaunchKernelGGL(k_block_table, dim3(bt_wgs), dim3(256), 0, st, P, c->blk_flag, c->bits, c->wprefix, c->act_blk, c->cnt, c->scan_slots, epoch);
-    hipLaunchKernelGGL(k_rank, dim3(rank_wgs), dim3(256), 0, st, P, c->key, c->rank, c->cell_cnt, c->bits, c->wprefix,
+    hipLaunchKernelGGL(k_rank, dim3(plan.rank_wgs), dim3(256), 0, st, P, c->key, c->rank, c->cell_cnt, c->bits, c->wprefix,
                        c->cnt, (const uint32_t *)c->act_blk, nbr);
   }
-  uint32_t *const counters = keyed ? c->cellcnt_key : c->cell_cnt;
-#define MPM_CT(K, CT) (keyed ? K<CT, true> : K<CT, false>)
-  auto ct_list = ct == 16 ? MPM_CT(k_cell_table, 16) : (ct == 32 ? MPM_CT(k_cell_table, 32) : MPM_CT(k_cell_table, 64));
-  auto ct_plain = ct == 16 ? MPM_CT(k_cell_table_plain, 16) : (ct == 32 ? MPM_CT(k_cell_table_plain, 32) : MPM_CT(k_cell_table_plain, 64));
-  const uint32_t ct_wgs = std::min(ct_chunks, c->list_valid ? scan_limit(c, (const void *)ct_list) : scan_limit(c, (const void *)ct_plain));
-  if (c->list_valid && epoch - c->list_clear_epoch >= (1u << 22)) {
-    // the list form's scan words keep 23 bits of the epoch, and a word is only rewritten when that form runs with the chunk in use: one
-    // left from epoch e would match again at e + 2^23 (8.4 M sorts: reachable in a long run).  Zeroing them every 2^22 sorts keeps every
-    // surviving word younger than that; the epoch field 0 is never published.
-    HIPCHK(c, hipMemsetAsync(c->scan_slots + c->bt_slots + c->ct_slots, 0, sizeof(unsigned long long) * c->ct_slots, st));
-    c->list_clear_epoch = epoch;
-  }
-  if (c->list_valid)  // (the two forms publish different scan words: each has its own slots)
-    hipLaunchKernelGGL(ct_list, dim3(ct_wgs), dim3(256), 0, st, P,
-                       c->cnt, counters, c->act_start, c->cell_start, c->scan_slots + c->bt_slots + c->ct_slots, epoch, c->rank_runs_mul,
+  if (plan.build_list) {  // (the two forms publish different scan words: each has its own slots)
+    const auto kern = cell_table_kernel(plan);
+    const uint32_t ct_wgs = std::min(plan.ct_chunks, scan_limit(c, (const void *)kern));
+    if (epoch - c->list_clear_epoch >= (1u << 22)) {
+      // the list form's scan words keep 23 bits of the epoch, and a word is only rewritten when that form runs with the chunk in use: one
+      // left from epoch e would match again at e + 2^23 (8.4 M sorts: reachable in a long run).  Zeroing them every 2^22 sorts keeps every
+      // surviving word younger than that; the epoch field 0 is never published.
+      HIPCHK(c, hipMemsetAsync(c->scan_slots + c->bt_slots + c->ct_slots, 0, sizeof(unsigned long long) * c->ct_slots, st));
+      c->list_clear_epoch = epoch;
+    }
+    hipLaunchKernelGGL(kern, dim3(ct_wgs), dim3(256), 0, st, P,
+                       c->cnt, counters, c->act_start, c->cell_start, c->scan_slots + c->bt_slots + c->ct_slots, epoch, c->knobs.rank_runs_mul,
                        c->chunk_blk, nbr, c->own_list, c->d_stats, (const uint32_t *)c->act_blk, (const uint32_t *)c->bits, (const uint32_t *)c->wprefix);
-  else
-    hipLaunchKernelGGL(ct_plain, dim3(ct_wgs), dim3(256), 0, st, P,
-                       c->cnt, counters, c->act_start, c->cell_start, c->scan_slots + c->bt_slots, epoch, c->rank_runs_mul, c->chunk_blk,
+  } else {
+    const auto kern = cell_table_plain_kernel(plan);
+    const uint32_t ct_wgs = std::min(plan.ct_chunks, scan_limit(c, (const void *)kern));
+    hipLaunchKernelGGL(kern, dim3(ct_wgs), dim3(256), 0, st, P,
+                       c->cnt, counters, c->act_start, c->cell_start, c->scan_slots + c->bt_slots, epoch, c->knobs.rank_runs_mul, c->chunk_blk,
                        c->d_stats, (const uint32_t *)c->act_blk);
-#undef MPM_CT
-  if (keyed)
+  }
+  if (plan.keyed)
     hipLaunchKernelGGL(k_perm_keyed, dim3(pg), dim3(256), 0, st, P, (const Counters *)c->cnt, c->key, c->rank, c->cell_start, c->perm,
                        (const uint32_t *)c->bits, (const uint32_t *)c->wprefix);
   else
@@ -1214,20 +1242,17 @@ static int do_sort(mpmhip_ctx *c) {
   if (c->deterministic) {
     // every cell's entries in ascending creation id (k_sort.h: k_cell_order); rank[] is idle until the next sort: the ordered index goes
     // there and then IS the index
-    if (c->cell_order_form == 0) {  // (A/B: one lane per cell over the whole table)
-      const int cg = (int)std::min<uint64_t>(8192u, ((uint64_t)P.max_blocks * BC + 255) / 256);
-      hipLaunchKernelGGL((ids_cached ? k_cell_order<true> : k_cell_order<false>), dim3(cg), dim3(256), 0, st, P, (const Counters *)c->cnt,
+    if (plan.cell_order_form == 0)
+      hipLaunchKernelGGL((ids_cached ? k_cell_order<true> : k_cell_order<false>), dim3(plan.cell_order_wgs), dim3(256), 0, st, P, (const Counters *)c->cnt,
                          (const uint32_t *)c->cell_start, (const uint32_t *)c->perm, (const float4 *)c->rg.get(), c->rank);
-    } else {  // one wave per active block through LDS: 7 workgroups per CU resident (22 KiB each), a few blocks per wave
-      const int cg = (int)std::min<uint64_t>((uint64_t)c->n_cus * (uint64_t)c->cell_order_wgs, ((uint64_t)P.max_blocks + 3) / 4);
-      hipLaunchKernelGGL((ids_cached ? k_cell_order_blocks<true> : k_cell_order_blocks<false>), dim3(std::max(1, cg)), dim3(256), 0, st, P,
+    else
+      hipLaunchKernelGGL((ids_cached ? k_cell_order_blocks<true> : k_cell_order_blocks<false>), dim3(plan.cell_order_wgs), dim3(256), 0, st, P,
                          (const Counters *)c->cnt, (const uint32_t *)c->cell_start, (const uint32_t *)c->perm, (const float4 *)c->rg.get(), c->rank);
-    }
     std::swap(c->perm, c->rank);
   }
   // (k_cell_table's last chunk stores (live particles, active blocks, owner entries) of this sort straight into the pinned page,
-  // never waited for: the host picks the G2P walk by how full the blocks are (g2p_is_packed) and sizes the grid pass's launch
-  // from numbers that may be a few substeps old)
+  // never waited for: the host picks the G2P walk by how full the blocks are and sizes the grid pass's launch from numbers
+  // that may be a few substeps old: facts)
   c->rec.sort_done();  // (key[] now holds k_rank's packed (rank, cell index) words)
   int rc = launch_check(c, "sort");
   if (rc) return rc;
@@ -1262,14 +1287,13 @@ static int do_reorder(mpmhip_ctx *c) {
 }
 
 static RigidXfer rigid_xfer(mpmhip_ctx *c);
-// bit t set = some particle group of the ctx is of material type t
 // The plain transfer kernel (every block away from the bodies) and the colour-aware one (the flagged blocks) touch disjoint
 // blocks and particles, and each is latency-bound at two waves per SIMD: they run side by side, the colour-aware kernel on a
 // second stream that waits for what the ctx stream has enqueued so far (fork) and is waited for before anything else (join).
 static int rigid_fork(mpmhip_ctx *c, hipStream_t *s, int which) {
   auto &R = c->rigid;
   *s = c->stream;
-  if (!(R.concurrent & which)) return MPMHIP_OK;
+  if (!(c->knobs.rigid_concurrent & which)) return MPMHIP_OK;
   if (!R.side) {
     // the highest priority: the colour-aware kernels are the longer ones of a pair and get their wave slots first
     // (8 M scene: 1.163 -> 1.150 ms per substep against the default priority)
@@ -1290,15 +1314,11 @@ static int rigid_join(mpmhip_ctx *c, hipStream_t s) {
   HIPCHK(c, hipStreamWaitEvent(c->stream, c->rigid.ev_join, 0));
   return MPMHIP_OK;
 }
-static uint32_t material_mask(const mpmhip_ctx *c) {
-  uint32_t mask = 0;
-  for (const GroupParams &g : c->groups) mask |= 1u << (g.type & 31);
-  return mask;
-}
 static int do_rigid_apply_tmp(mpmhip_ctx *c);
 static int rigid_imp_rows(mpmhip_ctx *c);
 
 static int do_p2g(mpmhip_ctx *c, int phase = 0) {
+  const lp::P2GPlan plan = lp::plan_p2g(c->knobs, facts(c));
   if (!c->rec.affine_valid()) {
     hipLaunchKernelGGL(k_affine, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, c->rg, c->rp, c->rb,
                        c->d_groups);
@@ -1308,19 +1328,15 @@ static int do_p2g(mpmhip_ctx *c, int phase = 0) {
   // 0.237 (two waves splitting the nodes) and 0.225 (two waves splitting the particles).  Splitting the particles does
   // not help small problems either (128^3 / 1 M, where only 2 448 waves exist: 34 us with one wave per block, 37 with
   // two, 48 with four)
-  const bool rigid = rigid_active(c);
   hipStream_t rs = c->stream;
-  if (rigid) { if (int rc = rigid_fork(c, &rs, 1)) return rc; }
-  hipLaunchKernelGGL(rigid ? k_p2g<true> : k_p2g<false>, dim3(c->p2g_wgs), dim3(64), 0, c->stream, c->P,
+  if (plan.rigid) { if (int rc = rigid_fork(c, &rs, 1)) return rc; }
+  hipLaunchKernelGGL(plan.rigid ? k_p2g<true> : k_p2g<false>, dim3(plan.wgs), dim3(64), 0, c->stream, c->P,
                      (const float4 *)c->rp.get(), c->cnt, c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, c->T, phase,
-                     rigid ? (const uint8_t *)c->rigid.d_blk_rigid : (const uint8_t *)nullptr);
-  if (rigid) {  // blocks near a body (block_op_rigid), then RigidBody::apply_tmp_velocity (src/transfer.cpp:578-580)
-    // (deterministic mode: the all-material form with the impulse rows, summed by do_rigid_apply_tmp)
-    auto rk = c->deterministic ? k_p2g_rigid<MAT_ALL | MAT_DET>
-                               : one_material(material_mask(c), k_p2g_rigid<MAT_ALL>, [](auto m) { return k_p2g_rigid<m.value>; });
-    if (c->deterministic) { if (int rc = rigid_imp_rows(c)) return rc; }
-    hipLaunchKernelGGL(rk, dim3(c->rigid_wgs), dim3(64), 0, rs, c->P, (const float4 *)c->rp.get(), (const float4 *)c->rg.get(), c->cnt,
-                       c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, rigid_xfer(c));
+                     plan.rigid ? (const uint8_t *)c->rigid.d_blk_rigid : (const uint8_t *)nullptr);
+  if (plan.rigid) {  // blocks near a body (block_op_rigid), then RigidBody::apply_tmp_velocity (src/transfer.cpp:578-580)
+    if (plan.rigid_mats.kind == lp::MatSet::ALL_DET) { if (int rc = rigid_imp_rows(c)) return rc; }
+    hipLaunchKernelGGL(rigid_p2g_kernel(plan.rigid_mats), dim3(plan.rigid_wgs), dim3(64), 0, rs, c->P, (const float4 *)c->rp.get(),
+                       (const float4 *)c->rg.get(), c->cnt, c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, rigid_xfer(c));
     if (int rc = rigid_join(c, rs)) return rc;
     if (int rc = do_rigid_apply_tmp(c)) return rc;
   }
@@ -1328,119 +1344,47 @@ static int do_p2g(mpmhip_ctx *c, int phase = 0) {
 }
 // dense: what the kernels' `dense` argument points at; nullptr: the ctx's staging array of the dense views (modes 1-3; unused in mode 0)
 static int do_grid(mpmhip_ctx *c, int mode, int phase = 0, float4 *dense = nullptr) {
+  const lp::GridPlan plan = lp::plan_grid(c->knobs, facts(c), mode, c->list_valid);
   if (!dense) dense = c->dense;
   c->P.t = c->t;  // this->current_t of the substep in flight (src/mpm.cpp:532-533)
   c->LS.dirichlet = c->dirichlet ? 1 : 0;
-  // mode 0 (the substep's pass) and mode 4 (energy) walk the owner list when the last sort built one (do_sort: small problems and
-  // every tiled ctx): one wave per touched grid block, launched at the size of the list as the last sort reported it (+ 12 %; the
-  // walk is a grid-stride loop, so a stale number costs time, never correctness).  Otherwise, and for the dense views: the walks
-  // of rounds 1-4 — per block at >= 2 M slots, per (block, candidate) below.
-  if ((mode == 0 || mode == 4 || mode == 5) && c->list_valid) {
-    const volatile FillStats *fs = reinterpret_cast<const volatile FillStats *>(c->h_pinned + mpmhip_ctx::FILL_STATS_WORD);
-    uint64_t n_own = fs->n_own;
-    if (n_own == 0) n_own = std::min<uint64_t>((uint64_t)c->P.max_blocks * 8u, 32768u);  // (before the first sort has reported)
-    int wgs = (int)std::min<uint64_t>(8192u, std::max<uint64_t>(64u, (n_own + n_own / 8 + 3) / 4 + 8));
-    if (c->grid_wgs > 0) wgs = c->grid_wgs;
-    const bool sdf = mode == 0 && c->LS.sdf.phi0;  // sampled level set: the instantiation that reads it
-    hipLaunchKernelGGL(mode == 0 ? (sdf ? k_grid_list<0, true> : k_grid_list<0>) : (mode == 4 ? k_grid_list<4> : k_grid_list<5>), dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, (const uint32_t *)c->nbr,
-                       (const uint32_t *)c->own_list, c->tiles, c->gridv, c->fat_slot, reinterpret_cast<double *>(dense), c->T,
-                       c->d_boxes_cur, c->LS, phase);
-    return launch_check(c, "grid");
-  }
-  if ((mode == 4 || mode == 5) && c->T.n_boxes > 0)
+  if (plan.refuse_energy_on_tiled)
     // (only the owner-list walk knows which rank counts a halo node's kinetic energy — the lowest that holds mass on it; the per-block
     // walk would add every halo node on every rank that holds it)
     return fail(c, MPMHIP_EINVAL, "calculate_energy of a tiled ctx needs the owner-list walk of the grid pass: do not set MPMHIP_GRID_WALK=0");
-  const bool per_cand = mode == 0 && c->n_slots < (2 << 20);  // small per-GPU problem: latency-bound, see k_grid.h
-  auto kern = mode == 0 ? (per_cand ? k_grid_blocks<0, true> : k_grid_blocks<0, false>)
-                        : (mode == 1 ? k_grid_blocks<1, false>
-                                     : (mode == 2 ? k_grid_blocks<2, false>
-                                                  : (mode == 3 ? k_grid_blocks<3, false>
-                                                               : (mode == 4 ? k_grid_blocks<4, false> : k_grid_blocks<5, false>))));
-  if (mode == 0 && c->LS.sdf.phi0) kern = per_cand ? k_grid_blocks<0, true, true> : k_grid_blocks<0, false, true>;
-  int wgs = per_cand ? 16384 : 4096;
-  if (c->grid_wgs > 0 && mode == 0) wgs = c->grid_wgs;
-  hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), 0, c->stream, c->P, c->cnt, c->act_blk, c->bits, c->wprefix, c->tiles,
-                     c->gridv, c->fat_slot, dense, c->T, c->d_boxes_cur, c->LS, phase);
+  if (plan.walk == lp::GridWalk::LIST)
+    hipLaunchKernelGGL(grid_list_kernel(plan, mode), dim3(plan.wgs), dim3(256), 0, c->stream, c->P, c->cnt, (const uint32_t *)c->nbr,
+                       (const uint32_t *)c->own_list, c->tiles, c->gridv, c->fat_slot, reinterpret_cast<double *>(dense), c->T,
+                       c->d_boxes_cur, c->LS, phase);
+  else
+    hipLaunchKernelGGL(grid_blocks_kernel(plan, mode), dim3(plan.wgs), dim3(256), 0, c->stream, c->P, c->cnt, c->act_blk, c->bits, c->wprefix,
+                       c->tiles, c->gridv, c->fat_slot, dense, c->T, c->d_boxes_cur, c->LS, phase);
   return launch_check(c, "grid");
 }
-// which G2P kernel the plain blocks of the next substep get (bench.py names the kernel of its roofline after it).  By size and by
-// how full the blocks are: k_g2p's chunks stay inside a block, so with 512 particles per block (the lattice the reference's benchmark
-// seeds) they are full and it is the faster walk by a few microseconds on most boxes; with 350 per block (the same scene after the
-// impact) a third of its lanes idle and the packed walk wins by 30 us.  The numbers come from the sort, a few substeps late.
-static bool g2p_is_packed(const mpmhip_ctx *c, int phase) {
-  bool packed = c->g2p_packed != 0;
-  if (c->g2p_packed < 0) {
-    const volatile uint32_t *fill = c->h_pinned + mpmhip_ctx::FILL_STATS_WORD;  // {live particles, active blocks} of a recent sort (0, 0 before the first)
-    const uint32_t n_live = fill[0], n_act = fill[1];
-    packed = c->n_slots >= (2 << 20) && n_act > 0 && (uint64_t)n_live < (uint64_t)n_act * 448u;
-  }
-  const uint32_t mask = material_mask(c);
-  const bool one_plain_material = mask && !(mask & (mask - 1)) && mask != (1u << MPMHIP_VISCO);
-  return packed && one_plain_material && !rigid_active(c) && !c->P.store_b && phase == 0 && !c->T.enabled && c->chunk_blk;
-}
 static int do_g2p(mpmhip_ctx *c, int phase = 0) {
+  const lp::G2PPlan plan = lp::plan_g2p(c->knobs, facts(c), phase);
   c->P.t = c->t;
-  const bool sb = c->P.store_b != 0;
-  // __launch_bounds__(256, 2) only PERMITS 256 VGPRs; what decides the speed is whether the allocation stays <= 168, i.e.
-  // whether THREE workgroups fit a CU's register file (512 per SIMD lane): 168 VGPRs 0.303 ms, 180 VGPRs 0.347 ms on the same
-  // box (profiles/r03_b_ab_vgpr.txt).  Forcing the bound (256, 3) makes the ALL-material kernel spill (its scratch reloads
-  // wait on the prefetched records: vmcnt is shared and in-order) and costs the others 3 % (profiles/r03_h_ab_refactor.txt),
-  // so the budget is met by specialising instead and guarded by tests/test_kernel_budget_cpu.py:
-  // the kernel is instantiated per material SET (k_g2p.h: MATS): one material in the whole ctx (the benchmark configurations,
-  // most scene scripts) -> the kernel that carries only that material's constitutive code (sand: 2 833 instructions and 153
-  // VGPRs against 5 552 / 180 for all eight); no visco group -> the set without it (161 VGPRs: visco, with two eigen-solves
-  // and a matrix exponential, is what pushes the full kernel over the budget).
-  constexpr uint32_t NO_VISCO = MAT_ALL & ~(1u << MPMHIP_VISCO);
-  const uint32_t mask = material_mask(c);
-  const bool rigid = rigid_active(c), no_visco = !(mask & (1u << MPMHIP_VISCO));
-  auto kern = sb ? (no_visco ? k_g2p<256, G2P_MIN_WAVES, true, true, false, NO_VISCO> : k_g2p<256, 2, true, true>)
-                 : (no_visco ? k_g2p<256, G2P_MIN_WAVES, true, false, false, NO_VISCO> : k_g2p<256, 2, true, false>);
-  if (rigid) {
-    kern = sb ? (no_visco ? k_g2p<256, G2P_MIN_WAVES, true, true, true, NO_VISCO> : k_g2p<256, 2, true, true, true>)
-              : (no_visco ? k_g2p<256, G2P_MIN_WAVES, true, false, true, NO_VISCO> : k_g2p<256, 2, true, false, true>);
-    if (!sb) kern = one_material(mask, kern, [](auto m) { return k_g2p<256, G2P_MIN_WAVES, true, false, true, m.value>; });
-  } else if (!sb) {
-    kern = one_material(mask, kern, [](auto m) { return k_g2p<256, G2P_MIN_WAVES, true, false, false, m.value>; });
-  }
-  // packed chunks (k_g2p_packed.h): -3.5 us of 303 on the lattice of C3, -14 us of 373 after impact; at 1 M particles +7 us of 50
-  // (768 workgroups with a handful of chunks each: the walk's set-up is not amortised) — hence by size
-  // (one-material instantiations only: they stay below the 168 VGPRs of three workgroups per CU — 163 to 167; the kernel for
-  // mixed materials would have 177, the visco one 183: those scenes keep k_g2p)
-  decltype(&k_g2p_packed<256, G2P_MIN_WAVES, false, 1u << MPMHIP_SAND>) pk = nullptr;
-  if (g2p_is_packed(c, phase))
-    pk = one_material<1u << MPMHIP_VISCO>(mask, pk, [](auto m) { return k_g2p_packed<256, G2P_MIN_WAVES, false, m.value>; });
-  if (pk) {
-    // four times the device's resident set (three workgroups per CU): with equal work items what is left of the launch's tail is
-    // the partly filled last round — 4 096 workgroups are 5.33 rounds of 768.  At C3, lattice / after impact: 3 072 -> 287 / 336 us,
-    // 4 096 -> 287 / 352, 6 144 -> 291 / 343, 2 304 -> 296 / 346, 1 536 -> 292 / 350, 768 -> 304 / 350 (profiles/r04_u_g2p_wgs.txt)
-    const int wgs = c->g2p_wgs > 0 ? c->g2p_wgs : (c->n_slots < (2 << 20) ? 768 : 12 * c->n_cus);
-    hipLaunchKernelGGL(pk, dim3(wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(),
+  // what every G2P kernel takes; tail: the chunk table (packed), the phase (per block), the bodies (colour-aware)
+  auto launch = [&](auto kern, int wgs, hipStream_t s, auto... tail) {
+    hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), 0, s, c->P, (const float4 *)c->rg.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(),
                        (float4 *)c->rb2.get(), c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
-                       c->blk_flag, (const LevelSetDev *)c->d_LS, (const uint32_t *)c->chunk_blk);
-    c->rec.g2p_done(sb, c->P.pidc != nullptr);
+                       c->blk_flag, (const LevelSetDev *)c->d_LS, tail...);
+  };
+  if (plan.packed) {
+    launch(g2p_packed_kernel(plan), plan.wgs, c->stream, (const uint32_t *)c->chunk_blk);
+    c->rec.g2p_done(plan.store_b, c->P.pidc != nullptr);
     return launch_check(c, "g2p_packed");
   }
   hipStream_t rs = c->stream;
-  if (rigid) { if (int rc = rigid_fork(c, &rs, 2)) return rc; }
-  // 4 096 workgroups at 8 M particles (2 048 / 8 192 measured no better); below ~2 M slots the device's resident set (three
-  // workgroups per CU = 768) walking ~6 chunks each WITH the record prefetch beats one chunk per workgroup: 51.9 -> 46.1 us at
-  // 1 M particles (profiles/r04_b_knobs.txt; 512 and 1 024 are slower again)
-  const int g2p_wgs = c->g2p_wgs > 0 ? c->g2p_wgs : (c->n_slots < (2 << 20) ? 768 : 4096);
-  hipLaunchKernelGGL(kern, dim3(g2p_wgs), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(),
-                     (float4 *)c->rb2.get(), c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
-                     c->blk_flag, (const LevelSetDev *)c->d_LS, phase_box(c->T), phase);
-  if (rigid) {
-    auto rk = c->deterministic ? k_g2p_rigid<MAT_ALL | MAT_DET>
-                               : one_material(mask, k_g2p_rigid<MAT_ALL>, [](auto m) { return k_g2p_rigid<m.value>; });
-    if (c->deterministic) { if (int rc = rigid_imp_rows(c)) return rc; }
-    hipLaunchKernelGGL(rk, dim3(c->rigid_wgs / 2), dim3(256), 0, rs, c->P, (const float4 *)c->rg.get(), (float4 *)c->rg2.get(), (float4 *)c->rp2.get(),
-                       (float4 *)c->rb2.get(), c->cnt, c->act_blk, c->act_start, c->perm, c->d_groups, c->gridv, c->fat_slot, c->cnt, c->key,
-                       c->blk_flag, (const LevelSetDev *)c->d_LS, rigid_xfer(c));
+  if (plan.rigid) { if (int rc = rigid_fork(c, &rs, 2)) return rc; }
+  launch(g2p_kernel(plan), plan.wgs, c->stream, phase_box(c->T), phase);
+  if (plan.rigid) {
+    if (plan.rigid_mats.kind == lp::MatSet::ALL_DET) { if (int rc = rigid_imp_rows(c)) return rc; }
+    launch(rigid_g2p_kernel(plan.rigid_mats), plan.rigid_wgs, rs, rigid_xfer(c));
     if (int rc = rigid_join(c, rs)) return rc;
     if (int rc = do_rigid_apply_tmp(c)) return rc;
   }
-  c->rec.g2p_done(sb, c->P.pidc != nullptr);
+  c->rec.g2p_done(plan.store_b, c->P.pidc != nullptr);
   return launch_check(c, "g2p");
 }
 
@@ -2366,12 +2310,12 @@ int mpmhip_reserve(mpmhip_ctx *c, int64_t max_particles) {
 // the launch bound of the chained scans as a function of what the occupancy API answered (no device needed: scan_grid_for)
 int mpmhip_debug_scan_grid(int32_t n_cus, int32_t per_cu, int32_t env_request, uint32_t *limit, uint32_t *resident) {
   if (!limit || !resident || n_cus < 1 || per_cu < 0) return MPMHIP_EINVAL;
-  *limit = scan_grid_for(n_cus, per_cu, env_request);
-  *resident = scan_resident_set(n_cus, per_cu);
+  *limit = lp::scan_grid_for(n_cus, per_cu, env_request);
+  *resident = lp::scan_resident_set(n_cus, per_cu);
   return MPMHIP_OK;
 }
 int64_t mpmhip_debug_live_buffers(void) { return hostmem::g_live_buffers.load(std::memory_order_relaxed); }
-int mpmhip_debug_g2p_is_packed(const mpmhip_ctx *c) { return c ? (g2p_is_packed(c, 0) ? 1 : 0) : MPMHIP_EINVAL; }
+int mpmhip_debug_g2p_is_packed(const mpmhip_ctx *c) { return c ? (lp::plan_g2p(c->knobs, facts(c), 0).packed ? 1 : 0) : MPMHIP_EINVAL; }
 int mpmhip_debug_copy_bandwidth(mpmhip_ctx *c, size_t bytes, int32_t iters, double *gb_per_s) {
   if (!c || !gb_per_s || iters <= 0 || bytes < 16) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
