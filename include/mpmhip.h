@@ -755,6 +755,12 @@ int mpmhip_debug_copy_bandwidth(mpmhip_ctx *ctx, size_t bytes, int32_t iters, do
 /* measurement helper: 1 when the next substep's G2P is k_g2p_packed (chunks of 256 consecutive sorted positions; large
  * one-material problems without rigid bodies or tiling), 0 when it is k_g2p (chunks inside one block) */
 int mpmhip_debug_g2p_is_packed(const mpmhip_ctx *ctx);
+/* test helper: what plan_g2p / plan_p2g (csrc/launch_plan.h) answer for the ctx as it stands, i.e. which instantiations of the
+ * transfer kernels the next substep launches.  Nothing is launched.  out[0] packed (k_g2p_packed instead of k_g2p), [1] material set
+ * of k_g2p / k_g2p_packed: 0 ONE, 1 NO_VISCO, 2 ALL, [2] its bit 1 << material when ONE, else 0, [3] STORE_B, [4] RIGID (k_p2g_rigid
+ * and k_g2p_rigid take the blocks near a body), [5] material set of those two: 0 ONE, 2 ALL, 3 ALL_DET, [6] its bit when ONE, [7] 1 when
+ * P2G's colour-aware kernel runs, on the set of [5] / [6] */
+int mpmhip_debug_transfer_plan(const mpmhip_ctx *ctx, int32_t out[8]);
 /* the launch bound of the single-pass (chained) scans of the sort as a function of the occupancy API's answer: `limit` = workgroups
  * the host launches at most, `resident` = workgroups the device certainly keeps resident (one per CU below the API's number, at most
  * 7).  Pure host arithmetic (no device): mpmhip_create checks limit <= resident for every such kernel; the waits are bounded besides. */

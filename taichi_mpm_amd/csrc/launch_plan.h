@@ -242,4 +242,21 @@ inline G2PPlan plan_g2p(const Knobs &k, const Facts &f, int phase) {
   return p;
 }
 
+// ------------------------------------------------------------------------------------------------ which transfer kernels
+// The instantiations of the transfer kernels a substep launches, as eight words (mpmhip_debug_transfer_plan; the tests assert the
+// form they mean to cover before they compare numbers): [0] packed, [1] kind and [2] bit of the set k_g2p / k_g2p_packed carry,
+// [3] STORE_B, [4] RIGID, [5] kind and [6] bit of the set of k_p2g_rigid / k_g2p_rigid, [7] P2G launches k_p2g_rigid on that set
+inline void transfer_plan_words(const Knobs &k, const Facts &f, int32_t out[8]) {
+  const G2PPlan g = plan_g2p(k, f, 0);
+  const P2GPlan p = plan_p2g(k, f);
+  out[0] = g.packed;
+  out[1] = (int32_t)g.mats.kind;
+  out[2] = g.mats.kind == MatSet::ONE ? (int32_t)g.mats.bit : 0;
+  out[3] = g.store_b;
+  out[4] = g.rigid;
+  out[5] = (int32_t)g.rigid_mats.kind;
+  out[6] = g.rigid_mats.kind == MatSet::ONE ? (int32_t)g.rigid_mats.bit : 0;
+  out[7] = p.rigid && p.rigid_mats == g.rigid_mats;
+}
+
 }  // namespace lp

@@ -2316,6 +2316,11 @@ int mpmhip_debug_scan_grid(int32_t n_cus, int32_t per_cu, int32_t env_request, u
 }
 int64_t mpmhip_debug_live_buffers(void) { return hostmem::g_live_buffers.load(std::memory_order_relaxed); }
 int mpmhip_debug_g2p_is_packed(const mpmhip_ctx *c) { return c ? (lp::plan_g2p(c->knobs, facts(c), 0).packed ? 1 : 0) : MPMHIP_EINVAL; }
+int mpmhip_debug_transfer_plan(const mpmhip_ctx *c, int32_t out[8]) {
+  if (!c || !out) return MPMHIP_EINVAL;
+  lp::transfer_plan_words(c->knobs, facts(c), out);
+  return MPMHIP_OK;
+}
 int mpmhip_debug_copy_bandwidth(mpmhip_ctx *c, size_t bytes, int32_t iters, double *gb_per_s) {
   if (!c || !gb_per_s || iters <= 0 || bytes < 16) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));

@@ -327,6 +327,19 @@ def load_obj_triangles(path):
     return np.asarray(tris, np.float32)
 
 
+def transfer_plan(words):
+    """the eight words of mpmhip_debug_transfer_plan as a dict: `packed` (k_g2p_packed instead of k_g2p), `mats` the material set
+    that kernel is instantiated for — ("ONE", material name), ("NO_VISCO", None) or ("ALL", None) —, `store_b`, `rigid` (k_g2p_rigid
+    takes the blocks near a body), `rigid_mats` the set of the colour-aware kernels (as `mats`, or ("ALL_DET", None)), `p2g_rigid`
+    (k_p2g_rigid runs, on that set)"""
+    names = {1 << t: name for name, t in MATERIAL_IDS.items()}
+
+    def mats(kind, bit):
+        return (("ONE", "NO_VISCO", "ALL", "ALL_DET")[kind], names[bit] if kind == 0 else None)
+    return {"packed": bool(words[0]), "mats": mats(words[1], words[2]), "store_b": bool(words[3]), "rigid": bool(words[4]),
+            "rigid_mats": mats(words[5], words[6]), "p2g_rigid": bool(words[7])}
+
+
 # config keys of MPM<dim>::initialize / substep that change the physics and are NOT implemented here: a scene that sets them to
 # anything but the inert default is refused instead of being simulated differently (key: inert value, where the reference reads it)
 UNSUPPORTED_KEYS = {
@@ -1011,6 +1024,14 @@ class Simulation3D:
         """name of the G2P kernel the next substep's plain blocks get (measurement helper: bench.py names its roofline after it)"""
         self._ensure_ctx()
         return "k_g2p_packed" if self._check(self._L.mpmhip_debug_g2p_is_packed(self._ctx)) else "k_g2p"
+
+    def transfer_kernels(self):
+        """which instantiations of the transfer kernels the next substep launches, for the ctx as it stands (include/mpmhip.h:
+        mpmhip_debug_transfer_plan; nothing is launched): see transfer_plan()"""
+        self._ensure_ctx()
+        out = (C.c_int32 * 8)()
+        self._check(self._L.mpmhip_debug_transfer_plan(self._ctx, out))
+        return transfer_plan(list(out))
 
     def copy_bandwidth(self, nbytes=1 << 30, iters=5):
         """GB/s (read + written) of a plain streaming copy on this GPU: the measured yardstick next to the nominal peak"""

@@ -56,6 +56,43 @@ def make_state(x, type_name, dx, density=400.0, ppc=8, seed=1, vel_scale=1.0, pe
     return orc.State(x, v, B, F, aux, np.zeros(n, np.int32), gp[None, :], np.array([t], np.int32))
 
 
+def mixed_state(x, mats, dx, seed, **kw):
+    """the particles at x dealt out to the materials `mats` by a seeded permutation (equal shares to within one particle), so that
+    materials mix inside every cell; one group per material, each seeded like make_state's.  The particles are stored group by
+    group: the order in which a simulation that is given the groups in turn numbers them."""
+    which = np.random.default_rng(seed).permutation(len(x)) % len(mats)
+    parts = [make_state(x[which == g], m, dx, seed=seed + 1 + g, **kw) for g, m in enumerate(mats)]
+    return orc.State(*(np.concatenate([getattr(p, f) for p in parts]) for f in ("x", "v", "B", "F", "aux")),
+                     np.concatenate([np.full(p.n, g, np.int32) for g, p in enumerate(parts)]),
+                     np.stack([p.gparams[0] for p in parts]), np.array([p.gtype[0] for p in parts], np.int32))
+
+
+def sort_key(x, dx):
+    """the key the device sorts by: Morton(block) << 6 | cell in the block (blocks of 4^3 cells; the cell of a particle is the base
+    node of its quadratic stencil)"""
+    base = np.floor(x.astype(np.float32) * np.float32(1 / dx) - np.float32(0.5)).astype(np.int64)
+
+    def spread(v):
+        r = np.zeros_like(v)
+        for b in range(10):
+            r |= ((v >> b) & 1) << (3 * b)
+        return r
+    blk = base >> 2
+    return ((spread(blk[:, 0]) << 2 | spread(blk[:, 1]) << 1 | spread(blk[:, 2])) << 6) | ((base[:, 0] & 3) << 4) | \
+        ((base[:, 1] & 3) << 2) | (base[:, 2] & 3)
+
+
+def fewest_kinds_in_a_window(x, kind, dx, window=64):
+    """over every run of `window` consecutive particles in key order (a wave of a transfer kernel): the smallest number of
+    different values of kind[] in it"""
+    k = kind[np.argsort(sort_key(x, dx), kind="stable")]
+    present = np.zeros(len(k) - window + 1, np.int64)
+    for g in np.unique(kind):
+        c = np.concatenate([[0], np.cumsum(k == g)])
+        present += (c[window:] - c[:-window]) > 0
+    return int(present.min())
+
+
 def rel_l2(a, b):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)

@@ -1,5 +1,5 @@
 """Seeded CPIC scenes (a rigid body cutting through / pushing a block of particles) shared by the fixture generator
-(tests/golden/make_golden.py -> ref_cpic.npz) and the tests."""
+(tests/golden/make_golden.py -> ref_cpic.npz, ref_cpic_materials.npz) and the tests."""
 import numpy as np
 
 from oracle import oracle as orc
@@ -48,6 +48,28 @@ CASES = [("plate_jelly", "plate", "jelly", 5, dict(penalty=1e3)), ("box_jelly", 
          ("scripted_plate_jelly", "scripted", "jelly", 8, dict())]
 
 
+# The colour-aware kernels for the materials and material sets CASES does not reach (tests/kernel_forms.py): the box falling into
+# the block, once per remaining material and twice with the block's particles dealt out to several materials by a seeded
+# permutation, so that the particles beside the body are of every material.  A list of its own with a fixture of its own
+# (ref_cpic_materials.npz: particles and body after the substeps only — body creation and the distance field do not depend on the
+# material, and box_jelly covers them).
+MIXED8 = ("jelly", "snow", "sand", "water", "linear", "elastic", "von_mises", "visco")
+MIXED7 = MIXED8[:-1]
+MATERIAL_CASES = [("box_%s" % m, "box", m, 5, dict(penalty=1e3)) for m in ("snow", "linear", "elastic", "von_mises", "visco")] + \
+                 [("box_mixed8", "box", MIXED8, 5, dict(penalty=1e3)), ("box_mixed7", "box", MIXED7, 5, dict(penalty=1e3))]
+MIXED_SEED = 5
+
+
+def material_groups(material, n):
+    """[(material, indices into the block's particles)]: the whole block for one material; for a tuple of materials particle i
+    belongs to material permutation[i] % len(materials).  The groups are added in this order on both sides, so the creation ids
+    run group by group."""
+    if isinstance(material, str):
+        return [(material, np.arange(n))]
+    which = np.random.default_rng(MIXED_SEED).permutation(n) % len(material)
+    return [(m, np.flatnonzero(which == g)) for g, m in enumerate(material)]
+
+
 def script_functions():
     """the scripts as float32 python callables (what a scene script hands to add_particles(type='rigid', ...))"""
     f32 = np.float32
@@ -77,7 +99,8 @@ def build_reference(refmpm, body, material, **cfg):
     else:
         b = dict(BODIES[body])
         rid = ref.add_rigid(b.pop("mesh"), **b)
-    ref.add_particles(material, MASS, VOL, x, v)
+    for m, idx in material_groups(material, len(x)):
+        ref.add_particles(m, MASS, VOL, x[idx], v[idx])
     return ref, rid
 
 
@@ -91,7 +114,8 @@ def build_device(tm, body, material, **cfg):
                                          scripted_rotation=rot)))
     else:
         rid = int(sim.add_particles(dict(type="rigid", **BODIES[body])))
-    sim.add_particles(dict(type=material, positions=x, velocities=v, params=group_row(material)))
+    for m, idx in material_groups(material, len(x)):
+        sim.add_particles(dict(type=m, positions=x[idx], velocities=v[idx], params=group_row(m)))
     return sim, rid
 
 

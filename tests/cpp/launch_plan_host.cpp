@@ -259,6 +259,32 @@ int lp_known_configurations() {
   return 0;
 }
 
+// The header's answer for one (Facts, Knobs) pair in the eight words of mpmhip_debug_transfer_plan: tests/test_launch_plan_cpu.py
+// sweeps it to enumerate the forms of the transfer kernels a ctx can be given, and holds them against tests/kernel_forms.py.
+// flags: 1 rigid, 2 store_b, 4 tiled, 8 deterministic, 16 no chunk table
+void lp_transfer_plan(uint32_t mask, int64_t n_slots, uint32_t n_live, uint32_t n_act, int flags, int g2p_packed, int32_t out[8]) {
+  Knobs k;
+  k.g2p_packed = g2p_packed;
+  Facts f;
+  f.mask = mask; f.n_slots = n_slots; f.n_live = n_live; f.n_act = n_act;
+  f.rigid = flags & 1; f.store_b = flags & 2; f.tiled = flags & 4; f.deterministic = flags & 8; f.has_chunk_blk = !(flags & 16);
+  transfer_plan_words(k, f, out);
+}
+
+// the words by hand: the bench line after the impact, a mixed ctx beside a body with apic_b kept, the deterministic mode
+int lp_transfer_words() {
+  int32_t w[8];
+  lp_transfer_plan(1u << MPMHIP_SAND, 8 * M, 8 * M, 24000, 0, -1, w);
+  CHECK(w[0] == 1 && w[1] == 0 && w[2] == (1 << MPMHIP_SAND) && w[3] == 0 && w[4] == 0 && w[5] == 0 && w[6] == (1 << MPMHIP_SAND) && w[7] == 0);
+  lp_transfer_plan(1u << MPMHIP_SAND | 1u << MPMHIP_VISCO, 4000, 0, 0, 1 | 2, 1, w);
+  CHECK(w[0] == 0 && w[1] == 2 && w[2] == 0 && w[3] == 1 && w[4] == 1 && w[5] == 2 && w[6] == 0 && w[7] == 1);
+  lp_transfer_plan(1u << MPMHIP_SAND | 1u << MPMHIP_ELASTIC, 4000, 0, 0, 1 | 8, -1, w);
+  CHECK(w[0] == 0 && w[1] == 1 && w[2] == 0 && w[3] == 0 && w[4] == 1 && w[5] == 3 && w[6] == 0 && w[7] == 1);
+  lp_transfer_plan(1u << MPMHIP_VISCO, 4000, 0, 0, 1, 1, w);  // visco alone: its own kernels, never the packed walk
+  CHECK(w[0] == 0 && w[1] == 0 && w[2] == (1 << MPMHIP_VISCO) && w[4] == 1 && w[5] == 0 && w[6] == (1 << MPMHIP_VISCO) && w[7] == 1);
+  return 0;
+}
+
 // (moved with the plans; mpmhip_debug_scan_grid forwards here and tests/test_host_cpu.py sweeps it through that export)
 int lp_scan_grid() {
   CHECK(scan_resident_set(256, 5) == 1024u && scan_grid_for(256, 5, 0) == 480u && scan_grid_for(256, 5, 10000) == 640u);
@@ -269,8 +295,8 @@ int lp_scan_grid() {
 }
 
 int main() {
-  int (*const all[])() = {lp_env, lp_sort, lp_p2g, lp_grid, lp_g2p, lp_known_configurations, lp_scan_grid};
-  const char *const names[] = {"lp_env", "lp_sort", "lp_p2g", "lp_grid", "lp_g2p", "lp_known_configurations", "lp_scan_grid"};
+  int (*const all[])() = {lp_env, lp_sort, lp_p2g, lp_grid, lp_g2p, lp_known_configurations, lp_transfer_words, lp_scan_grid};
+  const char *const names[] = {"lp_env", "lp_sort", "lp_p2g", "lp_grid", "lp_g2p", "lp_known_configurations", "lp_transfer_words", "lp_scan_grid"};
   int failed = 0;
   for (size_t i = 0; i < sizeof all / sizeof all[0]; i++)
     if (const int line = all[i]()) {

@@ -331,6 +331,29 @@ def cpic_fixture(here):
     np.savez_compressed(os.path.join(here, "ref_cpic.npz"), **out)
 
 
+def cpic_materials_arrays():
+    """cs.MATERIAL_CASES: the particles (by creation id), their colours and the body after the case's whole substeps"""
+    from tests import cpic_scenes as cs
+    out = {}
+    for name, body, material, n, cfg in cs.MATERIAL_CASES:
+        sim, rid = cs.build_reference(ref, body, material, **cfg)
+        sim.substep(n)
+        p = sim.download(by_id=True)
+        out[name + "_x"], out[name + "_v"], out[name + "_F"] = p["x"], p["v"], p["F"]
+        o = np.argsort(sim.download(by_id=False)["id"], kind="stable")
+        out[name + "_states"] = sim.particle_cdf()["states"][o]
+        out[name + "_body"] = cs.rigid_vector(sim.rigid_state(rid))
+        sim.close()
+        print("cpic_materials", name, len(p["x"]), "particles,", int((out[name + "_states"] != 0).sum()), "coloured particles")
+    return out
+
+
+def cpic_materials_fixture(here):
+    """the colour-aware transfers for the materials and material sets ref_cpic.npz does not hold (tests/cpic_scenes.py:
+    MATERIAL_CASES) -> ref_cpic_materials.npz, ref_cpic_materials.2.npz"""
+    save_golden("ref_cpic_materials", **cpic_materials_arrays())
+
+
 def cpic2d_fixture(here):
     """the same for MPM<2> (generic transfers with the colour test, segments instead of triangles)"""
     from tests import cpic_scenes as cs
@@ -419,6 +442,8 @@ def main():
             mpm2d_fixture(here)
         elif w == "cpic":
             cpic_fixture(here)
+        elif w == "cpic_materials":
+            cpic_materials_fixture(here)
         elif w == "cpic2d":
             cpic2d_fixture(here)
         elif w == "joints":

@@ -262,6 +262,30 @@ def test_live_reference_reproduces_its_cpic_fixture():
         np.testing.assert_array_equal(cs.rigid_vector(sim.rigid_state(rid)), g[name + "_body"])
 
 
+def test_live_reference_reproduces_its_cpic_materials_fixture():
+    """tests/golden/ref_cpic_materials.npz (make_golden.py cpic_materials): every array of every case, bit for bit — what the
+    target writes does not change from one run to the next, and the scenes of tests/cpic_scenes.py still are the recorded ones"""
+    from oracle import refmpm
+    if not refmpm.available():
+        pytest.skip("oracle/_ref/libmpm_ref.so is not built")
+    import importlib.util
+    from tests import cpic_scenes as cs
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(HERE, "golden", "make_golden.py"))
+    make_golden = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make_golden)
+    refmpm.set_threads(1)
+    g, again = load_golden("ref_cpic_materials"), make_golden.cpic_materials_arrays()
+    assert sorted(g) == sorted(again) and len(g) == 5 * len(cs.MATERIAL_CASES)
+    for k in g:
+        np.testing.assert_array_equal(again[k], g[k], err_msg=k)
+    # the mixed scenes hold every material beside the body: coloured particles in each group
+    for name, body, material, n, cfg in cs.MATERIAL_CASES:
+        at = 0
+        for m, idx in cs.material_groups(material, len(g[name + "_x"])):  # (creation ids run group by group)
+            assert (g[name + "_states"][at:at + len(idx)] != 0).sum() > (500 if isinstance(material, str) else 100), (name, m)
+            at += len(idx)
+
+
 def test_rigid_body_shim_mass_properties_are_the_textbook_ones():
     """the rigid body under the compiled reference is OURS (oracle/taichi_shim/.../rigid_body_shim.h): a solid box and a
     square shell must have their closed-form mass and inertia, whatever the mesh's position before recentring"""

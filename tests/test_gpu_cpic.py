@@ -1,4 +1,5 @@
-"""CPIC rigid coupling on the device against the REFERENCE's own code: tests/golden/ref_cpic.npz holds output of
+"""CPIC rigid coupling on the device against the REFERENCE's own code: tests/golden/ref_cpic.npz (and ref_cpic_materials.npz, for
+the materials and material sets the first leaves out) holds output of
 src/rigid_transfer.cpp, src/mpm_rigid_body.cpp and the rigid branches of src/transfer.cpp compiled in place
 (oracle/_ref/libmpm_ref.so; generator tests/golden/make_golden.py cpic).  The rigid BODY under that code is the shim's
 (oracle/taichi_shim/taichi/dynamics/rigid_body_shim.h: the taichi core's is not in the reference tree) — what an impulse
@@ -15,6 +16,8 @@ import numpy as np
 import pytest
 
 from tests import cpic_scenes as cs
+from tests import kernel_forms as kf
+from tests.common import load_golden
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(__file__)
@@ -91,11 +94,17 @@ def test_colored_distance_field_and_particle_colours_match_the_reference(tm, gol
     np.testing.assert_allclose(bh["normal"][o][near], gold[name + "_p_normal"][near], rtol=0, atol=2e-4)
 
 
-def check_run(name, gold, h, body_vec):
+def check_run(name, gold, h, body_vec, groups=None):
+    """groups: [(label, positions in creation order)] — the particles are compared group by group (the material groups of a mixed
+    scene: a pooled norm hides one wrong group behind the others); None: all at once"""
     assert len(h["x"]) == len(gold[name + "_x"])
-    assert np.abs(h["x"] - gold[name + "_x"]).max() <= 5e-6, np.abs(h["x"] - gold[name + "_x"]).max()
-    assert rel_l2(h["v"], gold[name + "_v"]) <= 2e-4, rel_l2(h["v"], gold[name + "_v"])
-    assert rel_l2(h["F"], gold[name + "_F"]) <= 1e-4, rel_l2(h["F"], gold[name + "_F"])
+    for label, m in groups or [("all", slice(None))]:
+        ex = np.abs(h["x"][m] - gold[name + "_x"][m]).max()
+        ev, eF = rel_l2(h["v"][m], gold[name + "_v"][m]), rel_l2(h["F"][m], gold[name + "_F"][m])
+        print("%s %s: x %.3e (5e-6), v %.3e (2e-4), F %.3e (1e-4)" % (name, label, ex, ev, eF))
+        assert ex <= 5e-6, (label, ex)
+        assert ev <= 2e-4, (label, ev)
+        assert eF <= 1e-4, (label, eF)
     assert (h["states"].astype(np.uint32) != gold[name + "_states"]).sum() <= 5
     a = gold[name + "_body"]
     np.testing.assert_allclose(body_vec[0:7], a[0:7], rtol=0, atol=2e-6)  # position, rotation
@@ -112,6 +121,7 @@ def test_substeps_with_a_rigid_body_match_the_reference(tm, gold, case):
     material sees its surface velocity."""
     name, body, material, n, cfg = case
     sim, rid = cs.build_device(tm, body, material, **cfg)
+    kf.assert_runs(sim, kf.g2p(material, rigid=True), *kf.beside_a_body(material))
     sim.run_substeps(n)
     h = sim.get_particles(sort_by_id=True)
     vec = cs.rigid_vector(sim.get_rigid_state(rid))
@@ -120,8 +130,62 @@ def test_substeps_with_a_rigid_body_match_the_reference(tm, gold, case):
     if body == "scripted":
         assert abs(vec[1] - (cs.SCRIPT["p0"][1] + cs.SCRIPT["vel"][1] * n * cs.DT)) < 1e-6
     else:  # the body has received impulses from the material: its velocity is not just gravity's
-        free = np.array(cs.BODIES[body].get("initial_velocity", (0, 0, 0)), np.float64) + np.array([0, -10.0, 0]) * n * cs.DT
-        assert np.abs(vec[7:10] - free).max() > 1e-6
+        assert np.abs(vec[7:10] - free_fall(body, n)).max() > 1e-6
+
+
+def free_fall(body, n):
+    """velocity of a body that met nothing for n substeps"""
+    return np.array(cs.BODIES[body].get("initial_velocity", (0, 0, 0)), np.float64) + np.array([0, -10.0, 0]) * n * cs.DT
+
+
+@pytest.fixture(scope="module")
+def gold_materials():
+    return load_golden("ref_cpic_materials")
+
+
+ONE_MATERIAL_CASES = [c for c in cs.MATERIAL_CASES if isinstance(c[2], str)]
+MIXED_CASES = [c for c in cs.MATERIAL_CASES if not isinstance(c[2], str)]
+
+
+@pytest.mark.parametrize("case", ONE_MATERIAL_CASES, ids=[c[0] for c in ONE_MATERIAL_CASES])
+def test_cpic_substeps_match_the_reference_for_every_material(tm, gold_materials, case):
+    """test_substeps_with_a_rigid_body_match_the_reference for the materials its cases leave out: the one-material instantiations
+    of k_p2g_rigid / k_g2p_rigid (the impulse walk evaluates the material's calculate_force()) and of k_g2p<.., RIGID> beside them,
+    against tests/golden/ref_cpic_materials.npz with check_run's tolerances.  What the scene can tell apart: the recorded velocities
+    of two materials differ by 3e-3 .. 1e-2 (rel-L2) — except linear / jelly (1e-5: both are linear at these strains) and elastic /
+    von Mises (equal: nothing yields within five substeps), which this scene cannot distinguish."""
+    name, body, material, n, cfg = case
+    sim, rid = cs.build_device(tm, body, material, **cfg)
+    kf.assert_runs(sim, kf.g2p(material, rigid=True), *kf.beside_a_body(material))
+    sim.run_substeps(n)
+    h = sim.get_particles(sort_by_id=True)
+    vec = cs.rigid_vector(sim.get_rigid_state(rid))
+    check_run(name, gold_materials, h, vec)
+    assert (h["states"] != 0).sum() > 500
+    assert np.abs(vec[7:10] - free_fall(body, n)).max() > 1e-6
+
+
+@pytest.mark.parametrize("mode", ["default", "deterministic", "keep_apic_b"])
+@pytest.mark.parametrize("case", MIXED_CASES, ids=[c[0] for c in MIXED_CASES])
+def test_cpic_mixed_materials_match_the_reference(tm, gold_materials, case, mode):
+    """the block's particles dealt out to eight / seven materials by a seeded permutation, so the particles beside the body are of
+    every material: k_p2g_rigid / k_g2p_rigid<MAT_ALL> and k_g2p<.., RIGID, ALL / NO_VISCO> in the default mode, the forms with
+    the impulse rows (ALL_DET) in the deterministic mode, STORE_B and RIGID together with keep_apic_b — all against the same
+    recorded run of the reference, material group by material group"""
+    name, body, material, n, cfg = case
+    sim, rid = cs.build_device(tm, body, material, deterministic=mode == "deterministic", keep_apic_b=mode == "keep_apic_b", **cfg)
+    kf.assert_runs(sim, kf.g2p("ALL" if "visco" in material else "NO_VISCO", store_b=mode == "keep_apic_b", rigid=True),
+                   *kf.beside_a_body("ALL_DET" if mode == "deterministic" else "ALL"))
+    sim.run_substeps(n)
+    h = sim.get_particles(sort_by_id=True)
+    vec = cs.rigid_vector(sim.get_rigid_state(rid))
+    groups, at = [], 0
+    for m, idx in cs.material_groups(material, len(h["x"])):  # (creation ids run group by group)
+        groups.append((m, slice(at, at + len(idx))))
+        at += len(idx)
+    check_run(name, gold_materials, h, vec, groups)
+    assert (h["states"] != 0).sum() > 500
+    assert np.abs(vec[7:10] - free_fall(body, n)).max() > 1e-6
 
 
 def test_live_reference_agrees_with_the_device_on_a_longer_run(tm):

@@ -13,7 +13,8 @@ import os
 import numpy as np
 import pytest
 
-from tests.common import lattice_cube, make_state, rel_l2
+from tests import kernel_forms as kf
+from tests.common import fewest_kinds_in_a_window, lattice_cube, make_state, mixed_state, rel_l2, sort_key
 
 pytestmark = pytest.mark.gpu
 
@@ -143,17 +144,7 @@ def test_sort_is_a_permutation_in_key_order_and_drops_dead(tm, orc):
     assert np.array_equal(got["x"], s.x[got["id"]]) and np.array_equal(got["F"], s.F[got["id"]])
     # the first sort also reorders the records physically (reorder_interval, src/mpm.cpp:811-813): slot order is
     # now key order = Morton(block) << 6 | cell-in-block
-    base = np.floor(got["x"].astype(np.float32) * np.float32(1 / DX) - np.float32(0.5)).astype(np.int64)
-
-    def spread(v):
-        r = np.zeros_like(v)
-        for b in range(10):
-            r |= ((v >> b) & 1) << (3 * b)
-        return r
-    blk = base >> 2
-    key = ((spread(blk[:, 0]) << 2 | spread(blk[:, 1]) << 1 | spread(blk[:, 2])) << 6) | ((base[:, 0] & 3) << 4) | \
-        ((base[:, 1] & 3) << 2) | (base[:, 2] & 3)
-    assert np.all(np.diff(key) >= 0)
+    assert np.all(np.diff(sort_key(got["x"], DX)) >= 0)
     sim.close()
 
 
@@ -227,13 +218,15 @@ def test_every_form_of_the_sort_gives_the_same_substep(tm, monkeypatch):
                     assert np.array_equal(got[f], ref[f]), (v1, walk, ct, f, float(np.abs(got[f] - ref[f]).max()))
 
 
-def test_packed_g2p_walk_equals_the_per_block_walk(tm, monkeypatch):
+@pytest.mark.parametrize("mat", kf.PACKED_MATS)
+def test_packed_g2p_walk_equals_the_per_block_walk(tm, monkeypatch, mat):
     """k_g2p_packed (chunks of 256 consecutive sorted positions, whatever blocks they belong to: csrc/k_g2p_packed.h) against k_g2p on the
     same scene: a dense cube (chunks inside one block, tiles reused along a run), spray (a chunk touches more blocks than the
     workgroup keeps tiles for: several passes) and particles that leave the domain (dead slots behind the live range).  The
     library picks the packed walk by size (from 2 M slots on); the knob forces it either way.  Deterministic mode: the two walks put
     different particles into one wave, and since round 6 nothing a particle computes depends on its wave (Jacobi sweeps and the
-    refinement of an ill-conditioned F are decided per lane) — the results agree bit for bit."""
+    refinement of an ill-conditioned F are decided per lane) — the results agree bit for bit.  For every material the packed walk is
+    instantiated for; the ctx has to report the walk the knob asks for, or the test would compare k_g2p with itself."""
     monkeypatch.setenv("MPMHIP_DETERMINISTIC", "1")
     rng = np.random.default_rng(31)
     dense = lattice_cube(RES, 8, 14, DX, jitter=0.2, seed=30)
@@ -242,10 +235,11 @@ def test_packed_g2p_walk_equals_the_per_block_walk(tm, monkeypatch):
     out = {}
     for knob in ("0", "1"):
         monkeypatch.setenv("MPMHIP_G2P_PACKED", knob)
-        s = make_state(x, "sand", DX, perturb_F=0.02, seed=32)
+        s = make_state(x, mat, DX, perturb_F=0.02, seed=32)
         s.v[-40:] = (0.0, 0.0, 500.0)  # these leave through the wall within a few substeps: deleted, their slots drop out
         sim = make_sim(tm, s)
         for _ in range(5):
+            kf.assert_runs(sim, kf.packed(mat) if knob == "1" else kf.g2p(mat))
             sim.substep()
         out[knob] = sim.get_particles()
         sim.close()
@@ -279,6 +273,15 @@ def test_p2g_and_grid_update_match_oracle(tm, orc, mat):
     sim.close()
 
 
+def g2p_from(sim, grid):
+    """G2P alone, from a grid given by the caller"""
+    sim.sort_particles_and_populate_grid()
+    sim.rasterize_optimized()                       # builds the tile / owner structure
+    sim.normalize_grid_and_apply_boundary_conditions()
+    sim.set_grid(grid)                              # identical grid on both sides
+    sim.resample_optimized()
+
+
 @pytest.mark.parametrize("keep", [True, False], ids=["apic_b_stored", "apic_b_folded"])
 @pytest.mark.parametrize("mat", MATS)
 def test_g2p_from_identical_grid_matches_oracle(tm, orc, mat, keep):
@@ -290,11 +293,9 @@ def test_g2p_from_identical_grid_matches_oracle(tm, orc, mat, keep):
     ref = s.copy()
     grid = orc.grid_update(cfg, orc.p2g(cfg, ref))
     sim = make_sim(tm, s, keep_apic_b=keep)
-    sim.sort_particles_and_populate_grid()
-    sim.rasterize_optimized()                       # builds the tile / owner structure
-    sim.normalize_grid_and_apply_boundary_conditions()
-    sim.set_grid(grid)                              # identical grid on both sides
-    sim.resample_optimized()
+    # (the one-material kernels exist only without apic_b: with it, the set without visco, or all of them for visco)
+    kf.assert_runs(sim, kf.g2p(("ALL" if mat == "visco" else "NO_VISCO") if keep else mat, store_b=keep))
+    g2p_from(sim, grid)
     got = sim.get_particles()
     orc.g2p(cfg, ref, grid)
     assert np.abs(got["x"] - ref.x).max() <= 1e-7
@@ -320,6 +321,123 @@ def test_full_substep_matches_oracle(tm, orc, mat):
     assert np.abs(got["x"] - ref.x).max() <= 2e-7
     assert rel_l2(got["v"], ref.v) <= 2e-5
     assert rel_l2(got["F"], ref.F) <= F_TOL.get(mat, 2e-5)
+    sim.close()
+
+
+@pytest.mark.parametrize("mat", kf.PACKED_MATS)
+def test_packed_g2p_from_identical_grid_matches_oracle(tm, orc, monkeypatch, mat):
+    """k_g2p_packed against the oracle itself, not only against k_g2p: the walk forced by the knob on a particle count that is no
+    multiple of its chunk of 256 (the last chunk is ragged), the bounds of the per-block walk in the same mode (apic_b folded)"""
+    monkeypatch.setenv("MPMHIP_G2P_PACKED", "1")
+    x = lattice_cube(RES, 9, 17, DX, jitter=0.2, seed=6)[:MIXED_N]
+    s = make_state(x, mat, DX, perturb_F=0.02, seed=7)
+    cfg = ocfg(orc)
+    ref = s.copy()
+    grid = orc.grid_update(cfg, orc.p2g(cfg, ref))
+    sim = make_sim(tm, s)
+    kf.assert_runs(sim, kf.packed(mat))
+    g2p_from(sim, grid)
+    kf.assert_runs(sim, kf.packed(mat))  # (also with what the sort has reported by now)
+    got = sim.get_particles()
+    orc.g2p(cfg, ref, grid)
+    assert len(got["x"]) == MIXED_N
+    assert np.abs(got["x"] - ref.x).max() <= 1e-7
+    assert rel_l2(got["v"], ref.v) <= 1e-5
+    assert rel_l2(got["B"], ref.B) <= 3e-4
+    assert rel_l2(got["F"], ref.F) <= F_TOL.get(mat, 1e-5)
+    assert np.abs(got["aux"] - ref.aux).max() <= 2e-5
+    sim.close()
+
+
+# ------------------------------------------------------------------------------------------ every material in every wave
+# The kernels for several materials (k_g2p<.., NO_VISCO> and k_g2p<.., ALL>) choose the constitutive model per particle.  In this
+# scene the material of a particle is drawn by a seeded permutation, so every wave of 64 consecutive particles in key order holds
+# nearly every material and takes every branch: a branch taken for the wave instead of the lane, or a material missing from a
+# kernel's set, shows in the group it hits.  Errors are taken per material group, never pooled: a pooled norm hides one wrong
+# group of 500 particles behind the stiff ones.  Each group has the bound of the same-named one-material test.
+MIXED_N = 8 ** 3 * 8 - 37  # 4 059: no multiple of 64 or 256
+MIXED = {"mixed8": (MATS, "ALL", 6), "mixed7": (MATS[:-1], "NO_VISCO", 5)}  # materials, the kernel's set, materials per wave at least
+
+
+def mixed_scene(scene, seed):
+    mats, mset, per_wave = MIXED[scene]
+    x = lattice_cube(RES, 9, 17, DX, jitter=0.2, seed=seed)[:MIXED_N]
+    s = mixed_state(x, mats, DX, seed + 1, perturb_F=0.02)
+    assert s.n == MIXED_N and fewest_kinds_in_a_window(s.x, s.gid, DX) >= per_wave
+    return s, mats, mset
+
+
+def check_groups(got, ref, mats, **bounds):
+    """per material group: x max abs, v / F / B rel-L2, aux max abs against bounds[field] (a number, or a function of the material).
+    Every figure is printed before anything is asserted; all groups are looked at before the first failure is raised."""
+    bad = []
+    for g, mat in enumerate(mats):
+        m = ref.gid == g
+        for f, bound in bounds.items():
+            a, b = got[f][m], getattr(ref, f)[m]
+            err = float(np.abs(a.astype(np.float64) - b).max()) if f in ("x", "aux") else rel_l2(a, b)
+            lim = bound(mat) if callable(bound) else bound
+            print("%-9s %-3s %.3e (bound %.0e, %d particles)" % (mat, f, err, lim, m.sum()))
+            if not err <= lim:
+                bad.append((mat, f, err, lim))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("keep", [True, False], ids=["apic_b_stored", "apic_b_folded"])
+@pytest.mark.parametrize("scene", sorted(MIXED))
+def test_mixed_g2p_from_identical_grid_matches_oracle(tm, orc, scene, keep):
+    """test_g2p_from_identical_grid_matches_oracle for the kernels of several materials.  A particle's result depends on the grid
+    and on itself only, so each group keeps the bounds of its one-material case."""
+    s, mats, mset = mixed_scene(scene, 6)
+    cfg = ocfg(orc)
+    ref = s.copy()
+    grid = orc.grid_update(cfg, orc.p2g(cfg, ref))
+    sim = make_sim(tm, s, keep_apic_b=keep)
+    kf.assert_runs(sim, kf.g2p(mset, store_b=keep))
+    g2p_from(sim, grid)
+    got = sim.get_particles()
+    orc.g2p(cfg, ref, grid)
+    assert len(got["x"]) == ref.n and np.array_equal(got["gid"], ref.gid)
+    check_groups(got, ref, mats, x=1e-7, v=1e-5, B=1e-5 if keep else 3e-4, F=lambda mat: F_TOL.get(mat, 1e-5), aux=2e-5)
+    sim.close()
+
+
+@pytest.mark.parametrize("scene", sorted(MIXED))
+def test_mixed_full_substep_matches_oracle(tm, orc, scene):
+    """test_full_substep_matches_oracle for the kernels of several materials"""
+    s, mats, mset = mixed_scene(scene, 8)
+    sim = make_sim(tm, s)
+    kf.assert_runs(sim, kf.g2p(mset))
+    sim.substep()
+    sim.synchronize()
+    got = sim.get_particles()
+    ref = s.copy()
+    orc.substep(ocfg(orc), ref)
+    assert len(got["x"]) == ref.n == MIXED_N and np.array_equal(got["id"], ref.ids) and np.array_equal(got["gid"], ref.gid)
+    check_groups(got, ref, mats, x=2e-7, v=2e-5, F=lambda mat: F_TOL.get(mat, 2e-5), aux=2e-5)
+    sim.close()
+
+
+@pytest.mark.parametrize("keep", [True, False], ids=["keep_b", "fold_b"])
+@pytest.mark.parametrize("scene", sorted(MIXED))
+def test_mixed_materials_match_oracle_over_three_substeps(tm, orc, scene, keep):
+    """three whole substeps in the manner of test_config_variants_match_oracle_over_three_substeps (its scene's velocities, both
+    storage modes of apic_b): the stress a kernel stored behind one G2P is what the next P2G scatters"""
+    mats, mset, per_wave = MIXED[scene]
+    x = lattice_cube(RES, 9, 17, DX, jitter=0.2, seed=81)[:MIXED_N]
+    s = mixed_state(x, mats, DX, 82, perturb_F=0.02, vel_scale=2.0)
+    assert fewest_kinds_in_a_window(s.x, s.gid, DX) >= per_wave
+    sim = make_sim(tm, s, keep_apic_b=keep)
+    kf.assert_runs(sim, kf.g2p(mset, store_b=keep))
+    cfg = ocfg(orc)
+    ref = s.copy()
+    for _ in range(3):
+        sim.substep()
+        orc.substep(cfg, ref)
+    kf.assert_runs(sim, kf.g2p(mset, store_b=keep))
+    got = sim.get_particles()
+    assert len(got["x"]) == ref.n == MIXED_N and np.array_equal(got["id"], ref.ids) and np.array_equal(got["gid"], ref.gid)
+    check_groups(got, ref, mats, x=5e-7, v=5e-5, F=lambda mat: F_TOL.get(mat, 5e-5), aux=2e-5)
     sim.close()
 
 
