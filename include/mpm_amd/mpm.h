@@ -89,6 +89,10 @@ class MPM<3> {
     check(mpmhip_set_articulation_iterations(ctx_, config.get("articulation_iterations", 100)), ctx_);  // src/mpm.h:279-280
     check(mpmhip_set_dirichlet(ctx_, dirichlet_ ? 1 : 0), ctx_);
     check(mpmhip_set_rigid_levelset_collision(ctx_, config.get("rigid_body_levelset_collision", false) ? 1 : 0), ctx_);  // src/mpm.cpp:535-538
+    // rigid-rigid collisions, MPM::rigidify (src/mpm_rigid_body.cpp:306-345): opt-in here (the reference's default is true)
+    if (config.get("rigid_body_collision", false))
+      check(mpmhip_set_rigid_collision(ctx_, 1, config.get("rigid_body_iterations", 5), config.get("rigid_penalty", 1e3f),
+                                       config.get("rigid_body_position_iterations", true) ? 1 : 0), ctx_);
     frame = 0;
     frame_count = 0;
   }

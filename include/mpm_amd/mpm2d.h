@@ -73,6 +73,8 @@ class MPM<2> {
     check(mpmhip2d_set_rigid_coupling(ctx_, config.get("penalty", 0.0f), config.get("pushing_force", 20000.0f)), ctx_);
     check(mpmhip2d_set_articulation_iterations(ctx_, config.get("articulation_iterations", 100)), ctx_);
     check(mpmhip2d_set_rigid_levelset_collision(ctx_, config.get("rigid_body_levelset_collision", false) ? 1 : 0), ctx_);  // src/mpm.cpp:535-538
+    if (config.get("rigid_body_collision", false))  // RigidSolver<2>::detect_rigid_collision: TC_NOT_IMPLEMENTED (src/rigid_body_solver.h:154-158)
+      throw std::runtime_error("rigid_body_collision = true is not implemented by the 2D simulation (nor by the reference's)");
     const float d = config.get("dirichlet_boundary_radius", 0.0f), vel = config.get("dirichlet_boundary_velocity", 0.0f);  // :374-399
     check(mpmhip2d_set_dirichlet(ctx_, d > 0 ? 1 : 0, config.get("dirichlet_distance_left", d), config.get("dirichlet_distance_right", d),
                                  config.get("dirichlet_boundary_left", vel), config.get("dirichlet_boundary_right", vel)), ctx_);

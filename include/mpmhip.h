@@ -824,8 +824,8 @@ int64_t mpmhip2d_download_colours(mpmhip2d_ctx *ctx, int64_t capacity, uint32_t 
  * src/mpm_rigid_body.cpp:130-252), rasterize_rigid_boundary / gather_cdf (src/rigid_transfer.cpp), the rigid branches of
  * the transfers (block_op_rigid, src/transfer.cpp:367-463,706-835) and advect_rigid_bodies (src/mpm_rigid_body.cpp:255-286).
  * Once a body exists, every substep runs: sort | rasterize_rigid_boundary | gather_cdf | P2G | grid | G2P | advect.
- * Not part of this library: rigid-rigid collisions (rigidify / libccd), rigid_body_levelset_collision (joints are:
- * mpmhip_add_articulation below).  Rigid bodies cannot be combined with the multi-GPU tiling or asynchronous stepping.
+ * Rigid-rigid collisions (rigidify) are an opt-in pass: mpmhip_set_rigid_collision at the end of this section; joints:
+ * mpmhip_add_articulation below.  Rigid bodies cannot be combined with the multi-GPU tiling or asynchronous stepping.
  * ------------------------------------------------------------------------------------------------------------------ */
 /* scripted_position(t) -> world position; scripted_rotation(t) -> Euler angles in degrees (applied X * Y * Z):
  * tc.function13 objects in the scene scripts (scripts/mls-cpic/sand_paddles.py:27, src/mpm_rigid_body.cpp:79-92) */
@@ -900,6 +900,36 @@ int mpmhip_download_cdf(mpmhip_ctx *ctx, uint32_t *states, float *distance);
 /* gather_cdf's per-particle results, live particles in slot order, 5 floats each: boundary_normal 3, boundary_distance,
  * near_boundary.  Valid between mpmhip_gather_cdf and the next G2P (a G2P moves the records). */
 int64_t mpmhip_download_boundary(mpmhip_ctx *ctx, float *out, int64_t n_capacity);
+
+/* ---- rigid-rigid collisions: MPM::rigidify (src/mpm_rigid_body.cpp:306-345), 3D only as in the reference
+ * (RigidSolver<2>::detect_rigid_collision is TC_NOT_IMPLEMENTED, src/rigid_body_solver.h:154-158).
+ * Detection replaces RigidSolver<3>::detect_rigid_collision (src/rigid_body_solver.h:160-198): libccd's ccdMPRPenetration on the convex
+ * hulls of the bodies' mesh vertices (supportRigid, :120-147) for every pair i > j >= 1 that is not fully scripted on both sides
+ * (:174-176) — convex hulls only, as there; a concave mesh collides as its hull.  The device reproduces libccd's single-precision
+ * arithmetic bit for bit (taichi_mpm_amd/csrc/k_rigid_collide.h).  The collision list is in (i, j) order; the reference's is in the
+ * order its TBB threads arrive (:167, :191-195).  Resolution replaces Collision::project_velocity / project_position (:39-87) and
+ * the loops of rigidify (src/mpm_rigid_body.cpp:325-344).
+ *
+ * mpmhip_set_rigid_collision: the config keys rigid_body_collision (src/mpm_rigid_body.cpp:308; OFF by default here, on in the
+ * reference), rigid_body_iterations (5), rigid_penalty (1e3), rigid_body_position_iterations (true) (:327-330).  MPMHIP_EINVAL on a
+ * ctx that takes no bodies (tiled, asynchronous) and for iterations < 0.  With the pass on and at least two bodies beside the
+ * background, every substep starts its rigid block with rigidify (src/mpm.cpp:468); with it off a substep issues what it issued
+ * before this entry point existed.  Snapshots carry the four settings. */
+int mpmhip_set_rigid_collision(mpmhip_ctx *ctx, int32_t enabled, int32_t iterations, float rigid_penalty, int32_t position_iterations);
+int mpmhip_rigidify(mpmhip_ctx *ctx); /* phase, like mpmhip_articulate: MPM::rigidify(base_delta_t) */
+/* the collisions the last rigidify resolved: 9 floats per row — body i, body j (i > j), depth, dir[3], pos[3] (Collision<3>, :20-37).
+ * Returns the length of the list; rows beyond cap are not written. */
+int64_t mpmhip_rigid_get_collisions(mpmhip_ctx *ctx, int64_t cap, float *out);
+/* the hull vertices of body id as the support mapping walks them (supportRigid, :136-146): body frame, three per triangle in
+ * element order, 3 floats each.  Returns the body's vertex count; vertices beyond cap_vertices are not written. */
+int64_t mpmhip_rigid_get_hull(mpmhip_ctx *ctx, int32_t id, int64_t cap_vertices, float *out);
+/* The detection kernel alone, no ctx (as mpmhip_debug_levelset_sample is for the sampler): pair q is cloud 2q against cloud 2q + 1;
+ * cloud k has the vertices [offsets[k], offsets[k + 1]) of verts [][3] (offsets[0] = 0, 2 n_pairs + 1 entries), the rotation
+ * rotations[9 k] (row-major; NULL: none, the vertices are used as they are) and the centre centres[3 k].  out: 9 floats per pair —
+ * hit (1 where ccdMPRPenetration returns 0), depth, dir[3], pos[3], the number of support calls.  MPMHIP_EHIP when a loop bound
+ * expired (libccd's max_iterations is unlimited).  Errors: mpmhip_last_error(NULL). */
+int mpmhip_rigid_mpr_test(int32_t device, int32_t n_pairs, const float *verts, const int64_t *offsets, const float *rotations,
+                          const float *centres, float *out);
 
 #ifdef __cplusplus
 }

@@ -187,6 +187,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip_rigid_get_samples", "mpmhip_rigid_get_mesh", "mpmhip2d_rigid_get_mesh", "mpmhip_rasterize_rigid_boundary", "mpmhip_gather_cdf", "mpmhip_advect_rigid_bodies", "mpmhip_download_cdf",
             "mpmhip_add_articulation", "mpmhip_num_articulations", "mpmhip_set_articulation_iterations", "mpmhip_articulate",
             "mpmhip_download_boundary",
+            "mpmhip_set_rigid_collision", "mpmhip_rigidify", "mpmhip_rigid_get_collisions", "mpmhip_rigid_get_hull", "mpmhip_rigid_mpr_test",
             "mpmhip_debug_copy_bandwidth", "mpmhip_debug_live_buffers", "mpmhip_debug_g2p_is_packed", "mpmhip_debug_transfer_plan", "mpmhip_debug_scan_grid", "mpmhip_debug_cond_census", "mpmhip_debug_gather_bandwidth", "mpmhip_debug_svd3", "mpmhip_debug_force", "mpmhip_debug_plasticity"]
 
 
@@ -421,6 +422,13 @@ def load():
     L.mpmhip_download_cdf.argtypes = [vp, up, fp]
     L.mpmhip_download_boundary.argtypes = [vp, fp, C.c_int64]
     L.mpmhip_download_boundary.restype = C.c_int64
+    L.mpmhip_set_rigid_collision.argtypes = [vp, C.c_int32, C.c_int32, C.c_float, C.c_int32]
+    L.mpmhip_rigidify.argtypes = [vp]
+    L.mpmhip_rigid_get_collisions.argtypes = [vp, C.c_int64, fp]
+    L.mpmhip_rigid_get_collisions.restype = C.c_int64
+    L.mpmhip_rigid_get_hull.argtypes = [vp, C.c_int32, C.c_int64, fp]
+    L.mpmhip_rigid_get_hull.restype = C.c_int64
+    L.mpmhip_rigid_mpr_test.argtypes = [C.c_int32, C.c_int32, fp, lp, fp, fp, fp]
     L.mpmhip2d_set_rigid_coupling.argtypes = [vp, C.c_float, C.c_float]
     L.mpmhip2d_set_rigid_levelset_collision.argtypes = [vp, C.c_int32]
     L.mpmhip2d_add_articulation.argtypes = [vp, P(JointConfig)]

@@ -33,6 +33,8 @@ class AsyncSimulation3D(Simulation3D):
         cfg = dict(config)
         cfg["keep_apic_b"] = True  # the P2G matrix depends on each advance's dt: it is rebuilt from apic_b (include/mpmhip.h)
         super().initialize(cfg)
+        if self.rigid_body_collision:
+            raise MPMError("rigid_body_collision=True: asynchronous stepping takes no rigid bodies, so there is nothing to collide")
         self.unit_delta_t = float(cfg.get("unit_delta_t", 1e-6))
         self.max_units = int(cfg.get("max_units", 8192))
         self.cfl_dt_mul = float(cfg.get("cfl_dt_mul", 1.0))

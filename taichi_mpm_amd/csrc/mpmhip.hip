@@ -92,6 +92,7 @@
 #include "k_g2p.h"
 #include "k_g2p_packed.h"
 #include "k_rigid_transfer.h"
+#include "k_rigid_collide.h"
 #include "k_debug.h"
 #include "k_sdf.h"
 #include "k_mesh_sdf.h"
@@ -343,6 +344,21 @@ struct mpmhip_ctx {
     std::vector<JointDev> joints;    // MPM::articulations, in the order they were added
     DevBuf<JointDev> d_joints;
     int joint_iterations = 100;      // 'articulation_iterations' (src/mpm.h:279-280)
+    // rigid-rigid collisions (MPM::rigidify; rigid_collide_api.h): opt-in, the device arrays come with the first run
+    struct Collide {
+      bool on = false;                 // config key rigid_body_collision
+      int iterations = 5;              // rigid_body_iterations
+      float penalty = 1e3f;            // rigid_penalty
+      bool position_iterations = true; // rigid_body_position_iterations
+      size_t n_verts = 0;              // what the arrays below were built for
+      int n_bodies = 0;
+      DevBuf<int> d_body, d_first, d_count;  // per hull vertex its body; per body its vertices in RigidState::d_elems
+      DevBuf<float4> d_r, d_p;               // per hull vertex R v and R v + pos of this substep
+      DevBuf<float> d_ctr;
+      DevBuf<MprPair> d_pairs;
+      DevBuf<RigidCollision> d_cols, d_hits; // per pair what the MPR found; the hits in (i, j) order
+      DevBuf<int> d_nhits;
+    } col;
   } rigid;
   bool overlap = false;        // mpmhip_set_overlap: split tiled substeps into boundary / interior work
   bool ov_active = false, interior_done = false;  // state of the substep in flight
@@ -951,6 +967,9 @@ static int read_counters(mpmhip_ctx *c, Counters &h) {
     return fail(c, MPMHIP_EHIP, "sort: a chained scan waited %.0f s for a chunk that never published its sum (k_sort.h): the launch did not "
                 "fit the device's resident set (another runtime, a partitioned device, a debugger?) — lower MPMHIP_SCAN_GRID",
                 (double)SCAN_WAIT_TICKS / 1e8);
+  if (h.error & RIGID_MPR_ERROR_BIT)
+    return fail(c, MPMHIP_EHIP, "rigid-rigid collisions: the portal refinement of a pair of bodies did not end within its loop bound "
+                "(MPR_MAX_* of k_rigid_collide.h); the pair was treated as not colliding");
   if (h.error & 4u)
     return fail(c, MPMHIP_ECAPACITY, "the colored distance field of the rigid bodies needs more than %u pages of 4^3 nodes: "
                 "recreate the ctx with a larger max_blocks", c->rigid.max_pages);
@@ -1408,6 +1427,7 @@ static int need_sorted(mpmhip_ctx *c, const char *who) {
 }
 
 #include "rigid_api.h"
+#include "rigid_collide_api.h"
 #include "mesh_sdf_api.h"
 
 int mpmhip_sort(mpmhip_ctx *c) {
@@ -1513,6 +1533,7 @@ int mpmhip_substep_begin(mpmhip_ctx *c) {
   // articulate + rasterize_rigid_boundary (src/mpm.cpp:466-472) next to the sort, gather_cdf (:506-508) behind both
   const bool bodies = rigid_active(c);
   hipStream_t rs = c->stream;
+  if (bodies && (rc = do_rigid_rigidify(c, c->P.dt))) return rc;  // rigidify opens the block (:468), on the ctx stream, before the fork
   if (bodies && ((rc = rigid_fork(c, &rs, 4)) || (rc = do_rigid_pre_a(c, rs)))) return rc;
   if ((rc = do_sort(c))) return rc;
   if (bodies && ((rc = rigid_join(c, rs)) || (rc = do_rigid_pre_b(c)))) return rc;
@@ -1695,8 +1716,16 @@ struct SnapRigid {
   char magic[8];  // "MPMRIGID"
   uint32_t n_bodies, n_joints, sizeof_body, sizeof_joint;
 };
+// ... and, behind the joints, the settings of the rigid-rigid collision pass (a blob that ends before it keeps the ctx's own)
+struct SnapRigidCollide {
+  char magic[8];  // "MPMRRCOL"
+  int32_t on, iterations, position_iterations;
+  float penalty;
+};
 static size_t snapshot_rigid_bytes(const mpmhip_ctx *c) {
-  return rigid_active(c) ? sizeof(SnapRigid) + sizeof(RigidBodyDev) * c->rigid.bodies.size() + sizeof(JointDev) * c->rigid.joints.size() : 0;
+  return rigid_active(c) ? sizeof(SnapRigid) + sizeof(RigidBodyDev) * c->rigid.bodies.size() + sizeof(JointDev) * c->rigid.joints.size() +
+                               sizeof(SnapRigidCollide)
+                         : 0;
 }
 static size_t snapshot_bytes(const mpmhip_ctx *c) {
   return sizeof(SnapHeader) + sizeof(GroupParams) * c->groups.size() +
@@ -1743,6 +1772,12 @@ int mpmhip_snapshot_save(mpmhip_ctx *c, void *dst, size_t cap) {
     memcpy(p, &r, sizeof r); p += sizeof r;
     HIPCHK(c, hipMemcpy(p, c->rigid.d_rb, sizeof(RigidBodyDev) * r.n_bodies, hipMemcpyDeviceToHost)); p += sizeof(RigidBodyDev) * r.n_bodies;
     if (r.n_joints) memcpy(p, c->rigid.joints.data(), sizeof(JointDev) * r.n_joints);
+    p += sizeof(JointDev) * r.n_joints;
+    SnapRigidCollide k;
+    memcpy(k.magic, "MPMRRCOL", 8);
+    k.on = c->rigid.col.on; k.iterations = c->rigid.col.iterations; k.position_iterations = c->rigid.col.position_iterations;
+    k.penalty = c->rigid.col.penalty;
+    memcpy(p, &k, sizeof k);
   }
   return MPMHIP_OK;
 }
@@ -1812,6 +1847,13 @@ int mpmhip_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
     HIPCHK(c, hipMemcpy(c->rigid.d_rb, q, sizeof(RigidBodyDev) * sr.n_bodies, hipMemcpyHostToDevice)); q += sizeof(RigidBodyDev) * sr.n_bodies;
     c->rigid.joints.assign((const JointDev *)q, (const JointDev *)q + sr.n_joints);
     if (sr.n_joints) HIPCHK(c, hipMemcpy(c->rigid.d_joints, c->rigid.joints.data(), sizeof(JointDev) * sr.n_joints, hipMemcpyHostToDevice));
+    q += sizeof(JointDev) * sr.n_joints;
+    SnapRigidCollide k;
+    if ((size_t)(q - (const char *)src) + sizeof k <= size && memcmp(q, "MPMRRCOL", 8) == 0) {
+      memcpy(&k, q, sizeof k);
+      c->rigid.col.on = k.on != 0; c->rigid.col.iterations = k.iterations; c->rigid.col.position_iterations = k.position_iterations != 0;
+      c->rigid.col.penalty = k.penalty;
+    }
   }
   return MPMHIP_OK;
 }
@@ -2076,6 +2118,7 @@ int mpmhip_set_partition(mpmhip_ctx *c, int32_t rank, const int32_t dims[3], con
                          const int32_t *cuts_y, const int32_t *cuts_z, int32_t margin) {
   if (!c || !dims || !cuts_x || !cuts_y || !cuts_z) return MPMHIP_EINVAL;
   if (c->rigid.enabled) return fail(c, MPMHIP_EINVAL, "a ctx with rigid bodies cannot be tiled");
+  if (c->rigid.col.on) return fail(c, MPMHIP_EINVAL, "rigid_body_collision: a tiled (multi-GPU) ctx has no rigid bodies");
   const int32_t *cuts[3] = {cuts_x, cuts_y, cuts_z};
   Tiling T;
   memset(&T, 0, sizeof T);
@@ -2529,6 +2572,7 @@ int mpmhip_async_enable(mpmhip_ctx *c, const mpmhip_async_config *cfg) {
   if (!c || !cfg) return MPMHIP_EINVAL;
   if (!(cfg->unit_delta_t > 0) || cfg->max_units < 1) return fail(c, MPMHIP_EINVAL, "unit_delta_t > 0 and max_units >= 1 required");
   if (rigid_active(c) || c->rigid.enabled) return fail(c, MPMHIP_EINVAL, "asynchronous stepping cannot be combined with rigid bodies");
+  if (c->rigid.col.on) return fail(c, MPMHIP_EINVAL, "rigid_body_collision: asynchronous stepping has no rigid bodies");
   if (c->T.enabled) return fail(c, MPMHIP_EINVAL, "asynchronous stepping cannot be combined with the multi-GPU tiling");
   HIPCHK(c, hipSetDevice(c->device));
   auto &A = c->async;

@@ -419,6 +419,14 @@ class Simulation3D:
         self.penalty = float(cfg.get("penalty", 0.0))               # CPIC, src/mpm.cpp:35
         self.pushing_force = float(cfg.get("pushing_force", 20000.0))  # src/mpm.cpp:40
         self.articulation_iterations = int(cfg.get("articulation_iterations", 100))  # src/mpm.h:279-280
+        # rigid-rigid collisions, MPM::rigidify (src/mpm_rigid_body.cpp:306-345).  Opt-in: the reference's default is True, this
+        # library's is False (scenes written before the pass existed keep their results)
+        self.rigid_body_collision = bool(cfg.get("rigid_body_collision", False))                       # :308
+        self.rigid_body_iterations = int(cfg.get("rigid_body_iterations", 5))                           # :327
+        self.rigid_penalty = float(cfg.get("rigid_penalty", 1e3))                                       # :329
+        self.rigid_body_position_iterations = bool(cfg.get("rigid_body_position_iterations", True))    # :330
+        if self.rigid_body_iterations < 0:
+            raise MPMError("rigid_body_iterations = %d: must not be negative" % self.rigid_body_iterations)
         self.config = cfg
         return self
 
@@ -448,6 +456,9 @@ class Simulation3D:
         self._check(self._L.mpmhip_set_articulation_iterations(self._ctx, self.articulation_iterations))
         self._check(self._L.mpmhip_set_dirichlet(self._ctx, int(self.dirichlet)))
         self._check(self._L.mpmhip_set_rigid_levelset_collision(self._ctx, int(self.rigid_body_levelset_collision)))
+        if self.rigid_body_collision:  # (absent or False: the entry point is never called, the ctx is what it was without the pass)
+            self._check(self._L.mpmhip_set_rigid_collision(self._ctx, 1, self.rigid_body_iterations, self.rigid_penalty,
+                                                           int(self.rigid_body_position_iterations)))
         self._apply_levelset()
         for mat, params in self._groups:
             self._check(self._L.mpmhip_add_group(self._ctx, mat, params.ctypes.data_as(C.POINTER(C.c_float))))
@@ -706,12 +717,13 @@ class Simulation3D:
         if cfg.get("scripted_rotation") is not None:
             r.scripted_rotation = script(cfg["scripted_rotation"])
         free = cfg.get("scripted_position") is None and float(cfg.get("density", 0.0)) > 0.0
-        if free and self._free_bodies >= 1 or (free or self._free_bodies) and len(self._rigids) >= 1:
-            # MPM::rigidify (src/mpm.cpp:468, libccd) is not part of this library: say so instead of letting bodies
-            # pass through each other silently
+        if not self.rigid_body_collision and (free and self._free_bodies >= 1 or (free or self._free_bodies) and len(self._rigids) >= 1):
+            # MPM::rigidify (src/mpm.cpp:468) is opt-in here (rigid_body_collision=True): without it, say so instead of letting
+            # bodies pass through each other silently
             import warnings
             warnings.warn("taichi_mpm_amd: rigid-rigid collisions (MPM::rigidify, src/mpm.cpp:468) are not implemented — "
-                          "bodies interact only through the material and through joints", RuntimeWarning, stacklevel=3)
+                          "bodies interact only through the material and through joints (set rigid_body_collision=True to "
+                          "collide their convex hulls)", RuntimeWarning, stacklevel=3)
         self._free_bodies += int(free)
         self._ensure_ctx()
         rid = self._check(self._L.mpmhip_add_rigid_body(self._ctx, C.byref(r), len(tri), tri.ctypes.data_as(C.POINTER(C.c_float))))
@@ -969,6 +981,31 @@ class Simulation3D:
 
     def articulate(self):  # src/mpm.h:278-319
         self._ensure_ctx(); self._check(self._L.mpmhip_articulate(self._ctx))
+
+    def rigidify(self):  # src/mpm_rigid_body.cpp:306-345
+        """MPM::rigidify(base_delta_t) alone: detect the collisions between the bodies' convex hulls and resolve them (a no-op
+        unless rigid_body_collision=True and the scene has two bodies or more)"""
+        self._ensure_ctx(); self._check(self._L.mpmhip_rigidify(self._ctx))
+
+    def get_rigid_collisions(self):
+        """the collisions the last rigidify resolved, in (i, j) order: a list of dicts with the bodies i > j, depth, normal (from
+        libccd's MPR: the direction body i has to move out of body j is -normal) and position"""
+        self._ensure_ctx()
+        fp = C.POINTER(C.c_float)
+        n = self._check(self._L.mpmhip_rigid_get_collisions(self._ctx, 0, None))
+        rows = np.zeros((max(n, 1), 9), np.float32)
+        if n:
+            self._check(self._L.mpmhip_rigid_get_collisions(self._ctx, n, rows.ctypes.data_as(fp)))
+        return [dict(i=int(r[0]), j=int(r[1]), depth=r[2], normal=r[3:6].copy(), position=r[6:9].copy()) for r in rows[:n]]
+
+    def get_rigid_hull(self, rid):
+        """(n, 3) the body-frame vertices whose convex hull collides, in the order the support mapping walks them"""
+        fp = C.POINTER(C.c_float)
+        n = self._check(self._L.mpmhip_rigid_get_hull(self._ctx, int(rid), 0, None))
+        v = np.zeros((n, 3), np.float32)
+        if n:
+            self._check(self._L.mpmhip_rigid_get_hull(self._ctx, int(rid), n, v.ctypes.data_as(fp)))
+        return v
 
     def advect_rigid_bodies(self):  # src/mpm_rigid_body.cpp:255-286
         self._ensure_ctx(); self._check(self._L.mpmhip_advect_rigid_bodies(self._ctx))

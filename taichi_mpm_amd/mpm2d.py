@@ -37,6 +37,9 @@ class Simulation2D:
         if "delta_t" in cfg:  # src/mpm.cpp:41-42
             raise MPMError("Please use 'base_delta_t' instead of 'delta_t'")
         check_unsupported_keys(cfg)
+        if cfg.get("rigid_body_collision", False):  # RigidSolver<2>::detect_rigid_collision is TC_NOT_IMPLEMENTED (src/rigid_body_solver.h:154-158)
+            raise MPMError("rigid_body_collision=True is not implemented by the 2D simulation (nor by the reference's: "
+                           "src/rigid_body_solver.h:154-158); leave the key out or set it to False")
         for k in ("benchmark_rasterize", "benchmark_resample"):  # (built for the 3D simulation only)
             if cfg.get(k, False):
                 raise MPMError("config key %r (src/mpm.cpp:516-538, 554-561) is not implemented by the 2D simulation" % k)
