@@ -128,6 +128,35 @@ class MPM<2> {
     return "";
   }
 
+  // --- add_particles(density_tex=...) with the periodic Poisson-disk tile (src/mpm.cpp:205-251), seeded on the device
+  // (include/mpmhip.h: mpmhip2d_seed_particles): the region is where the shapes' level set, read in the plane, is negative.  Keys:
+  // type, ppc (4), density, initial_velocity, pd_source + delta_t (an emitter, called before every frame), initial_dg and the
+  // material's.  Returns the number of particles added; a ctx that is too small is grown (mpmhip2d_reserve).
+  int64_t add_particles_region(const Config &config, const std::vector<mpmhip_shape> &shapes) {
+    if (shapes.size() > (size_t)MPMHIP_MAX_SHAPES) throw std::runtime_error("add_particles_region: too many shapes");
+    mpmhip2d_seed_desc d{};
+    d.n_shapes = (int32_t)shapes.size();
+    std::copy(shapes.begin(), shapes.end(), d.shapes);
+    return seed(config, d);
+  }
+  // ... the region as a sampled field: phi holds res[0] * res[1] values, the last axis fastest, world units
+  int64_t add_particles_region(const Config &config, const VectorI &lattice_res, const Vector &origin, real spacing,
+                               const std::vector<float> &phi) {
+    mpmhip2d_sdf_desc l;
+    size_t count = 1;
+    for (int k = 0; k < 2; k++) {
+      l.res[k] = lattice_res[k];
+      l.origin[k] = origin[k];
+      count *= (size_t)(lattice_res[k] > 0 ? lattice_res[k] : 0);
+    }
+    l.spacing = spacing;
+    if (phi.size() != count) throw std::runtime_error("add_particles_region: the array must hold res[0] * res[1] samples");
+    mpmhip2d_seed_desc d{};
+    d.sdf = &l;
+    d.phi = phi.data();
+    return seed(config, d);
+  }
+
   // --- add_particles(type='rigid') in 2D: the outline as n_segments x 4 floats (two end points each); keys as in 3D
   virtual std::string add_rigid_body(const Config &config, int64_t n_segments, const float *segments, ScriptPosition scripted_position = nullptr,
                                      ScriptRotation scripted_rotation = nullptr) {
@@ -263,6 +292,32 @@ class MPM<2> {
     }
     std::stable_sort(out.begin(), out.end(), [](const Particle2D &a, const Particle2D &b) { return a.id < b.id; });
     return out;
+  }
+  // the group of a seeding call (vol = dx^2 / ppc, mass = vol * density: create_particle(coord, maximum, config), :134) and the
+  // call; a ctx that is too small is grown once and the call repeated
+  int64_t seed(const Config &config, mpmhip2d_seed_desc &d) {
+    const std::string type = config.get("type", "");
+    const float ppc = config.get("ppc", config.get("maximum", 4.0f));
+    if (!(ppc > 0)) throw std::runtime_error("add_particles_region: ppc must be > 0");
+    const float vol = delta_x * delta_x / ppc;
+    const float mass = vol * config.get("density", 400.0f);
+    const ParticleType t = create_particle_type(type, config, mass, vol);
+    const int gid = mpmhip2d_add_group(ctx_, t.material, t.params);
+    check(gid, ctx_);
+    d.ppc = ppc;
+    const Vector v0 = config.get_vec("initial_velocity", Vector(0.0f, 0.0f));
+    for (int k = 0; k < 2; k++) d.velocity[k] = v0[k];
+    d.source = config.get("pd_source", false);
+    d.source_delta_t = config.get("delta_t", 1e-3f);  // src/mpm.cpp:224
+    d.initial_dg = t.initial_dg;
+    int64_t n = 0;
+    int rc = mpmhip2d_seed_particles(ctx_, gid, &d, &n);
+    if (rc == MPMHIP_ECAPACITY) {
+      check(mpmhip2d_reserve(ctx_, (mpmhip2d_num_slots(ctx_) + n) * 3 / 2), ctx_);
+      rc = mpmhip2d_seed_particles(ctx_, gid, &d, &n);
+    }
+    check(rc, ctx_);
+    return n;
   }
   static void check(int rc, const mpmhip2d_ctx *c) {
     if (rc < 0) throw std::runtime_error(std::string("libmpmhip error ") + std::to_string(rc) + ": " + mpmhip2d_last_error(c));

@@ -185,7 +185,8 @@ int mpmhip_set_levelset_keyframes(mpmhip_ctx *ctx, float t0, float t1, int32_t n
  * One level set at a time: a sampled set replaces the shapes and shapes replace a sampled set.  friction as above;
  * particle_collision and mpmhip_delete_particles_inside_level_set work with it.  A call with the lattice size of the installed set
  * reuses the device memory (the per-frame update of a dynamic level set allocates nothing).
- * Out of scope: the 2D solver (mpmhip2d_set_levelset takes shapes only), the reference's add_slope, open or self-intersecting
+ * Out of scope: a sampled BOUNDARY for the 2D solver (mpmhip2d_set_levelset takes shapes only; a sampled field fills a 2D
+ * region with particles: mpmhip2d_seed_particles), the reference's add_slope, open or self-intersecting
  * meshes (closed triangle meshes are voxelised on the device: mpmhip_set_levelset_mesh below), and
  * rigid_body_levelset_collision with a sampled set (refused with MPMHIP_EINVAL, here and in mpmhip_set_rigid_levelset_collision).
  * Tiled jobs and the asynchronous stepper go through the same per-ctx call and substep; they are not tested with it. */
@@ -287,7 +288,8 @@ int mpmhip_add_particles(mpmhip_ctx *ctx, int32_t group, int64_t n, const float 
  * *n_added = the number of new particles.  If they do not fit the ctx, nothing is written, *n_added is the number needed and the
  * call returns MPMHIP_ECAPACITY: mpmhip_reserve and call again.  MPMHIP_EINVAL with a message: inside a substep, on a tiled ctx,
  * an unknown group, ppc <= 0, a lattice mpmhip_set_levelset_sdf would refuse, more than 2^31 candidates.
- * Out of scope: the 2D solver, pd_packed, non-uniform densities, pd = False, point_cloud. */
+ * The 2D solver has the same call: mpmhip2d_seed_particles below.  Out of scope: pd_packed, non-uniform densities, pd = False,
+ * point_cloud. */
 typedef struct {
   int32_t n_shapes;
   mpmhip_shape shapes[MPMHIP_MAX_SHAPES];
@@ -688,6 +690,70 @@ int64_t mpmhip2d_num_particles(mpmhip2d_ctx *ctx); /* synchronises */
 int64_t mpmhip2d_download(mpmhip2d_ctx *ctx, int64_t capacity, float *x, float *v, float *F, float *B, float *aux, int32_t *gid,
                           int32_t *id);            /* live particles in slot order; NULL outputs are skipped; returns n */
 int mpmhip2d_download_grid(mpmhip2d_ctx *ctx, float *grid /* [(res0+1)(res1+1)][3] = (v.x, v.y, m) */);
+
+/* Seeding the 2D simulation on the device — mpmhip_seed_particles with dim = 2 (PoissonDiskSampler<2>: the same code path of the
+ * reference serves both dimensions, src/poisson_disk_sampler.h:157-252; only the spacing formula differs, :60-61).  A pure function
+ * of its inputs; no particle row passes through host memory.
+ *
+ * The tile: mpmhip2d_poisson_tile writes min(count, capacity) points, 2 floats each, to `out` (NULL allowed) and returns the count.
+ * Bridson's algorithm in the periodic box [-20, 20)^2, minimum distance 1, 30 attempts per active point, the first point at the
+ * centre, generated once per process in integer arithmetic (csrc/poisson_tile2d.h): the same bytes on every machine.
+ *
+ * The region is "where this level set is negative", independent of the ctx's boundary level set (which is not touched):
+ *   sdf == NULL   the first n_shapes of `shapes`, read in the plane exactly as mpmhip2d_set_levelset reads them (z ignored, a box
+ *                 unbounded along z, a sphere a disc; phi = min over the shapes);
+ *   sdf != NULL   a sampled field phi [res0][res1] (the last axis fastest, fp32, WORLD units; host array, uploaded by the call) on
+ *                 the lattice *sdf: sample (0, 0) at `origin`, one `spacing` > 0.  Read bilinearly with the rules of
+ *                 mpmhip_set_levelset_sdf, one axis fewer: u = (x - origin) * fl(1 / spacing); inside the lattice iff
+ *                 0 <= u <= res - 1 on both axes (a point outside is not in the region); cell c = clamp((int)u, 0, res - 2),
+ *                 f = u - c; lerp(a, b, f) = (1 - f) a + f b, along the last axis first.
+ * All arithmetic is fp32, in this order, nothing contracted (tests/seed2d_model.py restates it to the bit):
+ *   get ready   over the cell centres fl((i + 0.5) dx) of the res[0] x res[1] grid: min / max per axis of the centres inside the
+ *               region; min_corner = min - dx, max_corner = max + dx; no centre inside: MPMHIP_EINVAL "region is empty".
+ *               min_distance = (float)sqrt(dx^2 / ppc * 2 / 3) (in double), region_size = fl(40 min_distance),
+ *               replicas per axis = max(1, ceil((max_corner - min_corner) / region_size)).
+ *   candidates  c = i * n_replicas + r pairs tile point i with replica r (the replica index in C order, (ind0, ind1));
+ *               q = fl(tile_i * min_distance);  position = fl(fl(q + min_corner) + fl(region_size * (ind + 0.5))).
+ *               source = 1 (an emitter called before every frame): q = fl(q + fl(velocity * current_t)), wrapped into the period
+ *               q -= fl(floor(fl(fl(q / region_size) + 0.5)) * region_size) — the tile drifts with the jet.
+ *   acceptance  inside the region and not within 7 cells of a wall (MPM::near_boundary, src/mpm.h:269-276: X = fl(x * fl(1 / dx)),
+ *               min X < 7 or max (X - res) > -7).  source = 1: and position + advection is NOT inside, advection =
+ *               velocity * d + 0.5 * gravity * (d + base_delta_t) * d with d = source_delta_t (src/mpm.cpp:222-227).
+ *   order       the survivors are appended in ascending c with creation ids next_id + rank (the reference's order).
+ *   rows        x, velocity as given, F = initial_dg * I, B = 0, aux the material default of mpmhip2d_add_particles, the group.
+ * *n_added = the number of new particles.  If they do not fit the ctx, nothing is written, *n_added is the number needed and the
+ * call returns MPMHIP_ECAPACITY: mpmhip2d_reserve and call again.  MPMHIP_EINVAL with a message: an unknown group; ppc not finite
+ * or <= 0; a non-finite velocity, initial_dg or source_delta_t; a lattice with res < 2, a non-finite origin, a spacing that is not
+ * a finite number > 0, or phi == NULL; an empty region; more than 2^31 candidates; creation ids past 2^31; a resident asynchronous
+ * stepper (seed before mpmhip2d_async_begin).  The call synchronises the ctx's stream twice for a few words each; its work
+ * buffers belong to the ctx, only grow, and go with mpmhip2d_destroy.
+ * Out of scope: a sampled level set as the 2D BOUNDARY (mpmhip2d_set_levelset takes shapes only), pd_packed, non-uniform
+ * densities, pd = False, point_cloud.
+ *
+ * mpmhip2d_reserve: the particle arrays hold at least `capacity` particles afterwards (mpmhip2d_config.max_particles of a live
+ * ctx); their contents, the clocks, bodies and groups stay.  MPMHIP_OK at once when the capacity already suffices.
+ * mpmhip2d_num_slots: the rows the arrays hold, deleted ones included — what the capacity bounds (no synchronisation). */
+typedef struct {
+  int32_t res[2];
+  float origin[2];
+  float spacing;
+} mpmhip2d_sdf_desc;
+typedef struct {
+  int32_t n_shapes;
+  mpmhip_shape shapes[MPMHIP_MAX_SHAPES];
+  const mpmhip2d_sdf_desc *sdf; /* NULL: the region is given by the shapes */
+  const float *phi;
+  float ppc;                    /* particles per cell the spacing is chosen for (> 0) */
+  float velocity[2];
+  int32_t source;               /* 0 fill, 1 emitter shell */
+  float source_delta_t;
+  float initial_dg;
+  int32_t reserved;
+} mpmhip2d_seed_desc;
+int64_t mpmhip2d_poisson_tile(float *out, int64_t capacity);
+int mpmhip2d_seed_particles(mpmhip2d_ctx *ctx, int32_t group, const mpmhip2d_seed_desc *desc, int64_t *n_added);
+int mpmhip2d_reserve(mpmhip2d_ctx *ctx, int64_t capacity);
+int64_t mpmhip2d_num_slots(mpmhip2d_ctx *ctx);
 
 /* frame output of the 2D simulation — replaces MPM<2>::write_partio (src/visualize.cpp:17-100): the same .bgeo as the 3D
  * entry points above (z = 0), boundary particles of rigid bodies as rows of type 1; with a resident asynchronous stepper the rows

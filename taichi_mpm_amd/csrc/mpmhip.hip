@@ -103,6 +103,8 @@
 #include "k_mpm2d.h"
 #include "k_mpm2d_det.h"
 #include "k_async2d.h"
+#include "k_seed2d.h"
+#include "poisson_tile2d.h"
 
 
 // ================================================================================================ host side
@@ -2781,6 +2783,7 @@ struct mpmhip2d_ctx {
     DevBuf<AsyncCounters> d_cnt;
     PinnedBuf<AsyncCounters> h_cnt;
   } async;
+  mpm2d::SeedWork2 seed;  // mpmhip2d_seed_particles (seed2d_api.h): the tile and the work buffers of the candidate passes
 };
 static int a2_drop_view(mpmhip2d_ctx *m);
 static int a2_grow_particles(mpmhip2d_ctx *m, int64_t need);
@@ -3459,6 +3462,7 @@ int mpmhip2d_download_grid(mpmhip2d_ctx *m, float *grid) {  // (v.x, v.y, m) per
 
 #include "async2d_api.h"
 #include "frame2d_api.h"
+#include "seed2d_api.h"
 
 // ------------------------------------------------------------------------------------------------ debug math
 int mpmhip_debug_cond_census(mpmhip_ctx *c, double out[MPMHIP_COND_CENSUS_WORDS]) {

@@ -1,7 +1,8 @@
 """MPM<2> — the reference's 2D simulation (`tc_core.create_simulation2('mpm')`, src/mpm.cpp:983-986) on top of the
 mpmhip2d_* entry points of the C ABI (include/mpmhip.h).  Same surface as Simulation3D (taichi_mpm_amd/mpm.py) where it
 applies: `initialize`, `add_particles`, `set_levelset`, `step`, `get_current_time`, `get_particles`.  MPM<2> runs the
-generic transfer path (src/transfer.cpp:280-283,697-700)."""
+generic transfer path (src/transfer.cpp:280-283,697-700).  `add_particles(region=...)` fills a LevelSet or a SampledLevelSet2D on
+the device from the periodic Poisson-disk tile (include/mpmhip.h: mpmhip2d_seed_particles)."""
 import ctypes as C
 import os
 
@@ -19,6 +20,85 @@ def lattice_square(lower, higher, dx):
     cells = np.stack([ii, jj], -1).reshape(-1, 1, 2) + 0.5
     signs = np.array([[-1, -1], [1, -1], [-1, 1], [1, 1]], np.float64)
     return ((cells + 0.25 * signs[None]) * dx).reshape(-1, 2).astype(np.float32)
+
+
+class SampledLevelSet2D:
+    """A signed-distance field sampled on a regular lattice in the plane: the region of add_particles(region=...) — a disc, a polygon,
+    any free-form blob (it stands in for the reference's polygon and image textures).  `phi`: array of shape (res0, res1), world units,
+    negative inside; sample (i, j) sits at origin + (i, j) * spacing.  spacing=None: the cell size of the simulation it is given to.
+    Read bilinearly; outside the lattice there is no region.  It is a region only: set_levelset does not take it."""
+
+    def __init__(self, phi, origin=(0.0, 0.0), spacing=None):
+        a = np.asarray(phi)
+        if a.ndim != 2:
+            raise MPMError("SampledLevelSet2D: phi must have 2 axes, got shape %r" % (a.shape,))
+        if min(a.shape) < 2:
+            raise MPMError("SampledLevelSet2D: at least 2 samples per axis are needed, got shape %r" % (a.shape,))
+        a = np.ascontiguousarray(a, np.float32)
+        if not np.all(np.isfinite(a)):
+            raise MPMError("SampledLevelSet2D: phi holds non-finite values")
+        o = tuple(float(v) for v in origin)
+        if len(o) != 2 or not np.all(np.isfinite(o)):
+            raise MPMError("SampledLevelSet2D: origin must be two finite numbers, got %r" % (origin,))
+        if spacing is not None and not (np.isfinite(spacing) and float(spacing) > 0):
+            raise MPMError("SampledLevelSet2D: spacing must be a finite number > 0, got %r" % (spacing,))
+        self.phi, self.origin = a, o
+        self.spacing = None if spacing is None else float(spacing)
+
+    @property
+    def res(self):
+        return self.phi.shape
+
+    @staticmethod
+    def lattice_points(res, origin, spacing):
+        """(n, 2) float64 positions of the samples in the array's order"""
+        res = tuple(int(r) for r in res)
+        if len(res) != 2 or min(res) < 2:
+            raise MPMError("SampledLevelSet2D: res must be two numbers >= 2, got %r" % (res,))
+        if spacing is None or not (np.isfinite(spacing) and float(spacing) > 0):
+            raise MPMError("SampledLevelSet2D: spacing must be a finite number > 0, got %r" % (spacing,))
+        ax = [float(origin[k]) + np.arange(res[k], dtype=np.float64) * float(spacing) for k in range(2)]
+        return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 2)
+
+    @classmethod
+    def from_function(cls, f, res, origin=(0.0, 0.0), spacing=None):
+        """sample f, which maps an (n, 2) array of world positions to n values of phi"""
+        pts = cls.lattice_points(res, origin, spacing)
+        phi = np.empty(len(pts), np.float64)
+        for i in range(0, len(pts), 1 << 18):  # (chunks: f may build large temporaries)
+            phi[i:i + (1 << 18)] = np.asarray(f(pts[i:i + (1 << 18)]), np.float64).reshape(-1)
+        return cls(phi.reshape(tuple(int(r) for r in res)), origin, spacing)
+
+    @staticmethod
+    def polygon_distance(vertices, pts):
+        """signed distance (float64, negative inside) of the points pts (n, 2) to the simple closed polygon `vertices` (m, 2), in
+        either orientation: the distance to the nearest edge, the sign from the even-odd rule (a ray towards +x; an end point AT the
+        ray's height counts as below, so a vertex is crossed once)"""
+        v = np.asarray(vertices, np.float64).reshape(-1, 2)
+        if len(v) < 3 or not np.all(np.isfinite(v)):
+            raise MPMError("SampledLevelSet2D: a polygon needs at least 3 finite vertices")
+        p = np.asarray(pts, np.float64).reshape(-1, 2)
+        a, b = v, np.roll(v, -1, axis=0)
+        e = b - a
+        ee = np.maximum((e * e).sum(axis=1), 1e-300)
+        d2 = np.full(len(p), np.inf)
+        odd = np.zeros(len(p), bool)
+        for k in range(len(v)):
+            w = p - a[k]
+            t = np.clip((w @ e[k]) / ee[k], 0.0, 1.0)
+            r = w - t[:, None] * e[k]
+            d2 = np.minimum(d2, (r * r).sum(axis=1))
+            up_a, up_b = a[k, 1] > p[:, 1], b[k, 1] > p[:, 1]
+            cross = up_a != up_b
+            with np.errstate(divide="ignore", invalid="ignore"):
+                xc = a[k, 0] + (p[:, 1] - a[k, 1]) * (e[k, 0] / e[k, 1])
+            odd ^= cross & (p[:, 0] < xc)
+        return np.where(odd, -1.0, 1.0) * np.sqrt(d2)
+
+    @classmethod
+    def from_polygon(cls, vertices, res, origin=(0.0, 0.0), spacing=None):
+        """bake the signed distance of a simple closed polygon, vertices (m, 2) in world units"""
+        return cls.from_function(lambda x: cls.polygon_distance(vertices, x), res, origin, spacing)
 
 
 class Simulation2D:
@@ -130,7 +210,8 @@ class Simulation2D:
         self._check(self._L.mpmhip2d_add_particles(self._ctx, gi, len(x), ptr(x, 2), ptr(v, 2), ptr(F, 4), ptr(B, 4), ptr(aux, 1)))
 
     def add_particles(self, config):
-        """MPM<2>::add_particles (src/mpm.cpp:77-270) with explicit `positions=` (n, 2) or a `square=(lo, hi)` lattice"""
+        """MPM<2>::add_particles (src/mpm.cpp:77-270) with explicit `positions=` (n, 2), a `square=(lo, hi)` lattice, or `region=` —
+        a LevelSet or SampledLevelSet2D filled on the device from the periodic Poisson-disk tile (_seed_region)"""
         cfg = dict(config)
         ptype = cfg.get("type")
         if ptype == "rigid":  # src/mpm.cpp:80-83
@@ -139,12 +220,14 @@ class Simulation2D:
             raise MPMError("unknown particle type %r" % (ptype,))
         dx = self.delta_x
         maximum = float(cfg.get("ppc", cfg.get("maximum", 4)))
+        if "region" in cfg:
+            return self._seed_region(cfg, ptype, maximum)
         if "square" in cfg:
             x = lattice_square(int(cfg["square"][0]), int(cfg["square"][1]), dx)
         elif "positions" in cfg:
             x = np.ascontiguousarray(cfg["positions"], np.float32).reshape(-1, 2)
         else:
-            raise MPMError("add_particles needs positions= or square=(lo, hi)")
+            raise MPMError("add_particles needs positions=, square=(lo, hi) or region=")
         X = x.astype(np.float64) / dx
         keep = ~((X.min(1) < 7.0) | ((X - np.asarray(self.res)).max(1) > -7.0))  # src/mpm.cpp:129-132
         x = x[keep]
@@ -173,7 +256,76 @@ class Simulation2D:
         self._n_added += n
         return ""
 
+    def _seed_desc(self, cfg, ptype, ppc):
+        """the mpmhip2d_seed_desc of an add_particles(region=...) config, and the objects its pointers need alive"""
+        region, dx = cfg["region"], self.delta_x
+        if not (np.isfinite(ppc) and ppc > 0):
+            raise MPMError("add_particles(region=): ppc must be a finite number > 0, got %r" % (ppc,))
+        for k in ("velocities", "F", "B", "aux", "pd_packed", "point_cloud"):
+            if k in cfg and cfg[k] is not False:
+                raise MPMError("add_particles(region=) does not take %r" % k)
+        if not cfg.get("pd", True) or not cfg.get("pd_periodic", True):
+            raise MPMError("add_particles(region=) implements the periodic Poisson-disk tile only (pd and pd_periodic must stay True)")
+        if initial_aux(ptype, **cfg) != initial_aux(ptype):
+            raise MPMError("add_particles(region=) gives every particle the material's default state")
+        d = _lib.SeedDesc2D()
+        keep = []
+        if isinstance(region, SampledLevelSet2D):
+            sd = _lib.SdfDesc2D()
+            sd.res[:] = region.res
+            sd.origin[:] = region.origin
+            sd.spacing = dx if region.spacing is None else region.spacing
+            keep += [sd, region.phi]
+            d.sdf = C.pointer(sd)
+            d.phi = region.phi.ctypes.data_as(C.POINTER(C.c_float))
+        elif isinstance(region, LevelSet):
+            d.n_shapes = len(region.shapes)
+            for i, (t_, io, p) in enumerate(region.shapes):
+                d.shapes[i].type, d.shapes[i].inside_out = t_, io
+                d.shapes[i].p[:] = p
+        else:
+            raise MPMError("add_particles(region=) takes a LevelSet or a SampledLevelSet2D, got %r" % type(region).__name__)
+        d.ppc = ppc
+        v0 = cfg.get("initial_velocity", (0.0, 0.0))
+        d.velocity[:] = (float(v0[0]), float(v0[1]))
+        d.source = int(bool(cfg.get("pd_source", False)))
+        d.source_delta_t = float(cfg.get("delta_t", 1e-3))  # src/mpm.cpp:224
+        d.initial_dg = float(cfg.get("initial_dg", 1.0))  # src/particles.h:120
+        return d, keep
+
+    def _seed_region(self, cfg, ptype, ppc):
+        """add_particles(region=...): the reference's default fill, add_particles(density_tex=...) with the periodic Poisson-disk
+        tile (src/mpm.cpp:205-251), on the device (include/mpmhip.h: mpmhip2d_seed_particles).  region: a LevelSet (where its shapes,
+        read in the plane, are negative) or a SampledLevelSet2D.  Keys: ppc (4), initial_velocity, pd_source, delta_t (1e-3),
+        initial_dg, density and the material keys."""
+        dx = self.delta_x
+        d, keep = self._seed_desc(cfg, ptype, ppc)
+        vol = dx ** 2 / ppc  # pow<dim>(delta_x) / maximum, src/mpm.cpp:134
+        mass = vol * float(cfg.get("density", 400.0))
+        params, mat = group_params(ptype, mass, vol, **{k: v for k, v in cfg.items() if isinstance(v, (int, float))})
+        if "params" in cfg:
+            params = np.ascontiguousarray(cfg["params"], np.float32).reshape(16).copy()
+        self._ensure_ctx()  # (particles staged before the ctx existed are uploaded first: creation ids follow call order)
+        # an emitter calls before every frame with one material: its particles share a group row (a ctx holds 64 of them)
+        gi = next((i for i, (m_, p_) in enumerate(self._groups) if m_ == mat and p_.tobytes() == params.tobytes()), len(self._groups))
+        if gi == len(self._groups):
+            self._groups.append((mat, params))
+            self._check(self._L.mpmhip2d_add_group(self._ctx, mat, params.ctypes.data_as(C.POINTER(C.c_float))))
+        n = C.c_int64(0)
+        rc = self._L.mpmhip2d_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+        if rc == -4:  # MPMHIP_ECAPACITY: n is what the call needs; nothing was written
+            cap = max(int((int(self._L.mpmhip2d_num_slots(self._ctx)) + n.value) * 1.5), self.max_particles)
+            self._check(self._L.mpmhip2d_reserve(self._ctx, cap))
+            self._capacity = max(self._capacity, cap)
+            rc = self._L.mpmhip2d_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+        self._check(rc)
+        self._n_added += n.value
+        return ""
+
     def set_levelset(self, levelset):
+        if isinstance(levelset, SampledLevelSet2D):
+            raise MPMError("set_levelset: a SampledLevelSet2D is a region for add_particles(region=...) only; the 2D boundary takes "
+                           "a LevelSet or a DynamicLevelSet of shapes")
         self._levelset = levelset
         if self._ctx is not None:
             self._apply_levelset()
