@@ -697,7 +697,7 @@ int mpmhip2d_download_grid(mpmhip2d_ctx *ctx, float *grid /* [(res0+1)(res1+1)][
  *
  * The tile: mpmhip2d_poisson_tile writes min(count, capacity) points, 2 floats each, to `out` (NULL allowed) and returns the count.
  * Bridson's algorithm in the periodic box [-20, 20)^2, minimum distance 1, 30 attempts per active point, the first point at the
- * centre, generated once per process in integer arithmetic (csrc/poisson_tile2d.h): the same bytes on every machine.
+ * centre, generated once per process in integer arithmetic (csrc/poisson_tile.h): the same bytes on every machine.
  *
  * The region is "where this level set is negative", independent of the ctx's boundary level set (which is not touched):
  *   sdf == NULL   the first n_shapes of `shapes`, read in the plane exactly as mpmhip2d_set_levelset reads them (z ignored, a box

@@ -2,7 +2,7 @@
 // the host side of the ctx.  The kernels live next to this file, one header per phase:
 //   mpm_common.h (records, parameter blocks, Morton keys)   mpm_math.h (3x3 math, constitutive models, level set)
 //   k_sort.h  k_p2g.h  k_grid.h  k_g2p.h  k_tiling.h  k_particles.h  k_debug.h
-//   k_seed.h (particle seeding from the periodic Poisson-disk tile, poisson_tile.h)
+//   k_seed.h (particle seeding from the periodic Poisson-disk tiles, poisson_tile.h; both dimensions)
 //   k_bgeo.h (.bgeo frame rows)   k_mpm88.h (the 2D dense-grid demo, its own small object)
 // host_mem.h: DevBuf / PinnedBuf, the owners of every device and pinned array of the objects below (a new array needs a field and
 // its allocation, nothing else); what a kernel takes by value keeps raw pointers into them.
@@ -103,8 +103,6 @@
 #include "k_mpm2d.h"
 #include "k_mpm2d_det.h"
 #include "k_async2d.h"
-#include "k_seed2d.h"
-#include "poisson_tile2d.h"
 
 
 // ================================================================================================ host side
@@ -2692,7 +2690,6 @@ int mpmhip_async_set_time_int(mpmhip_ctx *c, int64_t t_int) {
 }
 
 #include "async_api.h"
-#include "seed_api.h"
 
 int mpmhip_debug_allowed_dt(mpmhip_ctx *c, int32_t material, const float params[MPMHIP_NPARAM], int64_t n, const float *F,
                             const float *aux, const float *v, float dx, float *out) {
@@ -2783,7 +2780,7 @@ struct mpmhip2d_ctx {
     DevBuf<AsyncCounters> d_cnt;
     PinnedBuf<AsyncCounters> h_cnt;
   } async;
-  mpm2d::SeedWork2 seed;  // mpmhip2d_seed_particles (seed2d_api.h): the tile and the work buffers of the candidate passes
+  SeedWork seed;  // mpmhip2d_seed_particles (seed_api.h): the tile and the work buffers of the candidate passes
 };
 static int a2_drop_view(mpmhip2d_ctx *m);
 static int a2_grow_particles(mpmhip2d_ctx *m, int64_t need);
@@ -3462,7 +3459,7 @@ int mpmhip2d_download_grid(mpmhip2d_ctx *m, float *grid) {  // (v.x, v.y, m) per
 
 #include "async2d_api.h"
 #include "frame2d_api.h"
-#include "seed2d_api.h"
+#include "seed_api.h"
 
 // ------------------------------------------------------------------------------------------------ debug math
 int mpmhip_debug_cond_census(mpmhip_ctx *c, double out[MPMHIP_COND_CENSUS_WORDS]) {

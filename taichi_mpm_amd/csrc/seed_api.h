@@ -1,173 +1,311 @@
-// taichi_mpm_amd/csrc/seed_api.h — host side of mpmhip_seed_particles (kernels: k_seed.h; tile: poisson_tile.h; rules: include/mpmhip.h)
-// Included by mpmhip.hip inside its extern "C" block.  A call synchronises twice for a few words each: the get-ready box (the number
-// of replicas sizes the candidate passes) and the survivors' count (the capacity check comes before anything is written).
+// taichi_mpm_amd/csrc/seed_api.h — host side of mpmhip_seed_particles, mpmhip2d_seed_particles and mpmhip2d_reserve (kernels: k_seed.h;
+// tiles: poisson_tile.h; rules: include/mpmhip.h).  Included by mpmhip.hip inside its extern "C" block, behind async2d_api.h and
+// frame2d_api.h: both ctx types are complete here.  One driver (seed_particles) carries the call for both dimensions; what a ctx does
+// its own way is in its adapter (Seed3, Seed2).  A call synchronises twice for a few words each: the get-ready box (the number of
+// replicas sizes the candidate passes) and the survivors' count (the capacity check comes before anything is written).
 #pragma once
 
-int64_t mpmhip_poisson_tile(float *out, int64_t capacity) {
-  const std::vector<float> &t = poisson_tile::tile();
-  const int64_t n = (int64_t)(t.size() / 3);
-  if (out && capacity > 0) memcpy(out, t.data(), sizeof(float) * 3 * (size_t)std::min(n, capacity));
-  return n;
+// the particle arrays hold at least `capacity` particles; what they hold stays.  The per-particle arrays of the CPIC coupling grow
+// with them (a2_grow_particles_any); those of the deterministic mode are scratch of one substep, sized by a capacity of their own
+// that det2_reserve compares with the ctx's at every substep: they follow at the next one.
+int mpmhip2d_reserve(mpmhip2d_ctx *m, int64_t capacity) {
+  if (!m) return MPMHIP_EINVAL;
+  if (capacity <= m->cap) return MPMHIP_OK;
+  HIPCHK2D(m, hipSetDevice(m->device));
+  return a2_grow_particles_any(m, capacity);
 }
+
+int64_t mpmhip2d_num_slots(mpmhip2d_ctx *m) { return m ? m->n : (int64_t)MPMHIP_EINVAL; }
 
 extern "C++" {
 namespace {
 
 #define SEED_NO_CONTRACT _Pragma("clang fp contract(off)")
 
-// the region of a seeding call as the kernels take it; a sampled field is uploaded into the ctx's buffer
-int seed_region(mpmhip_ctx *c, const mpmhip_seed_desc *d, SeedRegion &R) {
-  memset(&R, 0, sizeof R);
-  if (!d->sdf) {
+template <int D>
+int64_t seed_tile_out(float *out, int64_t capacity) {
+  const std::vector<float> &t = poisson_tile::tile<D>();
+  const int64_t n = (int64_t)(t.size() / D);
+  if (out && capacity > 0) memcpy(out, t.data(), sizeof(float) * D * (size_t)std::min(n, capacity));
+  return n;
+}
+
+template <class Region, class Desc>
+void seed_copy_shapes(Region &R, const Desc *d) {
+  R.n_shapes = d->n_shapes;
+  for (int i = 0; i < d->n_shapes; i++) {
+    R.s[i].type = d->shapes[i].type;
+    R.s[i].inside_out = d->shapes[i].inside_out;
+    for (int k = 0; k < 6; k++) R.s[i].p[k] = d->shapes[i].p[k];
+  }
+}
+
+// What the driver asks of a ctx beyond the fields both have under one name (stream, device, P.dx, P.idx, P.res, P.g, t, groups,
+// next_pid, seed): how an error is recorded, which calls are refused outright, how shapes become the region, the closed form of
+// min_distance from v = dx^D / ppc, the cap on the bounds launch, the base time step, and the commit: its checks in this ctx's order
+// with this ctx's codes, the sink, the bookkeeping behind the write.
+struct Seed3 {
+  static constexpr int D = 3;
+  using Ctx = mpmhip_ctx;
+  using Desc = mpmhip_seed_desc;
+  using Region = SeedRegion;
+  static int fail(Ctx *c, int code, const char *msg) { return ::fail(c, code, "%s", msg); }
+  static const char *refused(const Ctx *c) {
+    if (c->in_substep) return "seed_particles inside a substep";
+    if (c->T.enabled || c->tn.on) return "seed_particles on a tiled ctx: seed before the partition is set, or give each rank its positions";
+    return nullptr;
+  }
+  static int shapes(Ctx *c, const Desc *d, Region &R) {
     if (int rc = check_shapes(c, d->n_shapes, d->shapes)) return rc;
-    R.n_shapes = d->n_shapes;
-    for (int i = 0; i < d->n_shapes; i++) {
-      R.s[i].type = d->shapes[i].type;
-      R.s[i].inside_out = d->shapes[i].inside_out;
-      for (int k = 0; k < 6; k++) R.s[i].p[k] = d->shapes[i].p[k];
+    seed_copy_shapes(R, d);
+    return MPMHIP_OK;
+  }
+  static void set_field(Region &R, const float *phi) {  // one frame
+    R.sdf.phi0 = phi;
+    R.sdf.phi1 = nullptr;
+    R.sdf.t0 = 0.0f; R.sdf.t1 = 1.0f;
+  }
+  static float min_distance(double v) { return (float)std::cbrt(v * 13.0 / 18.0); }
+  static uint32_t max_bounds_wgs(const Ctx *c) { return (uint32_t)c->n_cus * 32u; }
+  static float base_dt(const Ctx *c) { return c->P.dt; }
+  template <class Write>
+  static int commit(Ctx *c, int32_t group, int64_t n, Write write) {
+    if (int rc = async_drop_view(c)) return rc;  // (resident async stepper: records that only mirror the pools go first)
+    if (c->n_slots + n > c->cap)
+      return ::fail(c, MPMHIP_ECAPACITY, "particle capacity exceeded: %lld + %lld > %lld", (long long)c->n_slots, (long long)n, (long long)c->cap);
+    if ((int64_t)c->next_pid + n > 0x7fffffffll) return ::fail(c, MPMHIP_ECAPACITY, "seed_particles: creation ids exceed 2^31");
+    if (int rc = ensure_b_current(c)) return rc;  // A of every particle is recomputed from apic_b
+    if (int rc = write(SeedSink3{reinterpret_cast<float4 *>(c->rg + c->n_slots), reinterpret_cast<float4 *>(c->rp + c->n_slots),
+                                 reinterpret_cast<float4 *>(c->rb + (size_t)c->n_slots * BW), c->groups[group].p[0]}))
+      return rc;
+    c->next_pid += (int32_t)n;
+    set_slots(c, c->n_slots + n);
+    return clear_block_flags(c, c->rec.particles_appended());
+  }
+};
+
+struct Seed2 {
+  static constexpr int D = 2;
+  using Ctx = mpmhip2d_ctx;
+  using Desc = mpmhip2d_seed_desc;
+  using Region = SeedRegion2;
+  static int fail(Ctx *m, int code, const char *msg) { return fail2d(m, code, msg); }
+  static const char *refused(const Ctx *m) {
+    return m->async.resident ? "seed_particles: not on a resident asynchronous stepper (seed before mpmhip2d_async_begin)" : nullptr;
+  }
+  static int shapes(Ctx *m, const Desc *d, Region &R) {
+    if (d->n_shapes < 0 || d->n_shapes > MPMHIP_MAX_SHAPES) return fail2d(m, MPMHIP_EINVAL, "seed_particles: n_shapes outside [0, " + std::to_string(MPMHIP_MAX_SHAPES) + "]");
+    for (int i = 0; i < d->n_shapes; i++)
+      if (d->shapes[i].type < 0 || d->shapes[i].type > 2) return fail2d(m, MPMHIP_EINVAL, "seed_particles: unknown shape type " + std::to_string(d->shapes[i].type));
+    seed_copy_shapes(R, d);
+    for (int i = 0; i < R.n_shapes; i++) {  // read in the plane, as mpmhip2d_set_levelset does
+      if (R.s[i].type == 2) { R.s[i].p[2] = -1e30f; R.s[i].p[5] = 1e30f; }  // a box in the plane: unbounded along z
+      else R.s[i].p[2] = 0.0f;
     }
     return MPMHIP_OK;
   }
-  const mpmhip_sdf_desc *L = d->sdf;
-  if (!d->phi) return fail(c, MPMHIP_EINVAL, "seed_particles: a sampled region needs its phi array");
+  static void set_field(Region &R, const float *phi) { R.sdf.phi = phi; }
+  static float min_distance(double v) { return (float)std::sqrt(v * 2.0 / 3.0); }
+  static uint32_t max_bounds_wgs(const Ctx *) { return 8192u; }
+  static float base_dt(const Ctx *m) { return m->base_dt; }
+  template <class Write>
+  static int commit(Ctx *m, int32_t, int64_t n, Write write) {
+    if ((int64_t)m->next_pid + n > 0x7fffffffll) return fail2d(m, MPMHIP_EINVAL, "seed_particles: creation ids exceed 2^31");
+    if (m->n + n > m->cap)
+      return fail2d(m, MPMHIP_ECAPACITY, "particle capacity exceeded: " + std::to_string(m->n) + " + " + std::to_string(n) + " > " + std::to_string(m->cap));
+    const size_t at = (size_t)m->n;  // the rows behind the resident ones
+    if (int rc = write(SeedSink2{reinterpret_cast<float2 *>(m->x + 2 * at), reinterpret_cast<float2 *>(m->v + 2 * at),
+                                 reinterpret_cast<float4 *>(m->F + 4 * at), reinterpret_cast<float4 *>(m->B + 4 * at), m->aux + at,
+                                 m->gid + at, m->pid + at}))
+      return rc;
+    m->next_pid += (int32_t)n;
+    m->n += n;
+    return MPMHIP_OK;
+  }
+};
+
+template <class A>
+__attribute__((format(printf, 3, 4))) int seed_fail(typename A::Ctx *c, int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  return A::fail(c, code, buf);
+}
+#define SEED_FAIL(...) return seed_fail<A>(c, MPMHIP_EINVAL, __VA_ARGS__)
+#define SEED_HIP(call)                                                                                                  \
+  do {                                                                                                                  \
+    const hipError_t e_ = (call);                                                                                       \
+    if (e_ != hipSuccess) return seed_fail<A>(c, MPMHIP_EHIP, "%s failed: %s", #call, hipGetErrorString(e_));          \
+  } while (0)
+#define SEED_LAUNCHED(what)                                                                                             \
+  do {                                                                                                                  \
+    const hipError_t e_ = hipGetLastError();                                                                            \
+    if (e_ != hipSuccess) return seed_fail<A>(c, MPMHIP_EHIP, "launch of %s failed: %s", what, hipGetErrorString(e_)); \
+  } while (0)
+
+// the region of a seeding call as the kernels take it; a sampled field is uploaded into the ctx's buffer
+template <class A>
+int seed_region(typename A::Ctx *c, const typename A::Desc *d, typename A::Region &R) {
+  constexpr int D = A::D;
+  memset(&R, 0, sizeof R);
+  if (!d->sdf) return A::shapes(c, d, R);
+  const auto *L = d->sdf;
+  if (!d->phi) SEED_FAIL("seed_particles: a sampled region needs its phi array");
   size_t count = 1;
-  for (int k = 0; k < 3; k++) {  // what mpmhip_set_levelset_sdf refuses
-    if (L->res[k] < 2) return fail(c, MPMHIP_EINVAL, "seed_particles: res[%d] = %d, at least 2 samples per axis are needed", k, L->res[k]);
-    if (!std::isfinite(L->origin[k])) return fail(c, MPMHIP_EINVAL, "seed_particles: origin[%d] is not finite", k);
+  for (int k = 0; k < D; k++) {  // what mpmhip_set_levelset_sdf refuses
+    if (L->res[k] < 2) SEED_FAIL("seed_particles: res[%d] = %d, at least 2 samples per axis are needed", k, L->res[k]);
+    if (!std::isfinite(L->origin[k])) SEED_FAIL("seed_particles: origin[%d] is not finite", k);
     count *= (size_t)L->res[k];
   }
-  if (!(L->spacing > 0.0f) || !std::isfinite(L->spacing)) return fail(c, MPMHIP_EINVAL, "seed_particles: spacing must be a finite number > 0");
-  if (count > ((size_t)1 << 31)) return fail(c, MPMHIP_EINVAL, "seed_particles: more than 2^31 samples");
+  if (!(L->spacing > 0.0f) || !std::isfinite(L->spacing)) SEED_FAIL("seed_particles: spacing must be a finite number > 0");
+  if (count > ((size_t)1 << 31)) SEED_FAIL("seed_particles: more than 2^31 samples");
   SeedWork &W = c->seed;
   if (count > W.phi_cap || !W.d_phi) {
     W.phi_cap = 0;
-    if (W.d_phi.alloc(count) != hipSuccess) return fail(c, MPMHIP_ENOMEM, "seed_particles: device allocation of %zu bytes failed", count * sizeof(float));
+    if (W.d_phi.alloc(count) != hipSuccess)
+      return seed_fail<A>(c, MPMHIP_ENOMEM, "seed_particles: device allocation of %zu bytes failed", count * sizeof(float));
     W.phi_cap = count;
   }
-  HIPCHK(c, hipMemcpyAsync(W.d_phi, d->phi, sizeof(float) * count, hipMemcpyHostToDevice, c->stream));
-  R.sdf.phi0 = W.d_phi;
-  R.sdf.phi1 = nullptr;
+  SEED_HIP(hipMemcpyAsync(W.d_phi, d->phi, sizeof(float) * count, hipMemcpyHostToDevice, c->stream));
+  A::set_field(R, W.d_phi);
   R.sdf.spacing = L->spacing; R.sdf.inv_spacing = 1.0f / L->spacing;
-  R.sdf.t0 = 0.0f; R.sdf.t1 = 1.0f;
-  for (int k = 0; k < 3; k++) { R.sdf.res[k] = L->res[k]; R.sdf.origin[k] = L->origin[k]; }
+  for (int k = 0; k < D; k++) { R.sdf.res[k] = L->res[k]; R.sdf.origin[k] = L->origin[k]; }
   return MPMHIP_OK;
 }
 
-// get_ready + the replicas (src/poisson_disk_sampler.h:34-69, :166-173) from the box of inside cell centres, in fp32
-void seed_get_ready(const mpmhip_ctx *c, const mpmhip_seed_desc *d, const int box[6], SeedParams &S) {
+// get_ready + the replicas (src/poisson_disk_sampler.h:34-69, :166-173) from the box of inside cell centres, in fp32.  The replicas
+// per axis stay floats and their product a double until the candidates are known to fit: a tiny spacing gives more than an integer
+// holds.  The product is exact where it counts: up to 2^31 every partial product is an integer a double holds, beyond it the
+// rounded value is beyond it too.
+template <class A>
+double seed_get_ready(const typename A::Ctx *c, float ppc, const int *box, SeedParams<A::D> &S, float nrep[A::D]) {
   SEED_NO_CONTRACT
+  constexpr int D = A::D;
   const float dx = c->P.dx;
-  const double v = (double)dx * (double)dx * (double)dx / (double)d->ppc;
-  S.min_distance = (float)std::cbrt(v * 13.0 / 18.0);
+  double v = (double)dx, n_rep = 1.0;
+  for (int k = 1; k < D; k++) v = v * (double)dx;
+  S.min_distance = A::min_distance(v / (double)ppc);
   S.region_size = 40.0f * S.min_distance;
-  S.n_rep = 1;
-  for (int k = 0; k < 3; k++) {
-    const float lo = ((float)box[k] + 0.5f) * dx, hi = ((float)box[3 + k] + 0.5f) * dx;
+  for (int k = 0; k < D; k++) {
+    const float lo = ((float)box[k] + 0.5f) * dx, hi = ((float)box[D + k] + 0.5f) * dx;
     const float min_corner = lo - dx, max_corner = hi + dx;
     const float size = max_corner - min_corner;
     S.min_corner[k] = min_corner;
-    S.nrep[k] = std::max(1, (int)std::ceil(size / S.region_size));
+    nrep[k] = std::max(1.0f, std::ceil(size / S.region_size));
+    n_rep *= (double)nrep[k];
   }
+  return n_rep;
 }
 
-}  // namespace
-}  // extern "C++"
-
-int mpmhip_seed_particles(mpmhip_ctx *c, int32_t group, const mpmhip_seed_desc *d, int64_t *n_added) {
+template <class A>
+int seed_particles(typename A::Ctx *c, int32_t group, const typename A::Desc *d, int64_t *n_added) {
   SEED_NO_CONTRACT
+  constexpr int D = A::D;
   if (!c) return MPMHIP_EINVAL;
   if (n_added) *n_added = 0;
-  if (!d) return fail(c, MPMHIP_EINVAL, "seed_particles: the description is required");
-  if (c->in_substep) return fail(c, MPMHIP_EINVAL, "seed_particles inside a substep");
-  if (c->T.enabled || c->tn.on) return fail(c, MPMHIP_EINVAL, "seed_particles on a tiled ctx: seed before the partition is set, or give each rank its positions");
-  if (group < 0 || group >= (int)c->groups.size()) return fail(c, MPMHIP_EINVAL, "unknown group %d", group);
-  if (!(d->ppc > 0.0f) || !std::isfinite(d->ppc)) return fail(c, MPMHIP_EINVAL, "seed_particles: ppc must be a finite number > 0");
-  for (int k = 0; k < 3; k++)
-    if (!std::isfinite(d->velocity[k])) return fail(c, MPMHIP_EINVAL, "seed_particles: velocity[%d] is not finite", k);
-  if (!std::isfinite(d->initial_dg)) return fail(c, MPMHIP_EINVAL, "seed_particles: initial_dg is not finite");
-  if (d->source && !std::isfinite(d->source_delta_t)) return fail(c, MPMHIP_EINVAL, "seed_particles: source_delta_t is not finite");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  SeedRegion R;
-  if (int rc = seed_region(c, d, R)) return rc;
+  if (!d) SEED_FAIL("seed_particles: the description is required");
+  if (const char *why = A::refused(c)) return A::fail(c, MPMHIP_EINVAL, why);
+  if (group < 0 || group >= (int)c->groups.size()) SEED_FAIL("unknown group %d", group);
+  if (!(d->ppc > 0.0f) || !std::isfinite(d->ppc)) SEED_FAIL("seed_particles: ppc must be a finite number > 0");
+  for (int k = 0; k < D; k++)
+    if (!std::isfinite(d->velocity[k])) SEED_FAIL("seed_particles: velocity[%d] is not finite", k);
+  if (!std::isfinite(d->initial_dg)) SEED_FAIL("seed_particles: initial_dg is not finite");
+  if (d->source && !std::isfinite(d->source_delta_t)) SEED_FAIL("seed_particles: source_delta_t is not finite");
+  SEED_HIP(hipSetDevice(c->device));
+  SEED_HIP(hipStreamSynchronize(c->stream));
+  typename A::Region R;
+  if (int rc = seed_region<A>(c, d, R)) return rc;
   SeedWork &W = c->seed;
   if (!W.d_tile) {
-    const std::vector<float> &t = poisson_tile::tile();
-    if (W.d_tile.alloc(t.size()) != hipSuccess) return fail(c, MPMHIP_ENOMEM, "seed_particles: device allocation of the tile failed");
-    W.n_tile = (uint32_t)(t.size() / 3);
-    HIPCHK(c, hipMemcpyAsync(W.d_tile, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice, c->stream));
+    const std::vector<float> &t = poisson_tile::tile<D>();
+    if (W.d_tile.alloc(t.size()) != hipSuccess) return seed_fail<A>(c, MPMHIP_ENOMEM, "seed_particles: device allocation of the tile failed");
+    W.n_tile = (uint32_t)(t.size() / D);
+    SEED_HIP(hipMemcpyAsync(W.d_tile, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice, c->stream));
   }
-  if (!W.d_box) HIPCHK(c, W.d_box.alloc(8));
+  if (!W.d_box) SEED_HIP(W.d_box.alloc(2 * D + 2));
 
-  SeedParams S;
+  SeedParams<D> S;
   memset(&S, 0, sizeof S);
-  for (int k = 0; k < 3; k++) S.res[k] = c->P.res[k];
+  uint64_t cells = 1;
+  for (int k = 0; k < D; k++) { S.res[k] = c->P.res[k]; cells *= (uint64_t)S.res[k]; }
   S.dx = c->P.dx; S.idx = c->P.idx;
   // ---- get ready: the box of the cell centres inside the region
-  int box[8] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1, 0, 0};
-  HIPCHK(c, hipMemcpyAsync(W.d_box, box, sizeof box, hipMemcpyHostToDevice, c->stream));
-  const uint64_t cells = (uint64_t)S.res[0] * (uint64_t)S.res[1] * (uint64_t)S.res[2];
-  const uint32_t bounds_wgs = (uint32_t)std::min<uint64_t>((cells + SEED_WG - 1) / SEED_WG, (uint64_t)c->n_cus * 32u);
-  hipLaunchKernelGGL(k_seed_bounds, dim3(bounds_wgs), dim3(SEED_WG), 0, c->stream, R, S, W.d_box.get());
-  if (int rc = launch_check(c, "seed_bounds")) return rc;
-  HIPCHK(c, hipMemcpyAsync(box, W.d_box, sizeof box, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (box[3] < 0) return fail(c, MPMHIP_EINVAL, "seed_particles: region is empty (no cell centre of the grid lies inside it)");
-  seed_get_ready(c, d, box, S);
-  const uint64_t n_rep = (uint64_t)S.nrep[0] * (uint64_t)S.nrep[1] * (uint64_t)S.nrep[2];
-  const uint64_t n_cand = n_rep * W.n_tile;
-  if (n_cand > (1ull << 31))
-    return fail(c, MPMHIP_EINVAL, "seed_particles: more than 2^31 candidates (%u tile points x %llu replicas): lower ppc or seed the region in parts",
-                W.n_tile, (unsigned long long)n_rep);
+  int box[2 * D + 2] = {};  // min per axis, max per axis, the survivors' count, a pad
+  for (int k = 0; k < D; k++) { box[k] = 0x7fffffff; box[D + k] = -1; }
+  SEED_HIP(hipMemcpyAsync(W.d_box, box, sizeof box, hipMemcpyHostToDevice, c->stream));
+  const uint32_t bounds_wgs = (uint32_t)std::min<uint64_t>((cells + SEED_WG - 1) / SEED_WG, A::max_bounds_wgs(c));
+  hipLaunchKernelGGL((k_seed_bounds<D, typename A::Region>), dim3(bounds_wgs), dim3(SEED_WG), 0, c->stream, R, S, W.d_box.get());
+  SEED_LAUNCHED("seed_bounds");
+  SEED_HIP(hipMemcpyAsync(box, W.d_box, sizeof box, hipMemcpyDeviceToHost, c->stream));
+  SEED_HIP(hipStreamSynchronize(c->stream));
+  if (box[D] < 0) SEED_FAIL("seed_particles: region is empty (no cell centre of the grid lies inside it)");
+  float nrep[D];
+  const double n_rep = seed_get_ready<A>(c, d->ppc, box, S, nrep);
+  const double n_cand = n_rep * (double)W.n_tile;
+  if (!(n_cand <= 2147483648.0))
+    SEED_FAIL("seed_particles: more than 2^31 candidates (%u tile points x %.0f replicas): lower ppc or seed the region in parts", W.n_tile, n_rep);
+  for (int k = 0; k < D; k++) S.nrep[k] = (uint32_t)nrep[k];
   S.n_rep = (uint32_t)n_rep; S.n_tile = W.n_tile; S.n_cand = (uint32_t)n_cand;
   S.source = d->source != 0;
-  const GroupParams &G = c->groups[group];
-  const int mat = G.type;
-  for (int k = 0; k < 3; k++) {
+  const int mat = c->groups[group].type;
+  for (int k = 0; k < D; k++) {
     S.velocity[k] = d->velocity[k];
     if (S.source) {  // src/mpm.cpp:222-227
       const float dt = d->source_delta_t;
       S.offset[k] = d->velocity[k] * c->t;
       const float a = d->velocity[k] * dt, b = 0.5f * c->P.g[k];
-      const float e = b * (dt + c->P.dt);
+      const float e = b * (dt + A::base_dt(c));
       S.advection[k] = a + e * dt;
     }
   }
   S.dg = d->initial_dg;
-  S.aux = (mat == MPMHIP_SNOW || mat == MPMHIP_WATER) ? 1.0f : (mat == MPMHIP_VISCO ? 1000.0f : 0.0f);  // as mpmhip_add_particles
-  S.mass = G.p[0];
-  S.gid = (uint32_t)group;
+  S.aux = (mat == MPMHIP_SNOW || mat == MPMHIP_WATER) ? 1.0f : (mat == MPMHIP_VISCO ? 1000.0f : 0.0f);  // as the ctx's add_particles
+  S.gid = group;
   S.pid0 = c->next_pid;
   // ---- count + scan
-  const uint32_t wgs = (uint32_t)((n_cand + SEED_PER_WG - 1) / SEED_PER_WG);
+  const uint32_t wgs = (uint32_t)(((uint64_t)S.n_cand + SEED_PER_WG - 1) / SEED_PER_WG);
   if (wgs > W.wg_cap || !W.d_words) {
     W.wg_cap = 0;
     if (W.d_words.alloc((size_t)wgs * SEED_WORDS) != hipSuccess || W.d_totals.alloc(wgs) != hipSuccess)
-      return fail(c, MPMHIP_ENOMEM, "seed_particles: device allocation for %llu candidates failed", (unsigned long long)n_cand);
+      return seed_fail<A>(c, MPMHIP_ENOMEM, "seed_particles: device allocation for %u candidates failed", S.n_cand);
     W.wg_cap = wgs;
   }
-  uint32_t *d_total = reinterpret_cast<uint32_t *>(W.d_box + 6);
-  hipLaunchKernelGGL(k_seed_count, dim3(wgs), dim3(SEED_WG), 0, c->stream, R, S, (const float *)W.d_tile, W.d_words.get(), W.d_totals.get());
+  uint32_t *d_total = reinterpret_cast<uint32_t *>(W.d_box + 2 * D);
+  hipLaunchKernelGGL((k_seed_count<D, typename A::Region>), dim3(wgs), dim3(SEED_WG), 0, c->stream, R, S, (const float *)W.d_tile,
+                     W.d_words.get(), W.d_totals.get());
   hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(SEED_SCAN_WG), 0, c->stream, W.d_totals.get(), wgs, d_total);
-  if (int rc = launch_check(c, "seed_count")) return rc;
+  SEED_LAUNCHED("seed_count");
   uint32_t total = 0;
-  HIPCHK(c, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  SEED_HIP(hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
+  SEED_HIP(hipStreamSynchronize(c->stream));
   const int64_t n = (int64_t)total;
   if (n_added) *n_added = n;
   if (n == 0) return MPMHIP_OK;
-  if (int rc = async_drop_view(c)) return rc;  // (resident async stepper: records that only mirror the pools go first)
-  if (c->n_slots + n > c->cap)
-    return fail(c, MPMHIP_ECAPACITY, "particle capacity exceeded: %lld + %lld > %lld", (long long)c->n_slots, (long long)n, (long long)c->cap);
-  if ((int64_t)c->next_pid + n > 0x7fffffffll) return fail(c, MPMHIP_ECAPACITY, "seed_particles: creation ids exceed 2^31");
-  if (int rc = ensure_b_current(c)) return rc;  // A of every particle is recomputed from apic_b
-  // ---- write the records
-  hipLaunchKernelGGL(k_seed_write, dim3(wgs), dim3(SEED_WG), 0, c->stream, S, (const float *)W.d_tile, (const unsigned long long *)W.d_words,
-                     (const uint32_t *)W.d_totals, reinterpret_cast<float4 *>(c->rg + c->n_slots), reinterpret_cast<float4 *>(c->rp + c->n_slots),
-                     reinterpret_cast<float4 *>(c->rb + (size_t)c->n_slots * BW));
-  if (int rc = launch_check(c, "seed_write")) return rc;
-  c->next_pid += (int32_t)n;
-  set_slots(c, c->n_slots + n);
-  return clear_block_flags(c, c->rec.particles_appended());
+  // ---- the ctx's checks, then the survivors go to its sink
+  return A::commit(c, group, n, [&](auto sink) {
+    hipLaunchKernelGGL((k_seed_write<D, decltype(sink)>), dim3(wgs), dim3(SEED_WG), 0, c->stream, S, (const float *)W.d_tile,
+                       (const unsigned long long *)W.d_words, (const uint32_t *)W.d_totals, sink);
+    SEED_LAUNCHED("seed_write");
+    return (int)MPMHIP_OK;
+  });
 }
+
+#undef SEED_FAIL
+#undef SEED_HIP
+#undef SEED_LAUNCHED
 #undef SEED_NO_CONTRACT
+
+}  // namespace
+}  // extern "C++"
+
+int64_t mpmhip_poisson_tile(float *out, int64_t capacity) { return seed_tile_out<3>(out, capacity); }
+int64_t mpmhip2d_poisson_tile(float *out, int64_t capacity) { return seed_tile_out<2>(out, capacity); }
+
+int mpmhip_seed_particles(mpmhip_ctx *c, int32_t group, const mpmhip_seed_desc *d, int64_t *n_added) {
+  return seed_particles<Seed3>(c, group, d, n_added);
+}
+int mpmhip2d_seed_particles(mpmhip2d_ctx *m, int32_t group, const mpmhip2d_seed_desc *d, int64_t *n_added) {
+  return seed_particles<Seed2>(m, group, d, n_added);
+}

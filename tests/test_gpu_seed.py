@@ -271,6 +271,13 @@ def test_refusals(tm, centre_sphere):
     d.ppc = PPC
     with pytest.raises(MPMError, match="unknown group 99"):
         sim._check(sim._L.mpmhip_seed_particles(sim._ctx, 99, C.byref(d), C.byref(n)))
+    # min_distance 9e-5 dx and 9e-11 dx: 26 dx / (40 min_distance) = 7e3 and 7e9 replicas per axis, the latter more than an int holds
+    for ppc in (1e12, 1e30):
+        d.ppc = ppc
+        with pytest.raises(MPMError, match=r"more than 2\^31 candidates"):
+            sim._check(sim._L.mpmhip_seed_particles(sim._ctx, 0, C.byref(d), C.byref(n)))
+        assert sim.get_num_particles() == 0
+    d.ppc = PPC
     sim.add_particles(dict(type="sand", region=sls, ppc=PPC))  # (a substep needs particles)
     count = sim.get_num_particles()
     sim._check(sim._L.mpmhip_substep_begin(sim._ctx))

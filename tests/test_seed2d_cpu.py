@@ -1,8 +1,9 @@
-"""The periodic blue-noise tile behind mpmhip2d_seed_particles (taichi_mpm_amd/csrc/poisson_tile2d.h) compiled for the host by g++
+"""The periodic blue-noise tile behind mpmhip2d_seed_particles (taichi_mpm_amd/csrc/poisson_tile.h) compiled for the host by g++
 (tests/cpp/poisson_tile2d_host.cpp: the header alone), the numpy model of the seeding call (tests/seed2d_model.py) on top of it,
 and SampledLevelSet2D.from_polygon.  No GPU needed; tests/test_gpu_seed2d.py compares the device with the model and takes its
 setup (RES, DX, PPC, the shape cases) from here."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -11,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "poisson_tile2d_host.cpp")
-HDR = os.path.join(ROOT, "taichi_mpm_amd", "csrc", "poisson_tile2d.h")
+HDR = os.path.join(ROOT, "taichi_mpm_amd", "csrc", "poisson_tile.h")
 OUT = os.path.join(ROOT, "tests", "cpp", "_build", "libpoisson_tile2d_host.so")
 
 # the setup of the 2D seeding tests: the tile is 40 * sqrt(1 / 6) dx = 16.33 dx wide
@@ -56,6 +57,13 @@ def tile():
 def test_two_generations_give_identical_bytes(tile):
     again = generate()
     assert again.shape == tile.shape and again.tobytes() == tile.tobytes()
+
+
+def test_tile_bytes_are_pinned(tile):
+    """the count and the SHA-256 of the fp32 array as handed out (C order).  The other tests compare two builds of the same header, so
+    a change of the generator would pass them; with the test below this pins the library's tile too"""
+    assert tile.shape == (997, 2) and tile.dtype == np.float32 and tile.nbytes == 7976
+    assert hashlib.sha256(tile.tobytes()).hexdigest() == "47ace1b1a365480c6351a2bce059bb4f2a2a8a86a29b5c712325ad84107c2714"
 
 
 def test_the_library_hands_out_the_same_tile(tile):

@@ -2,6 +2,7 @@
 (tests/cpp/poisson_tile_host.cpp: the header alone), and the numpy model of the seeding call (tests/seed_model.py) on top of it.
 No GPU needed; tests/test_gpu_seed.py compares the device with the model."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -40,6 +41,13 @@ def tile():
 def test_two_generations_give_identical_bytes(tile):
     again = generate()
     assert again.shape == tile.shape and again.tobytes() == tile.tobytes()
+
+
+def test_tile_bytes_are_pinned(tile):
+    """the count and the SHA-256 of the fp32 array as handed out (C order).  The other tests compare two builds of the same header, so
+    a change of the generator would pass them; with the test below this pins the library's tile too"""
+    assert tile.shape == (37177, 3) and tile.dtype == np.float32 and tile.nbytes == 446124
+    assert hashlib.sha256(tile.tobytes()).hexdigest() == "154d40d1172514708b2c3e5d94313f763577e149d1301a1e664f72f895f81bd2"
 
 
 def test_the_library_hands_out_the_same_tile(tile):
