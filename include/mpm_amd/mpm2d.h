@@ -87,6 +87,26 @@ class MPM<2> {
   void set_levelset(real t0, real t1, const std::vector<mpmhip_shape> &shapes0, const std::vector<mpmhip_shape> &shapes1, real friction) {
     check(mpmhip2d_set_levelset(ctx_, (int32_t)shapes0.size(), shapes0.data(), (int32_t)shapes1.size(), shapes1.data(), t0, t1, friction), ctx_);
   }
+  // sampled level set in the plane (include/mpmhip.h: mpmhip2d_set_levelset_sdf): phi holds res[0] * res[1] values, the last axis
+  // fastest, world units, negative inside the solid.  It replaces the shapes.
+  void set_levelset_sdf(const VectorI &lattice_res, const Vector &origin, real spacing, const std::vector<float> &phi, real friction) {
+    set_levelset_sdf(lattice_res, origin, spacing, 0.0f, 1.0f, phi, std::vector<float>(), friction);
+  }
+  // ... two key frames of one lattice, blended like the shapes' key frames above (phi1 empty: static)
+  void set_levelset_sdf(const VectorI &lattice_res, const Vector &origin, real spacing, real t0, real t1, const std::vector<float> &phi0,
+                        const std::vector<float> &phi1, real friction) {
+    mpmhip2d_sdf_desc d;
+    size_t count = 1;
+    for (int k = 0; k < 2; k++) {
+      d.res[k] = lattice_res[k];
+      d.origin[k] = origin[k];
+      count *= (size_t)(lattice_res[k] > 0 ? lattice_res[k] : 0);
+    }
+    d.spacing = spacing;
+    if (phi0.size() != count || (!phi1.empty() && phi1.size() != count))
+      throw std::runtime_error("set_levelset_sdf: the arrays must hold res[0] * res[1] samples");
+    check(mpmhip2d_set_levelset_sdf(ctx_, &d, phi0.data(), phi1.empty() ? nullptr : phi1.data(), t0, t1, friction), ctx_);
+  }
 
   // --- MPM<2>::add_particles (src/mpm.cpp:77-270): a lattice "square_lo" / "square_hi" in cells (4 particles per cell at the
   // +-0.25 dx points), or explicit positions through the overload
@@ -236,8 +256,8 @@ class MPM<2> {
     return frame_directory + name;
   }
   void visualize() { write_bgeo(); }
-  // --- MPM<2>::general_action (src/mpm.cpp:920-978): add_articulation, save / load (whole-state snapshot to / from "file_name";
-  // the scene — level set, configuration, the rigid bodies — is set up again before a load, as in the reference)
+  // --- MPM<2>::general_action (src/mpm.cpp:920-978): add_articulation, delete_particles_inside_level_set, save / load (whole-state
+  // snapshot to / from "file_name"; the scene — level set, configuration, the rigid bodies — is set up again before a load, as in the reference)
   std::string general_action(const Config &config) {
     const std::string action = config.get("action", "");
     if (action == "add_articulation") return add_articulation(config);
@@ -261,6 +281,11 @@ class MPM<2> {
         std::fclose(f);
         check(mpmhip2d_snapshot_load(ctx_, buf.data(), buf.size()), ctx_);
       }
+      return "";
+    }
+    if (action == "delete_particles_inside_level_set") {  // :962-974
+      int64_t deleted = 0;
+      check(mpmhip2d_delete_particles_inside_level_set(ctx_, &deleted), ctx_);
       return "";
     }
     throw std::runtime_error("general_action(action='" + action + "') is outside the scope of this build");

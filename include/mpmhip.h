@@ -185,10 +185,10 @@ int mpmhip_set_levelset_keyframes(mpmhip_ctx *ctx, float t0, float t1, int32_t n
  * One level set at a time: a sampled set replaces the shapes and shapes replace a sampled set.  friction as above;
  * particle_collision and mpmhip_delete_particles_inside_level_set work with it.  A call with the lattice size of the installed set
  * reuses the device memory (the per-frame update of a dynamic level set allocates nothing).
- * Out of scope: a sampled BOUNDARY for the 2D solver (mpmhip2d_set_levelset takes shapes only; a sampled field fills a 2D
- * region with particles: mpmhip2d_seed_particles), the reference's add_slope, open or self-intersecting
- * meshes (closed triangle meshes are voxelised on the device: mpmhip_set_levelset_mesh below), and
- * rigid_body_levelset_collision with a sampled set (refused with MPMHIP_EINVAL, here and in mpmhip_set_rigid_levelset_collision).
+ * The 2D solver takes a sampled boundary through mpmhip2d_set_levelset_sdf (below, the same rules with one axis fewer).
+ * Out of scope: the reference's add_slope, open or self-intersecting meshes (closed triangle meshes are voxelised on the device:
+ * mpmhip_set_levelset_mesh below; there is no mesh or outline voxeliser for 2D), and rigid_body_levelset_collision with a sampled
+ * set (refused with MPMHIP_EINVAL, here and in mpmhip_set_rigid_levelset_collision; the 2D calls refuse it alike).
  * Tiled jobs and the asynchronous stepper go through the same per-ctx call and substep; they are not tested with it. */
 typedef struct {
   int32_t res[3];
@@ -727,8 +727,9 @@ int mpmhip2d_download_grid(mpmhip2d_ctx *ctx, float *grid /* [(res0+1)(res1+1)][
  * a finite number > 0, or phi == NULL; an empty region; more than 2^31 candidates; creation ids past 2^31; a resident asynchronous
  * stepper (seed before mpmhip2d_async_begin).  The call synchronises the ctx's stream twice for a few words each; its work
  * buffers belong to the ctx, only grow, and go with mpmhip2d_destroy.
- * Out of scope: a sampled level set as the 2D BOUNDARY (mpmhip2d_set_levelset takes shapes only), pd_packed, non-uniform
- * densities, pd = False, point_cloud.
+ * The same array serves as the 2D BOUNDARY through mpmhip2d_set_levelset_sdf below, which decides phi < 0 as this call does.
+ * Out of scope: pd_packed, non-uniform densities, pd = False, point_cloud; for the boundary: add_slope,
+ * rigid_body_levelset_collision with a sampled set, a mesh voxeliser for 2D.
  *
  * mpmhip2d_reserve: the particle arrays hold at least `capacity` particles afterwards (mpmhip2d_config.max_particles of a live
  * ctx); their contents, the clocks, bodies and groups stay.  MPMHIP_OK at once when the capacity already suffices.
@@ -754,6 +755,43 @@ int64_t mpmhip2d_poisson_tile(float *out, int64_t capacity);
 int mpmhip2d_seed_particles(mpmhip2d_ctx *ctx, int32_t group, const mpmhip2d_seed_desc *desc, int64_t *n_added);
 int mpmhip2d_reserve(mpmhip2d_ctx *ctx, int64_t capacity);
 int64_t mpmhip2d_num_slots(mpmhip2d_ctx *ctx);
+int64_t mpmhip2d_capacity(mpmhip2d_ctx *ctx); /* particles the arrays hold now: mpmhip2d_reserve may give more than it was asked for */
+
+/* Sampled level set as the boundary of the 2D solver — mpmhip_set_levelset_sdf with one axis fewer:
+ *   lattice   res[k] >= 2 samples per axis, sample (0, 0) at `origin`, one `spacing` > 0 (world units, independent of the
+ *             simulation's delta_x); arrays in C order [i][j] (j fastest), fp32, WORLD units, negative inside the solid.  The ctx
+ *             keeps its own device copy (4 res[0] res[1] bytes per key frame).
+ *   phi       u = (x - origin) * fl(1 / spacing); cell c = clamp((int)u, 0, res - 2), f = u - c; bilinear in that cell,
+ *             lerp(a, b, f) = (1 - f) a + f b along the LAST axis first, then the first — the order of the seeding's sampled
+ *             region (mpmhip2d_seed_particles) — returned in grid units (times fl(1 / delta_x)).  A point outside
+ *             [origin, origin + (res - 1) spacing] on either axis has NO level set there: nothing is extrapolated.
+ *   gradient  per sample the central difference (phi[+1] - phi[-1]) * (0.5 / spacing), one-sided (weight 1 / spacing) on the array's
+ *             edges; the four samples' gradients interpolated like phi, normalised; a length below 1e-10 gives the zero vector.
+ *   phi1      NULL: static.  Else a second key frame on the same lattice, blended as in 3D: a = (t - t0) / (t1 - t0),
+ *             phi = (1 - a) phi0 + a phi1, the normal is the normalised lerp of the two unit gradients,
+ *             d phi / dt = (phi1 - phi0) / (t1 - t0); the grid pass forms the boundary velocity -d phi / dt n delta_x from it.
+ *   no contraction   no multiply-add of the sampler is fused: every kernel that inlines it gives the same bits for the same point,
+ *             and for one array `phi < 0` here and the seeding's "inside" decide identically at every point (a scene seeds a region
+ *             and bounds by its complement).  tests/sdf2d_model.py restates the sampler in numpy.
+ * Readers: the grid boundary condition (band -3 <= phi <= 0), particle_collision behind G2P (default and deterministic mode; the
+ * asynchronous stepper and the CPIC coupling run the same substep), mpmhip2d_delete_particles_inside_level_set.
+ * One level set at a time, in both directions: a sampled set replaces the shapes; mpmhip2d_set_levelset replaces a sampled set and
+ * frees its arrays.  A call with the installed lattice's size reuses the device memory (the per-frame update of a dynamic set
+ * allocates nothing); a static set after a dynamic one frees the second frame.  mpmhip2d_delete_particles_inside_level_set is refused
+ * on a resident asynchronous stepper.  MPMHIP_EINVAL with a message: desc or phi0 NULL, res[k] < 2, a non-finite origin, a spacing that is not a
+ * finite number > 0, more than 2^31 samples, t1 <= t0 with two frames, rigid_body_levelset_collision (refused in either order of
+ * the two calls: that pass keeps reading shapes).  The 2D substep is one host call that only enqueues work, so there is no "inside
+ * a substep" state to refuse; the call waits for the ctx's stream before it touches the arrays.
+ * Out of scope: add_slope, rigid_body_levelset_collision with a sampled set, a mesh voxeliser for 2D. */
+int mpmhip2d_set_levelset_sdf(mpmhip2d_ctx *ctx, const mpmhip2d_sdf_desc *desc, const float *phi0, const float *phi1 /* NULL = static */,
+                              float t0, float t1, float friction);
+/* general_action "delete_particles_inside_level_set" of MPM<2> (src/mpm.cpp:962-974): deletes every live particle whose level-set
+ * value (shapes or a sampled set, at the ctx's current time) at its position is negative; *deleted = their number */
+int mpmhip2d_delete_particles_inside_level_set(mpmhip2d_ctx *ctx, int64_t *deleted);
+/* the DEVICE's evaluation of the installed 2D level set (sampled or shapes) at n host-given points at time t: phi [n] in grid
+ * units, grad [n][2] the unit gradient, dphidt [n], hit [n] = 0 where there is no level set (then the rest is 0) */
+int mpmhip2d_debug_levelset_sample(mpmhip2d_ctx *ctx, int64_t n, const float *pos /* [n][2] */, float t, float *phi, float *grad,
+                                   float *dphidt, int32_t *hit);
 
 /* frame output of the 2D simulation — replaces MPM<2>::write_partio (src/visualize.cpp:17-100): the same .bgeo as the 3D
  * entry points above (z = 0), boundary particles of rigid bodies as rows of type 1; with a resident asynchronous stepper the rows

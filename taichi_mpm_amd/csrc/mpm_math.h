@@ -974,6 +974,92 @@ __device__ __forceinline__ void friction_project_exact(float v[3], const float v
   v[1] = ts * t1 + keep * n[1] + vb[1];
   v[2] = ts * t2 + keep * n[2] + vb[2];
 }
+
+// ---- the sampled level set in the plane (mpmhip2d_set_levelset_sdf): the rules above with one axis fewer.  The set is an SdfDev
+// whose res[2] is 1 and whose third origin / off entries are unused: phi [res0][res1], the last axis fastest.  Bilinear, the last
+// axis first — the order of SeedRegion2::inside_sdf (k_seed.h), so the seeding and the boundary decide phi < 0 identically for one
+// array (the grid-unit factor idx > 0 keeps the sign).
+__device__ __forceinline__ float sdf2_at(const SdfDev &S, const float *__restrict__ p, int i, int j) {
+  return p[(size_t)i * S.res[1] + j];
+}
+__device__ __forceinline__ void sdf2_sample_grad(const SdfDev &S, const float *__restrict__ p, int i, int j, float g[2]) {
+  SDF_NO_CONTRACT
+  const int im = max(i - 1, 0), ip = min(i + 1, S.res[0] - 1), jm = max(j - 1, 0), jp = min(j + 1, S.res[1] - 1);
+  g[0] = (sdf2_at(S, p, ip, j) - sdf2_at(S, p, im, j)) * ((ip - im == 2 ? 0.5f : 1.0f) * S.inv_spacing);
+  g[1] = (sdf2_at(S, p, i, jp) - sdf2_at(S, p, i, jm)) * ((jp - jm == 2 ? 0.5f : 1.0f) * S.inv_spacing);
+}
+__device__ __forceinline__ bool sdf2_locate(const SdfDev &S, const float x[2], int c[2], float f[2]) {
+  SDF_NO_CONTRACT
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const float u = (x[k] - S.origin[k]) * S.inv_spacing;
+    in = in && u >= 0.0f && u <= (float)(S.res[k] - 1);  // (false for a NaN)
+    c[k] = min(max((int)u, 0), S.res[k] - 2);
+    f[k] = u - (float)c[k];
+  }
+  return in;
+}
+__device__ __forceinline__ float sdf2_phi_frame(const SdfDev &S, const float *__restrict__ p, const int c[2], const float f[2]) {
+  SDF_NO_CONTRACT
+  const float a = sdf_lerp(sdf2_at(S, p, c[0], c[1]), sdf2_at(S, p, c[0], c[1] + 1), f[1]);
+  const float b = sdf_lerp(sdf2_at(S, p, c[0] + 1, c[1]), sdf2_at(S, p, c[0] + 1, c[1] + 1), f[1]);
+  return sdf_lerp(a, b, f[0]);
+}
+__device__ __forceinline__ void sdf2_normalize(float g[2]) {
+  SDF_NO_CONTRACT
+  const float len = sqrtf(g[0] * g[0] + g[1] * g[1]);
+  const float inv = len < 1e-10f ? 0.0f : 1.0f / len;
+  g[0] *= inv; g[1] *= inv;
+}
+// unit gradient of one key frame: the four samples' central-difference gradients interpolated like phi, then normalised
+__device__ __forceinline__ void sdf2_grad_frame(const SdfDev &S, const float *__restrict__ p, const int c[2], const float f[2],
+                                                float n[2]) {
+  SDF_NO_CONTRACT
+  float a[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    float g0[2], g1[2];
+    sdf2_sample_grad(S, p, c[0] + i, c[1], g0);
+    sdf2_sample_grad(S, p, c[0] + i, c[1] + 1, g1);
+#pragma unroll
+    for (int d = 0; d < 2; d++) a[i][d] = sdf_lerp(g0[d], g1[d], f[1]);
+  }
+#pragma unroll
+  for (int d = 0; d < 2; d++) n[d] = sdf_lerp(a[0][d], a[1][d], f[0]);
+  sdf2_normalize(n);
+}
+// phi (grid units) in the located cell, and the unit normal there; two key frames blend as sdf_blend_phi / sdf_blend_normal do
+__device__ __forceinline__ float sdf2_phi(const SdfDev &S, float t, float idx, const int c[2], const float f[2],
+                                          float *dphidt = nullptr) {
+  SDF_NO_CONTRACT
+  if (dphidt) *dphidt = 0.0f;
+  const float p0 = sdf2_phi_frame(S, S.phi0, c, f);
+  if (!S.phi1) return p0 * idx;
+  return sdf_blend_phi(S, t, idx, p0, sdf2_phi_frame(S, S.phi1, c, f), dphidt);
+}
+__device__ __forceinline__ void sdf2_normal(const SdfDev &S, float t, const int c[2], const float f[2], float n[2]) {
+  SDF_NO_CONTRACT
+  sdf2_grad_frame(S, S.phi0, c, f, n);
+  if (!S.phi1) return;
+  float n1[2];
+  sdf2_grad_frame(S, S.phi1, c, f, n1);
+  const float a = (t - S.t0) / (S.t1 - S.t0);
+#pragma unroll
+  for (int d = 0; d < 2; d++) n[d] = n[d] * (1.0f - a) + n1[d] * a;
+  sdf2_normalize(n);
+}
+__device__ __forceinline__ bool sdf2_eval(const SdfDev &S, float t, const float x[2], float idx, float &phi, float n[2],
+                                          float *dphidt = nullptr) {
+  SDF_NO_CONTRACT
+  if (dphidt) *dphidt = 0.0f;
+  int c[2];
+  float f[2];
+  if (!sdf2_locate(S, x, c, f)) return false;
+  phi = sdf2_phi(S, t, idx, c, f, dphidt);
+  sdf2_normal(S, t, c, f, n);
+  return true;
+}
 #undef SDF_NO_CONTRACT
 // whichever level set is installed
 __device__ __forceinline__ bool levelset_eval_any(const LevelSetDev &L, float t, const float x[3], float idx, float &phi,

@@ -102,6 +102,7 @@
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
 #include "k_mpm2d_det.h"
+#include "k_sdf2d.h"
 #include "k_async2d.h"
 
 
@@ -2716,6 +2717,10 @@ int mpmhip_debug_allowed_dt(mpmhip_ctx *c, int32_t material, const float params[
 struct mpmhip2d_ctx {
   mpm2d::Params P{};
   LevelSetDev LS{};
+  // sampled level set (mpmhip2d_set_levelset_sdf): this ctx's device copies of the key frames, [sdf_count] floats each; LS.sdf
+  // points at them (res[2] = 1) while the set is installed, and then LS.n == 0
+  DevBuf<float> d_sdf[2];
+  size_t sdf_count = 0;
   int device = 0;
   int64_t n = 0, cap = 0;
   DevBuf<float> x, v, F, B, aux, grid;
@@ -2860,6 +2865,8 @@ int mpmhip2d_set_levelset(mpmhip2d_ctx *m, int32_t n0, const mpmhip_shape *shape
   HIPCHK2D(m, hipSetDevice(m->device));
   HIPCHK2D(m, hipStreamSynchronize(m->stream));
   LevelSetDev &L = m->LS;
+  m->d_sdf[0].reset(); m->d_sdf[1].reset();  // shapes replace a sampled set: nothing of it survives
+  m->sdf_count = 0;
   memset(&L, 0, sizeof L);
   L.n = n0; L.friction = friction; L.dynamic = n1 >= 0; L.n1 = n1 >= 0 ? n1 : 0; L.t0 = t0; L.t1 = t1;
   auto put = [](ShapeDev &d, const mpmhip_shape &s) {
@@ -2871,6 +2878,89 @@ int mpmhip2d_set_levelset(mpmhip2d_ctx *m, int32_t n0, const mpmhip_shape *shape
   };
   for (int i = 0; i < n0; i++) put(L.s[i], shapes0[i]);
   for (int i = 0; i < L.n1; i++) put(L.s1[i], shapes1[i]);
+  return MPMHIP_OK;
+}
+
+// Sampled level set in the plane: see include/mpmhip.h.  The arrays are copied into device memory the ctx owns; a call with the
+// lattice size of the installed set (the per-frame update of a dynamic level set) reuses that memory.
+int mpmhip2d_set_levelset_sdf(mpmhip2d_ctx *m, const mpmhip2d_sdf_desc *d, const float *phi0, const float *phi1, float t0, float t1,
+                              float friction) {
+  if (!m) return MPMHIP_EINVAL;
+  if (!d || !phi0) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: the lattice description and the first key frame are required");
+  size_t count = 1;
+  for (int k = 0; k < 2; k++) {
+    if (d->res[k] < 2)
+      return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: res[" + std::to_string(k) + "] = " + std::to_string(d->res[k]) + ", at least 2 samples per axis are needed");
+    if (!std::isfinite(d->origin[k])) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: origin[" + std::to_string(k) + "] is not finite");
+    count *= (size_t)d->res[k];
+  }
+  if (!(d->spacing > 0.0f) || !std::isfinite(d->spacing)) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: spacing must be a finite number > 0");
+  if (count > ((size_t)1 << 31)) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: more than 2^31 samples");
+  if (phi1 && !(t1 > t0)) return fail2d(m, MPMHIP_EINVAL, "key frame times must satisfy t0 < t1");
+  if (m->ls_collision) return fail2d(m, MPMHIP_EINVAL, "rigid_body_levelset_collision is not supported with a sampled level set");
+  HIPCHK2D(m, hipSetDevice(m->device));
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));  // (kernels in flight read the arrays)
+  LevelSetDev &L = m->LS;
+  if (count != m->sdf_count) {
+    m->d_sdf[0].reset(); m->d_sdf[1].reset();
+    m->sdf_count = 0;
+    memset(&L.sdf, 0, sizeof L.sdf);
+    HIPCHK2D(m, m->d_sdf[0].alloc(count));
+    m->sdf_count = count;
+  }
+  if (phi1 && !m->d_sdf[1]) HIPCHK2D(m, m->d_sdf[1].alloc(count));
+  if (!phi1) m->d_sdf[1].reset();  // a static set keeps no second frame (a dynamic set's per-frame update always brings two)
+  HIPCHK2D(m, hipMemcpy(m->d_sdf[0], phi0, sizeof(float) * count, hipMemcpyHostToDevice));
+  if (phi1) HIPCHK2D(m, hipMemcpy(m->d_sdf[1], phi1, sizeof(float) * count, hipMemcpyHostToDevice));
+  const int dirichlet = L.dirichlet, pc = L.particle_collision;
+  memset(&L, 0, sizeof L);  // the sampled set replaces the shapes
+  L.dirichlet = dirichlet; L.particle_collision = pc;
+  L.friction = friction;
+  SdfDev &S = L.sdf;
+  S.phi0 = m->d_sdf[0];
+  S.phi1 = phi1 ? m->d_sdf[1].get() : nullptr;
+  S.res[0] = d->res[0]; S.res[1] = d->res[1]; S.res[2] = 1;
+  S.origin[0] = d->origin[0]; S.origin[1] = d->origin[1];
+  S.spacing = d->spacing; S.inv_spacing = 1.0f / d->spacing;
+  S.t0 = phi1 ? t0 : 0.0f; S.t1 = phi1 ? t1 : 1.0f;
+  return MPMHIP_OK;
+}
+
+// the device's level-set evaluation at host-given points (tests)
+int mpmhip2d_debug_levelset_sample(mpmhip2d_ctx *m, int64_t n, const float *pos, float t, float *phi, float *grad, float *dphidt,
+                                   int32_t *hit) {
+  if (!m || n <= 0 || !pos || !phi || !grad || !dphidt || !hit) return MPMHIP_EINVAL;
+  HIPCHK2D(m, hipSetDevice(m->device));
+  DevBuf<float> dP, dO;
+  HIPCHK2D(m, dP.alloc(2 * (size_t)n));
+  HIPCHK2D(m, dO.alloc(5 * (size_t)n));
+  HIPCHK2D(m, hipMemcpyAsync(dP, pos, sizeof(float) * 2 * n, hipMemcpyHostToDevice, m->stream));
+  hipLaunchKernelGGL(mpm2d::k2_debug_levelset_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, m->LS, t, m->P.idx, n,
+                     (const float *)dP, dO.get(), dO + n, dO + 3 * n, reinterpret_cast<int32_t *>(dO + 4 * n));
+  HIPCHK2D(m, hipGetLastError());
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  HIPCHK2D(m, hipMemcpy(phi, dO, sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIPCHK2D(m, hipMemcpy(grad, dO + n, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
+  HIPCHK2D(m, hipMemcpy(dphidt, dO + 3 * n, sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIPCHK2D(m, hipMemcpy(hit, dO + 4 * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return MPMHIP_OK;
+}
+
+int mpmhip2d_delete_particles_inside_level_set(mpmhip2d_ctx *m, int64_t *deleted) {
+  if (!m || !deleted) return MPMHIP_EINVAL;
+  *deleted = 0;
+  if (m->async.resident) return fail2d(m, MPMHIP_EINVAL, "delete_particles_inside_level_set: not on a resident asynchronous stepper");
+  if ((m->LS.n <= 0 && !m->LS.sdf.phi0) || m->n == 0) return MPMHIP_OK;
+  HIPCHK2D(m, hipSetDevice(m->device));
+  unsigned int before = 0, after = 0;
+  HIPCHK2D(m, hipMemcpyAsync(&before, m->n_dead, sizeof before, hipMemcpyDeviceToHost, m->stream));
+  m->P.t = m->t;
+  hipLaunchKernelGGL(mpm2d::k2_delete_inside, dim3((unsigned)((m->n + 255) / 256)), dim3(256), 0, m->stream, m->P, m->LS, m->n,
+                     (const float *)m->x, m->pid.get(), m->n_dead.get());
+  HIPCHK2D(m, hipGetLastError());
+  HIPCHK2D(m, hipMemcpyAsync(&after, m->n_dead, sizeof after, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  *deleted = (int64_t)after - (int64_t)before;
   return MPMHIP_OK;
 }
 
@@ -3146,7 +3236,9 @@ static int substep2d(mpmhip2d_ctx *m) {
   if (R.enabled && m->ls_collision) {
     if (int rc = rigid2_ls_collision(m)) return rc;
   }
-  hipLaunchKernelGGL(mpm2d::k_grid, gg, wg, 0, m->stream, m->P, m->LS, m->grid);
+  const bool sdf = m->LS.sdf.phi0 != nullptr;  // (a ctx without a sampled set launches what it always did)
+  if (sdf) hipLaunchKernelGGL(mpm2d::k_grid_sdf, gg, wg, 0, m->stream, m->P, m->LS, m->grid);
+  else hipLaunchKernelGGL(mpm2d::k_grid, gg, wg, 0, m->stream, m->P, m->LS, m->grid);
   if (det && R.enabled) {  // (without bodies k_g2p adds nothing across particles: the default launch is kept)
     hipLaunchKernelGGL(mpm2d::k2d_g2p, pg, wg, 0, m->stream, m->P, m->LS, (const uint32_t *)(m->det.start + nodes), (const uint32_t *)m->det.idx,
                        m->x, m->v, m->F, m->B, m->aux, (const int32_t *)m->gid, m->pid, (const GroupParams *)m->d_groups,
@@ -3157,6 +3249,8 @@ static int substep2d(mpmhip2d_ctx *m) {
                        m->pid, (const GroupParams *)m->d_groups, (const float *)m->grid, m->n_dead, R);
     if (R.enabled) hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->bodies.size());
   }
+  if (sdf && m->P.particle_collision && m->n)  // the push g2p_particle carries for shapes (LS.n == 0 here: it skipped it)
+    hipLaunchKernelGGL(mpm2d::k2_sdf_collide, pg, wg, 0, m->stream, m->P, m->LS.sdf, m->n, m->x.get(), m->v.get(), (const int32_t *)m->pid);
   if (R.enabled) {
     if (int rc = rigid2_advect(m)) return rc;
   }
@@ -3168,6 +3262,8 @@ static int substep2d(mpmhip2d_ctx *m) {
 // ---- CPIC rigid bodies in 2D: add_particles(type='rigid') of MPM<2> (src/mpm_rigid_body.cpp:130-252, dim = 2 branches)
 int mpmhip2d_set_rigid_levelset_collision(mpmhip2d_ctx *m, int32_t enabled) {
   if (!m) return MPMHIP_EINVAL;
+  if (enabled && m->LS.sdf.phi0)  // (k2_ls_collide reads shapes)
+    return fail2d(m, MPMHIP_EINVAL, "rigid_body_levelset_collision is not supported with a sampled level set");
   m->ls_collision = enabled != 0;
   return MPMHIP_OK;
 }

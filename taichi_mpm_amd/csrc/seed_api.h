@@ -16,6 +16,7 @@ int mpmhip2d_reserve(mpmhip2d_ctx *m, int64_t capacity) {
 }
 
 int64_t mpmhip2d_num_slots(mpmhip2d_ctx *m) { return m ? m->n : (int64_t)MPMHIP_EINVAL; }
+int64_t mpmhip2d_capacity(mpmhip2d_ctx *m) { return m ? m->cap : (int64_t)MPMHIP_EINVAL; }
 
 extern "C++" {
 namespace {

@@ -281,7 +281,8 @@ class DynamicLevelSet:
     def initialize(self, t0, t1, levelset0, levelset1):
         if not float(t1) > float(t0):
             raise MPMError("DynamicLevelSet needs t0 < t1")
-        s0, s1 = isinstance(levelset0, SampledLevelSet), isinstance(levelset1, SampledLevelSet)
+        # (a sampled key frame: a SampledLevelSet, or the 2D solver's SampledBoundary2D, which marks itself)
+        s0, s1 = (isinstance(l, SampledLevelSet) or getattr(l, "sampled_key_frame", False) for l in (levelset0, levelset1))
         m0, m1 = isinstance(levelset0, MeshLevelSet), isinstance(levelset1, MeshLevelSet)
         if m0 != m1:
             raise MPMError("DynamicLevelSet: a mesh key frame cannot be mixed with an analytic or an array key frame")
@@ -289,6 +290,8 @@ class DynamicLevelSet:
             raise MPMError("DynamicLevelSet: the two mesh key frames must share one lattice (res, origin, spacing) and band")
         if s0 != s1:
             raise MPMError("DynamicLevelSet: a sampled and an analytic key frame cannot be mixed")
+        if s0 and type(levelset0) is not type(levelset1):
+            raise MPMError("DynamicLevelSet: a 3D and a 2D sampled key frame cannot be mixed")
         if s0 and not levelset0.same_lattice(levelset1):
             raise MPMError("DynamicLevelSet: the two sampled key frames must share one lattice (res, origin, spacing)")
         self.t0, self.t1, self.levelset0, self.levelset1 = float(t0), float(t1), levelset0, levelset1
@@ -795,6 +798,9 @@ class Simulation3D:
     def set_levelset(self, levelset):
         """Simulation::set_levelset: a LevelSet, SampledLevelSet or MeshLevelSet (static) or a DynamicLevelSet (two key frames of one
         kind)"""
+        frames = (levelset.levelset0, levelset.levelset1) if isinstance(levelset, DynamicLevelSet) else (levelset,)
+        if any(getattr(l, "sampled_key_frame", False) for l in frames):
+            raise MPMError("set_levelset: a SampledBoundary2D bounds the 2D simulation; the 3D one takes a SampledLevelSet")
         self._levelset = levelset
         if self._ctx is not None:
             self._apply_levelset()

@@ -2,7 +2,8 @@
 mpmhip2d_* entry points of the C ABI (include/mpmhip.h).  Same surface as Simulation3D (taichi_mpm_amd/mpm.py) where it
 applies: `initialize`, `add_particles`, `set_levelset`, `step`, `get_current_time`, `get_particles`.  MPM<2> runs the
 generic transfer path (src/transfer.cpp:280-283,697-700).  `add_particles(region=...)` fills a LevelSet or a SampledLevelSet2D on
-the device from the periodic Poisson-disk tile (include/mpmhip.h: mpmhip2d_seed_particles)."""
+the device from the periodic Poisson-disk tile (include/mpmhip.h: mpmhip2d_seed_particles); `set_levelset` takes shapes or a
+SampledBoundary2D — a sampled field with a friction (include/mpmhip.h: mpmhip2d_set_levelset_sdf)."""
 import ctypes as C
 import os
 
@@ -10,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from .materials import MATERIAL_IDS, group_params, initial_aux
-from .mpm import DynamicLevelSet, LevelSet, MPMError, check_unsupported_keys
+from .mpm import DynamicLevelSet, LevelSet, MPMError, check_unsupported_keys, eval_shapes
 
 
 def lattice_square(lower, higher, dx):
@@ -26,7 +27,8 @@ class SampledLevelSet2D:
     """A signed-distance field sampled on a regular lattice in the plane: the region of add_particles(region=...) — a disc, a polygon,
     any free-form blob (it stands in for the reference's polygon and image textures).  `phi`: array of shape (res0, res1), world units,
     negative inside; sample (i, j) sits at origin + (i, j) * spacing.  spacing=None: the cell size of the simulation it is given to.
-    Read bilinearly; outside the lattice there is no region.  It is a region only: set_levelset does not take it."""
+    Read bilinearly; outside the lattice there is no region.  It is a region: a boundary needs a friction, which as_boundary() adds
+    (set_levelset takes the SampledBoundary2D it returns, not this)."""
 
     def __init__(self, phi, origin=(0.0, 0.0), spacing=None):
         a = np.asarray(phi)
@@ -99,6 +101,47 @@ class SampledLevelSet2D:
     def from_polygon(cls, vertices, res, origin=(0.0, 0.0), spacing=None):
         """bake the signed distance of a simple closed polygon, vertices (m, 2) in world units"""
         return cls.from_function(lambda x: cls.polygon_distance(vertices, x), res, origin, spacing)
+
+    @classmethod
+    def from_levelset(cls, ls, res, origin=(0.0, 0.0), spacing=None):
+        """bake an analytic LevelSet's shapes read in the plane (z = 0, a cuboid unbounded along z: as mpmhip2d_set_levelset reads
+        them), in float64"""
+        if not ls.shapes:
+            raise MPMError("SampledLevelSet2D.from_levelset: the LevelSet has no shapes")
+        if spacing is None:
+            spacing = ls.delta_x
+        shapes = []
+        for t_, io, p in ls.shapes:
+            p = list(p)
+            if t_ == 2:
+                p[2], p[5] = -1e30, 1e30
+            else:
+                p[2] = 0.0
+            shapes.append((t_, io, p))
+        return cls.from_function(lambda x: eval_shapes(shapes, np.concatenate([x, np.zeros((len(x), 1))], axis=1)), res, origin, spacing)
+
+    def as_boundary(self, friction=-1.0):
+        """this field as a boundary for Simulation2D.set_levelset: the same phi, origin and spacing, and a friction code"""
+        return SampledBoundary2D(self.phi, self.origin, self.spacing, friction)
+
+
+class SampledBoundary2D(SampledLevelSet2D):
+    """A sampled field as the BOUNDARY of the 2D simulation (include/mpmhip.h: mpmhip2d_set_levelset_sdf): a SampledLevelSet2D plus
+    the friction code a boundary needs (LevelSet's: -1 sticky, -2 slip, >= 0 Coulomb).  spacing=None resolves to the simulation's
+    delta_x when it is installed.  Two of one lattice make the key frames of a DynamicLevelSet."""
+
+    sampled_key_frame = True  # (DynamicLevelSet.initialize: mixes with shapes and other lattices are refused)
+
+    def __init__(self, phi, origin=(0.0, 0.0), spacing=None, friction=-1.0):
+        super().__init__(phi, origin, spacing)
+        self.friction = float(friction)
+
+    def set_friction(self, f):
+        self.friction = float(f)
+        return self
+
+    def same_lattice(self, other):
+        return self.res == other.res and self.origin == other.origin and self.spacing == other.spacing
 
 
 class Simulation2D:
@@ -316,16 +359,28 @@ class Simulation2D:
         if rc == -4:  # MPMHIP_ECAPACITY: n is what the call needs; nothing was written
             cap = max(int((int(self._L.mpmhip2d_num_slots(self._ctx)) + n.value) * 1.5), self.max_particles)
             self._check(self._L.mpmhip2d_reserve(self._ctx, cap))
-            self._capacity = max(self._capacity, cap)
+            self._capacity = int(self._L.mpmhip2d_capacity(self._ctx))  # (what the library has: it may give more than it was asked for)
             rc = self._L.mpmhip2d_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
         self._check(rc)
         self._n_added += n.value
         return ""
 
     def set_levelset(self, levelset):
-        if isinstance(levelset, SampledLevelSet2D):
-            raise MPMError("set_levelset: a SampledLevelSet2D is a region for add_particles(region=...) only; the 2D boundary takes "
-                           "a LevelSet or a DynamicLevelSet of shapes")
+        """a LevelSet (shapes), a SampledBoundary2D, or a DynamicLevelSet whose two key frames are of one of these kinds"""
+        if isinstance(levelset, SampledLevelSet2D) and not isinstance(levelset, SampledBoundary2D):
+            raise MPMError("set_levelset: a SampledLevelSet2D is a region for add_particles(region=...) only; a boundary needs a "
+                           "friction: pass region.as_boundary(friction=...)")
+        if isinstance(levelset, DynamicLevelSet):
+            s0, s1 = (isinstance(l, SampledBoundary2D) for l in (levelset.levelset0, levelset.levelset1))
+            if s0 != s1:
+                raise MPMError("set_levelset: a sampled and an analytic key frame cannot be mixed")
+            if s0 and not levelset.levelset0.same_lattice(levelset.levelset1):
+                raise MPMError("set_levelset: the two sampled key frames must share one lattice (res, origin, spacing)")
+            if not s0 and not all(isinstance(l, LevelSet) for l in (levelset.levelset0, levelset.levelset1)):
+                raise MPMError("set_levelset: the key frames of a 2D DynamicLevelSet are LevelSets or SampledBoundary2D")
+        sampled = isinstance(levelset, SampledBoundary2D) or (isinstance(levelset, DynamicLevelSet) and isinstance(levelset.levelset0, SampledBoundary2D))
+        if sampled and getattr(self, "config", {}).get("rigid_body_levelset_collision", False):
+            raise MPMError("rigid_body_levelset_collision is not supported with a sampled level set")
         self._levelset = levelset
         if self._ctx is not None:
             self._apply_levelset()
@@ -344,10 +399,38 @@ class Simulation2D:
             return
         if isinstance(ls, DynamicLevelSet):
             l0, l1 = ls.levelset0, ls.levelset1
+            if isinstance(l0, SampledBoundary2D):
+                self._set_sdf(l0, l1, ls.t0, ls.t1)
+                return
             self._check(self._L.mpmhip2d_set_levelset(self._ctx, len(l0.shapes), self._shapes(l0), len(l1.shapes), self._shapes(l1),
                                                       ls.t0, ls.t1, l0.friction))
+        elif isinstance(ls, SampledBoundary2D):
+            self._set_sdf(ls, None, 0.0, 1.0)
         else:
             self._check(self._L.mpmhip2d_set_levelset(self._ctx, len(ls.shapes), self._shapes(ls), -1, None, 0.0, 1.0, ls.friction))
+
+    def _set_sdf(self, l0, l1, t0, t1):
+        d = _lib.SdfDesc2D()
+        d.res[:] = l0.res
+        d.origin[:] = l0.origin
+        d.spacing = l0.spacing if l0.spacing is not None else self.delta_x
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.mpmhip2d_set_levelset_sdf(self._ctx, C.byref(d), l0.phi.ctypes.data_as(fp),
+                                                      l1.phi.ctypes.data_as(fp) if l1 is not None else None, t0, t1, l0.friction))
+
+    def sample_levelset(self, x, t=0.0):
+        """the device's evaluation of the installed level set (sampled or shapes) at positions (n, 2) at time t:
+        (phi in grid units, unit gradient (n, 2), d phi / dt, hit) — hit is False where there is no level set"""
+        self._ensure_ctx()
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, 2)
+        n = len(x)
+        phi, grad, dphidt, hit = np.zeros(n, np.float32), np.zeros((n, 2), np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        if n:
+            fp = C.POINTER(C.c_float)
+            self._check(self._L.mpmhip2d_debug_levelset_sample(self._ctx, n, x.ctypes.data_as(fp), float(t), phi.ctypes.data_as(fp),
+                                                               grad.ctypes.data_as(fp), dphidt.ctypes.data_as(fp),
+                                                               hit.ctypes.data_as(C.POINTER(C.c_int32))))
+        return phi, grad, dphidt, hit.astype(bool)
 
     def step(self, dt):
         self._ensure_ctx()
@@ -544,6 +627,11 @@ class Simulation2D:
             return ""
         if action == "load":  # src/mpm.cpp:950-960
             self.load_snapshot(config["file_name"])
+            return ""
+        if action == "delete_particles_inside_level_set":  # src/mpm.cpp:962-974
+            self._ensure_ctx()
+            n = C.c_int64(0)
+            self._check(self._L.mpmhip2d_delete_particles_inside_level_set(self._ctx, C.byref(n)))
             return ""
         raise MPMError("general_action(%r) is not part of the 2D build" % (action,))
 
