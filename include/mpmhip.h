@@ -792,6 +792,22 @@ int mpmhip2d_delete_particles_inside_level_set(mpmhip2d_ctx *ctx, int64_t *delet
  * units, grad [n][2] the unit gradient, dphidt [n], hit [n] = 0 where there is no level set (then the rest is 0) */
 int mpmhip2d_debug_levelset_sample(mpmhip2d_ctx *ctx, int64_t n, const float *pos /* [n][2] */, float t, float *phi, float *grad,
                                    float *dphidt, int32_t *hit);
+/* the DEVICE's 2D constitutive math on host-given rows, for parity tests (the 2D twins of mpmhip_debug_force / _plasticity / _svd3):
+ * the functions the 2D transfer kernels call (csrc/mpm2d_math.h), one lane per row on the ctx's stream.  Matrices are row-major
+ * [a b; c d].  MPMHIP_EINVAL for a NULL ctx or array (force_out may be NULL), n < 0, an unknown material id; n == 0 succeeds
+ * without a launch.
+ *   force:      out = calculate_force(F, aux) = -vol P(F) F^T
+ *   plasticity: (F, aux) <- plasticity(cdg, F, aux) in place (water keeps its F); with force_out also calculate_force of the
+ *               updated state, the order in which G2P and the next P2G run them
+ *   svd2:       the rotation U = [cu -su; su cu] and the signed singular values S (sign of det F on the smaller one) of
+ *               F F^T = U diag(S^2) U^T exactly as the models consume them */
+int mpmhip2d_debug_force(mpmhip2d_ctx *ctx, int32_t material, const float params[MPMHIP_NPARAM], int64_t n, const float *F /* [n][4] */,
+                         const float *aux /* [n] */, float *out /* [n][4] */);
+int mpmhip2d_debug_plasticity(mpmhip2d_ctx *ctx, int32_t material, const float params[MPMHIP_NPARAM], int64_t n,
+                              const float *cdg /* [n][4] */, float *F /* [n][4], in/out */, float *aux /* [n], in/out */,
+                              float *force_out /* [n][4] or NULL */);
+int mpmhip2d_debug_svd2(mpmhip2d_ctx *ctx, int64_t n, const float *F /* [n][4] */, float *cu /* [n] */, float *su /* [n] */,
+                        float *S /* [n][2] */);
 
 /* frame output of the 2D simulation — replaces MPM<2>::write_partio (src/visualize.cpp:17-100): the same .bgeo as the 3D
  * entry points above (z = 0), boundary particles of rigid bodies as rows of type 1; with a resident asynchronous stepper the rows

@@ -194,7 +194,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip2d_async_begin", "mpmhip2d_async_pool_particles", "mpmhip2d_async_step", "mpmhip2d_async_load_pools", "mpmhip2d_async_view_blocks",
             "mpmhip2d_async_state", "mpmhip2d_async_current_time", "mpmhip2d_async_table", "mpmhip2d_bgeo_size", "mpmhip2d_bgeo_encode", "mpmhip2d_write_bgeo", "mpmhip2d_snapshot_size", "mpmhip2d_snapshot_save", "mpmhip2d_snapshot_load",
             "mpmhip2d_set_rigid_coupling", "mpmhip2d_set_rigid_levelset_collision", "mpmhip2d_add_articulation", "mpmhip2d_set_articulation_iterations", "mpmhip2d_add_rigid_body", "mpmhip2d_rigid_get_state", "mpmhip2d_rigid_get_samples", "mpmhip2d_cdf_phase",
-            "mpmhip2d_download_cdf", "mpmhip2d_download_colours", "mpmhip2d_poisson_tile", "mpmhip2d_seed_particles", "mpmhip2d_reserve", "mpmhip2d_num_slots", "mpmhip2d_capacity", "mpmhip2d_set_levelset_sdf", "mpmhip2d_delete_particles_inside_level_set", "mpmhip2d_debug_levelset_sample",
+            "mpmhip2d_download_cdf", "mpmhip2d_download_colours", "mpmhip2d_poisson_tile", "mpmhip2d_seed_particles", "mpmhip2d_reserve", "mpmhip2d_num_slots", "mpmhip2d_capacity", "mpmhip2d_set_levelset_sdf", "mpmhip2d_delete_particles_inside_level_set", "mpmhip2d_debug_levelset_sample", "mpmhip2d_debug_force", "mpmhip2d_debug_plasticity", "mpmhip2d_debug_svd2",
             "mpmhip_set_rigid_coupling", "mpmhip_add_rigid_body", "mpmhip_num_rigid_bodies", "mpmhip_rigid_get_state", "mpmhip_rigid_set_velocity",
             "mpmhip_rigid_get_samples", "mpmhip_rigid_get_mesh", "mpmhip2d_rigid_get_mesh", "mpmhip_rasterize_rigid_boundary", "mpmhip_gather_cdf", "mpmhip_advect_rigid_bodies", "mpmhip_download_cdf",
             "mpmhip_add_articulation", "mpmhip_num_articulations", "mpmhip_set_articulation_iterations", "mpmhip_articulate",
@@ -387,6 +387,9 @@ def load():
     L.mpmhip2d_set_levelset_sdf.argtypes = [vp, P(SdfDesc2D), fp, fp, C.c_float, C.c_float, C.c_float]
     L.mpmhip2d_delete_particles_inside_level_set.argtypes = [vp, P(C.c_int64)]
     L.mpmhip2d_debug_levelset_sample.argtypes = [vp, C.c_int64, fp, C.c_float, fp, fp, fp, P(C.c_int32)]
+    L.mpmhip2d_debug_force.argtypes = [vp, C.c_int32, fp, C.c_int64, fp, fp, fp]
+    L.mpmhip2d_debug_plasticity.argtypes = [vp, C.c_int32, fp, C.c_int64, fp, fp, fp, fp]
+    L.mpmhip2d_debug_svd2.argtypes = [vp, C.c_int64, fp, fp, fp, fp]
     L.mpmhip2d_bgeo_size.argtypes = [vp, C.c_int32, P(C.c_size_t)]
     L.mpmhip2d_bgeo_encode.argtypes = [vp, C.c_int32, vp, C.c_size_t, P(C.c_size_t)]
     L.mpmhip2d_write_bgeo.argtypes = [vp, C.c_char_p, C.c_int32]

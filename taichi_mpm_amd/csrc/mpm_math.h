@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mpmhip.h"
+#include "group_params.h"  // GroupParams: the material id and parameter row of a particle group
 
 namespace mpm {
 
@@ -292,12 +293,6 @@ __device__ __forceinline__ void sandwich2(const mat3 &U, const float d1[3], cons
       R2(r, c) = v.y; R2(c, r) = v.y;
     }
 }
-
-struct GroupParams {
-  float p[MPMHIP_NPARAM];
-  int32_t type;
-  int32_t pad[3];
-};
 
 // calculate_force(): returns -vol * P(F) * F^T  (src/particles.h:134-137; bodies in src/particles.cpp)
 // MATS_: the material set the caller is compiled for (MAT_ALL below); a set of ONE material needs no type dispatch

@@ -102,6 +102,7 @@
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
 #include "k_mpm2d_det.h"
+#include "k_debug2d.h"
 #include "k_sdf2d.h"
 #include "k_async2d.h"
 
@@ -2943,6 +2944,74 @@ int mpmhip2d_debug_levelset_sample(mpmhip2d_ctx *m, int64_t n, const float *pos,
   HIPCHK2D(m, hipMemcpy(grad, dO + n, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
   HIPCHK2D(m, hipMemcpy(dphidt, dO + 3 * n, sizeof(float) * n, hipMemcpyDeviceToHost));
   HIPCHK2D(m, hipMemcpy(hit, dO + 4 * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return MPMHIP_OK;
+}
+
+// the device's 2D constitutive math at host-given rows (tests; k_debug2d.h)
+static int debug2d_group(mpmhip2d_ctx *m, int32_t material, const float *params, GroupParams &g) {
+  if (material < MPMHIP_VISCO || material > MPMHIP_ELASTIC) return fail2d(m, MPMHIP_EINVAL, "unknown material id " + std::to_string(material));
+  memset(&g, 0, sizeof g);
+  memcpy(g.p, params, sizeof g.p);
+  g.type = material;
+  return MPMHIP_OK;
+}
+static unsigned debug2d_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 1024); }  // grid-stride beyond
+
+int mpmhip2d_debug_force(mpmhip2d_ctx *m, int32_t material, const float params[MPMHIP_NPARAM], int64_t n, const float *F,
+                         const float *aux, float *out) {
+  if (!m || n < 0 || !params || !F || !aux || !out) return MPMHIP_EINVAL;
+  GroupParams g;
+  int rc = debug2d_group(m, material, params, g);
+  if (rc || n == 0) return rc;
+  HIPCHK2D(m, hipSetDevice(m->device));
+  DevBuf<float> dF, dA, dO;
+  HIPCHK2D(m, dF.alloc(4 * (size_t)n)); HIPCHK2D(m, dA.alloc((size_t)n)); HIPCHK2D(m, dO.alloc(4 * (size_t)n));
+  HIPCHK2D(m, hipMemcpyAsync(dF, F, sizeof(float) * 4 * n, hipMemcpyHostToDevice, m->stream));
+  HIPCHK2D(m, hipMemcpyAsync(dA, aux, sizeof(float) * n, hipMemcpyHostToDevice, m->stream));
+  hipLaunchKernelGGL(mpm2d::k2_debug_force, dim3(debug2d_blocks(n)), dim3(256), 0, m->stream, g, n, (const float *)dF, (const float *)dA,
+                     dO.get());
+  HIPCHK2D(m, hipGetLastError());
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  HIPCHK2D(m, hipMemcpy(out, dO, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+  return MPMHIP_OK;
+}
+
+int mpmhip2d_debug_plasticity(mpmhip2d_ctx *m, int32_t material, const float params[MPMHIP_NPARAM], int64_t n, const float *cdg,
+                              float *F, float *aux, float *force_out) {
+  if (!m || n < 0 || !params || !cdg || !F || !aux) return MPMHIP_EINVAL;
+  GroupParams g;
+  int rc = debug2d_group(m, material, params, g);
+  if (rc || n == 0) return rc;
+  HIPCHK2D(m, hipSetDevice(m->device));
+  DevBuf<float> dC, dF, dA, dO;
+  HIPCHK2D(m, dC.alloc(4 * (size_t)n)); HIPCHK2D(m, dF.alloc(4 * (size_t)n)); HIPCHK2D(m, dA.alloc((size_t)n));
+  if (force_out) HIPCHK2D(m, dO.alloc(4 * (size_t)n));
+  HIPCHK2D(m, hipMemcpyAsync(dC, cdg, sizeof(float) * 4 * n, hipMemcpyHostToDevice, m->stream));
+  HIPCHK2D(m, hipMemcpyAsync(dF, F, sizeof(float) * 4 * n, hipMemcpyHostToDevice, m->stream));
+  HIPCHK2D(m, hipMemcpyAsync(dA, aux, sizeof(float) * n, hipMemcpyHostToDevice, m->stream));
+  hipLaunchKernelGGL(mpm2d::k2_debug_plasticity, dim3(debug2d_blocks(n)), dim3(256), 0, m->stream, g, n, (const float *)dC, dF.get(),
+                     dA.get(), force_out ? dO.get() : (float *)nullptr);
+  HIPCHK2D(m, hipGetLastError());
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  HIPCHK2D(m, hipMemcpy(F, dF, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+  HIPCHK2D(m, hipMemcpy(aux, dA, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (force_out) HIPCHK2D(m, hipMemcpy(force_out, dO, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+  return MPMHIP_OK;
+}
+
+int mpmhip2d_debug_svd2(mpmhip2d_ctx *m, int64_t n, const float *F, float *cu, float *su, float *S) {
+  if (!m || n < 0 || !F || !cu || !su || !S) return MPMHIP_EINVAL;
+  if (n == 0) return MPMHIP_OK;
+  HIPCHK2D(m, hipSetDevice(m->device));
+  DevBuf<float> dF, dO;
+  HIPCHK2D(m, dF.alloc(4 * (size_t)n)); HIPCHK2D(m, dO.alloc(4 * (size_t)n));
+  HIPCHK2D(m, hipMemcpyAsync(dF, F, sizeof(float) * 4 * n, hipMemcpyHostToDevice, m->stream));
+  hipLaunchKernelGGL(mpm2d::k2_debug_svd, dim3(debug2d_blocks(n)), dim3(256), 0, m->stream, n, (const float *)dF, dO.get(), dO + n, dO + 2 * n);
+  HIPCHK2D(m, hipGetLastError());
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  HIPCHK2D(m, hipMemcpy(cu, dO, sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIPCHK2D(m, hipMemcpy(su, dO + n, sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIPCHK2D(m, hipMemcpy(S, dO + 2 * n, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
   return MPMHIP_OK;
 }
 

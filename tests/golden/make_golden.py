@@ -299,6 +299,223 @@ def mpm2d_fixture(here):
     print("mpm2d:", len(x), "particles")
 
 
+def _rot2(a):
+    return np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+
+
+def _polar2(F):
+    """(R, sigma [n, 2] descending with the sign of det F on the last) of [n, 2, 2] matrices, in double precision"""
+    U, s, Vt = np.linalg.svd(F)
+    neg = np.linalg.det(F) < 0
+    s = s.copy()
+    s[neg, 1] *= -1.0
+    U = U.copy()
+    U[neg, :, 1] *= -1.0
+    return U @ Vt, s
+
+
+def materials2d_branches(mat, gp, cdg, F, aux):
+    """which branch of the dim = 2 plasticity (src/particles.cpp) each row takes: the branch conditions restated in double
+    precision on the reference's INPUTS -> {class name: bool [n]}"""
+    n = len(F)
+    F, cdg = F.reshape(n, 2, 2).astype(np.float64), cdg.reshape(n, 2, 2).astype(np.float64)
+    with np.errstate(all="ignore"):
+        if mat == "snow":  # :222-242: sigma clamped into [1 - theta_c, 1 + theta_s]
+            sg = np.linalg.svd(cdg @ F, compute_uv=False)
+            return {"clamped below": (sg < 1.0 - gp[5]).any(1), "clamped above": (sg > 1.0 + gp[6]).any(1)}
+        if mat == "sand":  # :599-626
+            sg = np.linalg.svd(cdg @ F, compute_uv=False)
+            eps = np.log(np.maximum(sg, 1e-4)) - gp[5]
+            tr = eps.sum(1) + aux
+            hat = np.linalg.norm(eps - tr[:, None] / 2.0, axis=1)
+            dg = hat + (2.0 * gp[3] + 2.0 * gp[2]) / (2.0 * gp[2]) * tr * gp[4]
+            return {"tr >= 0": tr >= 0, "dg <= 0": (tr < 0) & (dg <= 0), "dg > 0": (tr < 0) & (dg > 0)}
+        if mat == "von_mises":  # :713-732
+            eps = np.log(np.linalg.svd(cdg @ F, compute_uv=False))
+            hat = eps - eps.mean(1, keepdims=True)
+            dg = (hat ** 2).sum(1) - gp[4] / (2.0 * gp[2])
+            return {"not yielded": dg <= 0, "yielded": dg > 0}
+        if mat == "visco":  # :102-112: gamma = clamp(dt nu (|P| - tau) / |P|, 0, 1), P of the state BEFORE the update
+            R, _ = _polar2(F)
+            J = np.linalg.det(F)
+            P = 2.0 * gp[2] * (F - R) + (gp[3] * (J - 1.0) * J)[:, None, None] * np.linalg.inv(F).transpose(0, 2, 1)
+            pn = np.sqrt((P ** 2).sum((1, 2)))
+            gamma = np.where(pn > 1e-5, np.clip(gp[6] * gp[4] * (pn - aux) / np.maximum(pn, 1e-30), 0.0, 1.0), 0.0)
+            return {"gamma == 0": gamma == 0, "gamma > 0": gamma > 0}
+    return {}
+
+
+def visco_stress_norm2d(gp, F):
+    n = len(F)
+    F = F.reshape(n, 2, 2).astype(np.float64)
+    R, _ = _polar2(F)
+    J = np.linalg.det(F)
+    P = 2.0 * gp[2] * (F - R) + (gp[3] * (J - 1.0) * J)[:, None, None] * np.linalg.inv(F).transpose(0, 2, 1)
+    return np.sqrt((P ** 2).sum((1, 2)))
+
+
+def materials2d_fixture(here):
+    """the 2D twin of materials_fixture: calculate_force / plasticity of MPMParticle<2> (src/particles.cpp with dim = 2) on seeded
+    deformation gradients — small strains, large strains, states past the yield surfaces / clamps.  The generator asserts that
+    its own rows reach every branch (materials2d_branches)."""
+    rng = np.random.default_rng(2025)
+    n = 384
+    out = {}
+    dx = 1.0 / 64
+    vol = dx ** 2 / 4
+    mass = 400.0 * vol
+    for mat in MATS:
+        kw = MAT_KW.get(mat, {})
+        gp, t = orc.group_params(mat, mass, vol, **kw)
+        amp = np.repeat([0.01, 0.05, 0.2], n // 3)[:, None, None]
+        F = (np.eye(2) + rng.normal(0, 1, (n, 2, 2)) * amp).astype(np.float32).reshape(n, 4)
+        cdg = (np.eye(2) + rng.normal(0, 1, (n, 2, 2)) * amp * 0.3).astype(np.float32).reshape(n, 4)
+        aux = {"snow": 1.0 + rng.normal(0, 0.05, n), "water": 1.0 + rng.normal(0, 0.05, n),
+               "sand": np.abs(rng.normal(0, 0.02, n)), "visco": np.full(n, 1000.0)}.get(mat, np.zeros(n)).astype(np.float32)
+        if mat in ("sand", "elastic", "von_mises"):  # Hencky models take log(sigma): keep det F > 0 (reference: NaN otherwise)
+            bad = np.linalg.det(F.reshape(n, 2, 2)) <= 0.05
+            F[bad] = np.eye(2, dtype=np.float32).reshape(4)
+        if mat == "visco":  # every second row: tau at half the state's stress norm, so that gamma > 0 occurs
+            aux[::2] = (0.5 * visco_stress_norm2d(gp, F))[::2].astype(np.float32)
+        force = ref.calculate_force(mat, mass, vol, F, aux, dim=2, **kw)
+        F2, aux2 = ref.plasticity(mat, mass, vol, cdg, F, aux, dim=2, **kw)
+        force2 = ref.calculate_force(mat, mass, vol, F2, aux2, dim=2, **kw)
+        assert np.isfinite(force).all() and np.isfinite(F2).all() and np.isfinite(aux2).all() and np.isfinite(force2).all(), mat
+        for name, rows in materials2d_branches(mat, gp, cdg, F, aux).items():
+            print("  %-9s %-14s %4d rows" % (mat, name, rows.sum()))
+            assert rows.sum() >= 10, (mat, name, int(rows.sum()))
+        out.update({mat + "_F": F, mat + "_cdg": cdg, mat + "_aux": aux, mat + "_force": force, mat + "_F2": F2, mat + "_aux2": aux2,
+                    mat + "_force2": force2, mat + "_gp": gp, mat + "_type": t})
+    np.savez_compressed(os.path.join(here, "ref_materials2d.npz"), mass=mass, vol=vol, dx=dx, **out)
+    print("materials2d:", n, "states x", len(MATS), "types")
+
+
+ILLCOND2D_TAGS = ("one_small", "balanced", "repeated", "scaled_rotation", "symmetric_diagonal", "sand_clamp")
+
+
+def illcond2d_states(seed=79):
+    """2x2 deformation gradients F = R(a) diag(sigma) R(b)^T with prescribed singular values: condition numbers 1 .. 1e4 in two
+    patterns at three scales, det F < 0 (the smaller sigma negated) up to cond 1e2, repeated and nearly repeated values, pure
+    scaled rotations (F F^T is a multiple of the identity: the `n2 <= 1e-30` fallback of csrc/mpm2d_math.h: eig_FFt, or right
+    beside it), symmetric / diagonal F and F whose rows have exactly equal norms (zero off-diagonal or zero difference of the
+    diagonal of F F^T), and singular values at and below sand's 1e-4 clamp.  Returns (F [n, 4] float32, cond [n], tag [n]
+    (index into ILLCOND2D_TAGS), negdet [n] bool)."""
+    rng = np.random.default_rng(seed)
+    F, cond, tag, neg = [], [], [], []
+
+    def add(m, c, t, n=False):
+        F.append(np.asarray(m, np.float64).reshape(4)); cond.append(c); tag.append(t); neg.append(n)
+
+    def rsr(sig):
+        return _rot2(rng.uniform(0, 2 * np.pi)) @ np.diag(sig) @ _rot2(rng.uniform(0, 2 * np.pi)).T
+    for c in (1.0, 10.0, 1e2, 1e3, 1e4):
+        for t, sig in ((0, (1.0, 1.0 / c)), (1, (c ** 0.5, c ** -0.5))):
+            for scale in (1.0, 0.8, 1.3):
+                for _ in range(3):
+                    add(rsr(np.array(sig) * scale), c, t)
+            if c <= 1e2:
+                for _ in range(3):
+                    add(rsr((sig[0], -sig[1])), c, t, True)
+    for sig in ((1.0, 1.0), (1.5, 1.5), (2.0, 2.0), (1.0, 1.0 + 1e-6)):
+        for _ in range(3):
+            add(rsr(sig), max(sig) / min(sig), 2)
+    for s in (1.0, 0.8, 1.3):
+        for a in (0.0, np.pi / 2, np.pi, 0.3):
+            add(s * _rot2(a), 1.0, 3)
+    for m in ([[1.2, 0.0], [0.0, 0.7]], [[0.7, 0.0], [0.0, 1.2]], [[1.0, 0.3], [0.3, 1.0]], [[1.1, 0.2], [0.2, 0.9]],
+              [[1.25, 0.0], [0.75, 1.0]],    # rows of equal norm: the diagonal of F F^T is equal EXACTLY (d = 0), x != 0
+              [[1.0, 0.5], [-0.25, 0.5]],    # orthogonal rows: x = 0, d != 0
+              [[0.9, 0.0], [0.0, 0.9]]):     # d = 0 and x = 0
+        sv = np.linalg.svd(np.array(m), compute_uv=False)
+        add(m, sv[0] / sv[1], 4)
+    for sig in ((1.0, 1e-4), (1.0, 5e-5), (2e-4, 0.9e-4)):
+        for _ in range(3):
+            add(rsr(sig), max(sig) / min(sig), 5)
+    return np.array(F, np.float32), np.array(cond), np.array(tag, np.int32), np.array(neg, bool)
+
+
+def illcond2d_fixture(here):
+    """the 2D twin of illcond_fixture: calculate_force / plasticity of MPMParticle<2> on illcond2d_states.  Rows are left out of
+    the comparison by construction only (`use`: det F < 0 for the Hencky models, whose reference takes the log of a negative
+    sigma); apart from those the reference must be finite on every row up to cond 1e3 (asserted here)."""
+    F, cond, tag, neg = illcond2d_states()
+    n = len(F)
+    rng = np.random.default_rng(80)
+    cdg = (np.eye(2) + rng.normal(0, 0.02, (n, 2, 2))).astype(np.float32).reshape(n, 4)
+    dx = 1.0 / 64
+    vol = dx ** 2 / 4
+    mass = 400.0 * vol
+    out = dict(F=F, cdg=cdg, cond=cond, tag=tag, negdet=neg)
+    F64 = F.reshape(n, 2, 2).astype(np.float64)
+    sv = np.linalg.svd(F64, compute_uv=False)  # of the float32 matrices as they are; descending, sign of det F on the last
+    sv[:, 1] *= np.sign(np.linalg.det(F64))
+    out["sigma"] = sv
+    assert np.array_equal(np.linalg.det(F64) < 0, neg)
+    clamp = tag == ILLCOND2D_TAGS.index("sand_clamp")
+    for mat in MATS:
+        kw = MAT_KW.get(mat, {})
+        aux = {"snow": np.ones(n), "water": np.ones(n), "visco": np.full(n, 1000.0)}.get(mat, np.zeros(n)).astype(np.float32)
+        use = ~neg if mat in ("sand", "elastic", "von_mises") else np.ones(n, bool)  # Hencky: log of a negative sigma is NaN
+        with np.errstate(all="ignore"):
+            force = ref.calculate_force(mat, mass, vol, F, aux, dim=2, **kw)
+            F2, aux2 = ref.plasticity(mat, mass, vol, cdg, F, aux, dim=2, **kw)
+            force2 = ref.calculate_force(mat, mass, vol, F2, aux2, dim=2, **kw)
+        fin = np.isfinite(force).all(1) & np.isfinite(F2).all(1) & np.isfinite(aux2) & np.isfinite(force2).all(1)
+        upto = use & (cond <= 1e3 * 1.0001) & ~clamp
+        assert fin[upto].all(), (mat, np.flatnonzero(upto & ~fin))
+        hi = use & (cond > 1e3 * 1.0001) & ~clamp
+        print("  %-9s non-finite reference rows: %d of %d at cond 1e4, %d of %d in the sand-clamp class"
+              % (mat, (hi & ~fin).sum(), hi.sum(), (clamp & use & ~fin).sum(), (clamp & use).sum()))
+        gp, t = orc.group_params(mat, mass, vol, **kw)
+        out.update({mat + "_aux": aux, mat + "_use": use, mat + "_force": force, mat + "_F2": F2, mat + "_aux2": aux2,
+                    mat + "_force2": force2, mat + "_gp": gp, mat + "_type": t})
+    np.savez_compressed(os.path.join(here, "ref_illcond2d.npz"), mass=mass, vol=vol, dx=dx, tags=np.array(ILLCOND2D_TAGS), **out)
+    print("illcond2d:", n, "states x", len(MATS), "types")
+
+
+MPM2D_STRETCH_MATS = ("jelly", "elastic")
+
+
+def mpm2d_stretch_state(res=64, seed=31):
+    """the particles of mpm2d_state with F replaced by seeded stretches R diag(sqrt c, 1 / sqrt c) R^T, det F = 1, c = 30 for the
+    even and 100 for the odd particles"""
+    x, v, _, B = mpm2d_state(res)
+    rng = np.random.default_rng(seed)
+    n = len(x)
+    c = np.where(np.arange(n) % 2 == 0, 30.0, 100.0)
+    a = rng.uniform(0, 2 * np.pi, n)
+    ca, sa = np.cos(a), np.sin(a)
+    s0, s1 = np.sqrt(c), 1.0 / np.sqrt(c)
+    F = np.stack([ca * ca * s0 + sa * sa * s1, ca * sa * (s0 - s1), ca * sa * (s0 - s1), sa * sa * s0 + ca * ca * s1], 1)
+    return x, v, F.astype(np.float32), B
+
+
+def mpm2d_stretch_fixture(here):
+    """ONE substep of the reference's MPM<2> on the `floor` case of mpm2d_fixture from strongly stretched particles
+    (mpm2d_stretch_state: cond(F) 30 and 100): the constitutive path of the transfer kernels on ill-conditioned F"""
+    res, dt = 64, 1e-4
+    dx = 1.0 / res
+    x, v, F, B = mpm2d_stretch_state(res)
+    vol = dx ** 2 / 4
+    c = MPM2D_CASES["floor"]
+    out = dict(x=x, v=v, F=F, B=B)
+    for mat in MPM2D_STRETCH_MATS:
+        gp, t = orc.group_params(mat, 400.0 * vol, vol, **MAT_KW.get(mat, {}))
+        out["gp_" + mat] = gp
+        sim = ref.Sim(res, dx, dt, dim=2, shapes=c["shapes"], friction=c["friction"], **c["cfg"])
+        sim.add_particles(mat, 400.0 * vol, vol, x, v, F, B, np.zeros(len(x), np.float32), **MAT_KW.get(mat, {}))
+        sim.substep(1)
+        d = sim.download()
+        sim.close()
+        state = np.concatenate([d["x"], d["v"], d["F"], d["B"], d["aux"][:, None]], 1)
+        assert len(state) == len(x) and np.isfinite(state).all(), mat  # nobody left the grid, nothing blew up
+        print("  stretch %-8s max |v| %.3g (in: %.3g), max |F| %.3g" % (mat, np.abs(d["v"]).max(), np.abs(v).max(), np.abs(d["F"]).max()))
+        out["floor_" + mat] = state
+        out["floor_%s_ids" % mat] = d["id"]
+    save_golden("ref_mpm2d_stretch", res=res, dx=dx, dt=dt, **out)
+    print("mpm2d_stretch:", len(x), "particles x", len(MPM2D_STRETCH_MATS), "materials")
+
+
 def cpic_fixture(here):
     """CPIC rigid coupling (src/rigid_transfer.cpp, src/mpm_rigid_body.cpp, rigid branches of src/transfer.cpp): per case
     the boundary particles, the colored distance field and the particles' colours after sort + rasterize + gather_cdf,
@@ -426,7 +643,8 @@ def joints_fixture(here):
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
     ref.set_threads(1)  # the generic P2G of the reference is racy with more than one thread
-    what = sys.argv[1:] or (list(MATS) + ["materials", "illcond", "kernels", "shapes", "mpm2d", "cpic", "cpic2d", "joints"])
+    what = sys.argv[1:] or (list(MATS) + ["materials", "illcond", "kernels", "shapes", "mpm2d", "cpic", "cpic2d", "joints",
+                                  "materials2d", "illcond2d", "mpm2d_stretch"])
     for w in what:
         if w in MATS:
             substep_fixture(here, w)
@@ -448,6 +666,12 @@ def main():
             cpic2d_fixture(here)
         elif w == "joints":
             joints_fixture(here)
+        elif w == "materials2d":
+            materials2d_fixture(here)
+        elif w == "illcond2d":
+            illcond2d_fixture(here)
+        elif w == "mpm2d_stretch":
+            mpm2d_stretch_fixture(here)
 
 
 if __name__ == "__main__":

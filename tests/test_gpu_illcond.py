@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests.common import lattice_cube
+from tests.materials2d_common import assert_illcond_bounds, cond_classes, errors, print_illcond_table  # shared with the 2D tests
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(__file__)
@@ -54,57 +55,15 @@ def device_outputs(sim, g, mat):
     return force, F2, aux2, force2
 
 
-def cond_classes(cond):
-    """rows by the decade of their condition number: 1 (< 3), 10, 1e2, 1e3, 1e4 (and beyond: sand's clamp rows)"""
-    dec = np.clip(np.round(np.log10(np.maximum(cond, 1.0))), 0, 4).astype(int)
-    return [(10.0 ** d, dec == d) for d in range(5)]
-
-
-def errors(g, mat, got):
-    """per condition class: max |error| of (force, F2, next force) relative to the largest entry of the row's reference value (at
-    least 1 % of the class's largest), after the absolute floor of the F - R cancellation for the stresses (as in
-    test_device_materials_match_the_reference)"""
-    force, F2, aux2, force2 = got
-    gp = g[mat + "_gp"]
-    atol = 2 * gp[2] * gp[1] * 4e-6 if mat != "water" else 0.0
-    # (det F < 0 with all |sigma| equal: WHICH singular direction carries the sign is arbitrary — the reference's svd and the device
-    # pick different ones and both are right; such an F has no well-defined polar decomposition.  Not a parity case.)
-    use = g[mat + "_use"] & ~(g["negdet"] & (g["cond"] < 1.5))
-    rows = []
-    for c, sel in cond_classes(g["cond"]):
-        want = [g[mat + "_force"], g[mat + "_F2"], g[mat + "_force2"]]
-        ok = sel & use & np.isfinite(want[0]).all(1) & np.isfinite(want[1]).all(1) & np.isfinite(want[2]).all(1)
-        if not ok.any():
-            rows.append((c, 0, 0.0, 0.0, 0.0))
-            continue
-        e = []
-        for have, w, floor in ((force, want[0], atol), (F2, want[1], 0.0), (force2, want[2], atol)):
-            scale = np.abs(w[ok]).max(1, keepdims=True)
-            scale = np.maximum(scale, 1e-2 * scale.max())  # (a rotation has no stress at all: such rows are measured against the class)
-            e.append(float((np.maximum(np.abs(have[ok] - w[ok]) - floor, 0.0) / scale).max()) if scale.max() > 0 else 0.0)
-        rows.append((c, int(ok.sum()), e[0], e[1], e[2]))
-    return rows
-
-
 @pytest.mark.parametrize("mat", MATS)
 def test_device_materials_on_ill_conditioned_deformation_gradients(ctx_sim, mat):
     g = np.load(os.path.join(HERE, "golden", "ref_illcond.npz"))
     rows = errors(g, mat, device_outputs(ctx_sim, g, mat))
-    print("\n%-9s  cond    rows   force     F_new     next force   (max error / largest entry of the row)" % mat)
-    for c, n, ef, eF, en in rows:
-        print("%-9s  %-7g %4d   %.2e  %.2e  %.2e" % (mat, c, n, ef, eF, en))
+    print_illcond_table(mat, rows)
     # the tolerances of the well-conditioned fixture (3e-5 stress, 2e-5 F) hold up to cond 1e2 — and, with the singular values
-    # measured on F, an order further; beyond that the error grows like eps cond (the numbers above; DESIGN.md section 2)
-    for c, n, ef, eF, en in rows:
-        if n == 0:
-            continue
-        if c <= 1e2:
-            assert ef <= 3e-5 and eF <= 2e-5 and en <= 3e-5, (mat, c, ef, eF, en)
-        elif c <= 1e3:  # measured: F_new <= 1.7e-4, stress <= 5e-5 — but 1.3e-3 / 3.3e-3 for the NEXT stress of von Mises / visco,
-            # whose return maps divide by the deviator's norm and raise to a power: the error of sigma_min is amplified there
-            assert ef <= 1e-4 and eF <= 4e-4 and en <= (8e-3 if mat in ("von_mises", "visco") else 2e-4), (mat, c, ef, eF, en)
-        else:  # cond 1e4: eps cond = 6e-4 of sigma_min is all fp32 can hold of F itself
-            assert ef <= 2e-3 and eF <= 5e-3 and en <= (0.15 if mat in ("von_mises", "visco") else 5e-3), (mat, c, ef, eF, en)
+    # measured on F, an order further; beyond that the error grows like eps cond.  Measured at cond 1e3:
+    # F_new <= 1.7e-4, stress <= 5e-5 — but 1.3e-3 / 3.3e-3 for the NEXT stress of von Mises / visco.
+    assert_illcond_bounds(mat, rows)
 
 
 def test_device_singular_values_keep_their_relative_accuracy(ctx_sim):
