@@ -892,6 +892,24 @@ int mpmhip_debug_transfer_plan(const mpmhip_ctx *ctx, int32_t out[8]);
 #define MPMHIP_COND_CENSUS_WORDS 264
 int mpmhip_debug_cond_census(mpmhip_ctx *ctx, double out[MPMHIP_COND_CENSUS_WORDS]);
 int mpmhip_debug_scan_grid(int32_t n_cus, int32_t per_cu, int32_t env_request, uint32_t *limit, uint32_t *resident);
+/* test helpers: a read-only view of what the last sort built, while the particles are still sorted (behind mpmhip_sort, before the next
+ * G2P, upload or deletion) — tests/test_gpu_sort_tables.py holds every table against a numpy model.  Both synchronise the ctx
+ * stream, launch nothing, and fail with MPMHIP_EINVAL unless the particles are sorted.
+ * mpmhip_debug_sort_info: out[0] n_slots, [1..6] the device counters n_sorted, n_active, n_dead, error (reported, not raised),
+ * rank_mode (the path of k_rank in the NEXT sort), n_own; what the plan chose: [7] 1 the keyed two-launch front / 0 the four launches,
+ * [8] 1 the cell table with neighbour rows + owner list / 0 the plain one, [9] blocks per chunk of the cell table, [10] form of the
+ * in-cell ordering (0 a lane per cell, 1 a wave per block; -1 the deterministic mode was off), [11] 1 that ordering read cached ids /
+ * 0 the records; [12] list_valid, [13] bitmap words, [14] max_blocks, [15] Morton bits per axis.
+ * mpmhip_debug_sort_array: copies array `which` to dst; returns the bytes written, or MINUS the bytes needed when capacity_bytes is
+ * too small (nothing is written; the sizes are multiples of 4, the errors MPMHIP_EINVAL and MPMHIP_EHIP are not).  All are 32-bit words.  na = min(n_active, max_blocks):  SLOT_ID [n_slots] creation id per slot, -1
+ * for a deleted slot; BITS, WPREFIX [bitmap words]; ACT_BLK [na]; ACT_START [na + 1]; CELL_START [64 na + 1]; PERM [n_sorted] the
+ * sorted index as the transfer kernels read it; NBR [32 na] and OWN_LIST [n_own] (empty unless list_valid); CHUNK_BLK
+ * [ceil(n_sorted / 256)] the block holding sorted position 256 k. */
+#define MPMHIP_SORT_INFO_WORDS 16
+enum { MPMHIP_SORT_SLOT_ID = 0, MPMHIP_SORT_BITS = 1, MPMHIP_SORT_WPREFIX = 2, MPMHIP_SORT_ACT_BLK = 3, MPMHIP_SORT_ACT_START = 4,
+       MPMHIP_SORT_CELL_START = 5, MPMHIP_SORT_PERM = 6, MPMHIP_SORT_NBR = 7, MPMHIP_SORT_OWN_LIST = 8, MPMHIP_SORT_CHUNK_BLK = 9 };
+int mpmhip_debug_sort_info(mpmhip_ctx *ctx, int64_t out[MPMHIP_SORT_INFO_WORDS]);
+int64_t mpmhip_debug_sort_array(mpmhip_ctx *ctx, int32_t which, void *dst, int64_t capacity_bytes);
 /* 64-byte record gather of KNOWN size — the access pattern of k_p2g / k_g2p (a lane fetches one whole record with four
  * 16-byte loads through an index): n (a power of two) records, index pattern 0 identity / 1 shuffled runs of 8 /
  * 2 fully shuffled.  Reads exactly (64 + 4) n bytes per launch: the yardstick rocprofv3's FETCH_SIZE is calibrated

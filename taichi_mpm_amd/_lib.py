@@ -200,7 +200,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip_add_articulation", "mpmhip_num_articulations", "mpmhip_set_articulation_iterations", "mpmhip_articulate",
             "mpmhip_download_boundary",
             "mpmhip_set_rigid_collision", "mpmhip_rigidify", "mpmhip_rigid_get_collisions", "mpmhip_rigid_get_hull", "mpmhip_rigid_mpr_test",
-            "mpmhip_debug_copy_bandwidth", "mpmhip_debug_live_buffers", "mpmhip_debug_g2p_is_packed", "mpmhip_debug_transfer_plan", "mpmhip_debug_scan_grid", "mpmhip_debug_cond_census", "mpmhip_debug_gather_bandwidth", "mpmhip_debug_svd3", "mpmhip_debug_force", "mpmhip_debug_plasticity"]
+            "mpmhip_debug_copy_bandwidth", "mpmhip_debug_live_buffers", "mpmhip_debug_g2p_is_packed", "mpmhip_debug_transfer_plan", "mpmhip_debug_scan_grid", "mpmhip_debug_cond_census", "mpmhip_debug_sort_info", "mpmhip_debug_sort_array", "mpmhip_debug_gather_bandwidth", "mpmhip_debug_svd3", "mpmhip_debug_force", "mpmhip_debug_plasticity"]
 
 
 def exported_symbols():
@@ -413,6 +413,9 @@ def load():
     L.mpmhip_debug_live_buffers.argtypes = []
     L.mpmhip_debug_live_buffers.restype = C.c_int64
     L.mpmhip_debug_g2p_is_packed.argtypes = [vp]
+    L.mpmhip_debug_sort_info.argtypes = [vp, P(C.c_int64)]
+    L.mpmhip_debug_sort_array.argtypes = [vp, C.c_int32, vp, C.c_int64]
+    L.mpmhip_debug_sort_array.restype = C.c_int64
     L.mpmhip_debug_transfer_plan.argtypes = [vp, P(C.c_int32)]
     L.mpmhip_debug_scan_grid.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(C.c_uint32), P(C.c_uint32)]
     L.mpmhip_debug_copy_bandwidth.argtypes = [vp, C.c_size_t, C.c_int32, P(C.c_double)]

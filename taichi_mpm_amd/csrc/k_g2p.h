@@ -18,7 +18,10 @@ __device__ __forceinline__ void g2p_particle(const Params &P, const float scale,
     // (lane_lds: five float4 of LDS private to this lane — its row of the wave's store-staging slab, idle until the records
     // are staged: scratch of the rare refinement of an ill-conditioned F, mpm_math.h: sym_eig3_refine)
     const float x0 = g0.x, x1 = g0.y, x2 = g0.z;
-    const float X0 = x0 * P.idx - ox, X1 = x1 * P.idx - oy, X2 = x2 * P.idx - oz;
+    // ONE rounding, spelled out: left to the compiler's contraction, k_g2p fused this into an fma and k_g2p_packed (which hoists x * idx
+    // out of its passes over a chunk's blocks) did not — on a grid whose dx is no power of two the two walks then disagreed in the last
+    // bit of the weights (tests/test_gpu_sort_tables.py, the 72^3 scene), and the host picks the walk from statistics that arrive late
+    const float X0 = fmaf(P.idx, x0, -ox), X1 = fmaf(P.idx, x1, -oy), X2 = fmaf(P.idx, x2, -oz);
     const int c0 = (int)(X0 - 0.5f), c1 = (int)(X1 - 0.5f), c2 = (int)(X2 - 0.5f);
     const float r0 = X0 - (float)c0, r1 = X1 - (float)c1, r2 = X2 - (float)c2;
     float w0[3], w1[3], w2[3];

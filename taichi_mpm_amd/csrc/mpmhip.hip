@@ -221,6 +221,10 @@ struct mpmhip_ctx {
   FillStats *d_stats = nullptr;  // device address of the pinned page's statistics words (h_pinned + FILL_STATS_WORD): k_cell_table stores there
   lp::Knobs knobs;               // the tuning switches of the substep path (launch_plan.h), read from the environment by mpmhip_create
   bool list_valid = false;       // the last sort built neighbour rows + owner list (do_sort -> do_grid)
+  struct LastSort {              // what the last do_sort launched (mpmhip_debug_sort_info: the tests of the sort's tables)
+    bool keyed = false, build_list = false, ids_cached = false, deterministic = false;
+    int ct = 0, cell_order_form = 0;
+  } last_sort;
   DevBuf<unsigned long long> scan_slots;  // [256] k_block_table + [ct_grid] k_cell_table: {epoch, chunk sum}
   uint32_t list_clear_epoch = 0;  // sort epoch at which the scan words of the list form of k_cell_table were last zeroed (do_sort)
   uint32_t sort_epoch = 0, bt_slots = 0, ct_slots = 0;  // scan_slots: [bt_slots] k_block_table | [ct_slots] k_cell_table_plain | [ct_slots] k_cell_table
@@ -1218,6 +1222,8 @@ static int do_sort(mpmhip_ctx *c) {
   // pidc[] holds the ids of the current key[]: k_build_keys wrote both just now, or the last G2P did
   const bool ids_cached = P.pidc && (build_keys || c->rec.pidc_valid());
   c->list_valid = plan.build_list;
+  c->last_sort.keyed = plan.keyed; c->last_sort.build_list = plan.build_list; c->last_sort.ct = plan.ct;
+  c->last_sort.cell_order_form = plan.cell_order_form; c->last_sort.ids_cached = ids_cached; c->last_sort.deterministic = c->deterministic;
   uint32_t *const nbr = plan.build_list ? c->nbr : nullptr;
   uint32_t epoch = ++c->sort_epoch;
   if ((epoch & 0x7FFFFFu) == 0u) epoch = ++c->sort_epoch;  // (k_cell_table's scan words keep 23 bits of it; 0 = never published)
@@ -2365,6 +2371,58 @@ int mpmhip_debug_transfer_plan(const mpmhip_ctx *c, int32_t out[8]) {
   if (!c || !out) return MPMHIP_EINVAL;
   lp::transfer_plan_words(c->knobs, facts(c), out);
   return MPMHIP_OK;
+}
+// read-only view of what the last do_sort left (include/mpmhip.h): the facts, then one array per call
+static int sort_view_counters(mpmhip_ctx *c, Counters &h) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->rec.sorted()) return fail(c, MPMHIP_EINVAL, "debug_sort: the particles are not sorted: call mpmhip_sort first");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(&h, c->cnt, sizeof h, hipMemcpyDeviceToHost));  // (not read_counters: the error word is reported, not raised)
+  return MPMHIP_OK;
+}
+int mpmhip_debug_sort_info(mpmhip_ctx *c, int64_t out[MPMHIP_SORT_INFO_WORDS]) {
+  if (!c || !out) return MPMHIP_EINVAL;
+  Counters h;
+  if (int rc = sort_view_counters(c, h)) return rc;
+  const auto &s = c->last_sort;
+  const int64_t words[MPMHIP_SORT_INFO_WORDS] = {
+      c->n_slots, h.n_sorted, h.n_active, h.n_dead, h.error, h.rank_mode, h.n_own, s.keyed ? 1 : 0, s.build_list ? 1 : 0, s.ct,
+      s.deterministic ? s.cell_order_form : -1, s.ids_cached ? 1 : 0, c->list_valid ? 1 : 0, c->P.nbw, c->P.max_blocks, c->P.kbits};
+  memcpy(out, words, sizeof words);
+  return MPMHIP_OK;
+}
+int64_t mpmhip_debug_sort_array(mpmhip_ctx *c, int32_t which, void *dst, int64_t capacity_bytes) {
+  if (!c || (!dst && capacity_bytes > 0) || capacity_bytes < 0) return MPMHIP_EINVAL;
+  Counters h;
+  if (int rc = sort_view_counters(c, h)) return rc;
+  const size_t na = std::min(h.n_active, c->P.max_blocks), ns = std::min<size_t>(h.n_sorted, (size_t)c->n_slots);
+  const void *src = nullptr;
+  size_t words = 0;
+  switch (which) {
+    case MPMHIP_SORT_SLOT_ID: words = (size_t)c->n_slots; break;  // (gathered from the records below)
+    case MPMHIP_SORT_BITS: src = c->bits.get(); words = c->P.nbw; break;
+    case MPMHIP_SORT_WPREFIX: src = c->wprefix.get(); words = c->P.nbw; break;
+    case MPMHIP_SORT_ACT_BLK: src = c->act_blk.get(); words = na; break;
+    case MPMHIP_SORT_ACT_START: src = c->act_start.get(); words = na + 1; break;
+    case MPMHIP_SORT_CELL_START: src = c->cell_start.get(); words = na * BC + 1; break;
+    case MPMHIP_SORT_PERM: src = c->perm.get(); words = ns; break;
+    case MPMHIP_SORT_NBR: src = c->nbr.get(); words = c->list_valid ? na * 32 : 0; break;
+    case MPMHIP_SORT_OWN_LIST: src = c->own_list.get(); words = c->list_valid ? std::min<size_t>(h.n_own, (size_t)c->P.max_blocks * 8) : 0; break;
+    case MPMHIP_SORT_CHUNK_BLK: src = c->chunk_blk.get(); words = c->chunk_blk ? (ns + 255) / 256 : 0; break;
+    default: return fail(c, MPMHIP_EINVAL, "debug_sort_array: unknown array %d", which);
+  }
+  const int64_t bytes = (int64_t)(words * sizeof(uint32_t));
+  if (bytes > capacity_bytes) return -bytes;
+  if (bytes == 0) return 0;
+  if (which == MPMHIP_SORT_SLOT_ID) {
+    std::vector<RecG> hg(words);
+    HIPCHK(c, hipMemcpy(hg.data(), c->rg, sizeof(RecG) * words, hipMemcpyDeviceToHost));
+    int32_t *q = (int32_t *)dst;
+    for (size_t i = 0; i < words; i++) q[i] = hg[i].pid < 0 ? -1 : hg[i].pid;
+  } else {
+    HIPCHK(c, hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDeviceToHost));
+  }
+  return bytes;
 }
 int mpmhip_debug_copy_bandwidth(mpmhip_ctx *c, size_t bytes, int32_t iters, double *gb_per_s) {
   if (!c || !gb_per_s || iters <= 0 || bytes < 16) return MPMHIP_EINVAL;

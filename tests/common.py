@@ -67,10 +67,30 @@ def mixed_state(x, mats, dx, seed, **kw):
                      np.stack([p.gparams[0] for p in parts]), np.array([p.gtype[0] for p in parts], np.int32))
 
 
-def sort_key(x, dx):
+def sort_key(x, dx, res=None, v=None, ids=None, clean_boundary=False):
     """the key the device sorts by: Morton(block) << 6 | cell in the block (blocks of 4^3 cells; the cell of a particle is the base
-    node of its quadratic stencil)"""
-    base = np.floor(x.astype(np.float32) * np.float32(1 / dx) - np.float32(0.5)).astype(np.int64)
+    node of its quadratic stencil).  With `res` (three nodes counts) the slots the device deletes get -1, as particle_key of
+    csrc/mpm_common.h decides it in fp32: a non-finite x or v, an id < 0, the 7-cell margin when clean_boundary, X < 0.5, or a
+    stencil that leaves the grid (base + 2 > res, per axis)."""
+    idx = np.float32(1.0) / np.float32(dx)  # (Params::idx)
+    with np.errstate(invalid="ignore", over="ignore"):
+        X = x.astype(np.float32) * idx
+        if res is None:
+            alive = np.ones(len(X), bool)
+        else:
+            r = np.asarray(res, np.float32)
+            alive = np.isfinite(x).all(1)
+            if v is not None:
+                alive &= np.isfinite(v).all(1)
+            if ids is not None:
+                alive &= np.asarray(ids) >= 0
+            if clean_boundary:
+                alive &= ~((X.min(1) < np.float32(7.0)) | ((X - r).max(1) > np.float32(-7.0)))
+            alive &= (X >= np.float32(0.5)).all(1)
+        base = np.floor(np.where(alive[:, None], X, np.float32(0.5)) - np.float32(0.5)).astype(np.int64)
+    if res is not None:
+        alive &= (base + 2 <= np.asarray(res, np.int64)).all(1)
+        base[~alive] = 0
 
     def spread(v):
         r = np.zeros_like(v)
@@ -78,8 +98,9 @@ def sort_key(x, dx):
             r |= ((v >> b) & 1) << (3 * b)
         return r
     blk = base >> 2
-    return ((spread(blk[:, 0]) << 2 | spread(blk[:, 1]) << 1 | spread(blk[:, 2])) << 6) | ((base[:, 0] & 3) << 4) | \
+    key = ((spread(blk[:, 0]) << 2 | spread(blk[:, 1]) << 1 | spread(blk[:, 2])) << 6) | ((base[:, 0] & 3) << 4) | \
         ((base[:, 1] & 3) << 2) | (base[:, 2] & 3)
+    return np.where(alive, key, -1)
 
 
 def fewest_kinds_in_a_window(x, kind, dx, window=64):

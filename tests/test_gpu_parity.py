@@ -123,6 +123,7 @@ def test_device_constitutive_models_match_oracle(tm, orc, mat):
 
 # ------------------------------------------------------------------------------------------ sort
 def test_sort_is_a_permutation_in_key_order_and_drops_dead(tm, orc):
+    """(the tables behind the sorted index are compared with a model one by one in tests/test_gpu_sort_tables.py)"""
     x = lattice_cube(RES, 5, 12, DX, jitter=0.3, seed=2)  # cells 5,6 lie inside the 7-cell deletion margin
     rng = np.random.default_rng(3)
     x = x[rng.permutation(len(x))]
@@ -152,7 +153,8 @@ def test_crowded_cells_take_the_side_array_of_the_sort(tm, orc, monkeypatch):
     """k_rank packs (rank, cell) into one word per slot and spills ranks that do not fit into a side array; with the
     test knob (a 3-bit rank field) every cell of this scene spills — the substep must come out exactly as without it,
     in both orders of the slots (long runs -> one atomic per run; shuffled -> the LDS hash path after the first sort).  In the
-    deterministic mode (cells in creation-id order behind the sort) bit for bit."""
+    deterministic mode (cells in creation-id order behind the sort) bit for bit.  (tests/test_gpu_sort_tables.py reads the index itself,
+    with the knob and at kbits = 7, where five bits of rank are what production has.)"""
     monkeypatch.setenv("MPMHIP_DETERMINISTIC", "1")
     x = lattice_cube(RES, 9, 15, DX, jitter=0.3, seed=21)
     x = np.concatenate([x, x + np.float32(1e-3), x - np.float32(1e-3)])  # 24 particles per cell
@@ -183,7 +185,7 @@ def test_every_form_of_the_sort_gives_the_same_substep(tm, monkeypatch):
     table; with the owner list of the grid pass (k_cell_table + k_grid_list) or without (k_cell_table_plain + k_grid_blocks).  All twelve
     combinations on one scene (dense runs + spray + leavers, so dead slots and short runs occur) must agree with the default — in the
     deterministic mode bit for bit (none of the forms changes an operand or an order of the arithmetic), and that mode with the default
-    one to the order of the sums inside a cell."""
+    one to the order of the sums inside a cell.  (What each form leaves in its tables: tests/test_gpu_sort_tables.py.)"""
     rng = np.random.default_rng(41)
     dense = lattice_cube(RES, 8, 14, DX, jitter=0.2, seed=40)
     spray = (rng.uniform(6.0, 26.0, (2500, 3)) * DX).astype(np.float32)
