@@ -6,6 +6,8 @@
                                    A call is timed by the host clock from the call to the end of a device synchronise, on a ctx
                                    created (and sized) beforehand.  The points of the positions= calls are the region= call's own
                                    output, downloaded once: sampling them on the host is not part of any number.
+  python profiles/seed2d_ab.py --sampled   the same disc baked on the grid's nodes (1025^2 samples, uploaded by every call): the
+                                   region is read by the boundary's sampler.  (Under MPMHIP_LIB_VARIANT=parent: the parent's library.)
 A set-up cost: there is no target."""
 import os
 import statistics
@@ -38,6 +40,8 @@ def main():
     import taichi_mpm_amd as tm
     tm.load()
     disc = tm.LevelSet().add_sphere((0.5, 0.5, 0.0), R_CELLS / RES)
+    if "--sampled" in sys.argv[1:]:
+        disc = tm.SampledLevelSet2D.from_levelset(disc, (RES + 1, RES + 1), (0.0, 0.0), 1.0 / RES)
     _, n, x = timed_fill(tm, want_x=True, region=disc)  # (also the warm-up of the region= path)
     timed_fill(tm, positions=x)
     tr, tp = [], []
@@ -48,8 +52,8 @@ def main():
         tr.append(r[0])
         tp.append(p[0])
     n_tile = int(tm.load().mpmhip2d_poisson_tile(None, 0))
-    print("disc r = %d dx at %d^2, ppc 4: %d particles (%.3f per cell of the disc; tile of %d points)" % (
-        R_CELLS, RES, n, n / (np.pi * R_CELLS ** 2), n_tile))
+    print("%sdisc r = %d dx at %d^2, ppc 4: %d particles (%.3f per cell of the disc; tile of %d points)" % (
+        "sampled " if "--sampled" in sys.argv[1:] else "", R_CELLS, RES, n, n / (np.pi * R_CELLS ** 2), n_tile))
     for label, t, moved in (("region=   ", tr, 0), ("positions=", tp, n * 60)):
         print("  %s median %9.3f ms   min %9.3f   max %9.3f   (%d calls)   particle bytes through the host: %d" % (
             label, 1e3 * statistics.median(t), 1e3 * min(t), 1e3 * max(t), len(t), moved))

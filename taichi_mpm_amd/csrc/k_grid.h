@@ -96,11 +96,11 @@ __device__ __forceinline__ void sdf_node_bc(const Params &P, const LevelSetDev &
     const float xw[3] = {gi * P.dx, gj * P.dx, gk * P.dx};
     int c[3];
     float f[3];
-    band = sdf_locate(LS.sdf, xw, c, f);
+    band = sdf_locate<3>(LS.sdf, xw, c, f);
     if (band) {
-      phi = sdf_phi(LS.sdf, P.t, P.idx, c, f, &dphidt);
+      phi = sdf_phi<3>(LS.sdf, P.t, P.idx, c, f, &dphidt);
       band = !(phi < -3.0f || 0.0f < phi);
-      if (band) sdf_normal(LS.sdf, P.t, c, f, nrm);
+      if (band) sdf_normal<3>(LS.sdf, P.t, c, f, nrm);
     }
   }
   if (band) {

@@ -25,11 +25,11 @@ __global__ __launch_bounds__(256) void k_sdf_collide(Params P, const Counters *_
       const float x[3] = {g0.x, g0.y, g0.z};
       int c[3];
       float f[3];
-      if (sdf_locate(S, x, c, f)) {
-        const float phi = sdf_phi(S, P.t, P.idx, c, f);
+      if (sdf_locate<3>(S, x, c, f)) {
+        const float phi = sdf_phi<3>(S, P.t, P.idx, c, f);
         if (phi < 0.0f && key[pos] != INVALID) {
           float gr[3];
-          sdf_normal(S, P.t, c, f, gr);
+          sdf_normal<3>(S, P.t, c, f, gr);
           const float4 q0 = rp[(size_t)pos * 4], q1 = rp[(size_t)pos * 4 + 1];
           float v[3] = {q0.w, q1.x, q1.y};
           const float vn = gr[0] * v[0] + gr[1] * v[1] + gr[2] * v[2];

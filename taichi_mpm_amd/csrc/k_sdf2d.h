@@ -1,5 +1,5 @@
 // taichi_mpm_amd/csrc/k_sdf2d.h — MPM<2> against a sampled level set (mpmhip2d_set_levelset_sdf; rules: include/mpmhip.h; the sampler:
-// mpm_math.h, sdf2_*).  Part of libmpmhip.  A ctx without a sampled set launches none of these kernels except k2_delete_inside: its
+// mpm_math.h, the sdf_* templates at D = 2).  Part of libmpmhip.  A ctx without a sampled set launches none of these kernels except k2_delete_inside: its
 // substep is k_mpm2d.h's, unchanged.  With one installed:
 //   k_grid_sdf        k_grid's node update with the boundary condition read from the lattice
 //   k2_sdf_collide    particle_collision behind G2P.  g2p_particle pushes against shapes inside its particle loop (LS.n > 0); a sampled
@@ -17,7 +17,7 @@ namespace mpm2d {
 // whichever level set is installed, read in the plane
 __device__ __forceinline__ bool levelset_eval_any2(const LevelSetDev &LS, float t, const float x[2], float idx, float &phi, float n[2],
                                                    float *dphidt = nullptr) {
-  if (LS.sdf.phi0) return mpm::sdf2_eval(LS.sdf, t, x, idx, phi, n, dphidt);
+  if (LS.sdf.phi0) return mpm::sdf_eval<2>(LS.sdf, t, x, idx, phi, n, dphidt);
   const float xw[3] = {x[0], x[1], 0.0f};
   float g[3] = {0.0f, 0.0f, 0.0f};
   const bool hit = mpm::levelset_eval(LS, t, xw, idx, phi, g, dphidt);
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void k_grid_sdf(Params P, LevelSetDev LS, floa
   if (m != 0.0f) {
     const float xn[2] = {(float)(t / ny) * P.dx, (float)(t % ny) * P.dx};
     float phi, dphidt, nrm[2];
-    if (mpm::sdf2_eval(LS.sdf, P.t, xn, P.idx, phi, nrm, &dphidt) && !(phi < -3.0f || 0.0f < phi)) {
+    if (mpm::sdf_eval<2>(LS.sdf, P.t, xn, P.idx, phi, nrm, &dphidt) && !(phi < -3.0f || 0.0f < phi)) {
       const float vb[2] = {-dphidt * nrm[0] * P.dx, -dphidt * nrm[1] * P.dx};
       friction_project2(v, vb, nrm, LS.friction);
     }
@@ -64,11 +64,11 @@ __global__ __launch_bounds__(256) void k2_sdf_collide(Params P, mpm::SdfDev S, i
   const float xx[2] = {x[2 * p], x[2 * p + 1]};
   int c[2];
   float f[2];
-  if (!mpm::sdf2_locate(S, xx, c, f)) return;
-  const float phi = mpm::sdf2_phi(S, P.t, P.idx, c, f);
+  if (!mpm::sdf_locate<2>(S, xx, c, f)) return;
+  const float phi = mpm::sdf_phi<2>(S, P.t, P.idx, c, f);
   if (!(phi < 0.0f)) return;
   float gr[2];
-  mpm::sdf2_normal(S, P.t, c, f, gr);
+  mpm::sdf_normal<2>(S, P.t, c, f, gr);
   const float nv[2] = {v[2 * p], v[2 * p + 1]};
   const float vn = gr[0] * nv[0] + gr[1] * nv[1];
   x[2 * p] = xx[0] - gr[0] * phi * P.dx; x[2 * p + 1] = xx[1] - gr[1] * phi * P.dx;

@@ -17,8 +17,8 @@
 
 namespace mpm {
 
-// no multiply-add of the candidate arithmetic or of the 2D field sampler may be fused: tests/seed_model.py and tests/seed2d_model.py
-// reproduce the positions to the bit
+// no multiply-add of the candidate arithmetic may be fused: tests/seed_model.py and tests/seed2d_model.py reproduce the positions to
+// the bit (a sampled region's field is read by mpm_math.h's sampler, which forbids the same for itself)
 #define SEED_NO_CONTRACT _Pragma("clang fp contract(off)")
 
 constexpr int SEED_WG = 256;            // lanes per workgroup
@@ -27,7 +27,8 @@ constexpr int SEED_PER_WG = SEED_WG * SEED_ROUNDS;
 constexpr int SEED_WORDS = SEED_PER_WG / 64;  // ballot words per workgroup
 constexpr int SEED_SCAN_WG = 1024;
 
-// where a 3D region's level set is negative: shapes, or (sdf.phi0 != null) one sampled frame
+// where a region's level set is negative: shapes, or (sdf.phi0 != null) one frame of a sampled field read by the boundary's own
+// sampler (mpm_math.h: sdf_locate, sdf_phi_frame), so the seeding and the boundary decide alike for one array
 struct SeedRegion {
   int n_shapes;
   ShapeDev s[MPMHIP_MAX_SHAPES];
@@ -37,52 +38,27 @@ struct SeedRegion {
     if (sdf.phi0) {
       int c[3];
       float f[3];
-      if (!sdf_locate(sdf, x, c, f)) return false;  // outside the lattice: not in the region
-      return sdf_phi_frame(sdf, sdf.phi0, c, f) < 0.0f;
+      if (!sdf_locate<3>(sdf, x, c, f)) return false;  // outside the lattice: not in the region
+      return sdf_phi_frame<3>(sdf, sdf.phi0, c, f) < 0.0f;
     }
     float phi, n[3];
     return levelset_eval_key(s, n_shapes, x, idx, phi, n) && phi < 0.0f;
   }
 };
 
-// a sampled 2D region: phi [res0][res1] (the last axis fastest) in world units, sample (0, 0) at `origin`, one `spacing`
-struct Sdf2Dev {
-  const float *phi;
-  int res[2];
-  float origin[2];
-  float spacing, inv_spacing;
-};
-
-// where a 2D region's level set is negative: shapes read in the plane (as mpmhip2d_set_levelset stores them), or (sdf.phi != null)
-// a sampled field
+// the same in the plane: shapes read as mpmhip2d_set_levelset stores them, or a field phi [res0][res1]
 struct SeedRegion2 {
   int n_shapes;
   ShapeDev s[MPMHIP_MAX_SHAPES];
-  Sdf2Dev sdf;
-
-  // the 3D sampler's rules (mpm_math.h: sdf_locate, sdf_phi_frame) with one axis fewer: bilinear, the last axis first; a point
-  // outside the lattice is not in the region
-  __device__ __forceinline__ bool inside_sdf(const float x[2]) const {
-    SEED_NO_CONTRACT
-    bool in = true;
-    int c[2];
-    float f[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-      const float u = (x[k] - sdf.origin[k]) * sdf.inv_spacing;
-      in = in && u >= 0.0f && u <= (float)(sdf.res[k] - 1);  // (false for a NaN)
-      c[k] = min(max((int)u, 0), sdf.res[k] - 2);
-      f[k] = u - (float)c[k];
-    }
-    if (!in) return false;
-    const float *p = sdf.phi + (size_t)c[0] * sdf.res[1] + c[1];
-    const float a = sdf_lerp(p[0], p[1], f[1]);
-    const float b = sdf_lerp(p[sdf.res[1]], p[sdf.res[1] + 1], f[1]);
-    return sdf_lerp(a, b, f[0]) < 0.0f;
-  }
+  SdfDev sdf;
 
   __device__ __forceinline__ bool inside(const float x[2], float idx) const {
-    if (sdf.phi) return inside_sdf(x);
+    if (sdf.phi0) {
+      int c[2];
+      float f[2];
+      if (!sdf_locate<2>(sdf, x, c, f)) return false;
+      return sdf_phi_frame<2>(sdf, sdf.phi0, c, f) < 0.0f;
+    }
     const float xw[3] = {x[0], x[1], 0.0f};
     float phi, n[3];
     return levelset_eval_key(s, n_shapes, xw, idx, phi, n) && phi < 0.0f;

@@ -20,15 +20,9 @@ int msdf_reserve(mpmhip_ctx *c, DevBuf<uint32_t> &p, size_t &cap, size_t count) 
 // argument checks shared by the two entry points; fills L
 int msdf_check_args(mpmhip_ctx *c, const char *who, const mpmhip_sdf_desc *d, int32_t n_tri, const float *tri, float band, MeshLattice &L) {
   if (!d || !tri) return fail(c, MPMHIP_EINVAL, "%s: the lattice description and the triangles are required", who);
-  size_t count = 1;
-  for (int k = 0; k < 3; k++) {
-    if (d->res[k] < 2) return fail(c, MPMHIP_EINVAL, "%s: res[%d] = %d, at least 2 samples per axis are needed", who, k, d->res[k]);
-    if (!std::isfinite(d->origin[k])) return fail(c, MPMHIP_EINVAL, "%s: origin[%d] is not finite", who, k);
-    count *= (size_t)d->res[k];
-    L.res[k] = d->res[k]; L.origin[k] = d->origin[k]; L.tiles[k] = (d->res[k] + 7) / 8;
-  }
-  if (!(d->spacing > 0.0f) || !std::isfinite(d->spacing)) return fail(c, MPMHIP_EINVAL, "%s: spacing must be a finite number > 0", who);
-  if (count > ((size_t)1 << 31)) return fail(c, MPMHIP_EINVAL, "%s: more than 2^31 samples", who);
+  std::string why;
+  if (!sdf_lattice::check<3>(d->res, d->origin, d->spacing, why)) return fail(c, MPMHIP_EINVAL, "%s: %s", who, why.c_str());
+  for (int k = 0; k < 3; k++) { L.res[k] = d->res[k]; L.origin[k] = d->origin[k]; L.tiles[k] = (d->res[k] + 7) / 8; }
   L.spacing = d->spacing;
   L.words = d->res[2] / 32 + 1;
   if (L.words > 256) return fail(c, MPMHIP_EINVAL, "%s: res[2] = %d, the column pass holds at most 8191 samples per column", who, d->res[2]);
@@ -153,8 +147,8 @@ int mpmhip_set_levelset_mesh(mpmhip_ctx *c, const mpmhip_sdf_desc *d, int32_t n_
   if (!rc && tri1) rc = msdf_verdict(c, c->mesh_work[1], c->stream, "set_levelset_mesh", " of the second key frame");
   if (rc) return rc;  // (msdf_verdict synchronised the stream: no kernel in flight reads the arrays below)
   if ((rc = sdf_reserve(c, d, tri1 != nullptr))) return rc;
-  if ((rc = msdf_distance(c, c->mesh_work[0], c->stream, L, band, c->d_sdf[0]))) return rc;
-  if (tri1 && (rc = msdf_distance(c, c->mesh_work[1], c->stream, L, band, c->d_sdf[1]))) return rc;
+  if ((rc = msdf_distance(c, c->mesh_work[0], c->stream, L, band, c->sdf.frame[0]))) return rc;
+  if (tri1 && (rc = msdf_distance(c, c->mesh_work[1], c->stream, L, band, c->sdf.frame[1]))) return rc;
   return sdf_install(c, d, tri1 != nullptr, t0, t1, friction);
 }
 
@@ -164,10 +158,10 @@ int mpmhip_download_levelset_sdf(mpmhip_ctx *c, int32_t frame, float *dst, int64
   if (!dst) return fail(c, MPMHIP_EINVAL, "download_levelset_sdf: the destination is required");
   if (!c->LS.sdf.phi0) return fail(c, MPMHIP_EINVAL, "download_levelset_sdf: no sampled level set is installed");
   if (frame < 0 || frame > 1 || (frame == 1 && !c->LS.sdf.phi1)) return fail(c, MPMHIP_EINVAL, "download_levelset_sdf: there is no key frame %d", frame);
-  if (capacity < (int64_t)c->sdf_count)
-    return fail(c, MPMHIP_EINVAL, "download_levelset_sdf: room for %lld samples, the set has %zu", (long long)capacity, c->sdf_count);
+  if (capacity < (int64_t)c->sdf.count)
+    return fail(c, MPMHIP_EINVAL, "download_levelset_sdf: room for %lld samples, the set has %zu", (long long)capacity, c->sdf.count);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(dst, c->d_sdf[frame], sizeof(float) * c->sdf_count, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(dst, c->sdf.frame[frame], sizeof(float) * c->sdf.count, hipMemcpyDeviceToHost));
   return MPMHIP_OK;
 }

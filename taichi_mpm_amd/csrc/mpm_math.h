@@ -806,35 +806,46 @@ __device__ __forceinline__ bool levelset_eval(const LevelSetDev &L, float t, con
   return true;
 }
 
-// ---- the sampled level set
-// No multiply-add of the sampler may be fused: every kernel that inlines it (both walks of the grid pass, the collision pass, the
-// deletion, the test entry) then computes the same bits for the same point, whatever its surroundings make the compiler prefer — the
-// walks agree bitwise and a particle is inside for one kernel exactly when it is for another — and tests/sdf_model.py reproduces
-// the device to the bit.
+// ---- the sampled level set, in space (D = 3) and in the plane (D = 2: mpmhip2d_set_levelset_sdf and the 2D seeding; such a set is
+// an SdfDev whose res[2] is 1 and whose third origin / off entries are unused, phi [res0][res1]).  One sampler serves every reader of
+// either dimension: the seeding and the boundary decide phi < 0 identically for one array because they run the same code.
+// No multiply-add of the sampler may be fused: every kernel that inlines it (both walks of the grid pass, the collision passes, the
+// deletion, the seeding, the test entries) then computes the same bits for the same point, whatever its surroundings make the
+// compiler prefer — the walks agree bitwise and a particle is inside for one kernel exactly when it is for another — and
+// tests/sdf_model.py reproduces the device to the bit.
 #define SDF_NO_CONTRACT _Pragma("clang fp contract(off)")
-__device__ __forceinline__ float sdf_at(const SdfDev &S, const float *__restrict__ p, int i, int j, int k) {
-  return p[((size_t)i * S.res[1] + j) * S.res[2] + k];
+template <int D>
+__device__ __forceinline__ float sdf_at(const SdfDev &S, const float *__restrict__ p, const int i[D]) {
+  size_t at = (size_t)i[0];
+#pragma unroll
+  for (int k = 1; k < D; k++) at = at * S.res[k] + i[k];
+  return p[at];
 }
-// central-difference gradient of the sample (i, j, k), one-sided on the array's faces; d phi / d x, dimensionless
-__device__ __forceinline__ void sdf_sample_grad(const SdfDev &S, const float *__restrict__ p, int i, int j, int k, float g[3]) {
+// central-difference gradient of the sample i, one-sided on the array's faces; d phi / d x, dimensionless
+template <int D>
+__device__ __forceinline__ void sdf_sample_grad(const SdfDev &S, const float *__restrict__ p, const int i[D], float g[D]) {
   SDF_NO_CONTRACT
-  const int im = max(i - 1, 0), ip = min(i + 1, S.res[0] - 1), jm = max(j - 1, 0), jp = min(j + 1, S.res[1] - 1);
-  const int km = max(k - 1, 0), kp = min(k + 1, S.res[2] - 1);
-  g[0] = (sdf_at(S, p, ip, j, k) - sdf_at(S, p, im, j, k)) * ((ip - im == 2 ? 0.5f : 1.0f) * S.inv_spacing);
-  g[1] = (sdf_at(S, p, i, jp, k) - sdf_at(S, p, i, jm, k)) * ((jp - jm == 2 ? 0.5f : 1.0f) * S.inv_spacing);
-  g[2] = (sdf_at(S, p, i, j, kp) - sdf_at(S, p, i, j, km)) * ((kp - km == 2 ? 0.5f : 1.0f) * S.inv_spacing);
+#pragma unroll
+  for (int a = 0; a < D; a++) {
+    int lo[D], hi[D];
+#pragma unroll
+    for (int k = 0; k < D; k++) lo[k] = hi[k] = i[k];
+    lo[a] = max(i[a] - 1, 0); hi[a] = min(i[a] + 1, S.res[a] - 1);
+    g[a] = (sdf_at<D>(S, p, hi) - sdf_at<D>(S, p, lo)) * ((hi[a] - lo[a] == 2 ? 0.5f : 1.0f) * S.inv_spacing);
+  }
 }
 __device__ __forceinline__ float sdf_lerp(float a, float b, float f) {
   SDF_NO_CONTRACT
   return (1.0f - f) * a + f * b;
 }
-// the cell c (its lowest sample) that holds x and the position f in [0, 1]^3 inside it; false: x lies outside the lattice on some
+// the cell c (its lowest sample) that holds x and the position f in [0, 1]^D inside it; false: x lies outside the lattice on some
 // axis — there is no level set there, nothing is extrapolated
-__device__ __forceinline__ bool sdf_locate(const SdfDev &S, const float x[3], int c[3], float f[3]) {
+template <int D>
+__device__ __forceinline__ bool sdf_locate(const SdfDev &S, const float x[D], int c[D], float f[D]) {
   SDF_NO_CONTRACT
   bool in = true;
 #pragma unroll
-  for (int k = 0; k < 3; k++) {
+  for (int k = 0; k < D; k++) {
     const float u = (x[k] - S.origin[k]) * S.inv_spacing;
     in = in && u >= 0.0f && u <= (float)(S.res[k] - 1);  // (false for a NaN)
     c[k] = min(max((int)u, 0), S.res[k] - 2);
@@ -842,49 +853,53 @@ __device__ __forceinline__ bool sdf_locate(const SdfDev &S, const float x[3], in
   }
   return in;
 }
-// trilinear interpolation of one key frame in the cell c: the last axis first, the first axis last
-__device__ __forceinline__ float sdf_phi_frame(const SdfDev &S, const float *__restrict__ p, const int c[3], const float f[3]) {
+// multilinear interpolation of one key frame in the cell c: the last axis first, the first axis last.  A call reduces the axes
+// A .. D-1 at the corner whose bit k says which of the two samples axis k < A takes; each pair is interpolated as soon as it is read.
+template <int D, int A = 0>
+__device__ __forceinline__ float sdf_phi_frame(const SdfDev &S, const float *__restrict__ p, const int c[D], const float f[D],
+                                               int corner = 0) {
   SDF_NO_CONTRACT
-  float a[2];
+  if constexpr (A == D) {
+    int i[D];
 #pragma unroll
-  for (int i = 0; i < 2; i++) {
-    float b[2];
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-      b[j] = sdf_lerp(sdf_at(S, p, c[0] + i, c[1] + j, c[2]), sdf_at(S, p, c[0] + i, c[1] + j, c[2] + 1), f[2]);
-    a[i] = sdf_lerp(b[0], b[1], f[1]);
+    for (int k = 0; k < D; k++) i[k] = c[k] + ((corner >> k) & 1);
+    return sdf_at<D>(S, p, i);
+  } else {
+    const float lo = sdf_phi_frame<D, A + 1>(S, p, c, f, corner);
+    const float hi = sdf_phi_frame<D, A + 1>(S, p, c, f, corner | 1 << A);
+    return sdf_lerp(lo, hi, f[A]);
   }
-  return sdf_lerp(a[0], a[1], f[0]);
 }
-__device__ __forceinline__ void sdf_normalize(float g[3]) {
+template <int D>
+__device__ __forceinline__ void sdf_normalize(float g[D]) {
   SDF_NO_CONTRACT
-  const float len = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+  float s = g[0] * g[0];
+#pragma unroll
+  for (int k = 1; k < D; k++) s = s + g[k] * g[k];
+  const float len = sqrtf(s);
   const float inv = len < 1e-10f ? 0.0f : 1.0f / len;
-  g[0] *= inv; g[1] *= inv; g[2] *= inv;
+#pragma unroll
+  for (int k = 0; k < D; k++) g[k] *= inv;
 }
-// unit gradient of one key frame: the eight samples' central-difference gradients interpolated like phi, then normalised (second
-// order on curved surfaces; the derivative of the trilinear interpolant itself is first order)
-__device__ __forceinline__ void sdf_grad_frame(const SdfDev &S, const float *__restrict__ p, const int c[3], const float f[3],
-                                               float n[3]) {
+// unit gradient of one key frame: the 2^D samples' central-difference gradients interpolated like phi, then (A = 0, the caller's
+// instance) normalised (second order on curved surfaces; the derivative of the multilinear interpolant itself is first order)
+template <int D, int A = 0>
+__device__ __forceinline__ void sdf_grad_frame(const SdfDev &S, const float *__restrict__ p, const int c[D], const float f[D], float n[D],
+                                               int corner = 0) {
   SDF_NO_CONTRACT
-  float a[2][3];
+  if constexpr (A == D) {
+    int i[D];
 #pragma unroll
-  for (int i = 0; i < 2; i++) {
-    float b[2][3];
+    for (int k = 0; k < D; k++) i[k] = c[k] + ((corner >> k) & 1);
+    sdf_sample_grad<D>(S, p, i, n);
+  } else {
+    float hi[D];
+    sdf_grad_frame<D, A + 1>(S, p, c, f, n, corner);
+    sdf_grad_frame<D, A + 1>(S, p, c, f, hi, corner | 1 << A);
 #pragma unroll
-    for (int j = 0; j < 2; j++) {
-      float g0[3], g1[3];
-      sdf_sample_grad(S, p, c[0] + i, c[1] + j, c[2], g0);
-      sdf_sample_grad(S, p, c[0] + i, c[1] + j, c[2] + 1, g1);
-#pragma unroll
-      for (int d = 0; d < 3; d++) b[j][d] = sdf_lerp(g0[d], g1[d], f[2]);
-    }
-#pragma unroll
-    for (int d = 0; d < 3; d++) a[i][d] = sdf_lerp(b[0][d], b[1][d], f[1]);
+    for (int d = 0; d < D; d++) n[d] = sdf_lerp(n[d], hi[d], f[A]);
+    if constexpr (A == 0) sdf_normalize<D>(n);
   }
-#pragma unroll
-  for (int d = 0; d < 3; d++) n[d] = sdf_lerp(a[0][d], a[1][d], f[0]);
-  sdf_normalize(n);
 }
 // phi at time t in grid units (and d phi / dt) from the two frames' values in world units — the blend of levelset_eval
 __device__ __forceinline__ float sdf_blend_phi(const SdfDev &S, float t, float idx, float p0, float p1, float *dphidt) {
@@ -894,40 +909,43 @@ __device__ __forceinline__ float sdf_blend_phi(const SdfDev &S, float t, float i
   if (dphidt) *dphidt = (p1 - p0) / (S.t1 - S.t0);
   return (1.0f - a) * p0 + a * p1;
 }
-__device__ __forceinline__ void sdf_blend_normal(const SdfDev &S, float t, float n[3], const float n1[3]) {
+template <int D>
+__device__ __forceinline__ void sdf_blend_normal(const SdfDev &S, float t, float n[D], const float n1[D]) {
   SDF_NO_CONTRACT
   const float a = (t - S.t0) / (S.t1 - S.t0);
 #pragma unroll
-  for (int d = 0; d < 3; d++) n[d] = n[d] * (1.0f - a) + n1[d] * a;
-  sdf_normalize(n);
+  for (int d = 0; d < D; d++) n[d] = n[d] * (1.0f - a) + n1[d] * a;
+  sdf_normalize<D>(n);
 }
 // phi (grid units) in the located cell, and the unit normal there
-__device__ __forceinline__ float sdf_phi(const SdfDev &S, float t, float idx, const int c[3], const float f[3],
-                                         float *dphidt = nullptr) {
+template <int D>
+__device__ __forceinline__ float sdf_phi(const SdfDev &S, float t, float idx, const int c[D], const float f[D], float *dphidt = nullptr) {
   SDF_NO_CONTRACT
   if (dphidt) *dphidt = 0.0f;
-  const float p0 = sdf_phi_frame(S, S.phi0, c, f);
+  const float p0 = sdf_phi_frame<D>(S, S.phi0, c, f);
   if (!S.phi1) return p0 * idx;
-  return sdf_blend_phi(S, t, idx, p0, sdf_phi_frame(S, S.phi1, c, f), dphidt);
+  return sdf_blend_phi(S, t, idx, p0, sdf_phi_frame<D>(S, S.phi1, c, f), dphidt);
 }
-__device__ __forceinline__ void sdf_normal(const SdfDev &S, float t, const int c[3], const float f[3], float n[3]) {
+template <int D>
+__device__ __forceinline__ void sdf_normal(const SdfDev &S, float t, const int c[D], const float f[D], float n[D]) {
   SDF_NO_CONTRACT
-  sdf_grad_frame(S, S.phi0, c, f, n);
+  sdf_grad_frame<D>(S, S.phi0, c, f, n);
   if (!S.phi1) return;
-  float n1[3];
-  sdf_grad_frame(S, S.phi1, c, f, n1);
-  sdf_blend_normal(S, t, n, n1);
+  float n1[D];
+  sdf_grad_frame<D>(S, S.phi1, c, f, n1);
+  sdf_blend_normal<D>(S, t, n, n1);
 }
 // levelset_eval for a sampled set
-__device__ __forceinline__ bool sdf_eval(const SdfDev &S, float t, const float x[3], float idx, float &phi, float n[3],
+template <int D>
+__device__ __forceinline__ bool sdf_eval(const SdfDev &S, float t, const float x[D], float idx, float &phi, float n[D],
                                          float *dphidt = nullptr) {
   SDF_NO_CONTRACT
   if (dphidt) *dphidt = 0.0f;
-  int c[3];
-  float f[3];
-  if (!sdf_locate(S, x, c, f)) return false;
-  phi = sdf_phi(S, t, idx, c, f, dphidt);
-  sdf_normal(S, t, c, f, n);
+  int c[D];
+  float f[D];
+  if (!sdf_locate<D>(S, x, c, f)) return false;
+  phi = sdf_phi<D>(S, t, idx, c, f, dphidt);
+  sdf_normal<D>(S, t, c, f, n);
   return true;
 }
 // The grid pass at the node (gi, gj, gk) of a lattice-aligned set: one load per key frame, the band test -3 <= phi <= 0 first, and
@@ -939,16 +957,17 @@ __device__ __forceinline__ bool sdf_node_in_band(const SdfDev &S, float t, int g
   const int i = gi + S.off[0], j = gj + S.off[1], k = gk + S.off[2];
   if ((unsigned)i >= (unsigned)S.res[0] || (unsigned)j >= (unsigned)S.res[1] || (unsigned)k >= (unsigned)S.res[2]) return false;
   dphidt = 0.0f;
-  const float p0 = sdf_at(S, S.phi0, i, j, k);
-  phi = S.phi1 ? sdf_blend_phi(S, t, idx, p0, sdf_at(S, S.phi1, i, j, k), &dphidt) : p0 * idx;
+  const int s[3] = {i, j, k};
+  const float p0 = sdf_at<3>(S, S.phi0, s);
+  phi = S.phi1 ? sdf_blend_phi(S, t, idx, p0, sdf_at<3>(S, S.phi1, s), &dphidt) : p0 * idx;
   if (phi < -3.0f || 0.0f < phi) return false;
-  sdf_sample_grad(S, S.phi0, i, j, k, n);
-  sdf_normalize(n);
+  sdf_sample_grad<3>(S, S.phi0, s, n);
+  sdf_normalize<3>(n);
   if (S.phi1) {
     float n1[3];
-    sdf_sample_grad(S, S.phi1, i, j, k, n1);
-    sdf_normalize(n1);
-    sdf_blend_normal(S, t, n, n1);
+    sdf_sample_grad<3>(S, S.phi1, s, n1);
+    sdf_normalize<3>(n1);
+    sdf_blend_normal<3>(S, t, n, n1);
   }
   return true;
 }
@@ -969,97 +988,11 @@ __device__ __forceinline__ void friction_project_exact(float v[3], const float v
   v[1] = ts * t1 + keep * n[1] + vb[1];
   v[2] = ts * t2 + keep * n[2] + vb[2];
 }
-
-// ---- the sampled level set in the plane (mpmhip2d_set_levelset_sdf): the rules above with one axis fewer.  The set is an SdfDev
-// whose res[2] is 1 and whose third origin / off entries are unused: phi [res0][res1], the last axis fastest.  Bilinear, the last
-// axis first — the order of SeedRegion2::inside_sdf (k_seed.h), so the seeding and the boundary decide phi < 0 identically for one
-// array (the grid-unit factor idx > 0 keeps the sign).
-__device__ __forceinline__ float sdf2_at(const SdfDev &S, const float *__restrict__ p, int i, int j) {
-  return p[(size_t)i * S.res[1] + j];
-}
-__device__ __forceinline__ void sdf2_sample_grad(const SdfDev &S, const float *__restrict__ p, int i, int j, float g[2]) {
-  SDF_NO_CONTRACT
-  const int im = max(i - 1, 0), ip = min(i + 1, S.res[0] - 1), jm = max(j - 1, 0), jp = min(j + 1, S.res[1] - 1);
-  g[0] = (sdf2_at(S, p, ip, j) - sdf2_at(S, p, im, j)) * ((ip - im == 2 ? 0.5f : 1.0f) * S.inv_spacing);
-  g[1] = (sdf2_at(S, p, i, jp) - sdf2_at(S, p, i, jm)) * ((jp - jm == 2 ? 0.5f : 1.0f) * S.inv_spacing);
-}
-__device__ __forceinline__ bool sdf2_locate(const SdfDev &S, const float x[2], int c[2], float f[2]) {
-  SDF_NO_CONTRACT
-  bool in = true;
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const float u = (x[k] - S.origin[k]) * S.inv_spacing;
-    in = in && u >= 0.0f && u <= (float)(S.res[k] - 1);  // (false for a NaN)
-    c[k] = min(max((int)u, 0), S.res[k] - 2);
-    f[k] = u - (float)c[k];
-  }
-  return in;
-}
-__device__ __forceinline__ float sdf2_phi_frame(const SdfDev &S, const float *__restrict__ p, const int c[2], const float f[2]) {
-  SDF_NO_CONTRACT
-  const float a = sdf_lerp(sdf2_at(S, p, c[0], c[1]), sdf2_at(S, p, c[0], c[1] + 1), f[1]);
-  const float b = sdf_lerp(sdf2_at(S, p, c[0] + 1, c[1]), sdf2_at(S, p, c[0] + 1, c[1] + 1), f[1]);
-  return sdf_lerp(a, b, f[0]);
-}
-__device__ __forceinline__ void sdf2_normalize(float g[2]) {
-  SDF_NO_CONTRACT
-  const float len = sqrtf(g[0] * g[0] + g[1] * g[1]);
-  const float inv = len < 1e-10f ? 0.0f : 1.0f / len;
-  g[0] *= inv; g[1] *= inv;
-}
-// unit gradient of one key frame: the four samples' central-difference gradients interpolated like phi, then normalised
-__device__ __forceinline__ void sdf2_grad_frame(const SdfDev &S, const float *__restrict__ p, const int c[2], const float f[2],
-                                                float n[2]) {
-  SDF_NO_CONTRACT
-  float a[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    float g0[2], g1[2];
-    sdf2_sample_grad(S, p, c[0] + i, c[1], g0);
-    sdf2_sample_grad(S, p, c[0] + i, c[1] + 1, g1);
-#pragma unroll
-    for (int d = 0; d < 2; d++) a[i][d] = sdf_lerp(g0[d], g1[d], f[1]);
-  }
-#pragma unroll
-  for (int d = 0; d < 2; d++) n[d] = sdf_lerp(a[0][d], a[1][d], f[0]);
-  sdf2_normalize(n);
-}
-// phi (grid units) in the located cell, and the unit normal there; two key frames blend as sdf_blend_phi / sdf_blend_normal do
-__device__ __forceinline__ float sdf2_phi(const SdfDev &S, float t, float idx, const int c[2], const float f[2],
-                                          float *dphidt = nullptr) {
-  SDF_NO_CONTRACT
-  if (dphidt) *dphidt = 0.0f;
-  const float p0 = sdf2_phi_frame(S, S.phi0, c, f);
-  if (!S.phi1) return p0 * idx;
-  return sdf_blend_phi(S, t, idx, p0, sdf2_phi_frame(S, S.phi1, c, f), dphidt);
-}
-__device__ __forceinline__ void sdf2_normal(const SdfDev &S, float t, const int c[2], const float f[2], float n[2]) {
-  SDF_NO_CONTRACT
-  sdf2_grad_frame(S, S.phi0, c, f, n);
-  if (!S.phi1) return;
-  float n1[2];
-  sdf2_grad_frame(S, S.phi1, c, f, n1);
-  const float a = (t - S.t0) / (S.t1 - S.t0);
-#pragma unroll
-  for (int d = 0; d < 2; d++) n[d] = n[d] * (1.0f - a) + n1[d] * a;
-  sdf2_normalize(n);
-}
-__device__ __forceinline__ bool sdf2_eval(const SdfDev &S, float t, const float x[2], float idx, float &phi, float n[2],
-                                          float *dphidt = nullptr) {
-  SDF_NO_CONTRACT
-  if (dphidt) *dphidt = 0.0f;
-  int c[2];
-  float f[2];
-  if (!sdf2_locate(S, x, c, f)) return false;
-  phi = sdf2_phi(S, t, idx, c, f, dphidt);
-  sdf2_normal(S, t, c, f, n);
-  return true;
-}
 #undef SDF_NO_CONTRACT
 // whichever level set is installed
 __device__ __forceinline__ bool levelset_eval_any(const LevelSetDev &L, float t, const float x[3], float idx, float &phi,
                                                   float n[3], float *dphidt = nullptr) {
-  if (L.sdf.phi0) return sdf_eval(L.sdf, t, x, idx, phi, n, dphidt);
+  if (L.sdf.phi0) return sdf_eval<3>(L.sdf, t, x, idx, phi, n, dphidt);
   return levelset_eval(L, t, x, idx, phi, n, dphidt);
 }
 

@@ -82,6 +82,7 @@
 #include "host_mem.h"
 #include "record_state.h"
 #include "launch_plan.h"
+#include "sdf_lattice.h"
 #include "mpm_common.h"
 #include "k_sort.h"
 #include "k_particles.h"
@@ -196,6 +197,42 @@ static thread_local std::string g_create_error;
 
 enum { PH_SORT = 0, PH_P2G = 1, PH_EXCH = 2, PH_GRID = 3, PH_G2P = 4, PH_COUNT = 5 };
 
+// A ctx's device copies of its sampled level set's key frames (mpmhip_set_levelset_sdf, mpmhip2d_set_levelset_sdf), [count] floats
+// each.  They live until the lattice's size changes, shapes replace the set, or the ctx goes; the ctx's LS.sdf points at them while
+// the set is installed.
+struct SdfFrames {
+  DevBuf<float> frame[2];
+  size_t count = 0;
+  void release() {
+    frame[0].reset(); frame[1].reset();
+    count = 0;
+  }
+  // arrays for a set of n samples: a set of the installed one's size keeps its memory; any other takes S, which points into the old
+  // arrays, down with them first.  The stream must be idle (kernels in flight read the arrays).
+  hipError_t reserve(SdfDev &S, size_t n, bool two) {
+    if (n != count) {
+      release();
+      memset(&S, 0, sizeof S);
+      if (hipError_t e = frame[0].alloc(n); e != hipSuccess) return e;
+      count = n;
+    }
+    return two && !frame[1] ? frame[1].alloc(n) : hipSuccess;
+  }
+};
+
+// the lattice of a description (mpmhip_sdf_desc: D = 3, mpmhip2d_sdf_desc: D = 2) and its key frames as the kernels read them; a set
+// in the plane has res[2] = 1.  `aligned` and `off` are left as they are: only the 3D grid pass knows them (sdf_install).
+template <int D, class Desc>
+static void sdf_fill(SdfDev &S, const Desc &d, const float *phi0, const float *phi1, float t0, float t1) {
+  S.phi0 = phi0; S.phi1 = phi1;
+  for (int k = 0; k < 3; k++) {
+    S.res[k] = k < D ? d.res[k] : 1;
+    if (k < D) S.origin[k] = d.origin[k];
+  }
+  S.spacing = d.spacing; S.inv_spacing = 1.0f / d.spacing;
+  S.t0 = phi1 ? t0 : 0.0f; S.t1 = phi1 ? t1 : 1.0f;
+}
+
 struct mpmhip_ctx {
   mpmhip_config cfg;
   Params P;
@@ -257,10 +294,7 @@ struct mpmhip_ctx {
   // tiling
   LevelSetDev LS;
   DevBuf<LevelSetDev> d_LS;  // device copy for k_g2p (k_grid takes it by value)
-  // sampled level set (mpmhip_set_levelset_sdf): this ctx's device copies of the key frames, [sdf_count] floats each; they live until
-  // the lattice changes, shapes replace the set, or the ctx goes (LS.sdf points at them while the set is installed)
-  DevBuf<float> d_sdf[2];
-  size_t sdf_count = 0;
+  SdfFrames sdf;            // mpmhip_set_levelset_sdf / _mesh: the installed sampled level set's key frames
   SeedWork seed;            // mpmhip_seed_particles: the tile and the work buffers, kept between calls (seed_api.h)
   MeshSdfWork mesh_work[2];  // mpmhip_set_levelset_mesh: the voxeliser's buffers per key frame, kept between calls
   int particle_collision_cfg = 0;  // the config's particle_collision.  P.particle_collision is 0 while a sampled set is installed:
@@ -751,14 +785,13 @@ int mpmhip_set_dirichlet(mpmhip_ctx *c, int32_t enabled) {
 }
 
 static void sdf_release(mpmhip_ctx *c) {
-  c->d_sdf[0].reset(); c->d_sdf[1].reset();
-  c->sdf_count = 0;
+  c->sdf.release();
   memset(&c->LS.sdf, 0, sizeof c->LS.sdf);
   c->P.particle_collision = c->particle_collision_cfg;
 }
 
-int mpmhip_set_levelset_shapes(mpmhip_ctx *c, int32_t n, const mpmhip_shape *shapes, float friction) {
-  if (!c || n < 0 || n > MPMHIP_MAX_SHAPES || (n > 0 && !shapes)) return MPMHIP_EINVAL;
+static int check_shapes(mpmhip_ctx *c, int32_t n, const mpmhip_shape *shapes) {
+  if (n < 0 || n > MPMHIP_MAX_SHAPES || (n > 0 && !shapes)) return fail(c, MPMHIP_EINVAL, "between 0 and %d level-set shapes", MPMHIP_MAX_SHAPES);
   for (int i = 0; i < n; i++) {
     if (shapes[i].type < 0 || shapes[i].type > 2) return fail(c, MPMHIP_EINVAL, "shape %d: unknown type %d", i, shapes[i].type);
     if (shapes[i].type == 1 && !(shapes[i].p[3] > 0)) return fail(c, MPMHIP_EINVAL, "shape %d: sphere radius must be > 0", i);
@@ -766,6 +799,13 @@ int mpmhip_set_levelset_shapes(mpmhip_ctx *c, int32_t n, const mpmhip_shape *sha
       for (int k = 0; k < 3; k++)
         if (!(shapes[i].p[k] < shapes[i].p[3 + k])) return fail(c, MPMHIP_EINVAL, "shape %d: cuboid needs lo < hi", i);
   }
+  return MPMHIP_OK;
+}
+
+int mpmhip_set_levelset_shapes(mpmhip_ctx *c, int32_t n, const mpmhip_shape *shapes, float friction) {
+  // (a bad count or a missing array is refused without a message here; check_shapes words it for the other entries)
+  if (!c || n < 0 || n > MPMHIP_MAX_SHAPES || (n > 0 && !shapes)) return MPMHIP_EINVAL;
+  if (int rc = check_shapes(c, n, shapes)) return rc;
   if (c->LS.sdf.phi0) {  // shapes replace a sampled set: nothing of it survives
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -787,18 +827,6 @@ int mpmhip_set_levelset_shapes(mpmhip_ctx *c, int32_t n, const mpmhip_shape *sha
   return MPMHIP_OK;
 }
 
-static int check_shapes(mpmhip_ctx *c, int32_t n, const mpmhip_shape *shapes) {
-  if (n < 0 || n > MPMHIP_MAX_SHAPES || (n > 0 && !shapes)) return fail(c, MPMHIP_EINVAL, "between 0 and %d level-set shapes", MPMHIP_MAX_SHAPES);
-  for (int i = 0; i < n; i++) {
-    if (shapes[i].type < 0 || shapes[i].type > 2) return fail(c, MPMHIP_EINVAL, "shape %d: unknown type %d", i, shapes[i].type);
-    if (shapes[i].type == 1 && !(shapes[i].p[3] > 0)) return fail(c, MPMHIP_EINVAL, "shape %d: sphere radius must be > 0", i);
-    if (shapes[i].type == 2)
-      for (int k = 0; k < 3; k++)
-        if (!(shapes[i].p[k] < shapes[i].p[3 + k])) return fail(c, MPMHIP_EINVAL, "shape %d: cuboid needs lo < hi", i);
-  }
-  return MPMHIP_OK;
-}
-
 int mpmhip_set_levelset_keyframes(mpmhip_ctx *c, float t0, float t1, int32_t n0, const mpmhip_shape *shapes0, int32_t n1,
                                   const mpmhip_shape *shapes1, float friction) {
   if (!c) return MPMHIP_EINVAL;
@@ -816,32 +844,19 @@ int mpmhip_set_levelset_keyframes(mpmhip_ctx *c, float t0, float t1, int32_t n0,
   return MPMHIP_OK;
 }
 
-// device arrays for a sampled set of d's lattice: a lattice of the installed set's size keeps its memory.  The stream must be idle
-// (kernels in flight read the arrays).
+// device arrays for a sampled set of d's lattice (a static set keeps a second frame it already has: the next dynamic one reuses it)
 static int sdf_reserve(mpmhip_ctx *c, const mpmhip_sdf_desc *d, bool two) {
-  const size_t count = (size_t)d->res[0] * d->res[1] * d->res[2];
-  if (count != c->sdf_count) {
-    c->d_sdf[0].reset(); c->d_sdf[1].reset();
-    c->sdf_count = 0;
-    c->LS.sdf.phi0 = c->LS.sdf.phi1 = nullptr;
-    HIPCHK(c, c->d_sdf[0].alloc(count));
-    c->sdf_count = count;
-  }
-  if (two && !c->d_sdf[1]) HIPCHK(c, c->d_sdf[1].alloc(count));
+  HIPCHK(c, c->sdf.reserve(c->LS.sdf, (size_t)d->res[0] * d->res[1] * d->res[2], two));
   return MPMHIP_OK;
 }
 
-// c->d_sdf[0 / 1] hold the key frames: make them the ctx's level set
+// c->sdf.frame[0 / 1] hold the key frames: make them the ctx's level set
 static int sdf_install(mpmhip_ctx *c, const mpmhip_sdf_desc *d, bool two, float t0, float t1, float friction) {
   SdfDev &S = c->LS.sdf;
-  S.phi0 = c->d_sdf[0];
-  S.phi1 = two ? c->d_sdf[1] : nullptr;
-  S.spacing = d->spacing; S.inv_spacing = 1.0f / d->spacing;
-  S.t0 = two ? t0 : 0.0f; S.t1 = two ? t1 : 1.0f;
+  sdf_fill<3>(S, *d, c->sdf.frame[0], two ? c->sdf.frame[1].get() : nullptr, t0, t1);
   // the one-load path of the grid pass: same spacing as the grid and the origin on a node (to 1e-4 of a cell)
   S.aligned = d->spacing == c->P.dx;
   for (int k = 0; k < 3; k++) {
-    S.res[k] = d->res[k]; S.origin[k] = d->origin[k];
     const float o = d->origin[k] * c->P.idx, r = nearbyintf(o);
     if (!(fabsf(o - r) <= 1e-4f) || fabsf(r) > 65536.0f) S.aligned = 0;
     S.off[k] = S.aligned ? -(int)r : 0;
@@ -860,22 +875,17 @@ int mpmhip_set_levelset_sdf(mpmhip_ctx *c, const mpmhip_sdf_desc *d, const float
   if (!c) return MPMHIP_EINVAL;
   if (!d || !phi0) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: the lattice description and the first key frame are required");
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf inside a substep");
-  size_t count = 1;
-  for (int k = 0; k < 3; k++) {
-    if (d->res[k] < 2) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: res[%d] = %d, at least 2 samples per axis are needed", k, d->res[k]);
-    if (!std::isfinite(d->origin[k])) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: origin[%d] is not finite", k);
-    count *= (size_t)d->res[k];
-  }
-  if (!(d->spacing > 0.0f) || !std::isfinite(d->spacing)) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: spacing must be a finite number > 0");
-  if (count > ((size_t)1 << 31)) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: more than 2^31 samples");
+  std::string why;
+  const size_t count = sdf_lattice::check<3>(d->res, d->origin, d->spacing, why);
+  if (!count) return fail(c, MPMHIP_EINVAL, "set_levelset_sdf: %s", why.c_str());
   if (phi1 && !(t1 > t0)) return fail(c, MPMHIP_EINVAL, "key frame times must satisfy t0 < t1");
   if (c->rigid.ls_collision)
     return fail(c, MPMHIP_EINVAL, "rigid_body_levelset_collision is not supported with a sampled level set");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // (kernels in flight read the arrays)
   if (int rc = sdf_reserve(c, d, phi1 != nullptr)) return rc;
-  HIPCHK(c, hipMemcpy(c->d_sdf[0], phi0, sizeof(float) * count, hipMemcpyHostToDevice));
-  if (phi1) HIPCHK(c, hipMemcpy(c->d_sdf[1], phi1, sizeof(float) * count, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->sdf.frame[0], phi0, sizeof(float) * count, hipMemcpyHostToDevice));
+  if (phi1) HIPCHK(c, hipMemcpy(c->sdf.frame[1], phi1, sizeof(float) * count, hipMemcpyHostToDevice));
   return sdf_install(c, d, phi1 != nullptr, t0, t1, friction);
 }
 
@@ -2776,10 +2786,7 @@ int mpmhip_debug_allowed_dt(mpmhip_ctx *c, int32_t material, const float params[
 struct mpmhip2d_ctx {
   mpm2d::Params P{};
   LevelSetDev LS{};
-  // sampled level set (mpmhip2d_set_levelset_sdf): this ctx's device copies of the key frames, [sdf_count] floats each; LS.sdf
-  // points at them (res[2] = 1) while the set is installed, and then LS.n == 0
-  DevBuf<float> d_sdf[2];
-  size_t sdf_count = 0;
+  SdfFrames sdf;  // mpmhip2d_set_levelset_sdf: the installed sampled level set's key frames (LS.n == 0 while it is installed)
   int device = 0;
   int64_t n = 0, cap = 0;
   DevBuf<float> x, v, F, B, aux, grid;
@@ -2924,8 +2931,7 @@ int mpmhip2d_set_levelset(mpmhip2d_ctx *m, int32_t n0, const mpmhip_shape *shape
   HIPCHK2D(m, hipSetDevice(m->device));
   HIPCHK2D(m, hipStreamSynchronize(m->stream));
   LevelSetDev &L = m->LS;
-  m->d_sdf[0].reset(); m->d_sdf[1].reset();  // shapes replace a sampled set: nothing of it survives
-  m->sdf_count = 0;
+  m->sdf.release();  // shapes replace a sampled set: nothing of it survives
   memset(&L, 0, sizeof L);
   L.n = n0; L.friction = friction; L.dynamic = n1 >= 0; L.n1 = n1 >= 0 ? n1 : 0; L.t0 = t0; L.t1 = t1;
   auto put = [](ShapeDev &d, const mpmhip_shape &s) {
@@ -2946,42 +2952,23 @@ int mpmhip2d_set_levelset_sdf(mpmhip2d_ctx *m, const mpmhip2d_sdf_desc *d, const
                               float friction) {
   if (!m) return MPMHIP_EINVAL;
   if (!d || !phi0) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: the lattice description and the first key frame are required");
-  size_t count = 1;
-  for (int k = 0; k < 2; k++) {
-    if (d->res[k] < 2)
-      return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: res[" + std::to_string(k) + "] = " + std::to_string(d->res[k]) + ", at least 2 samples per axis are needed");
-    if (!std::isfinite(d->origin[k])) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: origin[" + std::to_string(k) + "] is not finite");
-    count *= (size_t)d->res[k];
-  }
-  if (!(d->spacing > 0.0f) || !std::isfinite(d->spacing)) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: spacing must be a finite number > 0");
-  if (count > ((size_t)1 << 31)) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: more than 2^31 samples");
+  std::string why;
+  const size_t count = sdf_lattice::check<2>(d->res, d->origin, d->spacing, why);
+  if (!count) return fail2d(m, MPMHIP_EINVAL, "set_levelset_sdf: " + why);
   if (phi1 && !(t1 > t0)) return fail2d(m, MPMHIP_EINVAL, "key frame times must satisfy t0 < t1");
   if (m->ls_collision) return fail2d(m, MPMHIP_EINVAL, "rigid_body_levelset_collision is not supported with a sampled level set");
   HIPCHK2D(m, hipSetDevice(m->device));
   HIPCHK2D(m, hipStreamSynchronize(m->stream));  // (kernels in flight read the arrays)
   LevelSetDev &L = m->LS;
-  if (count != m->sdf_count) {
-    m->d_sdf[0].reset(); m->d_sdf[1].reset();
-    m->sdf_count = 0;
-    memset(&L.sdf, 0, sizeof L.sdf);
-    HIPCHK2D(m, m->d_sdf[0].alloc(count));
-    m->sdf_count = count;
-  }
-  if (phi1 && !m->d_sdf[1]) HIPCHK2D(m, m->d_sdf[1].alloc(count));
-  if (!phi1) m->d_sdf[1].reset();  // a static set keeps no second frame (a dynamic set's per-frame update always brings two)
-  HIPCHK2D(m, hipMemcpy(m->d_sdf[0], phi0, sizeof(float) * count, hipMemcpyHostToDevice));
-  if (phi1) HIPCHK2D(m, hipMemcpy(m->d_sdf[1], phi1, sizeof(float) * count, hipMemcpyHostToDevice));
+  HIPCHK2D(m, m->sdf.reserve(L.sdf, count, phi1 != nullptr));
+  if (!phi1) m->sdf.frame[1].reset();  // a static set keeps no second frame (a dynamic set's per-frame update always brings two)
+  HIPCHK2D(m, hipMemcpy(m->sdf.frame[0], phi0, sizeof(float) * count, hipMemcpyHostToDevice));
+  if (phi1) HIPCHK2D(m, hipMemcpy(m->sdf.frame[1], phi1, sizeof(float) * count, hipMemcpyHostToDevice));
   const int dirichlet = L.dirichlet, pc = L.particle_collision;
   memset(&L, 0, sizeof L);  // the sampled set replaces the shapes
   L.dirichlet = dirichlet; L.particle_collision = pc;
   L.friction = friction;
-  SdfDev &S = L.sdf;
-  S.phi0 = m->d_sdf[0];
-  S.phi1 = phi1 ? m->d_sdf[1].get() : nullptr;
-  S.res[0] = d->res[0]; S.res[1] = d->res[1]; S.res[2] = 1;
-  S.origin[0] = d->origin[0]; S.origin[1] = d->origin[1];
-  S.spacing = d->spacing; S.inv_spacing = 1.0f / d->spacing;
-  S.t0 = phi1 ? t0 : 0.0f; S.t1 = phi1 ? t1 : 1.0f;
+  sdf_fill<2>(L.sdf, *d, m->sdf.frame[0], phi1 ? m->sdf.frame[1].get() : nullptr, t0, t1);
   return MPMHIP_OK;
 }
 

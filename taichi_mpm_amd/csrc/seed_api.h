@@ -1,7 +1,8 @@
 // taichi_mpm_amd/csrc/seed_api.h — host side of mpmhip_seed_particles, mpmhip2d_seed_particles and mpmhip2d_reserve (kernels: k_seed.h;
 // tiles: poisson_tile.h; rules: include/mpmhip.h).  Included by mpmhip.hip inside its extern "C" block, behind async2d_api.h and
 // frame2d_api.h: both ctx types are complete here.  One driver (seed_particles) carries the call for both dimensions; what a ctx does
-// its own way is in its adapter (Seed3, Seed2).  A call synchronises twice for a few words each: the get-ready box (the number of
+// its own way is in its adapter (Seed3, Seed2).  A sampled region's lattice is judged by sdf_lattice.h and becomes the SdfDev of the
+// boundary's sampler (mpmhip.hip: sdf_fill; mpm_math.h).  A call synchronises twice for a few words each: the get-ready box (the number of
 // replicas sizes the candidate passes) and the survivors' count (the capacity check comes before anything is written).
 #pragma once
 
@@ -61,11 +62,6 @@ struct Seed3 {
     seed_copy_shapes(R, d);
     return MPMHIP_OK;
   }
-  static void set_field(Region &R, const float *phi) {  // one frame
-    R.sdf.phi0 = phi;
-    R.sdf.phi1 = nullptr;
-    R.sdf.t0 = 0.0f; R.sdf.t1 = 1.0f;
-  }
   static float min_distance(double v) { return (float)std::cbrt(v * 13.0 / 18.0); }
   static uint32_t max_bounds_wgs(const Ctx *c) { return (uint32_t)c->n_cus * 32u; }
   static float base_dt(const Ctx *c) { return c->P.dt; }
@@ -105,7 +101,6 @@ struct Seed2 {
     }
     return MPMHIP_OK;
   }
-  static void set_field(Region &R, const float *phi) { R.sdf.phi = phi; }
   static float min_distance(double v) { return (float)std::sqrt(v * 2.0 / 3.0); }
   static uint32_t max_bounds_wgs(const Ctx *) { return 8192u; }
   static float base_dt(const Ctx *m) { return m->base_dt; }
@@ -154,14 +149,9 @@ int seed_region(typename A::Ctx *c, const typename A::Desc *d, typename A::Regio
   if (!d->sdf) return A::shapes(c, d, R);
   const auto *L = d->sdf;
   if (!d->phi) SEED_FAIL("seed_particles: a sampled region needs its phi array");
-  size_t count = 1;
-  for (int k = 0; k < D; k++) {  // what mpmhip_set_levelset_sdf refuses
-    if (L->res[k] < 2) SEED_FAIL("seed_particles: res[%d] = %d, at least 2 samples per axis are needed", k, L->res[k]);
-    if (!std::isfinite(L->origin[k])) SEED_FAIL("seed_particles: origin[%d] is not finite", k);
-    count *= (size_t)L->res[k];
-  }
-  if (!(L->spacing > 0.0f) || !std::isfinite(L->spacing)) SEED_FAIL("seed_particles: spacing must be a finite number > 0");
-  if (count > ((size_t)1 << 31)) SEED_FAIL("seed_particles: more than 2^31 samples");
+  std::string why;
+  const size_t count = sdf_lattice::check<D>(L->res, L->origin, L->spacing, why);
+  if (!count) SEED_FAIL("seed_particles: %s", why.c_str());
   SeedWork &W = c->seed;
   if (count > W.phi_cap || !W.d_phi) {
     W.phi_cap = 0;
@@ -170,9 +160,7 @@ int seed_region(typename A::Ctx *c, const typename A::Desc *d, typename A::Regio
     W.phi_cap = count;
   }
   SEED_HIP(hipMemcpyAsync(W.d_phi, d->phi, sizeof(float) * count, hipMemcpyHostToDevice, c->stream));
-  A::set_field(R, W.d_phi);
-  R.sdf.spacing = L->spacing; R.sdf.inv_spacing = 1.0f / L->spacing;
-  for (int k = 0; k < D; k++) { R.sdf.res[k] = L->res[k]; R.sdf.origin[k] = L->origin[k]; }
+  sdf_fill<D>(R.sdf, *L, W.d_phi, nullptr, 0.0f, 1.0f);  // one frame
   return MPMHIP_OK;
 }
 

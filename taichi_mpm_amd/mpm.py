@@ -110,33 +110,80 @@ def eval_shapes(shapes, pts):
     return phi
 
 
-class SampledLevelSet:
+class _SampledField:
+    """What the sampled fields of both dimensions share (SampledLevelSet below; SampledLevelSet2D and SampledBoundary2D in mpm2d.py):
+    the validation of phi, origin and spacing, and the lattice helpers.  A subclass gives its dimension, the class name its messages
+    carry, and how it reads an origin (_coords: D floats; _origin: those, checked, for the constructor)."""
+
+    _DIM, _NAME, _COUNT = None, None, None
+
+    def _set_field(self, phi, origin, spacing):
+        who = self._NAME
+        a = np.asarray(phi)
+        if a.ndim != self._DIM:
+            raise MPMError("%s: phi must have %d axes, got shape %r" % (who, self._DIM, a.shape))
+        if min(a.shape) < 2:
+            raise MPMError("%s: at least 2 samples per axis are needed, got shape %r" % (who, a.shape))
+        a = np.ascontiguousarray(a, np.float32)
+        if not np.all(np.isfinite(a)):
+            raise MPMError("%s: phi holds non-finite values" % who)
+        o = self._origin(origin)
+        if spacing is not None and not (np.isfinite(spacing) and float(spacing) > 0):
+            raise MPMError("%s: spacing must be a finite number > 0, got %r" % (who, spacing))
+        self.phi, self.origin = a, o
+        self.spacing = None if spacing is None else float(spacing)
+
+    @property
+    def res(self):
+        return self.phi.shape
+
+    def same_lattice(self, other):
+        return self.res == other.res and self.origin == other.origin and self.spacing == other.spacing
+
+    @classmethod
+    def lattice_points(cls, res, origin, spacing):
+        """(n, D) float64 positions of the samples in the array's order"""
+        res = tuple(int(r) for r in res)
+        if len(res) != cls._DIM or min(res) < 2:
+            raise MPMError("%s: res must be %s numbers >= 2, got %r" % (cls._NAME, cls._COUNT, res))
+        if spacing is None or not (np.isfinite(spacing) and float(spacing) > 0):
+            raise MPMError("%s: spacing must be a finite number > 0, got %r" % (cls._NAME, spacing))
+        o = cls._coords(origin)
+        ax = [o[k] + np.arange(res[k], dtype=np.float64) * float(spacing) for k in range(cls._DIM)]
+        return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, cls._DIM)
+
+    @classmethod
+    def _sample(cls, f, res, origin, spacing):
+        """phi of from_function: f, which maps an (n, D) array of world positions to n values of phi, at the lattice's samples"""
+        pts = cls.lattice_points(res, origin, spacing)
+        phi = np.empty(len(pts), np.float64)
+        for i in range(0, len(pts), 1 << 20):  # (chunks: f may build large temporaries)
+            phi[i:i + (1 << 20)] = np.asarray(f(pts[i:i + (1 << 20)]), np.float64).reshape(-1)
+        return phi.reshape(tuple(int(r) for r in res))
+
+
+class SampledLevelSet(_SampledField):
     """A signed-distance field sampled on a regular lattice (include/mpmhip.h: mpmhip_set_levelset_sdf): boundaries of any shape.
     `phi`: array of shape (res0, res1, res2), world units, negative inside the solid; sample (i, j, k) sits at
     origin + (i, j, k) * spacing.  spacing=None: the cell size of the simulation it is given to.  Outside the lattice there is no
     level set; one level set at a time, so a floor is baked into the array (from_levelset bakes any analytic LevelSet)."""
 
+    _DIM, _NAME, _COUNT = 3, "SampledLevelSet", "three"
+
     def __init__(self, phi, origin=(0.0, 0.0, 0.0), spacing=None, friction=-1.0):
-        a = np.asarray(phi)
-        if a.ndim != 3:
-            raise MPMError("SampledLevelSet: phi must have 3 axes, got shape %r" % (a.shape,))
-        if min(a.shape) < 2:
-            raise MPMError("SampledLevelSet: at least 2 samples per axis are needed, got shape %r" % (a.shape,))
-        a = np.ascontiguousarray(a, np.float32)
-        if not np.all(np.isfinite(a)):
-            raise MPMError("SampledLevelSet: phi holds non-finite values")
+        self._set_field(phi, origin, spacing)
+        self.friction = float(friction)
+
+    @staticmethod
+    def _coords(origin):
+        return _vec3(origin, None)
+
+    @staticmethod
+    def _origin(origin):
         o = _vec3(origin, None)
         if not np.all(np.isfinite(o)):
             raise MPMError("SampledLevelSet: origin must be finite, got %r" % (o,))
-        if spacing is not None and not (np.isfinite(spacing) and float(spacing) > 0):
-            raise MPMError("SampledLevelSet: spacing must be a finite number > 0, got %r" % (spacing,))
-        self.phi, self.origin = a, o
-        self.spacing = None if spacing is None else float(spacing)
-        self.friction = float(friction)
-
-    @property
-    def res(self):
-        return self.phi.shape
+        return o
 
     def get_delta_x(self):
         if self.spacing is None:
@@ -147,31 +194,12 @@ class SampledLevelSet:
         self.friction = float(f)
         return self
 
-    def same_lattice(self, other):
-        return self.res == other.res and self.origin == other.origin and self.spacing == other.spacing
-
-    @staticmethod
-    def lattice_points(res, origin, spacing):
-        """(n, 3) float64 positions of the samples in the array's order"""
-        res = tuple(int(r) for r in res)
-        if len(res) != 3 or min(res) < 2:
-            raise MPMError("SampledLevelSet: res must be three numbers >= 2, got %r" % (res,))
-        if not (np.isfinite(spacing) and float(spacing) > 0):
-            raise MPMError("SampledLevelSet: spacing must be a finite number > 0, got %r" % (spacing,))
-        o = _vec3(origin, None)
-        ax = [o[k] + np.arange(res[k], dtype=np.float64) * float(spacing) for k in range(3)]
-        return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 3)
-
     @classmethod
     def from_function(cls, f, res, origin=(0.0, 0.0, 0.0), spacing=None, friction=-1.0):
         """sample f, which maps an (n, 3) array of world positions to n values of phi"""
         if spacing is None:
             raise MPMError("SampledLevelSet.from_function needs the spacing of the lattice")
-        pts = cls.lattice_points(res, origin, spacing)
-        phi = np.empty(len(pts), np.float64)
-        for i in range(0, len(pts), 1 << 20):  # (chunks: f may build large temporaries)
-            phi[i:i + (1 << 20)] = np.asarray(f(pts[i:i + (1 << 20)]), np.float64).reshape(-1)
-        return cls(phi.reshape(tuple(int(r) for r in res)), origin, spacing, friction)
+        return cls(cls._sample(f, res, origin, spacing), origin, spacing, friction)
 
     @classmethod
     def from_levelset(cls, ls, res, origin=(0.0, 0.0, 0.0), spacing=None):

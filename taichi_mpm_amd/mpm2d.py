@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from .materials import MATERIAL_IDS, group_params, initial_aux
-from .mpm import DynamicLevelSet, LevelSet, MPMError, check_unsupported_keys, eval_shapes
+from .mpm import DynamicLevelSet, LevelSet, MPMError, _SampledField, check_unsupported_keys, eval_shapes
 
 
 def lattice_square(lower, higher, dx):
@@ -23,53 +23,33 @@ def lattice_square(lower, higher, dx):
     return ((cells + 0.25 * signs[None]) * dx).reshape(-1, 2).astype(np.float32)
 
 
-class SampledLevelSet2D:
+class SampledLevelSet2D(_SampledField):
     """A signed-distance field sampled on a regular lattice in the plane: the region of add_particles(region=...) — a disc, a polygon,
     any free-form blob (it stands in for the reference's polygon and image textures).  `phi`: array of shape (res0, res1), world units,
     negative inside; sample (i, j) sits at origin + (i, j) * spacing.  spacing=None: the cell size of the simulation it is given to.
     Read bilinearly; outside the lattice there is no region.  It is a region: a boundary needs a friction, which as_boundary() adds
     (set_levelset takes the SampledBoundary2D it returns, not this)."""
 
+    _DIM, _NAME, _COUNT = 2, "SampledLevelSet2D", "two"
+
     def __init__(self, phi, origin=(0.0, 0.0), spacing=None):
-        a = np.asarray(phi)
-        if a.ndim != 2:
-            raise MPMError("SampledLevelSet2D: phi must have 2 axes, got shape %r" % (a.shape,))
-        if min(a.shape) < 2:
-            raise MPMError("SampledLevelSet2D: at least 2 samples per axis are needed, got shape %r" % (a.shape,))
-        a = np.ascontiguousarray(a, np.float32)
-        if not np.all(np.isfinite(a)):
-            raise MPMError("SampledLevelSet2D: phi holds non-finite values")
+        self._set_field(phi, origin, spacing)
+
+    @staticmethod
+    def _coords(origin):
+        return [float(origin[k]) for k in range(2)]
+
+    @staticmethod
+    def _origin(origin):
         o = tuple(float(v) for v in origin)
         if len(o) != 2 or not np.all(np.isfinite(o)):
             raise MPMError("SampledLevelSet2D: origin must be two finite numbers, got %r" % (origin,))
-        if spacing is not None and not (np.isfinite(spacing) and float(spacing) > 0):
-            raise MPMError("SampledLevelSet2D: spacing must be a finite number > 0, got %r" % (spacing,))
-        self.phi, self.origin = a, o
-        self.spacing = None if spacing is None else float(spacing)
-
-    @property
-    def res(self):
-        return self.phi.shape
-
-    @staticmethod
-    def lattice_points(res, origin, spacing):
-        """(n, 2) float64 positions of the samples in the array's order"""
-        res = tuple(int(r) for r in res)
-        if len(res) != 2 or min(res) < 2:
-            raise MPMError("SampledLevelSet2D: res must be two numbers >= 2, got %r" % (res,))
-        if spacing is None or not (np.isfinite(spacing) and float(spacing) > 0):
-            raise MPMError("SampledLevelSet2D: spacing must be a finite number > 0, got %r" % (spacing,))
-        ax = [float(origin[k]) + np.arange(res[k], dtype=np.float64) * float(spacing) for k in range(2)]
-        return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 2)
+        return o
 
     @classmethod
     def from_function(cls, f, res, origin=(0.0, 0.0), spacing=None):
         """sample f, which maps an (n, 2) array of world positions to n values of phi"""
-        pts = cls.lattice_points(res, origin, spacing)
-        phi = np.empty(len(pts), np.float64)
-        for i in range(0, len(pts), 1 << 18):  # (chunks: f may build large temporaries)
-            phi[i:i + (1 << 18)] = np.asarray(f(pts[i:i + (1 << 18)]), np.float64).reshape(-1)
-        return cls(phi.reshape(tuple(int(r) for r in res)), origin, spacing)
+        return cls(cls._sample(f, res, origin, spacing), origin, spacing)
 
     @staticmethod
     def polygon_distance(vertices, pts):
@@ -139,9 +119,6 @@ class SampledBoundary2D(SampledLevelSet2D):
     def set_friction(self, f):
         self.friction = float(f)
         return self
-
-    def same_lattice(self, other):
-        return self.res == other.res and self.origin == other.origin and self.spacing == other.spacing
 
 
 class Simulation2D:

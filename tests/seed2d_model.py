@@ -1,4 +1,4 @@
-"""numpy model of mpmhip2d_seed_particles (include/mpmhip.h; csrc/k_seed2d.h, csrc/seed2d_api.h) — the yardstick of the 2D seeding
+"""numpy model of mpmhip2d_seed_particles (include/mpmhip.h; csrc/k_seed.h, csrc/seed_api.h at D = 2) — the yardstick of the 2D seeding
 tests.  tests/seed_model.py with dim = 2: it restates, in fp32 and in the device's order of operations (every operation rounded),
 PoissonDiskSampler<2>::sample_from_periodic_data and sample_from_source (src/poisson_disk_sampler.h:157-252) behind get_ready (:34-69):
 
@@ -12,8 +12,8 @@ PoissonDiskSampler<2>::sample_from_periodic_data and sample_from_source (src/poi
               [source: and position + advection NOT inside; advection = v * d + ((0.5 * g) * (d + base_dt)) * d]
   order       survivors in ascending c, creation ids first_id + rank
 
-A sampled region is read bilinearly with the 3D sampler's rules, one axis fewer (the device forbids contraction there, so the model
-is exact); shapes are evaluated with the formulas of levelset_eval_key in the plane, where the device's compiler may contract a
+A sampled region is read by the boundary's own sampler (csrc/mpm_math.h: sdf_locate, sdf_phi_frame at D = 2; the device forbids
+contraction there, so the model is exact); shapes are evaluated with the formulas of levelset_eval_key in the plane, where the device's compiler may contract a
 multiply and an add: a shape test sets candidates with |phi| below a margin aside."""
 import ctypes as C
 

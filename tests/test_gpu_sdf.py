@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests.common import lattice_cube, load_golden, make_state, rel_l2
-from tests.sdf_model import SdfModel
+from tests.sdf_model import SdfModel, sampler_points, well_conditioned
 
 pytestmark = pytest.mark.gpu
 FIELDS = ("x", "v", "F", "aux")
@@ -40,21 +40,6 @@ DX5 = 1.0 / 32
 RES5, ORG5, H5 = (40, 36, 33), (-0.1, 0.02, -0.05), 0.03
 
 
-def _points(rng, n):
-    """inside cells, on cell faces, exactly on samples, outside the lattice (and a NaN)"""
-    res, org = np.array(RES5), np.array(ORG5)
-    hi = org + (res - 1) * H5
-    inside = rng.uniform(org, hi, (n // 2, 3))
-    face = rng.uniform(org, hi, (n // 5, 3))
-    ax = rng.integers(0, 3, len(face))
-    face[np.arange(len(face)), ax] = org[ax] + rng.integers(0, res[ax], len(face)) * H5
-    on = org + np.stack([rng.integers(0, res[k], n // 5) for k in range(3)], 1) * H5
-    out = rng.uniform(org - 0.2, hi + 0.2, (n - len(inside) - len(face) - len(on), 3))
-    x = np.concatenate([inside, face, on, out]).astype(np.float32)
-    x[-1] = (np.nan, 0.3, 0.3)
-    return x
-
-
 def _fields():
     plane = lambda n, d: (lambda x: x @ np.asarray(n, np.float64) + d)
     sphere = lambda c, r: (lambda x: np.linalg.norm(x - np.asarray(c, np.float64), axis=1) - r)
@@ -65,26 +50,27 @@ def _fields():
 
 @pytest.mark.parametrize("shape", ["plane", "sphere", "torus"])
 def test_device_sampler_matches_the_model(tm, shape):
-    """mpmhip_debug_levelset_sample at 10^5 points, static and at three times between two key frames.
+    """mpmhip_debug_levelset_sample at 10^5 points (inside cells, on cell faces, on samples, outside, a NaN), static and at three
+    times between two key frames.
 
-    Both sides evaluate the same expressions in fp32 in the same order (tests/sdf_model.py); the cell and the weights come from a
-    subtraction and a multiplication that cannot be fused, so they — and `hit` — are identical.  The device may fuse the multiply
-    and the add of an interpolation (1 - f) a + f b, which removes ONE rounding of at most half an ulp of the largest magnitude
-    involved; nothing is amplified on the way up (convex combinations).
-      phi     7 interpolations per frame: <= 7 * 2^-24 M, M = max |phi| over the cell's samples; two frames and their blend
-              (one more fusable add): <= 15 * 2^-24 M.  Asserted: 2^-20 M = 16 * 2^-24 M.
+    Both sides evaluate the same expressions in fp32 in the same order, every operation rounded on its own (tests/sdf_model.py; the
+    device's sampler forbids the contraction of a multiply and an add, csrc/mpm_math.h: SDF_NO_CONTRACT, and its division and square
+    root are correctly rounded).  So `hit`, phi and dphidt are equal bit for bit at every point, and the normal wherever it is well
+    conditioned.  The bounds a sampler that did contract would meet stay asserted beside that; they say how far a failure is off:
+      phi     a fused interpolation (1 - f) a + f b removes ONE rounding of at most half an ulp of the largest magnitude involved,
+              and nothing is amplified on the way up (convex combinations).  7 interpolations per frame: <= 7 * 2^-24 M, M = max |phi|
+              over the cell's samples; two frames and their blend: <= 15 * 2^-24 M.  Asserted: 2^-20 M = 16 * 2^-24 M.
       dphidt  (phi1 - phi0) / (t1 - t0) of two values that are each within 7 * 2^-24 M: 2^-20 M / (t1 - t0).
-      normal  the eight samples' gradients are differences and products: identical.  7 interpolations: the raw gradient is within
-              7 * 2^-24 G per component, G = the largest component among the cell's samples.  Its squared length may fuse two adds
-              (2^-24 relative on the length).  A unit vector g / |g| moves by at most (component error + length error) / |g|
-              = 15 * 2^-24 G / |g|; where G / |g| <= 2 that is 30 * 2^-24.  Two frames: the blend of two such normals (one more fused
-              add each way, 2 * 2^-24) normalised again, at most (2 * 30 + 2) / |blend| * 2^-24 with |blend| >= 0.97 here: 2^-18 = 64 * 2^-24,
-              asserted for both.  Where G / |g| > 2 (the centre line of a tube, the centre of a sphere) the direction is ill-conditioned
-              on both sides alike: there the normal must be a unit vector or zero."""
+      normal  the eight samples' gradients are differences and products.  7 interpolations: the raw gradient within 7 * 2^-24 G per
+              component, G = the largest component among the cell's samples; its squared length 2^-24 relative.  A unit vector
+              g / |g| moves by at most (component error + length error) / |g| = 15 * 2^-24 G / |g|; where G / |g| <= 2 that is
+              30 * 2^-24.  Two frames: the blend of two such normals normalised again, at most (2 * 30 + 2) / |blend| * 2^-24 with
+              |blend| >= 0.97 here: 2^-18 = 64 * 2^-24, asserted for both.  Where G / |g| > 2 (the centre line of a tube, the centre
+              of a sphere) the direction is ill-conditioned: there the normal must be a unit vector or zero."""
     f0, f1 = _fields()[shape]
     s0 = tm.SampledLevelSet.from_function(f0, RES5, ORG5, H5, friction=0.3)
     s1 = tm.SampledLevelSet.from_function(f1, RES5, ORG5, H5, friction=0.3)
-    x = _points(np.random.default_rng(11), 100000)
+    x = sampler_points(np.random.default_rng(11), 100000, RES5, ORG5, H5)
     sim = _sim(tm, 32, DX5, 1e-4)
     t0, t1 = 0.5, 2.0
     for times in ((None,), (0.7, 1.25, 1.9)):
@@ -95,7 +81,7 @@ def test_device_sampler_matches_the_model(tm, shape):
             sim.set_levelset(tm.DynamicLevelSet().initialize(t0, t1, s0, s1))
             model = SdfModel(s0.phi, ORG5, H5, DX5, s1.phi, t0, t1)
         hit_m, c, f = model.locate(x)
-        M, G = model.cell_max_abs(c), model.cell_max_grad(c)
+        M = model.cell_max_abs(c)
         for t in times:
             phi, g, dphidt, hit = sim.sample_levelset(x, 0.0 if t is None else t)
             mphi, mg, mdphidt, _ = model.sample(x, 0.0 if t is None else t)
@@ -103,27 +89,21 @@ def test_device_sampler_matches_the_model(tm, shape):
             assert not phi[~hit].any() and not g[~hit].any() and not dphidt[~hit].any()
             h = hit
             worst = (np.abs(phi - mphi)[h] / (2.0 ** -20 * M[h])).max()
-            print("%s t=%s: |dphi| / (2^-20 M) <= %.3f" % (shape, t, worst))
+            print("%s t=%s: |dphi| / (2^-20 M) <= %.3f, %d of %d hits differ in a bit" % (shape, t, worst, (phi != mphi)[h].sum(), h.sum()))
             assert worst <= 1.0
             if t is None:
                 assert not dphidt.any()
             else:
                 assert np.all(np.abs(dphidt - mdphidt)[h] <= 2.0 ** -20 * M[h] / (t1 - t0))
-            raw = model.raw_gradient(model.phi0, c, f)
-            well = h & (G <= 2 * np.linalg.norm(raw, axis=1))
-            if t is not None:
-                raw1 = model.raw_gradient(model.phi1, c, f)
-                well &= G <= 2 * np.linalg.norm(raw1, axis=1)
-                n0 = raw / np.maximum(np.linalg.norm(raw, axis=1), 1e-30)[:, None]
-                n1 = raw1 / np.maximum(np.linalg.norm(raw1, axis=1), 1e-30)[:, None]
-                a = (t - t0) / (t1 - t0)
-                well &= np.linalg.norm(n0 * (1 - a) + n1 * a, axis=1) >= 0.97
+            _, well = well_conditioned(model, x, t)
             assert well.sum() > 0.9 * h.sum()
             worst = np.abs(g - mg)[well].max() / 2.0 ** -18
             print("%s t=%s: |dn| / 2^-18 <= %.3f over %d of %d points" % (shape, t, worst, well.sum(), h.sum()))
             assert worst <= 1.0
             ln = np.linalg.norm(g[h], axis=1)
             assert np.all((np.abs(ln - 1) < 1e-5) | (ln == 0))
+            assert np.array_equal(phi[h], mphi[h]) and np.array_equal(dphidt[h], mdphidt[h])  # the bits
+            assert np.array_equal(g[well], mg[well])
     # the same entry evaluates analytic shapes
     sim.set_levelset(tm.LevelSet(friction=0.3).add_sphere((0.4, 0.5, 0.4), 0.3))
     phi, g, _, hit = sim.sample_levelset(x[:1000])

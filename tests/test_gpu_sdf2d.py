@@ -1,5 +1,5 @@
 """Sampled signed-distance level sets as boundaries of the 2D solver (include/mpmhip.h: mpmhip2d_set_levelset_sdf; run with -m gpu on
-an MI355X): the device sampler against its numpy model (tests/sdf2d_model.py) and against the seeding's sampled region
+an MI355X): the device sampler against its numpy model (tests/sdf_model.py at D = 2) and against the seeding's sampled region
 (tests/seed2d_model.py), baked floors and a baked disc against the REFERENCE's 2D fixture (tests/golden/ref_mpm2d.npz) and against
 the analytic path of this library, a baked container, a polygon hopper — a boundary no mpmhip_shape expresses —, the deterministic
 mode, the asynchronous stepper and the CPIC coupling over a sampled floor, replacement, deletion, the refusals and the C++ layer.
@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 from tests.common import load_golden, rel_l2
-from tests.sdf2d_model import H1, ORG1, RES1, T0, T1, TIMES, Sdf2DModel, sampler_fields, sampler_points, well_conditioned
+from tests.sdf2d_model import H1, ORG1, RES1, T0, T1, TIMES, Sdf2DModel, sampler_fields
+from tests.sdf_model import sampler_points, well_conditioned
 from tests.seed2d_model import SampledRegion2D, ShapeRegion2D
 
 pytestmark = pytest.mark.gpu
@@ -108,11 +109,12 @@ def test_device_sampler_matches_the_model(tm, shape):
     """mpmhip2d_debug_levelset_sample at 20 000 points (inside cells, on lattice lines, on samples, outside, a NaN) on a lattice with a
     shifted origin and spacing != dx, static and at three times between two key frames.
 
-    Both sides evaluate the same expressions in fp32 in the same order (tests/sdf2d_model.py); the cell and the weights come from a
-    subtraction and a multiplication that cannot be fused, so they — and `hit` — are identical.  The bound is the one of
-    tests/test_gpu_sdf.py::test_device_sampler_matches_the_model with the 2D counts: it allows the device to fuse the multiply and
-    the add of an interpolation (1 - f) a + f b, which removes ONE rounding of at most half an ulp of the largest magnitude involved;
-    nothing is amplified on the way up (convex combinations).  (The sampler forbids that fusion, so the device is expected well inside.)
+    Both sides evaluate the same expressions in fp32 in the same order (tests/sdf_model.py); the cell and the weights come from a
+    subtraction and a multiplication that cannot be fused, so they — and `hit` — are identical.  The sampler forbids every fusion
+    (csrc/mpm_math.h: SDF_NO_CONTRACT), so phi and dphidt are equal bit for bit at every hit and the normal wherever it is well
+    conditioned.  Beside that the bound of tests/test_gpu_sdf.py::test_device_sampler_matches_the_model with the 2D counts stays
+    asserted, which says how far a failure is off: a fused interpolation (1 - f) a + f b removes ONE rounding of at most half an ulp
+    of the largest magnitude involved; nothing is amplified on the way up (convex combinations).
       phi     3 interpolations per frame: <= 3 * 2^-24 M, M = max |phi| over the cell's samples; two frames and their blend
               (one more fusable add): <= 7 * 2^-24 M.  Asserted: 2^-21 M = 8 * 2^-24 M.
       dphidt  (phi1 - phi0) / (t1 - t0) of two values that are each within 3 * 2^-24 M: 2^-21 M / (t1 - t0).
@@ -127,7 +129,7 @@ def test_device_sampler_matches_the_model(tm, shape):
     f0, f1 = sampler_fields()[shape]
     s0 = tm.SampledLevelSet2D.from_function(f0, RES1, ORG1, H1).as_boundary(0.3)
     s1 = tm.SampledLevelSet2D.from_function(f1, RES1, ORG1, H1).as_boundary(0.3)
-    x = sampler_points(np.random.default_rng(11), 20000)
+    x = sampler_points(np.random.default_rng(11), 20000, RES1, ORG1, H1)
     sim = make_sim(tm)
     for times in ((None,), TIMES):
         if times[0] is None:
@@ -158,6 +160,8 @@ def test_device_sampler_matches_the_model(tm, shape):
             assert worst <= 1.0
             ln = np.linalg.norm(g[h], axis=1)
             assert np.all((np.abs(ln - 1) < 1e-5) | (ln == 0))
+            assert np.array_equal(phi[h], mphi[h]) and np.array_equal(dphidt[h], mdphidt[h])  # the bits
+            assert np.array_equal(g[well], mg[well])
     # the same entry evaluates analytic shapes, read in the plane
     sim.set_levelset(tm.LevelSet(friction=0.3).add_sphere((0.4, 0.5, 0.0), 0.3))
     phi, g, _, hit = sim.sample_levelset(x[:1000])
@@ -364,7 +368,7 @@ def test_sampled_container_keeps_particles_like_the_analytic_one(tm):
     """the 2D form of tests/test_gpu_sdf.py's container: a water block thrown into the corner of an inside-out box, friction -2,
     particle_collision, 40 substeps, in the analytic box and in the same box baked at spacing dx.  The sampled run's largest excursion
     beyond the true box is at most the analytic run's own plus the largest one-step projection residual of this array
-    (tests/sdf2d_model.py: projection_residual); the interpolated phi of a container never exceeds the true one (phi is concave
+    (tests/sdf_model.py: projection_residual); the interpolated phi of a container never exceeds the true one (phi is concave
     inside it), so no interpolation term is added."""
     from taichi_mpm_amd.mpm2d import lattice_square
     x = lattice_square(20, 32, DX) + np.array([7 * DX, 0.0], F)  # x in 0.42 .. 0.61 -> the right wall at 0.6 and the floor at 0.3

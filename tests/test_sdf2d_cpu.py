@@ -1,7 +1,7 @@
-"""The 2D sampled level set without a GPU: the numpy model of the sampler (tests/sdf2d_model.py) against closed forms and against
+"""The 2D sampled level set without a GPU: the numpy model of the sampler (tests/sdf_model.py at D = 2) against closed forms and against
 the seeding's sampled region (tests/seed2d_model.py), the Python surface (SampledBoundary2D, from_levelset, the refusals), and the
-ctypes mirror of mpmhip2d_sdf_desc.  (The argument checking of mpmhip2d_set_levelset_sdf lives in mpmhip.hip beside the device
-calls, not in a header that builds for the host: it is exercised on the GPU, tests/test_gpu_sdf2d.py::test_every_refusal.)"""
+ctypes mirror of mpmhip2d_sdf_desc.  (The argument checking of mpmhip2d_set_levelset_sdf is exercised through the entry point on
+the GPU, tests/test_gpu_sdf2d.py::test_every_refusal.)"""
 import ctypes as C
 
 import numpy as np
@@ -10,7 +10,8 @@ import pytest
 import taichi_mpm_amd as tm
 from taichi_mpm_amd import _lib
 from taichi_mpm_amd.mpm import DynamicLevelSet, LevelSet, MPMError
-from tests.sdf2d_model import H1, ORG1, RES1, T0, T1, TIMES, Sdf2DModel, sampler_fields, sampler_points, well_conditioned
+from tests.sdf2d_model import H1, ORG1, RES1, T0, T1, TIMES, Sdf2DModel, sampler_fields
+from tests.sdf_model import sampler_points, well_conditioned
 from tests.seed2d_model import SampledRegion2D, ShapeRegion2D
 
 DX = 1.0 / 64
@@ -22,7 +23,7 @@ def test_the_sampler_tests_fields_are_well_conditioned(shape):
     """what the GPU test excludes from its normal comparison stays under 10 % of the hits, for every field and time it uses"""
     f0, f1 = sampler_fields()[shape]
     p0, p1 = _bake(f0, RES1, ORG1, H1).phi, _bake(f1, RES1, ORG1, H1).phi
-    x = sampler_points(np.random.default_rng(11), 20000)
+    x = sampler_points(np.random.default_rng(11), 20000, RES1, ORG1, H1)
     for model, times in ((Sdf2DModel(p0, ORG1, H1, DX), (None,)), (Sdf2DModel(p0, ORG1, H1, DX, p1, T0, T1), TIMES)):
         for t in times:
             hit, well = well_conditioned(model, x, t)
