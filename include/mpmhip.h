@@ -827,7 +827,7 @@ int mpmhip2d_snapshot_load(mpmhip2d_ctx *ctx, const void *src, size_t size);
  * src/async/async_mpm.cpp:423-427): the asynchronous stepper of mpmhip_async_begin / _step above for the 2D simulation
  * object.  A scheduler block is the reference's 2D SPGrid block, 8 x 16 nodes (SPGrid_Mask<5, 5, 2>); the block scheduler
  * (limits, neighbour lists, the action table of an advance) is the same host code as in 3D (csrc/async_sched.h); the pools
- * and backup pools are a device-resident store of 64-byte containers (csrc/k_async2d.h), and no particle data crosses the
+ * and backup pools are a device-resident store of 64-byte containers (csrc/k_async.h), and no particle data crosses the
  * host boundary while stepping.
  *   _begin            initialize (:13-55); not with rigid bodies.  After it mpmhip2d_step IS the asynchronous step (the
  *                     reference's virtual Simulation::step) and mpmhip2d_substep is refused.

@@ -2,8 +2,8 @@
 `create_simulation2('async_mpm')` (class AsyncMPM<dim>, src/async/async_mpm.{h,cpp}; TC_IMPLEMENTATION(Simulation3D,
 AsyncMPM3D, "async_mpm") / (Simulation2D, AsyncMPM2D, "async_mpm"), :423-427).
 
-Everything of it runs inside libmpmhip (csrc/async_sched.h: the block scheduler of both dimensions; csrc/async_api.h,
-csrc/k_async.h: 3D; csrc/async2d_api.h, csrc/k_async2d.h: 2D; C ABI: include/mpmhip.h "AsyncMPM, second half", "AsyncMPM<2>"):
+Everything of it runs inside libmpmhip (csrc/async_sched.h: the block scheduler csrc/async_api.h: the store's
+driver, csrc/k_async.h: its kernels — each for both dimensions; C ABI: include/mpmhip.h "AsyncMPM, second half", "AsyncMPM<2>"):
 the particle pools and backup pools of every scheduler block are a device-resident store, `advance(limit)` gathers its
 working set with index kernels, runs one ordinary substep with dt = unit_delta_t * limit and files the results back; the
 block tables and the walk over the power-of-two levels are C++ host code, as in the reference.  This module is the Python

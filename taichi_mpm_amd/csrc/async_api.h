@@ -1,129 +1,398 @@
-// taichi_mpm_amd/csrc/async_api.h — host side of the device-resident asynchronous stepper (included by mpmhip.hip inside
-// extern "C").  Part of libmpmhip.  Device side: k_async.h.
+// taichi_mpm_amd/csrc/async_api.h — host side of the device-resident asynchronous stepper for both ctx types (included by
+// mpmhip.hip inside extern "C", behind both ctx definitions).  Part of libmpmhip.  Device side: k_async.h; block scheduler:
+// async_sched.h; the store: AsyncStore (mpmhip.hip).
 //
 // AsyncMPM<dim> (src/async/async_mpm.{h,cpp}): per scheduler block a continuous_dt_limit (a power of two of unit_delta_t),
 // a particle pool at the block's own time and a backup pool at an earlier time; step() walks the power-of-two levels and
 // advance(limit) runs ONE ordinary substep, dt = unit_delta_t * limit, on the blocks of that level plus frozen copies of
 // their neighbours.  Here the block tables (a few integers per block) and the level walk are host code, as in the reference;
-// every container stays in HBM (k_async.h: the store), and an advance costs four small kernels around the substep and
-// two 16-byte read-backs (how many particles the working set has; how many containers were appended / freed).
+// every container stays in HBM (k_async.h: the store), and an advance costs four small kernels around the substep and one
+// 32-byte read-back (how many particles the working set has; how many containers were appended / freed; the append cursor).
+//
+// ONE driver (as_*), templated on the ctx type, carries both dimensions.  Fields both ctx types have under one name are used
+// directly (stream, device, cap, t, P.dt, P.dx, P.idx, next_pid, d_groups, async); what a ctx does its own way comes first, as
+// overloads on mpmhip_ctx * / mpmhip2d_ctx *.
 
-static int async_store_reserve(mpmhip_ctx *c, uint32_t need) {  // room for `need` containers in total
+struct AsTimer {  // wall time of a host-side section, accumulated into c->async.prof_ms[k] (synchronising sections included)
+  double &acc; std::chrono::steady_clock::time_point t0;
+  explicit AsTimer(double &a) : acc(a), t0(std::chrono::steady_clock::now()) {}
+  ~AsTimer() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// ---- what a ctx does its own way
+static int as_fail(mpmhip_ctx *c, int code, const std::string &msg) { return fail(c, code, "%s", msg.c_str()); }
+static int as_fail(mpmhip2d_ctx *m, int code, const std::string &msg) { return fail2d(m, code, msg); }
+static const char *as_begin_first(const mpmhip_ctx *) { return "mpmhip_async_begin first"; }
+static const char *as_begin_first(const mpmhip2d_ctx *) { return "mpmhip2d_async_begin first"; }
+// Launch caps, in workgroups of 256: of the passes over the store, of the filing pass over the working set, of the compaction
+// (a chained scan: every launched workgroup must be resident — scan_limit asks the occupancy API, 64 always are).  The values
+// are each dimension's own from before the two steppers shared this file; whether any of them matters for speed has not been measured.
+static uint32_t as_store_wgs(const mpmhip_ctx *) { return 4096; }
+static uint32_t as_store_wgs(const mpmhip2d_ctx *) { return 2048; }
+static uint32_t as_file_wgs(const mpmhip_ctx *) { return 8192; }
+static uint32_t as_file_wgs(const mpmhip2d_ctx *) { return 2048; }
+static uint32_t as_compact_wgs(mpmhip_ctx *c) { return scan_limit(c, (const void *)k_async_compact<Store3>); }
+static uint32_t as_compact_wgs(mpmhip2d_ctx *) { return 64; }
+// the device views of the store (twin: the compaction's target) and of the working set
+static Store3 as_store(const mpmhip_ctx *c, bool twin = false) {
+  const AsyncStore &S = c->async.store;
+  auto L = [&](int l) { return twin ? S.lane[l].b.get() : S.lane[l].a.get(); };
+  return Store3{twin ? S.tag2 : S.tag, (int32_t *)L(0), (float4 *)L(1), (float4 *)L(2)};
+}
+static Store2 as_store(const mpmhip2d_ctx *m, bool twin = false) {
+  const AsyncStore &S = m->async.store;
+  return Store2{twin ? S.tag2 : S.tag, (float4 *)(twin ? S.lane[0].b.get() : S.lane[0].a.get())};
+}
+static Work3 as_work(const mpmhip_ctx *c) { return Work3{(float4 *)c->rg.get(), (float4 *)c->rp.get(), (float4 *)c->rb.get(), c->d_groups}; }
+static Work2 as_work(const mpmhip2d_ctx *m) { return Work2{m->x, m->v, m->F, m->B, m->aux, m->gid, m->pid}; }
+static int64_t as_slots(const mpmhip_ctx *c) { return c->n_slots; }
+static int64_t as_slots(const mpmhip2d_ctx *m) { return m->n; }
+// room for n working slots
+static int as_make_room(mpmhip_ctx *c, int64_t n) { return n > c->cap ? mpmhip_reserve(c, n + 1024) : MPMHIP_OK; }
+static int as_make_room(mpmhip2d_ctx *m, int64_t n) { return a2_grow_particles(m, n); }
+static int as_ensure_blk_of(mpmhip_ctx *c) { return async_ensure_particle_arrays(c); }
+static int as_ensure_blk_of(mpmhip2d_ctx *m) {
+  auto &A = m->async;
+  if (A.blk_of_cap < m->cap) {
+    HIPCHK2D(m, A.d_blk_of.alloc((size_t)m->cap));
+    A.blk_of_cap = m->cap;
+  }
+  return MPMHIP_OK;
+}
+// the working set is now n slots, none of them dead (the count is zeroed on the ctx stream, between the stepper's launches)
+static int as_working_set(mpmhip_ctx *c, int64_t n) {
+  if (int rc = drop_records(c, DEAD_ZERO_ON_STREAM)) return rc;
+  set_slots(c, n);
+  return MPMHIP_OK;
+}
+static int as_working_set(mpmhip2d_ctx *m, int64_t n) {
+  m->n = n;
+  HIPCHK2D(m, hipMemsetAsync(m->n_dead, 0, sizeof(unsigned int), m->stream));
+  return MPMHIP_OK;
+}
+static int as_substep(mpmhip_ctx *c) {
+  AsTimer sub(c->async.prof_ms[3]);
+  if (int rc = mpmhip_substep(c)) return rc;
+  if (c->async.profile_sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MPMHIP_OK;
+}
+static int as_substep(mpmhip2d_ctx *m) { return substep2d(m); }
+static int as_before_filing(mpmhip_ctx *c) { return ensure_b_current(c); }  // (the containers hold apic_b)
+static int as_before_filing(mpmhip2d_ctx *) { return MPMHIP_OK; }
+static void as_end_step(mpmhip_ctx *c) { set_slots(c, 0); }
+static void as_end_step(mpmhip2d_ctx *m) { m->n = 0; m->P.dt = m->base_dt; }
+// the 3D profile (mpmhip_async_profile): section k of prof_ms; an advance is counted where its timer starts
+static AsTimer as_timer(mpmhip_ctx *c, int k) {
+  if (k == 2) c->async.prof_ms[5] += 1.0;
+  return AsTimer(c->async.prof_ms[k]);
+}
+static int as_timer(mpmhip2d_ctx *, int) { return 0; }
+
+extern "C++" {
+namespace {
+
+#define AS_CHK(call)                                                                                                    \
+  do {                                                                                                                  \
+    const hipError_t e_ = (call);                                                                                       \
+    if (e_ != hipSuccess) return as_fail(c, MPMHIP_EHIP, std::string(#call " failed: ") + hipGetErrorString(e_));      \
+  } while (0)
+#define AS_LAUNCHED(what)                                                                                               \
+  do {                                                                                                                  \
+    const hipError_t e_ = hipGetLastError();                                                                            \
+    if (e_ != hipSuccess) return as_fail(c, MPMHIP_EHIP, std::string("launch of " what " failed: ") + hipGetErrorString(e_)); \
+  } while (0)
+
+template <class Ctx>
+dim3 as_grid(const Ctx *c, uint32_t n) { return dim3(std::min<uint32_t>(std::max<uint32_t>((n + 255) / 256, 1), as_store_wgs(c))); }
+
+template <class Ctx>
+int as_enter(Ctx *c) {  // every entry point of a resident stepper
+  if (!c->async.resident) return as_fail(c, MPMHIP_EINVAL, as_begin_first(c));
+  AS_CHK(hipSetDevice(c->device));
+  return MPMHIP_OK;
+}
+// a new session on this ctx: an empty store (whatever an earlier session left goes), the block times of sched_begin
+template <class Ctx>
+int as_begin(Ctx *c, std::initializer_list<size_t> lane_bytes) {
+  auto &A = c->async;
+  if (int rc = async_drop_view(c)) return rc;
+  AS_CHK(hipStreamSynchronize(c->stream));
+  A.resident = false;
+  A.sched_begin();  // block times, the reference's block order, cached_neighbours
+  A.d_blk_of.reset(); A.blk_of_cap = 0;  // (the next load_pools allocates it again)
+  const hipError_t e = A.store.reset(lane_bytes, A.rank_of);
+  if (e != hipSuccess) return as_fail(c, MPMHIP_ENOMEM, std::string("async store: tables of a new session: ") + hipGetErrorString(e));
+  A.resident = true;
+  return MPMHIP_OK;
+}
+
+template <class Ctx>
+int as_store_reserve(Ctx *c, uint32_t need) {  // room for `need` containers in total
   auto &S = c->async.store;
   if (need <= S.cap) return MPMHIP_OK;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t cap = std::max<uint32_t>(need + need / 2, 4096), keep = std::min(S.size_ub, S.cap);
-  hipError_t e = hipSuccess;
-  auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  A(S.g.regrow((size_t)keep * 4, (size_t)cap * 4, false)); A(S.w.regrow((size_t)keep * 4, (size_t)cap * 4, false));
-  A(S.tag.regrow((size_t)keep, (size_t)cap, false)); A(S.id.regrow((size_t)keep, (size_t)cap, false));
-  // (kernels walk [0, upper bound of the size): every tag behind the containers in use says FREE)
-  if (e == hipSuccess) A(hipMemset(S.tag + keep, 0xFF, sizeof(uint32_t) * (size_t)(cap - keep)));
-  S.g2.reset(); S.w2.reset(); S.tag2.reset(); S.id2.reset();  // (the compaction targets are re-allocated when a compaction runs)
-  if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "async store: growing to %u containers failed: %s", cap, hipGetErrorString(e));
-  S.cap = cap;
+  AS_CHK(hipStreamSynchronize(c->stream));
+  const hipError_t e = S.reserve(need);
+  if (e != hipSuccess) return as_fail(c, MPMHIP_ENOMEM, "async store: growing to " + std::to_string(AsyncStore::grown(need)) + " containers failed: " + hipGetErrorString(e));
   return MPMHIP_OK;
 }
 // the per-block action table of an advance -> S.d_tbl, ORDERED ON THE CTX STREAM behind the kernels that still read the
 // previous table (the ctx stream is non-blocking: a plain hipMemcpy would run beside them) and from pinned memory (the host
 // refills A.tbl right away): a ring of four pinned images — every advance synchronises the stream between its two uploads, so
 // an image is never rewritten while its copy is still pending
-static int async_upload_tbl(mpmhip_ctx *c) {
+template <class Ctx>
+int as_upload_tbl(Ctx *c) {
   auto &A = c->async;
   auto &S = A.store;
   const size_t nblk = A.tbl.size();
-  if (S.pin_cap < nblk) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, S.h_tbl_pin.alloc(4 * nblk));
-    S.pin_cap = nblk;
-  }
-  uint8_t *img = S.h_tbl_pin + (size_t)(S.pin_next++ & 3) * S.pin_cap;
+  uint8_t *img = S.h_tbl_pin + (size_t)(S.pin_next++ & 3) * nblk;
   memcpy(img, A.tbl.data(), nblk);
-  HIPCHK(c, hipMemcpyAsync(S.d_tbl, img, nblk, hipMemcpyHostToDevice, c->stream));
+  AS_CHK(hipMemcpyAsync(S.d_tbl, img, nblk, hipMemcpyHostToDevice, c->stream));
   return MPMHIP_OK;
 }
-static int async_best_reserve(mpmhip_ctx *c) {  // one dedup word per creation id
+template <class Ctx>
+int as_best_reserve(Ctx *c) {  // one dedup word per creation id
   auto &S = c->async.store;
   if ((int64_t)c->next_pid <= S.best_cap) return MPMHIP_OK;
-  const size_t cap = (size_t)c->next_pid + (size_t)c->next_pid / 2 + 1024;
-  HIPCHK(c, S.best.alloc(cap));
-  HIPCHK(c, hipMemsetAsync(S.best, 0xFF, sizeof(unsigned long long) * cap, c->stream));
+  const size_t cap = AsyncStore::ids_grown((size_t)c->next_pid);
+  AS_CHK(S.best.alloc(cap));
+  AS_CHK(hipMemsetAsync(S.best, 0xFF, sizeof(unsigned long long) * cap, c->stream));
   S.best_cap = (int64_t)cap;
   return MPMHIP_OK;
 }
 // the ONE read-back of an advance: the transient counters (reset behind the copy) and the append cursor.  Folds what earlier
 // launches appended / freed into the host's view of the store.
-static int async_counters(mpmhip_ctx *c, AsyncCounters &h, bool reset_after) {
+template <class Ctx>
+int as_counters(Ctx *c, AsyncCounters &h) {
   auto &S = c->async.store;
-  AsyncCounters *pin = reinterpret_cast<AsyncCounters *>(c->h_pinned + 64);  // (the ctx's pinned page; the substep counters sit at its start)
-  HIPCHK(c, hipMemcpyAsync(pin, S.d_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
-  if (reset_after) HIPCHK(c, hipMemsetAsync(S.d_cnt, 0, 16, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  h = *pin;
+  AS_CHK(hipMemcpyAsync(S.h_cnt, S.d_cnt, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  AS_CHK(hipMemsetAsync(S.d_cnt, 0, 16, c->stream));
+  AS_CHK(hipStreamSynchronize(c->stream));
+  h = *S.h_cnt;
   if (h.pad[0] & SCAN_ERROR_BIT)
-    return fail(c, MPMHIP_EHIP, "async store: a chained scan of the compaction waited %.0f s for a chunk that never published (k_sort.h: "
-                "the launch did not fit the device's resident set?)", (double)SCAN_WAIT_TICKS / 1e8);
-  if (reset_after) {
-    S.live += h.n_append; S.live -= std::min(S.live, h.n_freed);
-    S.size = S.size_ub = h.size;
-    c->async.pending_counters = false;
-  }
+    return as_fail(c, MPMHIP_EHIP, "async store: a chained scan of the compaction waited " + std::to_string(SCAN_WAIT_TICKS / 100000000ull) +
+                                       " s for a chunk that never published (k_sort.h: the launch did not fit the device's resident set?)");
+  S.fold(h.n_append, h.n_freed, h.size);
+  S.pending_counters = false;
   return MPMHIP_OK;
 }
-struct AsTimer {  // wall time of a host-side section, accumulated into c->async.prof_ms[k] (synchronising sections included)
-  double &acc; std::chrono::steady_clock::time_point t0;
-  explicit AsTimer(double &a) : acc(a), t0(std::chrono::steady_clock::now()) {}
-  ~AsTimer() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-static int as_grid(uint32_t n) { return (int)std::min<uint32_t>(std::max<uint32_t>((n + 255) / 256, 1), 4096); }
-
-static int async_compact(mpmhip_ctx *c);
-// (called right behind a read-back: S.size and S.live are exact)
-static int async_compact_if_needed(mpmhip_ctx *c, uint32_t incoming) {
-  auto &S = c->async.store;
-  const uint32_t dead = S.size - std::min(S.size, S.live);
-  // squeeze when the freed containers outnumber the live ones (the passes over the tags then cost twice what they must), or
-  // when that avoids growing the store
-  if (!(dead > S.live + 65536 || (S.size + incoming > S.cap && dead > S.size / 4))) return MPMHIP_OK;
-  return async_compact(c);
+// counters a previous advance left on the device (appended / freed containers): folded into the host's view of the store
+template <class Ctx>
+int as_settle(Ctx *c) {
+  AsyncCounters h;
+  return c->async.store.pending_counters ? as_counters(c, h) : MPMHIP_OK;
 }
-static int async_compact(mpmhip_ctx *c) {
+// (called with the counters settled: S.size and S.live are exact.)  The store holds exactly its live containers afterwards.
+template <class Ctx>
+int as_compact(Ctx *c) {
   auto &S = c->async.store;
   if (S.size == 0) return MPMHIP_OK;
-  AsTimer whole(c->async.prof_ms[4]);
-  if (!S.g2) {
-    hipError_t e = hipSuccess;
-    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    A(S.g2.alloc((size_t)S.cap * 4)); A(S.w2.alloc((size_t)S.cap * 4)); A(S.tag2.alloc((size_t)S.cap)); A(S.id2.alloc((size_t)S.cap));
-    if (e != hipSuccess) return fail(c, MPMHIP_ENOMEM, "async store: compaction buffers: %s", hipGetErrorString(e));
-  }
-  HIPCHK(c, hipMemsetAsync(S.tag2, 0xFF, sizeof(uint32_t) * (size_t)S.cap, c->stream));
+  auto whole = as_timer(c, 4);
+  (void)whole;
+  if (const hipError_t e = S.reserve_twins(); e != hipSuccess) return as_fail(c, MPMHIP_ENOMEM, std::string("async store: compaction buffers: ") + hipGetErrorString(e));
+  AS_CHK(hipMemsetAsync(S.tag2, 0xFF, sizeof(uint32_t) * (size_t)S.cap, c->stream));
   const uint32_t nchunks = (S.size + 1023) / 1024;
   if (nchunks + 1 > S.scan_cap) {
-    HIPCHK(c, S.d_scan.alloc((size_t)nchunks + 1024));
-    HIPCHK(c, hipMemsetAsync(S.d_scan, 0, sizeof(unsigned long long) * ((size_t)nchunks + 1024), c->stream));
+    AS_CHK(S.d_scan.alloc((size_t)nchunks + 1024));
+    AS_CHK(hipMemsetAsync(S.d_scan, 0, sizeof(unsigned long long) * ((size_t)nchunks + 1024), c->stream));
     S.scan_cap = nchunks + 1024;
   }
-  hipLaunchKernelGGL(k_async_compact, dim3(std::min<uint32_t>(nchunks, scan_limit(c, (const void *)k_async_compact))), dim3(256), 0, c->stream, S.size,
-                     (const uint32_t *)S.tag, (const int32_t *)S.id, (const float4 *)S.g, (const float4 *)S.w, S.tag2, S.id2, S.g2, S.w2,
-                     S.d_scan, ++S.scan_epoch, S.d_cnt);
-  if (int rc = launch_check(c, "async_compact")) return rc;
-  std::swap(S.g, S.g2); std::swap(S.w, S.w2); std::swap(S.tag, S.tag2); std::swap(S.id, S.id2);
+  const auto V = as_store(c), V2 = as_store(c, true);
+  hipLaunchKernelGGL(k_async_compact<decltype(as_store(c))>, dim3(std::min(nchunks, as_compact_wgs(c))), dim3(256), 0, c->stream, S.size, V, V2,
+                     S.d_scan.get(), ++S.scan_epoch, S.d_cnt.get());
+  AS_LAUNCHED("async_compact");
+  S.swap_twins();
   AsyncCounters h;
-  if (int rc = async_counters(c, h, true)) return rc;  // (size = live = what the scan counted)
+  if (int rc = as_counters(c, h)) return rc;  // (size = live = what the scan counted)
   S.live = h.size;
   S.compactions++;
   return MPMHIP_OK;
 }
 
-// the ctx's records hold a view of the pools (load_pools): they are copies, dropped before anything else uses the records
-static int async_drop_view(mpmhip_ctx *c) {
+// the ctx's particles hold a view of the pools (load_pools): they are copies, dropped before anything else uses the arrays
+template <class Ctx>
+int as_drop_view(Ctx *c) {
   auto &A = c->async;
-  if (!A.resident || !A.records_are_view) return MPMHIP_OK;
-  A.records_are_view = false;
-  return drop_records(c, DEAD_ZERO_SYNC);
+  if (!A.resident || !A.store.view) return MPMHIP_OK;
+  A.store.view = false;
+  return as_working_set(c, 0);
 }
 
+// the working set (n slots) -> containers behind the store's end; all_to_pool: every particle goes to its block's pool
+template <class Ctx>
+int as_file(Ctx *c, uint32_t n, int all_to_pool) {
+  auto &A = c->async;
+  auto &S = A.store;
+  if (int rc = as_store_reserve(c, AsyncStore::sum(S.size, n))) return rc;
+  const uint32_t wgs = std::min<uint32_t>(std::max<uint32_t>((n + 255) / 256, 1), as_file_wgs(c));
+  hipLaunchKernelGGL(k_async_file<decltype(as_work(c))>, dim3(wgs), dim3(256), 0, c->stream, c->P.idx, n, as_work(c), (const uint8_t *)S.d_tbl,
+                     all_to_pool, A.nb[0], A.nb[1], A.nb[2], S.cap, as_store(c), S.d_cnt.get());
+  AS_LAUNCHED("async_file");
+  return MPMHIP_OK;
+}
+
+// AsyncMPM<dim>::add_particles (src/async/async_mpm.cpp:57-75): the particles currently in the ctx's arrays (just added) move to
+// the particle pools of their blocks; the arrays are empty afterwards (creation ids keep counting: next_pid stays).
+template <class Ctx>
+int as_pool_particles(Ctx *c) {
+  if (int rc = as_enter(c)) return rc;
+  if (int rc = as_drop_view(c)) return rc;
+  if (as_slots(c) == 0) return MPMHIP_OK;
+  if (int rc = as_settle(c)) return rc;
+  if (int rc = as_before_filing(c)) return rc;
+  if (int rc = as_file(c, (uint32_t)as_slots(c), 1)) return rc;
+  AsyncCounters h;
+  if (int rc = as_counters(c, h)) return rc;
+  return as_working_set(c, 0);
+}
+
+// AsyncMPM<dim>::update_dt_limits (src/async/async_mpm.cpp:90-253) over the resident pools
+template <class Ctx>
+int as_update_dt_limits(Ctx *c) {
+  auto &A = c->async;
+  auto &S = A.store;
+  const uint32_t nblk = (uint32_t)A.nblk();
+  auto whole = as_timer(c, 0);
+  (void)whole;
+  hipLaunchKernelGGL(k_async_table_reset, as_grid(c, nblk), dim3(256), 0, c->stream, nblk, A.d_tab.get());
+  hipLaunchKernelGGL(k_async_store_reduce<decltype(as_store(c))>, as_grid(c, S.size_ub), dim3(256), 0, c->stream, c->P.dx, S.size_ub, as_store(c),
+                     (const GroupParams *)c->d_groups, A.d_tab.get());
+  AS_LAUNCHED("async_store_reduce");
+  A.scratch = A.continuous;
+  if (int rc = async_limits_from_table(c)) return rc;  // the block state machine shared with mpmhip_async_update_dt_limits
+  if (A.scratch != A.continuous) A.limits_version++;
+  auto lists = as_timer(c, 1);
+  (void)lists;
+  A.rebuild_lists();  // larger / smaller neighbours per level (:183-247), local_min_dt_limit (:165-182)
+  return MPMHIP_OK;
+}
+
+// AsyncMPM<dim>::advance (src/async/async_mpm.cpp:255-373)
+template <class Ctx>
+int as_advance(Ctx *c, int64_t limit) {
+  auto &A = c->async;
+  auto &S = A.store;
+  const int64_t t = A.current_t_int;
+  auto whole = as_timer(c, 2);
+  (void)whole;
+  if (!A.plan_gather(limit)) return as_fail(c, MPMHIP_EINVAL, A.sched_err);
+  if (int rc = as_best_reserve(c)) return rc;
+  if (int rc = as_upload_tbl(c)) return rc;
+  // the working set holds at most one container per id (duplicates are dropped by the gather), i.e. at most
+  // min(containers, ids handed out) particles: the ctx's arrays get that room BEFORE the gather writes into them — a
+  // C-ABI caller may have pooled several batches of up to `cap` particles each (pool_particles empties the slots)
+  if (int rc = as_make_room(c, std::min<int64_t>((int64_t)S.size_ub, (int64_t)c->next_pid))) return rc;
+  hipLaunchKernelGGL(k_async_mark<decltype(as_store(c))>, as_grid(c, S.size_ub), dim3(256), 0, c->stream, S.size_ub, as_store(c),
+                     (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best.get());
+  hipLaunchKernelGGL(k_async_gather<decltype(as_work(c))>, as_grid(c, S.size_ub), dim3(256), 0, c->stream, S.size_ub, as_store(c),
+                     (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best.get(), as_work(c), S.d_cnt.get());
+  AS_LAUNCHED("async_gather");
+  AsyncCounters h;
+  if (int rc = as_counters(c, h)) return rc;  // the one read-back of an advance (also settles the previous one's appends)
+  const uint32_t n_work = h.n_work;
+  if ((int64_t)n_work > c->cap)
+    return as_fail(c, MPMHIP_ECAPACITY, "async: a working set of " + std::to_string(n_work) + " particles exceeds the ctx capacity " + std::to_string(c->cap));
+  A.update_counter += n_work;
+  // ONE ordinary substep of the working set with this level's dt (:327-329; step() sets base_delta_t / current_t, :405-408)
+  if (int rc = as_working_set(c, n_work)) return rc;  // the gather replaced the ctx's particles by the working set
+  c->P.dt = A.cfg.unit_delta_t * (float)limit;
+  c->t = A.cfg.unit_delta_t * (float)t;
+  if (n_work) {
+    if (int rc = as_substep(c)) return rc;
+  }
+  const bool any_clear = A.plan_file(limit);  // update backup_t and particle_t (:331-343), destinations of the results
+  if (int rc = as_upload_tbl(c)) return rc;
+  if (any_clear)
+    hipLaunchKernelGGL(k_async_clear, as_grid(c, S.size), dim3(256), 0, c->stream, S.size, S.tag.get(), (const uint8_t *)S.d_tbl, S.d_cnt.get());
+  if (n_work) {
+    if (S.wants_compaction(n_work)) {  // (right behind the read-back: S.size and S.live are exact)
+      if (int rc = as_compact(c)) return rc;
+    }
+    if (int rc = as_file(c, n_work, 0)) return rc;
+    S.size_ub = AsyncStore::sum(S.size, n_work);  // (the exact size comes with the next read-back)
+  }
+  AS_LAUNCHED("async_clear");
+  S.pending_counters = true;
+  return MPMHIP_OK;
+}
+
+// AsyncMPM<dim>::step (src/async/async_mpm.cpp:380-421)
+template <class Ctx>
+int as_step(Ctx *c, float dt) {
+  auto &A = c->async;
+  if (int rc = as_enter(c)) return rc;
+  if (dt < 0) return as_fail(c, MPMHIP_EINVAL, "AsyncMPM::step(dt < 0) is the synchronous substep of the base class");
+  if (int rc = as_pool_particles(c)) return rc;  // (drops a view; pools particles added since the last step)
+  A.request_t += dt;
+  do {
+    if (int rc = as_update_dt_limits(c)) return rc;
+    for (int64_t d = A.max_delta_t_int; d >= A.min_delta_t_int; d >>= 1)
+      if (A.current_t_int % d == 0) {
+        if (int rc = as_advance(c, d)) return rc;
+      }
+    A.finish_round();
+  } while (A.current_t < A.request_t);
+  if (int rc = as_settle(c)) return rc;
+  as_end_step(c);  // the arrays held the last working set: the state is in the pools
+  c->t = A.current_t;
+  A.step_counter++;
+  return MPMHIP_OK;
+}
+
+// {current_t_int, update_counter, min_delta_t_int, max_delta_t_int, live containers, store size, compactions, steps}
+template <class Ctx>
+int as_state(Ctx *c, int64_t out[8]) {
+  auto &A = c->async;
+  if (int rc = as_enter(c)) return rc;
+  if (int rc = as_settle(c)) return rc;
+  out[0] = A.current_t_int; out[1] = A.update_counter; out[2] = A.min_delta_t_int; out[3] = A.max_delta_t_int;
+  out[4] = A.store.live; out[5] = A.store.size; out[6] = A.store.compactions; out[7] = A.step_counter;
+  return MPMHIP_OK;
+}
+
+// AsyncMPM<dim>::visualize's particle list (src/async/async_visualize.cpp:17-26,86-96): ALL containers of all particle pools
+// become the ctx's particles (each at its block's particle_t; an id can occur more than once, as in the reference), so that
+// frame output, downloads, energy and snapshots of the base class see the whole state, not the last working set; d_blk_of gets
+// the pool block of each.  The view is dropped by the next step or add.
+template <class Ctx>
+int as_load_pools(Ctx *c) {
+  auto &A = c->async;
+  auto &S = A.store;
+  if (int rc = as_pool_particles(c)) return rc;  // (drops an earlier view; pools particles added since)
+  if (int rc = as_settle(c)) return rc;
+  if (int rc = as_make_room(c, (int64_t)S.live)) return rc;
+  if (int rc = as_ensure_blk_of(c)) return rc;
+  hipLaunchKernelGGL(k_async_load<decltype(as_work(c))>, as_grid(c, S.size), dim3(256), 0, c->stream, S.size, as_store(c), as_work(c),
+                     A.d_blk_of.get(), S.d_cnt.get());
+  AS_LAUNCHED("async_load");
+  AsyncCounters h;
+  if (int rc = as_counters(c, h)) return rc;
+  if (int rc = as_working_set(c, h.n_work)) return rc;  // k_async_load replaced the ctx's particles by the view
+  S.view = true;
+  return MPMHIP_OK;
+}
+
+// the reduced table -> the block state machine of AsyncMPM<dim>::update_dt_limits (AsyncSched::limits_from_table)
+template <class Ctx>
+int async_limits_from_table(Ctx *c) {
+  auto &A = c->async;
+  const size_t nblk = A.nblk();
+  if (A.h_tab_cap < 3 * nblk) {  // pinned staging (a copy into pageable memory is staged by the runtime: ~50 us more)
+    AS_CHK(A.h_tab.alloc(3 * nblk));
+    A.h_tab_cap = 3 * nblk;
+  }
+  AS_CHK(hipMemcpyAsync(A.h_tab, A.d_tab, sizeof(uint32_t) * 3 * nblk, hipMemcpyDeviceToHost, c->stream));
+  AS_CHK(hipStreamSynchronize(c->stream));
+  if (!A.limits_from_table(A.h_tab, c->P.dx)) return as_fail(c, MPMHIP_EINVAL, A.sched_err);
+  return MPMHIP_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+static int async_drop_view(mpmhip_ctx *c) { return as_drop_view(c); }
+static int async_drop_view(mpmhip2d_ctx *m) { return as_drop_view(m); }
+
+// ------------------------------------------------------------------------------------------------ the 3D entry points
 // AsyncMPM<dim>::initialize (src/async/async_mpm.cpp:13-55) on top of mpmhip_async_enable: the pools become device-resident
 int mpmhip_async_begin(mpmhip_ctx *c, const mpmhip_async_config *cfg) {
   if (!c || !cfg) return MPMHIP_EINVAL;
@@ -132,164 +401,11 @@ int mpmhip_async_begin(mpmhip_ctx *c, const mpmhip_async_config *cfg) {
   if (!c->P.store_b) return fail(c, MPMHIP_EINVAL, "asynchronous stepping needs a ctx that keeps apic_b (discard_apic_b = 0): the "
                                                    "P2G matrix depends on each advance's dt and is rebuilt from it");
   if (int rc = mpmhip_async_enable(c, cfg)) return rc;
-  auto &A = c->async;
-  auto &S = A.store;
-  A.sched_begin();  // block times, the reference's block order, cached_neighbours
-  const size_t nblk = A.nblk();
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, S.d_tbl.alloc(nblk));
-  HIPCHK(c, S.d_rank.alloc(nblk));
-  HIPCHK(c, S.d_cnt.alloc(1));
-  HIPCHK(c, hipMemcpy(S.d_rank, A.rank_of.data(), sizeof(uint32_t) * nblk, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemset(S.d_cnt, 0, sizeof(AsyncCounters)));
-  S.size = S.size_ub = S.live = 0;
-  A.resident = true;
-  return MPMHIP_OK;
+  return as_begin(c, {sizeof(int32_t), 4 * sizeof(float4), 4 * sizeof(float4)});  // lanes: id, g, w (k_async.h: Store3)
 }
-
-static int async_settle(mpmhip_ctx *c);
-// AsyncMPM<dim>::add_particles (src/async/async_mpm.cpp:57-75): the particles currently in the ctx's records (just added by
-// mpmhip_add_particles) move to the particle pools of their blocks; the ctx's record arrays are empty afterwards.
-int mpmhip_async_pool_particles(mpmhip_ctx *c) {
-  if (!c) return MPMHIP_EINVAL;
-  auto &A = c->async;
-  auto &S = A.store;
-  if (!A.resident) return fail(c, MPMHIP_EINVAL, "mpmhip_async_begin first");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = async_drop_view(c)) return rc;
-  if (c->n_slots == 0) return MPMHIP_OK;
-  if (int rc = async_settle(c)) return rc;
-  if (int rc = ensure_b_current(c)) return rc;
-  if (int rc = async_store_reserve(c, S.size + (uint32_t)c->n_slots)) return rc;
-  hipLaunchKernelGGL(k_async_file, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(),
-                     (const float4 *)c->rp.get(), (const float4 *)c->rb.get(), (const uint8_t *)S.d_tbl, 1, A.nb[0], A.nb[1], A.nb[2], S.cap,
-                     S.g, S.w, S.tag, S.id, S.d_cnt);
-  if (int rc = launch_check(c, "async_file")) return rc;
-  AsyncCounters h;
-  if (int rc = async_counters(c, h, true)) return rc;
-  return drop_records(c, DEAD_ZERO_SYNC);  // (creation ids keep counting: next_pid stays)
-}
-
-// AsyncMPM<dim>::update_dt_limits (src/async/async_mpm.cpp:90-253) over the resident pools
-static int async_update_dt_limits(mpmhip_ctx *c) {
-  auto &A = c->async;
-  auto &S = A.store;
-  const size_t nblk = A.continuous.size();
-  AsTimer whole(A.prof_ms[0]);
-  hipLaunchKernelGGL(k_async_table_reset, dim3(as_grid((uint32_t)nblk)), dim3(256), 0, c->stream, (uint32_t)nblk, A.d_tab);
-  hipLaunchKernelGGL(k_async_store_reduce, dim3(as_grid(S.size_ub)), dim3(256), 0, c->stream, c->P, S.size_ub, (const uint32_t *)S.tag,
-                     (const float4 *)S.g, (const float4 *)S.w, (const GroupParams *)c->d_groups, A.d_tab);
-  if (int rc = launch_check(c, "async_store_reduce")) return rc;
-  A.scratch = A.continuous;
-  if (int rc = async_limits_from_table(c)) return rc;  // the block state machine shared with mpmhip_async_update_dt_limits
-  if (A.scratch != A.continuous) A.limits_version++;
-  AsTimer lists(A.prof_ms[1]);
-  A.rebuild_lists();  // larger / smaller neighbours per level (:183-247), local_min_dt_limit (:165-182)
-  return MPMHIP_OK;
-}
-
-// AsyncMPM<dim>::advance (src/async/async_mpm.cpp:255-373)
-static int async_advance(mpmhip_ctx *c, int64_t limit) {
-  auto &A = c->async;
-  auto &S = A.store;
-  const int64_t t = A.current_t_int;
-  AsTimer whole(A.prof_ms[2]);
-  A.prof_ms[5] += 1.0;  // (advances)
-  if (!A.plan_gather(limit)) return fail(c, MPMHIP_EINVAL, "%s", A.sched_err.c_str());
-  if (int rc = async_best_reserve(c)) return rc;
-  if (int rc = async_upload_tbl(c)) return rc;
-  // the working set holds at most one container per id (duplicates are dropped by the gather), i.e. at most
-  // min(containers, ids handed out) records: the ctx's record arrays get that room BEFORE the gather writes into them — a
-  // C-ABI caller may have pooled several batches of up to `cap` particles each (mpmhip_async_pool_particles empties the slots)
-  {
-    const int64_t bound = std::min<int64_t>((int64_t)S.size_ub, (int64_t)c->next_pid);
-    if (bound > c->cap) {
-      if (int rc = mpmhip_reserve(c, bound + 1024)) return rc;
-    }
-  }
-  hipLaunchKernelGGL(k_async_mark, dim3(as_grid(S.size_ub)), dim3(256), 0, c->stream, S.size_ub, (const uint32_t *)S.tag,
-                     (const int32_t *)S.id, (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best);
-  hipLaunchKernelGGL(k_async_gather, dim3(as_grid(S.size_ub)), dim3(256), 0, c->stream, S.size_ub, S.tag, (const int32_t *)S.id,
-                     (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best, (const float4 *)S.g, (const float4 *)S.w,
-                     (const GroupParams *)c->d_groups, (float4 *)c->rg.get(), (float4 *)c->rp.get(), (float4 *)c->rb.get(), S.d_cnt);
-  if (int rc = launch_check(c, "async_gather")) return rc;
-  AsyncCounters h;
-  if (int rc = async_counters(c, h, true)) return rc;  // the one read-back of an advance (also settles the previous one's appends)
-  const uint32_t n_work = h.n_work;
-  if ((int64_t)n_work > c->cap) return fail(c, MPMHIP_ECAPACITY, "async: a working set of %u particles exceeds the ctx capacity %lld", n_work, (long long)c->cap);
-  A.update_counter += n_work;
-  // ONE ordinary substep of the working set with this level's dt (:327-329; step() sets base_delta_t / current_t, :405-408)
-  if (int rc = drop_records(c, DEAD_ZERO_ON_STREAM)) return rc;  // the gather replaced the records by the working set
-  set_slots(c, n_work);
-  c->P.dt = A.cfg.unit_delta_t * (float)limit;
-  c->t = A.cfg.unit_delta_t * (float)t;
-  if (n_work) {
-    AsTimer sub(A.prof_ms[3]);
-    if (int rc = mpmhip_substep(c)) return rc;
-    if (A.profile_sync) HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  const bool any_clear = A.plan_file(limit);  // update backup_t and particle_t (:331-343), destinations of the results
-  if (int rc = async_upload_tbl(c)) return rc;
-  if (any_clear)
-    hipLaunchKernelGGL(k_async_clear, dim3(as_grid(S.size)), dim3(256), 0, c->stream, S.size, S.tag, (const uint8_t *)S.d_tbl, S.d_cnt);
-  if (n_work) {
-    if (int rc = async_compact_if_needed(c, n_work)) return rc;
-    if (int rc = async_store_reserve(c, S.size + n_work)) return rc;
-    hipLaunchKernelGGL(k_async_file, dim3(particle_grid(n_work)), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(),
-                       (const float4 *)c->rp.get(), (const float4 *)c->rb.get(), (const uint8_t *)S.d_tbl, 0, A.nb[0], A.nb[1], A.nb[2], S.cap,
-                       S.g, S.w, S.tag, S.id, S.d_cnt);
-    S.size_ub = S.size + n_work;  // (the exact size comes with the next read-back)
-  }
-  if (int rc = launch_check(c, "async_file")) return rc;
-  A.pending_counters = true;
-  return MPMHIP_OK;
-}
-
-// counters a previous advance left on the device (appended / freed containers): folded into the host's view of the store
-static int async_settle(mpmhip_ctx *c) {
-  if (!c->async.pending_counters) return MPMHIP_OK;
-  AsyncCounters h;
-  return async_counters(c, h, true);
-}
-
-// AsyncMPM<dim>::step (src/async/async_mpm.cpp:380-421)
-int mpmhip_async_step(mpmhip_ctx *c, float dt) {
-  if (!c) return MPMHIP_EINVAL;
-  auto &A = c->async;
-  if (!A.resident) return fail(c, MPMHIP_EINVAL, "mpmhip_async_begin first");
-  if (dt < 0) return fail(c, MPMHIP_EINVAL, "AsyncMPM::step(dt < 0) is the synchronous substep of the base class");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = async_drop_view(c)) return rc;
-  if (c->n_slots) {  // (particles added since the last step and not yet pooled)
-    if (int rc = mpmhip_async_pool_particles(c)) return rc;
-  }
-  A.request_t += dt;
-  do {
-    if (int rc = async_update_dt_limits(c)) return rc;
-    for (int64_t d = A.max_delta_t_int; d >= A.min_delta_t_int; d >>= 1)
-      if (A.current_t_int % d == 0) {
-        if (int rc = async_advance(c, d)) return rc;
-      }
-    A.finish_round();
-  } while (A.current_t < A.request_t);
-  if (int rc = async_settle(c)) return rc;
-  set_slots(c, 0);  // the records held the last working set: the state is in the pools
-  c->t = A.current_t;
-  A.step_counter++;
-  return MPMHIP_OK;
-}
-
-// {current_t_int, update_counter, pool containers, backup containers + freed (store size - pool), compactions, store size}
-int mpmhip_async_state(mpmhip_ctx *c, int64_t out[8]) {
-  if (!c || !out) return MPMHIP_EINVAL;
-  auto &A = c->async;
-  if (!A.resident) return fail(c, MPMHIP_EINVAL, "mpmhip_async_begin first");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = async_settle(c)) return rc;
-  out[0] = A.current_t_int; out[1] = A.update_counter; out[2] = A.min_delta_t_int; out[3] = A.max_delta_t_int;
-  out[4] = A.store.live; out[5] = A.store.size; out[6] = A.store.compactions; out[7] = A.step_counter;
-  return MPMHIP_OK;
-}
+int mpmhip_async_pool_particles(mpmhip_ctx *c) { return c ? as_pool_particles(c) : MPMHIP_EINVAL; }
+int mpmhip_async_step(mpmhip_ctx *c, float dt) { return c ? as_step(c, dt) : MPMHIP_EINVAL; }
+int mpmhip_async_state(mpmhip_ctx *c, int64_t out[8]) { return c && out ? as_state(c, out) : MPMHIP_EINVAL; }
 // host wall time so far, ms: {update_dt_limits, of which neighbour lists, advance, of which the substep (only meaningful with
 // sync != 0: the stream is then synchronised behind every substep), compaction, number of advances}
 int mpmhip_async_profile(mpmhip_ctx *c, int32_t sync, double out[6]) {
@@ -320,21 +436,20 @@ int64_t mpmhip_async_block_times(mpmhip_ctx *c, int64_t capacity, int64_t *parti
 // only the count.  (Tests and host-side inspection: the stepping itself never calls this.)
 int64_t mpmhip_async_download_pools(mpmhip_ctx *c, int64_t capacity, float *rows, int32_t *block) {
   if (!c) return MPMHIP_EINVAL;
-  auto &A = c->async;
-  auto &S = A.store;
-  if (!A.resident) return fail(c, MPMHIP_EINVAL, "mpmhip_async_begin first");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = async_settle(c)) return rc;
+  auto &S = c->async.store;
+  if (int rc = as_enter(c)) return rc;
+  if (int rc = as_settle(c)) return rc;
   DevBuf<float> d_rows;
   DevBuf<uint32_t> d_blk;
   const size_t m = std::max<size_t>(S.size, 1);
   HIPCHK(c, d_rows.alloc(m * 27));
   HIPCHK(c, d_blk.alloc(m));
-  hipLaunchKernelGGL(k_async_export, dim3(as_grid(S.size)), dim3(256), 0, c->stream, S.size, (const uint32_t *)S.tag, (const float4 *)S.g,
-                     (const float4 *)S.w, d_rows, d_blk, S.d_cnt);
+  const Store3 V = as_store(c);
+  hipLaunchKernelGGL(k_async_export, as_grid(c, S.size), dim3(256), 0, c->stream, S.size, (const uint32_t *)V.tag, (const float4 *)V.g,
+                     (const float4 *)V.w, d_rows.get(), d_blk.get(), S.d_cnt.get());
   AsyncCounters h;
   if (int rc = launch_check(c, "async_export")) return rc;
-  if (int rc = async_counters(c, h, true)) return rc;
+  if (int rc = as_counters(c, h)) return rc;
   const int64_t n = (int64_t)h.n_work;
   if (!rows || !block || !n) return n;
   if (capacity < n) return fail(c, MPMHIP_ECAPACITY, "async download: %lld containers, room for %lld", (long long)n, (long long)capacity);
@@ -344,36 +459,14 @@ int64_t mpmhip_async_download_pools(mpmhip_ctx *c, int64_t capacity, float *rows
   return n;
 }
 
-// AsyncMPM<dim>::visualize's particle list (src/async/async_visualize.cpp:17-26,86-96): ALL containers of all particle pools
-// become the ctx's records (so that frame output, downloads, energy and snapshots of the base class see the whole state, not
-// the last working set), each with its pool block's (continuous, strength, cfl) limits for the `limit` attribute.
+// as_load_pools, and each particle of the view gets its pool block's (continuous, strength, cfl) limits for the frame's `limit` attribute
 int mpmhip_async_load_pools(mpmhip_ctx *c) {
   if (!c) return MPMHIP_EINVAL;
   auto &A = c->async;
-  auto &S = A.store;
-  if (!A.resident) return fail(c, MPMHIP_EINVAL, "mpmhip_async_begin first");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = async_settle(c)) return rc;
-  if (int rc = mpmhip_async_pool_particles(c)) return rc;  // (drops an earlier view; pools particles added since)
-  if ((int64_t)S.live > c->cap) {
-    if (int rc = mpmhip_reserve(c, (int64_t)S.live + 1024)) return rc;
-  }
-  const size_t nblk = A.continuous.size();
-  if (int rc = async_ensure_particle_arrays(c)) return rc;
-  std::fill(A.tbl.begin(), A.tbl.end(), (uint8_t)AT_POOL1);
-  if (int rc = async_upload_tbl(c)) return rc;
-  hipLaunchKernelGGL(k_async_load, dim3(as_grid(S.size)), dim3(256), 0, c->stream, S.size, (const uint32_t *)S.tag, (const float4 *)S.g,
-                     (const float4 *)S.w, (const GroupParams *)c->d_groups, (float4 *)c->rg.get(), (float4 *)c->rp.get(), (float4 *)c->rb.get(),
-                     A.d_blk_of, S.d_cnt);
-  if (int rc = launch_check(c, "async_load")) return rc;
-  AsyncCounters h;
-  if (int rc = async_counters(c, h, true)) return rc;
-  if (int rc = drop_records(c, DEAD_ZERO_SYNC)) return rc;  // k_async_load replaced the records by the view
-  set_slots(c, h.n_work);
-  A.records_are_view = true;
+  if (int rc = as_load_pools(c)) return rc;
   c->P.dt = c->cfg.dt;  // (the P2G matrices are rebuilt for the configured base step if anybody runs a synchronous substep)
-  // the frame's `limit` attribute: the limits of the container's POOL block
   if (c->n_slots) {
+    const size_t nblk = A.nblk();
     std::vector<int32_t> lim(3 * nblk);
     for (size_t b = 0; b < nblk; b++) { lim[3 * b] = (int32_t)A.continuous[b]; lim[3 * b + 1] = (int32_t)A.strength[b]; lim[3 * b + 2] = (int32_t)A.cfl[b]; }
     HIPCHK(c, hipMemcpy(A.d_blk_limits, lim.data(), sizeof(int32_t) * 3 * nblk, hipMemcpyHostToDevice));
@@ -387,8 +480,9 @@ int mpmhip_async_load_pools(mpmhip_ctx *c) {
 
 // ---- snapshots of the asynchronous stepper (the reference serialises every pool and the block table: TC_IO of
 // particle_pool_tmp / backup_pool_tmp / blocks, src/async/async_mpm.h:120-172).  Blob: header, group table, the per-block
-// integers, the store's live containers (compacted).  Loaded into a ctx of the same grid on which mpmhip_async_begin has run
-// with the same unit_delta_t; level set and configuration come from the scene, as for the synchronous snapshots.
+// integers, the store's live containers (compacted: tags, ids, g, w).  Loaded into a ctx of the same grid on which
+// mpmhip_async_begin has run with the same unit_delta_t; level set and configuration come from the scene, as for the
+// synchronous snapshots.
 struct SnapAsync {
   char magic[8];  // "MPMASYNC"
   uint32_t abi, n_groups;
@@ -402,15 +496,11 @@ static size_t async_snapshot_bytes(const mpmhip_ctx *c, size_t containers) {
   return sizeof(SnapAsync) + sizeof(GroupParams) * c->groups.size() + sizeof(int64_t) * 6 * c->async.continuous.size() +
          containers * (sizeof(uint32_t) + sizeof(int32_t) + 2 * 4 * sizeof(float4));
 }
-static int async_force_compaction(mpmhip_ctx *c) {  // the store holds exactly its live containers afterwards
-  if (int rc = async_settle(c)) return rc;
-  return async_compact(c);
-}
 int64_t mpmhip_async_snapshot_size(mpmhip_ctx *c) {
   if (!c || !c->async.resident) return MPMHIP_EINVAL;
-  if (hipSetDevice(c->device) != hipSuccess) return MPMHIP_EHIP;
-  if (int rc = mpmhip_async_pool_particles(c)) return rc;
-  if (int rc = async_force_compaction(c)) return rc;
+  if (int rc = as_pool_particles(c)) return rc;
+  if (int rc = as_settle(c)) return rc;
+  if (int rc = as_compact(c)) return rc;  // the store holds exactly its live containers afterwards
   return (int64_t)async_snapshot_bytes(c, c->async.store.size);
 }
 int mpmhip_async_snapshot_save(mpmhip_ctx *c, void *dst, size_t cap) {
@@ -436,14 +526,8 @@ int mpmhip_async_snapshot_save(mpmhip_ctx *c, void *dst, size_t cap) {
   memcpy(p, c->groups.data(), sizeof(GroupParams) * c->groups.size()); p += sizeof(GroupParams) * c->groups.size();
   const size_t nb = sizeof(int64_t) * (size_t)h.nblk;
   for (const std::vector<int64_t> *v : {&A.continuous, &A.strength, &A.cfl, &A.particle_t, &A.backup_t, &A.local_min}) { memcpy(p, v->data(), nb); p += nb; }
-  const size_t n = S.size;
-  if (n) {
-    HIPCHK(c, hipMemcpy(p, S.tag, sizeof(uint32_t) * n, hipMemcpyDeviceToHost)); p += sizeof(uint32_t) * n;
-    HIPCHK(c, hipMemcpy(p, S.id, sizeof(int32_t) * n, hipMemcpyDeviceToHost)); p += sizeof(int32_t) * n;
-    HIPCHK(c, hipMemcpy(p, S.g, sizeof(float4) * 4 * n, hipMemcpyDeviceToHost)); p += sizeof(float4) * 4 * n;
-    HIPCHK(c, hipMemcpy(p, S.w, sizeof(float4) * 4 * n, hipMemcpyDeviceToHost));
-    c->host_particle_bytes += (int64_t)n * 136;
-  }
+  HIPCHK(c, S.save(p, S.size));
+  c->host_particle_bytes += (int64_t)S.size * 136;
   return MPMHIP_OK;
 }
 int mpmhip_async_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
@@ -465,10 +549,11 @@ int mpmhip_async_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
   if (size != sizeof(SnapAsync) + sizeof(GroupParams) * (size_t)h.n_groups + sizeof(int64_t) * 6 * (size_t)h.nblk +
                   (size_t)h.containers * (sizeof(uint32_t) + sizeof(int32_t) + 2 * 4 * sizeof(float4)))
     return fail(c, MPMHIP_EINVAL, "snapshot size mismatch");
+  const char *containers = (const char *)src + sizeof h + sizeof(GroupParams) * h.n_groups + 6 * sizeof(int64_t) * (size_t)h.nblk;
   {  // the container arrays index the block table (tag), the block order and the per-id bids (id) on the device: a truncated
      // or foreign blob must not get that far
     const size_t n = (size_t)h.containers;
-    const char *q = (const char *)src + sizeof h + sizeof(GroupParams) * h.n_groups + 6 * sizeof(int64_t) * (size_t)h.nblk;
+    const char *q = containers;
     const uint32_t *tags = reinterpret_cast<const uint32_t *>(q);
     const int32_t *ids = reinterpret_cast<const int32_t *>(q + sizeof(uint32_t) * n);
     if (h.next_pid < 0) return fail(c, MPMHIP_EINVAL, "snapshot header inconsistent with this ctx (next id %d)", h.next_pid);
@@ -500,21 +585,9 @@ int mpmhip_async_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
   for (std::vector<int64_t> *v : {&A.continuous, &A.strength, &A.cfl, &A.particle_t, &A.backup_t, &A.local_min}) { memcpy(v->data(), p, nb); p += nb; }
   const size_t n = (size_t)h.containers;
   S.size = S.size_ub = S.live = 0;
-  if (int rc = async_store_reserve(c, (uint32_t)n + 1024)) return rc;
-  HIPCHK(c, hipMemset(S.tag, 0xFF, sizeof(uint32_t) * (size_t)S.cap));
-  if (n) {
-    HIPCHK(c, hipMemcpy(S.tag, p, sizeof(uint32_t) * n, hipMemcpyHostToDevice)); p += sizeof(uint32_t) * n;
-    HIPCHK(c, hipMemcpy(S.id, p, sizeof(int32_t) * n, hipMemcpyHostToDevice)); p += sizeof(int32_t) * n;
-    HIPCHK(c, hipMemcpy(S.g, p, sizeof(float4) * 4 * n, hipMemcpyHostToDevice)); p += sizeof(float4) * 4 * n;
-    HIPCHK(c, hipMemcpy(S.w, p, sizeof(float4) * 4 * n, hipMemcpyHostToDevice));
-    c->host_particle_bytes += (int64_t)n * 136;
-  }
-  S.size = S.size_ub = S.live = (uint32_t)n;
-  AsyncCounters z;
-  memset(&z, 0, sizeof z);
-  z.size = (uint32_t)n;
-  HIPCHK(c, hipMemcpy(S.d_cnt, &z, sizeof z, hipMemcpyHostToDevice));
-  A.pending_counters = false; A.records_are_view = false;
+  if (int rc = as_store_reserve(c, (uint32_t)n + 1024)) return rc;
+  HIPCHK(c, S.load(containers, n));
+  c->host_particle_bytes += (int64_t)n * 136;
   A.current_t_int = h.current_t_int; A.min_delta_t_int = h.min_delta_t_int; A.max_delta_t_int = h.max_delta_t_int;
   A.update_counter = h.update_counter; A.step_counter = h.step_counter;
   A.request_t = h.request_t; A.current_t = h.current_t;
@@ -523,4 +596,60 @@ int mpmhip_async_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
   c->t = A.current_t;
   // (the one drop that leaves n_dead alone: a count left by the last working set stays until the next advance zeroes it)
   return drop_records(c, DEAD_KEEP);
+}
+
+// ------------------------------------------------------------------------------------------------ the 2D entry points
+// AsyncMPM<2>::initialize (src/async/async_mpm.cpp:13-55) on top of mpmhip2d_create
+int mpmhip2d_async_begin(mpmhip2d_ctx *m, const mpmhip_async_config *cfg) {
+  if (!m || !cfg) return MPMHIP_EINVAL;
+  if (!(cfg->unit_delta_t > 0) || cfg->max_units < 1) return fail2d(m, MPMHIP_EINVAL, "unit_delta_t > 0 and max_units >= 1 required");
+  if (m->rigid_enabled) return fail2d(m, MPMHIP_EINVAL, "asynchronous stepping cannot be combined with rigid bodies");
+  HIPCHK2D(m, hipSetDevice(m->device));
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  auto &A = m->async;
+  A.sched_enable(2, m->P.res, *cfg);
+  HIPCHK2D(m, A.d_tab.alloc(3 * A.nblk()));
+  return as_begin(m, {4 * sizeof(float4)});  // lane: rec (k_async.h: Store2)
+}
+int mpmhip2d_async_pool_particles(mpmhip2d_ctx *m) { return m ? as_pool_particles(m) : MPMHIP_EINVAL; }
+int mpmhip2d_async_step(mpmhip2d_ctx *m, float dt) { return m ? as_step(m, dt) : MPMHIP_EINVAL; }
+int mpmhip2d_async_state(mpmhip2d_ctx *m, int64_t out[8]) { return m && out ? as_state(m, out) : MPMHIP_EINVAL; }
+double mpmhip2d_async_current_time(const mpmhip2d_ctx *m) { return m ? (double)m->async.current_t : 0.0; }
+// as_load_pools: mpmhip2d_download / _num_particles then see the whole state.  Returns the number of containers.
+int64_t mpmhip2d_async_load_pools(mpmhip2d_ctx *m) {
+  if (!m) return MPMHIP_EINVAL;
+  if (int rc = as_load_pools(m)) return rc;
+  return m->n;
+}
+
+// dense view of the block table: nb[2] blocks per axis (block b = bx nb[1] + by, 8 x 16 nodes each); any output may be NULL.
+// capacity < number of blocks: only the number is returned.
+int64_t mpmhip2d_async_table(mpmhip2d_ctx *m, int32_t nb[2], int64_t capacity, int64_t *strength, int64_t *cfl, int64_t *continuous,
+                             int64_t *count, int64_t *particle_t, int64_t *backup_t, int64_t *local_min) {
+  if (!m || !m->async.resident || !nb) return MPMHIP_EINVAL;
+  auto &A = m->async;
+  nb[0] = A.nb[0]; nb[1] = A.nb[1];
+  const int64_t n = (int64_t)A.nblk();
+  if (capacity < n) return n;
+  for (int64_t b = 0; b < n; b++) {
+    if (strength) strength[b] = A.strength[b];
+    if (cfl) cfl[b] = A.cfl[b];
+    if (continuous) continuous[b] = A.continuous[b];
+    if (count) count[b] = A.count[b];
+    if (particle_t) particle_t[b] = A.particle_t[b];
+    if (backup_t) backup_t[b] = A.backup_t[b];
+    if (local_min) local_min[b] = A.local_min[b];
+  }
+  return n;
+}
+// the pool block of every particle of the view, in the order mpmhip2d_download lists them
+int64_t mpmhip2d_async_view_blocks(mpmhip2d_ctx *m, int64_t capacity, int32_t *block) {
+  if (!m || !block) return MPMHIP_EINVAL;
+  auto &A = m->async;
+  if (!A.resident || !A.store.view) return fail2d(m, MPMHIP_EINVAL, "mpmhip2d_async_load_pools first");
+  if (capacity < m->n) return fail2d(m, MPMHIP_ECAPACITY, "block buffer too small");
+  HIPCHK2D(m, hipSetDevice(m->device));
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  if (m->n) HIPCHK2D(m, hipMemcpy(block, A.d_blk_of, sizeof(uint32_t) * (size_t)m->n, hipMemcpyDeviceToHost));
+  return m->n;
 }

@@ -6,8 +6,8 @@
 // levels; advance(limit) gathers the pools of the level's blocks plus frozen copies of their neighbours, runs ONE ordinary
 // substep and files the results back.  Everything that is a few integers per block lives here: the limit state machine
 // (update_dt_limits, :90-164), the neighbour lists per level (:183-253), and the per-block ACTION TABLE of an advance
-// (which pools to gather, re-tag, clear, and where results go: :255-373) that the device kernels of k_async.h (3D records)
-// and k_async2d.h (2D arrays) execute.  The particle containers themselves never come here: they stay in HBM.
+// (which pools to gather, re-tag, clear, and where results go: :255-373) that the device kernels of k_async.h execute.  The
+// particle containers themselves never come here: they stay in HBM; what the host counts of them is AsyncStoreCount, below.
 #pragma once
 #include <xmmintrin.h>
 
@@ -34,11 +34,37 @@ enum : uint8_t {
   AT_DEST_BACKUP = 64  // ... to its backup (:365-371)
 };
 
+// log2 of a scheduler block's extent in nodes, by dimension (SPGrid_Mask<5, 5, dim>::block_{x,y,z}bits): 8 x 16 nodes in 2D,
+// 4 x 4 x 8 in 3D.  Read by sched_enable and by async_block_of<D> (k_async.h).
+constexpr int ASYNC_BLOCK_SHIFT[4][3] = {{0, 0, 0}, {0, 0, 0}, {3, 4, 0}, {2, 2, 3}};
+
+// The host's count of the container store of a resident stepper (async_api.h) and the arithmetic on it that touches no HIP call.
+// Sizes are counted in 32 bits (a container index is half of a gather key): sums are formed in 64 and clamped.
+struct AsyncStoreCount {
+  uint32_t cap = 0, size = 0, live = 0;  // containers allocated / in use incl. freed ones / not freed (as of the last read-back)
+  uint32_t size_ub = 0;                  // upper bound of the size now (launch bound: tags behind the size say FREE)
+  // a read-back: what earlier launches appended and freed, and the append cursor
+  void fold(uint32_t n_append, uint32_t n_freed, uint32_t cursor) {
+    live += n_append; live -= std::min(live, n_freed);
+    size = size_ub = cursor;
+  }
+  // squeeze when the freed containers outnumber the live ones (the passes over the tags then cost twice what they must), or when
+  // that avoids growing the store.  Called right behind a read-back: size and live are exact.
+  bool wants_compaction(uint32_t incoming) const {
+    const uint32_t dead = size - std::min(size, live);
+    return dead > live + 65536ull || ((uint64_t)size + incoming > cap && dead > size / 4);
+  }
+  static uint32_t clamp32(uint64_t v) { return (uint32_t)std::min<uint64_t>(v, 0xffffffffull); }
+  static uint32_t sum(uint32_t a, uint32_t b) { return clamp32((uint64_t)a + b); }
+  static uint32_t grown(uint32_t need) { return std::max<uint32_t>(clamp32((uint64_t)need + need / 2), 4096); }  // containers to allocate for `need`
+  static size_t ids_grown(size_t next_pid) { return next_pid + next_pid / 2 + 1024; }                           // dedup words for `next_pid` ids
+};
+
 struct AsyncSched {
   mpmhip_async_config cfg{};
   int dim = 3;
   int nb[3] = {0, 0, 1};        // blocks per axis (block b = (bx nb[1] + by) nb[2] + bz; nb[2] = 1 in 2D)
-  int shift[3] = {2, 2, 3};     // log2 of a block's extent in nodes (SPGrid_Mask<5, 5, dim>::block_{x,y,z}bits)
+  int shift[3] = {2, 2, 3};     // ASYNC_BLOCK_SHIFT[dim]
   int max_neigh = 26;
   std::vector<uint32_t> boundary;  // "left_boundary" blocks (src/async/async_mpm.cpp:43-53)
   int64_t current_t_int = 0, min_delta_t_int = 1, max_delta_t_int = 1;
@@ -70,8 +96,8 @@ struct AsyncSched {
   void sched_enable(int dimension, const int *res, const mpmhip_async_config &c) {
     cfg = c;
     dim = dimension;
-    if (dim == 3) { shift[0] = 2; shift[1] = 2; shift[2] = 3; max_neigh = 26; }
-    else { shift[0] = 3; shift[1] = 4; shift[2] = 0; max_neigh = 8; }
+    for (int k = 0; k < 3; k++) shift[k] = ASYNC_BLOCK_SHIFT[dim][k];
+    max_neigh = dim == 3 ? 26 : 8;
     for (int k = 0; k < 3; k++) nb[k] = k < dim ? (res[k] >> shift[k]) + 1 : 1;
     const size_t n = (size_t)nb[0] * nb[1] * nb[2];
     strength.assign(n, 1ll << 31); cfl.assign(n, 1ll << 31); continuous.assign(n, 1);

@@ -40,7 +40,7 @@ static int bgeo2d_encode(mpmhip2d_ctx *m, int32_t verbose, void *dst, size_t cap
     HIPCHK2D(m, hipMemcpy(hB.data(), m->B, 16 * ns, hipMemcpyDeviceToHost)); HIPCHK2D(m, hipMemcpy(ha.data(), m->aux, 4 * ns, hipMemcpyDeviceToHost));
     HIPCHK2D(m, hipMemcpy(hg.data(), m->gid, 4 * ns, hipMemcpyDeviceToHost)); HIPCHK2D(m, hipMemcpy(hp.data(), m->pid, 4 * ns, hipMemcpyDeviceToHost));
     if (m->rigid_enabled) { hstate.resize(ns); HIPCHK2D(m, hipMemcpy(hstate.data(), m->d_states, 4 * ns, hipMemcpyDeviceToHost)); }
-    if (A.resident && A.view) { hblk.resize(ns); HIPCHK2D(m, hipMemcpy(hblk.data(), A.d_blk_of, 4 * ns, hipMemcpyDeviceToHost)); }
+    if (A.resident && A.store.view) { hblk.resize(ns); HIPCHK2D(m, hipMemcpy(hblk.data(), A.d_blk_of, 4 * ns, hipMemcpyDeviceToHost)); }
   }
   // live material particles in ascending creation id (write_partio sorts by id, :39-43; stable: an id can sit in several pools)
   std::vector<uint32_t> order;
@@ -143,8 +143,8 @@ static int snap2d_prepare(mpmhip2d_ctx *m) {  // a state the blob can describe: 
   HIPCHK2D(m, hipSetDevice(m->device));
   if (m->async.resident) {
     if (int rc = mpmhip2d_async_pool_particles(m)) return rc;  // (drops a view; pools what was added since)
-    if (int rc = a2_settle(m)) return rc;
-    if (int rc = a2_compact(m)) return rc;
+    if (int rc = as_settle(m)) return rc;
+    if (int rc = as_compact(m)) return rc;
   }
   HIPCHK2D(m, hipStreamSynchronize(m->stream));
   return MPMHIP_OK;
@@ -153,7 +153,7 @@ static size_t snap2d_bytes(const mpmhip2d_ctx *m) {
   size_t b = sizeof(Snap2D) + sizeof(GroupParams) * m->groups.size() + (size_t)m->n * (2 + 2 + 4 + 4 + 1 + 1 + 1) * 4;
   // (with rigid bodies also the particles' colour words — MPMParticle::states, the sticky history of which side of a body a particle is on)
   if (m->rigid_enabled) b += sizeof(mpm2d::Rigid2) * m->bodies.size() + sizeof(mpm2d::Joints2) + sizeof(uint32_t) * m->n_ranked + 4 * (size_t)m->n;
-  if (m->async.resident) b += sizeof(int64_t) * 6 * m->async.nblk() + (size_t)m->async.size * (4 + 64);
+  if (m->async.resident) b += sizeof(int64_t) * 6 * m->async.nblk() + (size_t)m->async.store.size * (4 + 64);
   return b;
 }
 int64_t mpmhip2d_snapshot_size(mpmhip2d_ctx *m) {
@@ -176,7 +176,7 @@ int mpmhip2d_snapshot_save(mpmhip2d_ctx *m, void *dst, size_t cap) {
   HIPCHK2D(m, hipMemcpy(&h.n_dead, m->n_dead, 4, hipMemcpyDeviceToHost));
   if (A.resident) {
     h.nb[0] = A.nb[0]; h.nb[1] = A.nb[1]; h.unit_delta_t = A.cfg.unit_delta_t; h.a_request_t = A.request_t; h.a_current_t = A.current_t;
-    h.nblk = (int64_t)A.nblk(); h.containers = A.size; h.current_t_int = A.current_t_int; h.min_delta_t_int = A.min_delta_t_int;
+    h.nblk = (int64_t)A.nblk(); h.containers = A.store.size; h.current_t_int = A.current_t_int; h.min_delta_t_int = A.min_delta_t_int;
     h.max_delta_t_int = A.max_delta_t_int; h.update_counter = A.update_counter; h.step_counter = A.step_counter;
   }
   char *p = (char *)dst;
@@ -200,7 +200,7 @@ int mpmhip2d_snapshot_save(mpmhip2d_ctx *m, void *dst, size_t cap) {
   if (A.resident) {
     const size_t nb = sizeof(int64_t) * A.nblk();
     for (const std::vector<int64_t> *v : {&A.continuous, &A.strength, &A.cfl, &A.particle_t, &A.backup_t, &A.local_min}) put(v->data(), nb);
-    HIPCHK2D(m, put_dev(A.tag, 4 * (size_t)A.size)); HIPCHK2D(m, put_dev(A.rec, 64 * (size_t)A.size));
+    HIPCHK2D(m, A.store.save(p, A.store.size));  // (tags, then the records)
   }
   return MPMHIP_OK;
 }
@@ -303,20 +303,13 @@ static int snap2d_load(mpmhip2d_ctx *m, const void *src, size_t size) {
   if (h.has_async) {
     const size_t nb = sizeof(int64_t) * (size_t)h.nblk;
     for (std::vector<int64_t> *v : {&A.continuous, &A.strength, &A.cfl, &A.particle_t, &A.backup_t, &A.local_min}) { memcpy(v->data(), arr, nb); arr += nb; }
-    A.size = A.size_ub = A.live = 0;
-    if (int rc = a2_store_reserve(m, (uint32_t)h.containers + 1024)) return rc;
-    HIPCHK2D(m, hipMemset(A.tag, 0xFF, sizeof(uint32_t) * (size_t)A.cap));
-    HIPCHK2D(m, get_dev(A.tag, 4 * (size_t)h.containers)); HIPCHK2D(m, get_dev(A.rec, 64 * (size_t)h.containers));
-    A.size = A.size_ub = A.live = (uint32_t)h.containers;
-    AsyncCounters z;
-    memset(&z, 0, sizeof z);
-    z.size = (uint32_t)h.containers;
-    HIPCHK2D(m, hipMemcpy(A.d_cnt, &z, sizeof z, hipMemcpyHostToDevice));
-    A.pending_counters = false; A.view = false;
+    A.store.size = A.store.size_ub = A.store.live = 0;
+    if (int rc = as_store_reserve(m, (uint32_t)h.containers + 1024)) return rc;
+    HIPCHK2D(m, A.store.load(arr, (size_t)h.containers));
     A.current_t_int = h.current_t_int; A.min_delta_t_int = h.min_delta_t_int; A.max_delta_t_int = h.max_delta_t_int;
     A.update_counter = h.update_counter; A.step_counter = h.step_counter; A.request_t = h.a_request_t; A.current_t = h.a_current_t;
     A.limits_version++;  // (the neighbour lists are rebuilt from the loaded limits at the next update)
-    if (m->next_pid > A.best_cap) { if (int rc = a2_best_reserve(m)) return rc; }
+    if (int rc = as_best_reserve(m)) return rc;
   }
   return MPMHIP_OK;
 }

@@ -1,19 +1,23 @@
-// taichi_mpm_amd/csrc/k_async.h — AsyncMPM on the device: the particle pools of the asynchronous stepper and the kernels that
-// move particles between them and the working set of an advance (AsyncMPM<dim>::advance, src/async/async_mpm.cpp:255-373;
-// gather_from_pool, src/async/async_mpm.h:198-234).  Part of libmpmhip; host side: async_api.h.
+// taichi_mpm_amd/csrc/k_async.h — AsyncMPM<dim> on the device, for both dimensions: the particle pools of the asynchronous stepper
+// and the kernels that move particles between them and the working set of an advance (AsyncMPM<dim>::advance,
+// src/async/async_mpm.cpp:255-373; gather_from_pool, src/async/async_mpm.h:198-234; create_simulation2('async_mpm'):
+// TC_IMPLEMENTATION(Simulation2D, AsyncMPM2D, "async_mpm"), :423-427).  Part of libmpmhip; host side: async_api.h.
 //
-// The reference keeps, per scheduler block (SPGrid block of 4 x 4 x 8 nodes), a `particle_pool` (containers at the block's
-// own time) and a `backup_pool` (copies at an earlier time).  Here both live in ONE device-resident STORE of containers
-// (two 64-byte records per container + a tag word + the particle id); a pool is the set of containers carrying its tag:
+// The reference keeps, per scheduler block (SPGrid block of 4 x 4 x 8 nodes, 8 x 16 in 2D), a `particle_pool` (containers at the
+// block's own time) and a `backup_pool` (copies at an earlier time).  Here both live in ONE device-resident STORE of containers
+// with a tag word each; a pool is the set of containers carrying its tag:
 //     tag = block | AS_BACKUP bit,  AS_FREE for a dropped container.
 // An advance never moves a container inside the store: it re-tags (pool -> backup, clear) in place, copies the winners of
-// the gather into the ctx's record arrays (the working set of ONE ordinary substep), and appends the results behind the
+// the gather into the ctx's particle arrays (the working set of ONE ordinary substep), and appends the results behind the
 // store's end.  Freed containers are squeezed out by an order-preserving compaction when they outnumber the live ones.
 // No particle data crosses the PCIe bus during stepping: the host sees block tables and four counters.
+//
+// The kernels are written once, over two small views passed by value: where a container's words lie (Store3, Store2) and how
+// the working set is laid out (Work3: the 3D ctx's records, Work2: the 2D object's arrays).
 #pragma once
 #include "mpm_common.h"
 #include "k_sort.h"
-#include "async_sched.h"  // the action bits AT_* of the per-block table
+#include "async_sched.h"  // the action bits AT_* of the per-block table, ASYNC_BLOCK_SHIFT
 
 namespace mpm {
 
@@ -24,8 +28,104 @@ struct AsyncCounters {
                                                // error word (bit 8: a chained scan of the compaction waited in vain, k_sort.h)
 };
 
-// One 64-byte record pair per container: g = the ctx's RecG image (x3, aux, F9, gid, id, -), w = {v3, -}, {apic_b[0..3]},
-// {apic_b[4..7]}, {apic_b[8], -, -, -}.
+// A 3D container: two 64-byte records + an id word.  g = the ctx's RecG image (x3, aux, F9, gid, id, -), w = {v3, -},
+// {apic_b[0..3]}, {apic_b[4..7]}, {apic_b[8], -, -, -}.
+struct Store3 {
+  static constexpr int D = 3;
+  uint32_t *tag;
+  int32_t *idw;
+  float4 *g, *w;
+  __device__ __forceinline__ int32_t id(uint32_t e) const { return idw[e]; }
+  __device__ __forceinline__ void copy_to(uint32_t e, const Store3 &to, uint32_t o) const {  // (every load before the first store)
+    const int32_t i = idw[e];
+    const float4 *sg = g + (size_t)e * 4, *sw = w + (size_t)e * 4;
+    const float4 g0 = sg[0], g1 = sg[1], g2 = sg[2], g3 = sg[3], w0 = sw[0], w1 = sw[1], w2 = sw[2], w3 = sw[3];
+    float4 *dg = to.g + (size_t)o * 4, *dw = to.w + (size_t)o * 4;
+    to.idw[o] = i;
+    dg[0] = g0; dg[1] = g1; dg[2] = g2; dg[3] = g3; dw[0] = w0; dw[1] = w1; dw[2] = w2; dw[3] = w3;
+  }
+  __device__ __forceinline__ void state(uint32_t e, mat3 &F, float v[3], float &aux, uint32_t &gid) const {
+    const float4 g0 = g[(size_t)e * 4], g1 = g[(size_t)e * 4 + 1], g2 = g[(size_t)e * 4 + 2], g3 = g[(size_t)e * 4 + 3];
+    const float4 w0 = w[(size_t)e * 4];
+    F.m[0] = g1.x; F.m[1] = g1.y; F.m[2] = g1.z; F.m[3] = g1.w; F.m[4] = g2.x; F.m[5] = g2.y; F.m[6] = g2.z; F.m[7] = g2.w; F.m[8] = g3.x;
+    v[0] = w0.x; v[1] = w0.y; v[2] = w0.z;
+    aux = g0.w; gid = __float_as_uint(g3.y);
+  }
+};
+// A 2D container: ONE 64-byte record {x2, v2}, {F4}, {apic_b4}, {aux, gid bits, id bits, -}.
+struct Store2 {
+  static constexpr int D = 2;
+  uint32_t *tag;
+  float4 *rec;
+  __device__ __forceinline__ int32_t id(uint32_t e) const { return __float_as_int(rec[(size_t)e * 4 + 3].z); }
+  __device__ __forceinline__ void copy_to(uint32_t e, const Store2 &to, uint32_t o) const {
+    const float4 *s = rec + (size_t)e * 4;
+    const float4 r0 = s[0], r1 = s[1], r2 = s[2], r3 = s[3];
+    float4 *d = to.rec + (size_t)o * 4;
+    d[0] = r0; d[1] = r1; d[2] = r2; d[3] = r3;
+  }
+  // get_allowed_dt has no dim-dependent term (src/particles.cpp:136-155 ...): the 2 x 2 F is embedded in a 3 x 3 one
+  __device__ __forceinline__ void state(uint32_t e, mat3 &F, float v[3], float &aux, uint32_t &gid) const {
+    const float4 r0 = rec[(size_t)e * 4], r1 = rec[(size_t)e * 4 + 1], r3 = rec[(size_t)e * 4 + 3];
+    F.m[0] = r1.x; F.m[1] = r1.y; F.m[2] = 0.0f; F.m[3] = r1.z; F.m[4] = r1.w; F.m[5] = 0.0f; F.m[6] = 0.0f; F.m[7] = 0.0f; F.m[8] = 1.0f;
+    v[0] = r0.z; v[1] = r0.w; v[2] = 0.0f;
+    aux = r3.x; gid = __float_as_uint(r3.y);
+  }
+};
+
+// The working set of a 3D ctx: its records (the P2G matrix A of RecP is rebuilt by k_affine: it depends on the advance's dt).
+struct Work3 {
+  using Store = Store3;
+  float4 *rg, *rp, *rb;
+  const GroupParams *groups;
+  __device__ __forceinline__ void from_store(uint32_t s, const Store3 &S, uint32_t e) const {
+    const float4 g0 = S.g[(size_t)e * 4], g1 = S.g[(size_t)e * 4 + 1], g2 = S.g[(size_t)e * 4 + 2], g3 = S.g[(size_t)e * 4 + 3];
+    const float4 w0 = S.w[(size_t)e * 4], w1 = S.w[(size_t)e * 4 + 1], w2 = S.w[(size_t)e * 4 + 2], w3 = S.w[(size_t)e * 4 + 3];
+    const float mass = groups[__float_as_uint(g3.y)].p[0];
+    rg[(size_t)s * 4] = g0; rg[(size_t)s * 4 + 1] = g1; rg[(size_t)s * 4 + 2] = g2; rg[(size_t)s * 4 + 3] = g3;
+    rp[(size_t)s * 4] = make_float4(g0.x, g0.y, g0.z, w0.x);
+    rp[(size_t)s * 4 + 1] = make_float4(w0.y, w0.z, 0.0f, 0.0f);
+    rp[(size_t)s * 4 + 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    rp[(size_t)s * 4 + 3] = make_float4(0.0f, 0.0f, 0.0f, mass);
+    rb[(size_t)s * 3] = w1; rb[(size_t)s * 3 + 1] = w2; rb[(size_t)s * 3 + 2] = w3;
+  }
+  __device__ __forceinline__ int32_t id(uint32_t i) const { return __float_as_int(rg[(size_t)i * 4 + 3].z); }
+  __device__ __forceinline__ void pos(uint32_t i, float x[3]) const {
+    const float4 g0 = rg[(size_t)i * 4];
+    x[0] = g0.x; x[1] = g0.y; x[2] = g0.z;
+  }
+  __device__ __forceinline__ void to_store(uint32_t i, const Store3 &S, uint32_t e) const {
+    const float4 g0 = rg[(size_t)i * 4], g1 = rg[(size_t)i * 4 + 1], g2 = rg[(size_t)i * 4 + 2], g3 = rg[(size_t)i * 4 + 3];
+    const float4 p0 = rp[(size_t)i * 4], p1 = rp[(size_t)i * 4 + 1];
+    const float4 b0 = rb[(size_t)i * 3], b1 = rb[(size_t)i * 3 + 1], b2 = rb[(size_t)i * 3 + 2];
+    S.g[(size_t)e * 4] = g0; S.g[(size_t)e * 4 + 1] = g1; S.g[(size_t)e * 4 + 2] = g2; S.g[(size_t)e * 4 + 3] = g3;
+    S.w[(size_t)e * 4] = make_float4(p0.w, p1.x, p1.y, 0.0f);
+    S.w[(size_t)e * 4 + 1] = b0; S.w[(size_t)e * 4 + 2] = b1; S.w[(size_t)e * 4 + 3] = b2;
+    S.idw[e] = __float_as_int(g3.z);
+  }
+};
+// The working set of the 2D object: its particle arrays (k_mpm2d.h).
+struct Work2 {
+  using Store = Store2;
+  float *x, *v, *F, *B, *aux;
+  int32_t *gid, *pid;
+  __device__ __forceinline__ void from_store(uint32_t s, const Store2 &S, uint32_t e) const {
+    const float4 r0 = S.rec[(size_t)e * 4], r1 = S.rec[(size_t)e * 4 + 1], r2 = S.rec[(size_t)e * 4 + 2], r3 = S.rec[(size_t)e * 4 + 3];
+    x[2 * s] = r0.x; x[2 * s + 1] = r0.y; v[2 * s] = r0.z; v[2 * s + 1] = r0.w;
+    F[4 * s] = r1.x; F[4 * s + 1] = r1.y; F[4 * s + 2] = r1.z; F[4 * s + 3] = r1.w;
+    B[4 * s] = r2.x; B[4 * s + 1] = r2.y; B[4 * s + 2] = r2.z; B[4 * s + 3] = r2.w;
+    aux[s] = r3.x; gid[s] = __float_as_int(r3.y); pid[s] = __float_as_int(r3.z);
+  }
+  __device__ __forceinline__ int32_t id(uint32_t i) const { return pid[i]; }
+  __device__ __forceinline__ void pos(uint32_t i, float p[3]) const { p[0] = x[2 * i]; p[1] = x[2 * i + 1]; p[2] = 0.0f; }
+  __device__ __forceinline__ void to_store(uint32_t i, const Store2 &S, uint32_t e) const {
+    const float4 r0 = make_float4(x[2 * i], x[2 * i + 1], v[2 * i], v[2 * i + 1]);
+    const float4 r1 = make_float4(F[4 * i], F[4 * i + 1], F[4 * i + 2], F[4 * i + 3]);
+    const float4 r2 = make_float4(B[4 * i], B[4 * i + 1], B[4 * i + 2], B[4 * i + 3]);
+    const float4 r3 = make_float4(aux[i], __int_as_float(gid[i]), __int_as_float(pid[i]), 0.0f);
+    S.rec[(size_t)e * 4] = r0; S.rec[(size_t)e * 4 + 1] = r1; S.rec[(size_t)e * 4 + 2] = r2; S.rec[(size_t)e * 4 + 3] = r3;
+  }
+};
 
 // gather_from_pool's "the first copy of an id wins" (particles_cnt[id] != global_cnt): copies are ordered by gather phase
 // (smaller-step pools, this step's pools, larger-step backups), then by the reference's block order, then by position in the
@@ -39,47 +139,39 @@ __device__ __forceinline__ int async_category(uint32_t tag, uint8_t act) {
   return (act & AT_BACKUP) ? 2 : -1;
 }
 
-__global__ __launch_bounds__(256) void k_async_mark(uint32_t size, const uint32_t *__restrict__ tag, const int32_t *__restrict__ id,
-                                                    const uint8_t *__restrict__ tbl, const uint32_t *__restrict__ rank_of,
-                                                    unsigned long long *__restrict__ best) {
+template <class Store>
+__global__ __launch_bounds__(256) void k_async_mark(uint32_t size, Store S, const uint8_t *__restrict__ tbl,
+                                                    const uint32_t *__restrict__ rank_of, unsigned long long *__restrict__ best) {
   for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < size; e += gridDim.x * blockDim.x) {
-    const uint32_t t = tag[e];
+    const uint32_t t = S.tag[e];
     if (t == AS_FREE) continue;
     const uint32_t b = t & ~AS_BACKUP;
     const int cat = async_category(t, tbl[b]);
-    if (cat >= 0) atomicMin(&best[id[e]], async_key((uint32_t)cat, rank_of[b], e));
+    if (cat >= 0) atomicMin(&best[S.id(e)], async_key((uint32_t)cat, rank_of[b], e));
   }
 }
 
-// winners -> the ctx's records (slot = order of arrival), then the in-place re-tagging of backup_current_dt_limit
-__global__ __launch_bounds__(256) void k_async_gather(uint32_t size, uint32_t *__restrict__ tag, const int32_t *__restrict__ id,
-                                                      const uint8_t *__restrict__ tbl, const uint32_t *__restrict__ rank_of,
-                                                      unsigned long long *__restrict__ best, const float4 *__restrict__ sg,
-                                                      const float4 *__restrict__ sw, const GroupParams *__restrict__ groups,
-                                                      float4 *__restrict__ rg, float4 *__restrict__ rp, float4 *__restrict__ rb,
-                                                      AsyncCounters *cnt) {
+// winners -> the working set (slot = order of arrival), then the in-place re-tagging of backup_current_dt_limit
+template <class Work>
+__global__ __launch_bounds__(256) void k_async_gather(uint32_t size, typename Work::Store S, const uint8_t *__restrict__ tbl,
+                                                      const uint32_t *__restrict__ rank_of, unsigned long long *__restrict__ best,
+                                                      Work W, AsyncCounters *cnt) {
   for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < size; e += gridDim.x * blockDim.x) {
-    const uint32_t t = tag[e];
+    const uint32_t t = S.tag[e];
     if (t == AS_FREE) continue;
     const uint32_t b = t & ~AS_BACKUP;
     const uint8_t act = tbl[b];
     const int cat = async_category(t, act);
-    if (cat >= 0 && best[id[e]] == async_key((uint32_t)cat, rank_of[b], e)) {
-      best[id[e]] = ~0ull;  // (one winner per id: the table is clean again after the pass)
-      const uint32_t s = atomicAdd(&cnt->n_work, 1u);
-      const float4 g0 = sg[(size_t)e * 4], g1 = sg[(size_t)e * 4 + 1], g2 = sg[(size_t)e * 4 + 2], g3 = sg[(size_t)e * 4 + 3];
-      const float4 w0 = sw[(size_t)e * 4], w1 = sw[(size_t)e * 4 + 1], w2 = sw[(size_t)e * 4 + 2], w3 = sw[(size_t)e * 4 + 3];
-      rg[(size_t)s * 4] = g0; rg[(size_t)s * 4 + 1] = g1; rg[(size_t)s * 4 + 2] = g2; rg[(size_t)s * 4 + 3] = g3;
-      const float mass = groups[__float_as_uint(g3.y)].p[0];
-      rp[(size_t)s * 4] = make_float4(g0.x, g0.y, g0.z, w0.x);  // (the P2G matrix A is rebuilt by k_affine: it depends on this advance's dt)
-      rp[(size_t)s * 4 + 1] = make_float4(w0.y, w0.z, 0.0f, 0.0f);
-      rp[(size_t)s * 4 + 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      rp[(size_t)s * 4 + 3] = make_float4(0.0f, 0.0f, 0.0f, mass);
-      rb[(size_t)s * 3] = w1; rb[(size_t)s * 3 + 1] = w2; rb[(size_t)s * 3 + 2] = w3;
+    if (cat >= 0) {
+      const int32_t id = S.id(e);
+      if (best[id] == async_key((uint32_t)cat, rank_of[b], e)) {
+        best[id] = ~0ull;  // (one winner per id: the table is clean again after the pass)
+        W.from_store(atomicAdd(&cnt->n_work, 1u), S, e);
+      }
     }
     if (act & AT_SWAP) {
-      if (t & AS_BACKUP) { tag[e] = AS_FREE; atomicAdd(&cnt->n_freed, 1u); }
-      else tag[e] = t | AS_BACKUP;
+      if (t & AS_BACKUP) { S.tag[e] = AS_FREE; atomicAdd(&cnt->n_freed, 1u); }
+      else S.tag[e] = t | AS_BACKUP;
     }
   }
 }
@@ -93,51 +185,43 @@ __global__ __launch_bounds__(256) void k_async_clear(uint32_t size, uint32_t *__
   }
 }
 
-// scheduler block of a position: the reference's SPGrid block (4 x 4 x 8 nodes) holding the particle's base node
-// (get_grid_base_pos, src/mpm.h:252-255; src/async/async_mpm.cpp:350-355); INVALID outside the block table
-__device__ __forceinline__ uint32_t async_block_of(const Params &P, float x0, float x1, float x2, int nbx, int nby, int nbz) {
-  const float X[3] = {x0 * P.idx, x1 * P.idx, x2 * P.idx};
-  if (!(X[0] >= 0.5f && X[1] >= 0.5f && X[2] >= 0.5f)) return INVALID;
-  const int bx = (int)(X[0] - 0.5f) >> 2, by = (int)(X[1] - 0.5f) >> 2, bz = (int)(X[2] - 0.5f) >> 3;
+// scheduler block of a position: the reference's SPGrid block holding the particle's base node (get_grid_base_pos,
+// src/mpm.h:252-255; src/async/async_mpm.cpp:350-355); INVALID outside the block table (nb[2] = 1 in 2D)
+template <int D>
+__device__ __forceinline__ uint32_t async_block_of(float idx, const float x[3], int nbx, int nby, int nbz) {
+  constexpr int s0 = ASYNC_BLOCK_SHIFT[D][0], s1 = ASYNC_BLOCK_SHIFT[D][1], s2 = ASYNC_BLOCK_SHIFT[D][2];
+  const float X0 = x[0] * idx, X1 = x[1] * idx, X2 = D == 3 ? x[2] * idx : 0.5f;
+  if (!(X0 >= 0.5f && X1 >= 0.5f && X2 >= 0.5f)) return INVALID;
+  const int bx = (int)(X0 - 0.5f) >> s0, by = (int)(X1 - 0.5f) >> s1, bz = (int)(X2 - 0.5f) >> s2;
   if (bx >= nbx || by >= nby || bz >= nbz) return INVALID;
   return ((uint32_t)bx * nby + by) * nbz + bz;
 }
 
 // the working set after its substep -> containers behind the store's end (":345-375 update backup_pool and particle_pool").
 // all_to_pool: AsyncMPM::add_particles (src/async/async_mpm.cpp:57-75) — every particle goes to its block's pool.
-__global__ __launch_bounds__(256) void k_async_file(Params P, const float4 *__restrict__ rg, const float4 *__restrict__ rp,
-                                                    const float4 *__restrict__ rb, const uint8_t *__restrict__ tbl, int all_to_pool,
-                                                    int nbx, int nby, int nbz, uint32_t cap, float4 *__restrict__ sg,
-                                                    float4 *__restrict__ sw, uint32_t *__restrict__ tag, int32_t *__restrict__ id,
-                                                    AsyncCounters *cnt) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < P.n_slots; i += gridDim.x * blockDim.x) {
-    const float4 g3 = rg[(size_t)i * 4 + 3];
-    const int32_t pid = __float_as_int(g3.z);
-    if (pid < 0) continue;  // deleted by the substep (clear_boundary_particles): not filed back, as in the reference
-    const float4 g0 = rg[(size_t)i * 4];
-    const uint32_t b = async_block_of(P, g0.x, g0.y, g0.z, nbx, nby, nbz);
+template <class Work>
+__global__ __launch_bounds__(256) void k_async_file(float idx, uint32_t n, Work W, const uint8_t *__restrict__ tbl, int all_to_pool,
+                                                    int nbx, int nby, int nbz, uint32_t cap, typename Work::Store S, AsyncCounters *cnt) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    if (W.id(i) < 0) continue;  // deleted by the substep (clear_boundary_particles): not filed back, as in the reference
+    float x[3];
+    W.pos(i, x);
+    const uint32_t b = async_block_of<Work::Store::D>(idx, x, nbx, nby, nbz);
     if (b == INVALID) continue;
     const uint8_t act = all_to_pool ? (uint8_t)AT_DEST_POOL : tbl[b];
     if (!(act & (AT_DEST_POOL | AT_DEST_BACKUP))) continue;
     const uint32_t e = atomicAdd(&cnt->size, 1u);  // (the append cursor lives on the device: the host knows an upper bound)
     if (e >= cap) { atomicSub(&cnt->size, 1u); continue; }  // (the host sized the store for the whole working set: cannot happen)
     atomicAdd(&cnt->n_append, 1u);
-    const float4 p0 = rp[(size_t)i * 4], p1 = rp[(size_t)i * 4 + 1];
-    sg[(size_t)e * 4] = g0; sg[(size_t)e * 4 + 1] = rg[(size_t)i * 4 + 1]; sg[(size_t)e * 4 + 2] = rg[(size_t)i * 4 + 2];
-    sg[(size_t)e * 4 + 3] = g3;
-    sw[(size_t)e * 4] = make_float4(p0.w, p1.x, p1.y, 0.0f);
-    sw[(size_t)e * 4 + 1] = rb[(size_t)i * 3]; sw[(size_t)e * 4 + 2] = rb[(size_t)i * 3 + 1]; sw[(size_t)e * 4 + 3] = rb[(size_t)i * 3 + 2];
-    tag[e] = (act & AT_DEST_POOL) ? b : (b | AS_BACKUP);
-    id[e] = pid;
+    W.to_store(i, S, e);
+    S.tag[e] = (act & AT_DEST_POOL) ? b : (b | AS_BACKUP);
   }
 }
 
 // order-preserving compaction of the store (chained single-pass scan of k_sort.h: chunk = 1024 containers)
-__global__ __launch_bounds__(256) void k_async_compact(uint32_t size, const uint32_t *__restrict__ tag, const int32_t *__restrict__ id,
-                                                       const float4 *__restrict__ sg, const float4 *__restrict__ sw,
-                                                       uint32_t *__restrict__ tag2, int32_t *__restrict__ id2,
-                                                       float4 *__restrict__ sg2, float4 *__restrict__ sw2,
-                                                       unsigned long long *__restrict__ slots, uint32_t epoch, AsyncCounters *cnt) {
+template <class Store>
+__global__ __launch_bounds__(256) void k_async_compact(uint32_t size, Store S, Store S2, unsigned long long *__restrict__ slots,
+                                                       uint32_t epoch, AsyncCounters *cnt) {
   __shared__ uint32_t lds[8];
   const uint32_t nchunks = (size + 1023u) / 1024u;
   uint32_t round = 0;
@@ -148,7 +232,7 @@ __global__ __launch_bounds__(256) void k_async_compact(uint32_t size, const uint
     uint32_t t[4], live = 0;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      t[j] = (e0 + j < size) ? tag[e0 + j] : AS_FREE;
+      t[j] = (e0 + j < size) ? S.tag[e0 + j] : AS_FREE;
       live += t[j] != AS_FREE;
     }
     uint32_t total;
@@ -158,10 +242,8 @@ __global__ __launch_bounds__(256) void k_async_compact(uint32_t size, const uint
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       if (t[j] == AS_FREE) continue;
-      const uint32_t e = e0 + j;
-      tag2[o] = t[j]; id2[o] = id[e];
-#pragma unroll
-      for (int q = 0; q < 4; q++) { sg2[(size_t)o * 4 + q] = sg[(size_t)e * 4 + q]; sw2[(size_t)o * 4 + q] = sw[(size_t)e * 4 + q]; }
+      S2.tag[o] = t[j];
+      S.copy_to(e0 + j, S2, o);
       o++;
     }
     if (chunk == nchunks - 1 && threadIdx.x == 255) { cnt->n_live = o; cnt->size = o; }
@@ -177,41 +259,36 @@ __global__ __launch_bounds__(256) void k_async_table_reset(uint32_t nblk, uint32
 
 // update_dt_limits, device half (src/async/async_mpm.cpp:91-111) over the POOL containers of the store: per block the
 // smallest get_allowed_dt(dx), the largest |v|^2 and the number of containers (same table as k_async_block_reduce)
-__global__ __launch_bounds__(256) void k_async_store_reduce(Params P, uint32_t size, const uint32_t *__restrict__ tag,
-                                                            const float4 *__restrict__ sg, const float4 *__restrict__ sw,
-                                                            const GroupParams *__restrict__ groups, uint32_t *__restrict__ tab) {
+template <class Store>
+__global__ __launch_bounds__(256) void k_async_store_reduce(float dx, uint32_t size, Store S, const GroupParams *__restrict__ groups,
+                                                            uint32_t *__restrict__ tab) {
   for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < size; e += gridDim.x * blockDim.x) {
-    const uint32_t t = tag[e];
+    const uint32_t t = S.tag[e];
     if (t == AS_FREE || (t & AS_BACKUP)) continue;
-    const float4 g0 = sg[(size_t)e * 4], g1 = sg[(size_t)e * 4 + 1], g2 = sg[(size_t)e * 4 + 2], g3 = sg[(size_t)e * 4 + 3];
-    const float4 w0 = sw[(size_t)e * 4];
     mat3 F;
-    F.m[0] = g1.x; F.m[1] = g1.y; F.m[2] = g1.z; F.m[3] = g1.w; F.m[4] = g2.x; F.m[5] = g2.y; F.m[6] = g2.z; F.m[7] = g2.w; F.m[8] = g3.x;
-    const float v[3] = {w0.x, w0.y, w0.z};
-    const float adt = allowed_dt(groups[__float_as_uint(g3.y)], F, g0.w, v, P.dx);
+    float v[3], aux;
+    uint32_t gid;
+    S.state(e, F, v, aux, gid);
+    const float adt = allowed_dt(groups[gid], F, aux, v, dx);
+    float v2 = v[0] * v[0];
+#pragma unroll
+    for (int k = 1; k < Store::D; k++) v2 += v[k] * v[k];
     atomicMin(&tab[3 * (size_t)t + 0], __float_as_uint(fmaxf(adt, 0.0f)));
-    atomicMax(&tab[3 * (size_t)t + 1], __float_as_uint(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+    atomicMax(&tab[3 * (size_t)t + 1], __float_as_uint(v2));
     atomicAdd(&tab[3 * (size_t)t + 2], 1u);
   }
 }
 
-// every pool container -> the ctx's records (AsyncMPM::visualize's particle list: duplicates of an id included, each with the
+// every pool container -> the working set (AsyncMPM::visualize's particle list: duplicates of an id included, each with the
 // block of the pool it sits in, src/async/async_visualize.cpp:17-26,86-96)
-__global__ __launch_bounds__(256) void k_async_load(uint32_t size, const uint32_t *__restrict__ tag, const float4 *__restrict__ sg,
-                                                    const float4 *__restrict__ sw, const GroupParams *__restrict__ groups,
-                                                    float4 *__restrict__ rg, float4 *__restrict__ rp, float4 *__restrict__ rb,
-                                                    uint32_t *__restrict__ blk_of, AsyncCounters *cnt) {
+template <class Work>
+__global__ __launch_bounds__(256) void k_async_load(uint32_t size, typename Work::Store S, Work W, uint32_t *__restrict__ blk_of,
+                                                    AsyncCounters *cnt) {
   for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < size; e += gridDim.x * blockDim.x) {
-    const uint32_t t = tag[e];
+    const uint32_t t = S.tag[e];
     if (t == AS_FREE || (t & AS_BACKUP)) continue;
     const uint32_t s = atomicAdd(&cnt->n_work, 1u);
-    const float4 g0 = sg[(size_t)e * 4], g3 = sg[(size_t)e * 4 + 3], w0 = sw[(size_t)e * 4];
-    rg[(size_t)s * 4] = g0; rg[(size_t)s * 4 + 1] = sg[(size_t)e * 4 + 1]; rg[(size_t)s * 4 + 2] = sg[(size_t)e * 4 + 2]; rg[(size_t)s * 4 + 3] = g3;
-    rp[(size_t)s * 4] = make_float4(g0.x, g0.y, g0.z, w0.x);
-    rp[(size_t)s * 4 + 1] = make_float4(w0.y, w0.z, 0.0f, 0.0f);
-    rp[(size_t)s * 4 + 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    rp[(size_t)s * 4 + 3] = make_float4(0.0f, 0.0f, 0.0f, groups[__float_as_uint(g3.y)].p[0]);
-    rb[(size_t)s * 3] = sw[(size_t)e * 4 + 1]; rb[(size_t)s * 3 + 1] = sw[(size_t)e * 4 + 2]; rb[(size_t)s * 3 + 2] = sw[(size_t)e * 4 + 3];
+    W.from_store(s, S, e);
     blk_of[s] = t;
   }
 }

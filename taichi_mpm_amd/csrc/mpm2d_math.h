@@ -1,6 +1,6 @@
 // taichi_mpm_amd/csrc/mpm2d_math.h — 2x2 math and the eight constitutive models of MPM<2> (src/particles.cpp with dim = 2).
 // Every 2D kernel evaluates its particles through these functions: k_p2g / k_g2p (k_mpm2d.h), the deterministic mode
-// (k_mpm2d_det.h), the CPIC transfers and the asynchronous stepper (k_async2d.h), and the test entries mpmhip2d_debug_*
+// (k_mpm2d_det.h), the CPIC transfers and the asynchronous stepper (k_async.h), and the test entries mpmhip2d_debug_*
 // (k_debug2d.h).  Plain C++ (MPM_HD as in k_joints.h): the same lines compile for the host in tests/cpp/mpm2d_math_host.cpp,
 // where tests/test_materials2d_cpu.py holds them to the reference's dim = 2 particles without a GPU.
 //

@@ -105,7 +105,6 @@
 #include "k_mpm2d_det.h"
 #include "k_debug2d.h"
 #include "k_sdf2d.h"
-#include "k_async2d.h"
 
 
 // ================================================================================================ host side
@@ -233,6 +232,98 @@ static void sdf_fill(SdfDev &S, const Desc &d, const float *phi0, const float *p
   S.t0 = phi1 ? t0 : 0.0f; S.t1 = phi1 ? t1 : 1.0f;
 }
 
+// The container store of a resident asynchronous stepper (driver: async_api.h; kernels and layouts: k_async.h), for both ctx types.
+// The payload of a container is a short list of LANES — bytes per container, the array, its compaction twin — so that growing,
+// compacting and the snapshots loop over lanes instead of naming arrays: 3D {id 4 B, g 64 B, w 64 B}, 2D {rec 64 B}.
+struct AsyncStore : AsyncStoreCount {
+  struct Lane { size_t bytes = 0; DevBuf<uint8_t> a, b; };
+  Lane lane[3];
+  int n_lanes = 0;
+  DevBuf<uint32_t> tag, tag2;
+  DevBuf<unsigned long long> best, d_scan;  // one dedup word per creation id; the slots of the compaction's chained scan
+  int64_t best_cap = 0;
+  uint32_t scan_cap = 0, scan_epoch = 0;
+  DevBuf<uint8_t> d_tbl;
+  PinnedBuf<uint8_t> h_tbl_pin;  // four pinned images of the action table (as_upload_tbl)
+  uint32_t pin_next = 0;
+  DevBuf<uint32_t> d_rank;
+  DevBuf<AsyncCounters> d_cnt;
+  PinnedBuf<AsyncCounters> h_cnt;
+  bool pending_counters = false;  // an advance left appends / frees on the device that the host has not folded in yet
+  bool view = false;              // the ctx's particles are copies of the pools (load_pools), not new particles
+  int64_t compactions = 0;
+
+  // Every call below wants the device set and the ctx's stream idle.
+  // an empty store for a block table of rank_of.size() blocks: whatever an earlier session left is released
+  hipError_t reset(std::initializer_list<size_t> lane_bytes, const std::vector<uint32_t> &rank_of) {
+    *this = AsyncStore();
+    for (size_t b : lane_bytes) lane[n_lanes++].bytes = b;
+    const size_t nblk = rank_of.size();
+    hipError_t e = hipSuccess;
+    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    A(d_tbl.alloc(nblk)); A(d_rank.alloc(nblk)); A(d_cnt.alloc(1)); A(h_tbl_pin.alloc(4 * nblk)); A(h_cnt.alloc(1));
+    if (e == hipSuccess) A(hipMemcpy(d_rank, rank_of.data(), sizeof(uint32_t) * nblk, hipMemcpyHostToDevice));
+    if (e == hipSuccess) A(hipMemset(d_cnt, 0, sizeof(AsyncCounters)));
+    return e;
+  }
+  hipError_t reserve(uint32_t need) {  // room for `need` containers in total; the containers in use stay
+    if (need <= cap) return hipSuccess;
+    const uint32_t ncap = grown(need), keep = std::min(size_ub, cap);
+    hipError_t e = tag.regrow(keep, ncap, false);
+    for (int l = 0; l < n_lanes && e == hipSuccess; l++) e = lane[l].a.regrow(keep * lane[l].bytes, ncap * lane[l].bytes, false);
+    // (kernels walk [0, upper bound of the size): every tag behind the containers in use says FREE)
+    if (e == hipSuccess) e = hipMemset(tag + keep, 0xFF, sizeof(uint32_t) * (size_t)(ncap - keep));
+    drop_twins();  // (the compaction targets are re-allocated when a compaction runs)
+    if (e == hipSuccess) cap = ncap;
+    return e;
+  }
+  void drop_twins() {
+    tag2.reset();
+    for (int l = 0; l < n_lanes; l++) lane[l].b.reset();
+  }
+  hipError_t reserve_twins() {
+    if (tag2) return hipSuccess;
+    hipError_t e = tag2.alloc(cap);
+    for (int l = 0; l < n_lanes && e == hipSuccess; l++) e = lane[l].b.alloc(cap * lane[l].bytes);
+    if (e != hipSuccess) drop_twins();
+    return e;
+  }
+  void swap_twins() {
+    std::swap(tag, tag2);
+    for (int l = 0; l < n_lanes; l++) std::swap(lane[l].a, lane[l].b);
+  }
+  // the first n containers <-> a host image: the tags, then lane after lane (the container part of both snapshot formats)
+  hipError_t save(char *dst, size_t n) const {
+    hipError_t e = n ? hipMemcpy(dst, tag, sizeof(uint32_t) * n, hipMemcpyDeviceToHost) : hipSuccess;
+    dst += sizeof(uint32_t) * n;
+    for (int l = 0; l < n_lanes && e == hipSuccess && n; dst += lane[l].bytes * n, l++) e = hipMemcpy(dst, lane[l].a, lane[l].bytes * n, hipMemcpyDeviceToHost);
+    return e;
+  }
+  hipError_t load(const char *src, size_t n) {  // (into a store reserved for at least n: the store then holds exactly these, all counted live)
+    hipError_t e = hipMemset(tag, 0xFF, sizeof(uint32_t) * (size_t)cap);
+    if (e == hipSuccess && n) e = hipMemcpy(tag, src, sizeof(uint32_t) * n, hipMemcpyHostToDevice);
+    src += sizeof(uint32_t) * n;
+    for (int l = 0; l < n_lanes && e == hipSuccess && n; src += lane[l].bytes * n, l++) e = hipMemcpy(lane[l].a, src, lane[l].bytes * n, hipMemcpyHostToDevice);
+    AsyncCounters z;
+    memset(&z, 0, sizeof z);
+    z.size = (uint32_t)n;
+    if (e == hipSuccess) e = hipMemcpy(d_cnt, &z, sizeof z, hipMemcpyHostToDevice);
+    size = size_ub = live = (uint32_t)n;
+    pending_counters = false; view = false;
+    return e;
+  }
+};
+// what both ctx types keep for the asynchronous stepper: the block scheduler (async_sched.h), the reduction table of
+// update_dt_limits with its pinned image, the pool block of every particle of a view, and the store
+struct AsyncResident : AsyncSched {
+  bool resident = false;
+  DevBuf<uint32_t> d_tab, d_blk_of;
+  int64_t blk_of_cap = 0;
+  PinnedBuf<uint32_t> h_tab;
+  size_t h_tab_cap = 0;
+  AsyncStore store;
+};
+
 struct mpmhip_ctx {
   mpmhip_config cfg;
   Params P;
@@ -311,35 +402,11 @@ struct mpmhip_ctx {
   int counts_cap = 0;
   bool compact_requested = false;
   bool in_substep = false;
-  struct AsyncState : AsyncSched {  // the block scheduler (async_sched.h) + what this ctx keeps on the device for it
+  struct AsyncState : AsyncResident {  // + the first half (mpmhip_async_enable), the frame's `limit` attribute, the profile
     bool enabled = false, limits_valid = false;
-    DevBuf<uint32_t> d_tab, d_blk_of;
     DevBuf<int32_t> d_blk_limits, d_particle_limits;
-    int64_t blk_of_cap = 0;
-    // the resident stepper (async_api.h): the device store of pool / backup containers
-    bool resident = false, pending_counters = false;
-    bool records_are_view = false;  // the ctx's records are copies of the pools (mpmhip_async_load_pools), not new particles
     double prof_ms[6] = {0, 0, 0, 0, 0, 0};
-    PinnedBuf<uint32_t> h_tab;
-    size_t h_tab_cap = 0;
     bool profile_sync = false;
-    struct Store {
-      uint32_t cap = 0, size = 0, live = 0;   // containers allocated / in use incl. freed ones / not freed (as of the last read-back)
-      uint32_t size_ub = 0;                   // upper bound of the size now (launch bound: tags behind the size say FREE)
-      DevBuf<float4> g, w, g2, w2;
-      DevBuf<uint32_t> tag, tag2;
-      DevBuf<int32_t> id, id2;
-      DevBuf<unsigned long long> best, d_scan;
-      int64_t best_cap = 0;
-      uint32_t scan_cap = 0, scan_epoch = 0;
-      DevBuf<uint8_t> d_tbl;
-      PinnedBuf<uint8_t> h_tbl_pin;  // four pinned images of the action table (async_upload_tbl)
-      size_t pin_cap = 0;
-      uint32_t pin_next = 0;
-      DevBuf<uint32_t> d_rank;
-      DevBuf<AsyncCounters> d_cnt;
-      int64_t compactions = 0;
-    } store;
   } async;
   int64_t host_particle_bytes = 0;  // particle data copied between host and device so far (uploads, downloads, snapshots)
   // CPIC rigid coupling (rigid_api.h): bodies 1.. (0 = background), their boundary particles, the colored distance field
@@ -729,7 +796,7 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   {
 #define MPM_CT_ALL(K) (const void *)K<16, false>, (const void *)K<32, false>, (const void *)K<64, false>, (const void *)K<16, true>, (const void *)K<32, true>, (const void *)K<64, true>
     const void *scans[] = {(const void *)k_sort_front, (const void *)k_block_table, MPM_CT_ALL(k_cell_table), MPM_CT_ALL(k_cell_table_plain),
-                           (const void *)k_async_compact};
+                           (const void *)k_async_compact<Store3>};
 #undef MPM_CT_ALL
     for (const void *k : scans) {
       int per_cu = 0;
@@ -2676,18 +2743,11 @@ static int async_reset_table(mpmhip_ctx *c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));  // (`init` lives on this stack frame)
   return MPMHIP_OK;
 }
-// the reduced table -> the block state machine of AsyncMPM<dim>::update_dt_limits (AsyncSched::limits_from_table)
-static int async_limits_from_table(mpmhip_ctx *c) {
-  auto &A = c->async;
-  const size_t nblk = A.strength.size();
-  if (A.h_tab_cap < 3 * nblk) {  // pinned staging (a copy into pageable memory is staged by the runtime: ~50 us more)
-    HIPCHK(c, A.h_tab.alloc(3 * nblk));
-    A.h_tab_cap = 3 * nblk;
-  }
-  HIPCHK(c, hipMemcpyAsync(A.h_tab, A.d_tab, sizeof(uint32_t) * 3 * nblk, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (!A.limits_from_table(A.h_tab, c->P.dx)) return fail(c, MPMHIP_EINVAL, "%s", A.sched_err.c_str());
-  return MPMHIP_OK;
+// the reduced table -> the block state machine of AsyncMPM<dim>::update_dt_limits (AsyncSched::limits_from_table): async_api.h
+extern "C++" {
+namespace {
+template <class Ctx> int async_limits_from_table(Ctx *c);
+}
 }
 
 int mpmhip_async_update_dt_limits(mpmhip_ctx *c) {  // AsyncMPM<dim>::update_dt_limits, src/async/async_mpm.cpp:90-164
@@ -2758,8 +2818,6 @@ int mpmhip_async_set_time_int(mpmhip_ctx *c, int64_t t_int) {
   c->async.current_t_int = t_int;
   return MPMHIP_OK;
 }
-
-#include "async_api.h"
 
 int mpmhip_debug_allowed_dt(mpmhip_ctx *c, int32_t material, const float params[MPMHIP_NPARAM], int64_t n, const float *F,
                             const float *aux, const float *v, float dx, float *out) {
@@ -2835,26 +2893,10 @@ struct mpmhip2d_ctx {
     DevBuf<uint8_t> scan_tmp;
     size_t scan_bytes = 0;
   } det;
-  // AsyncMPM<2> (async2d_api.h): the block scheduler + the device store of pool / backup containers (k_async2d.h)
-  struct Async2 : AsyncSched {
-    bool resident = false, pending_counters = false;
-    bool view = false;  // the particle arrays are copies of the pools (mpmhip2d_async_load_pools), not new particles
-    uint32_t cap = 0, size = 0, live = 0, size_ub = 0;  // containers allocated / in use incl. freed ones / not freed / upper bound now
-    DevBuf<float4> rec, rec2;
-    DevBuf<uint32_t> tag, tag2, d_tab, d_rank, d_blk_of;
-    PinnedBuf<uint32_t> h_tab;
-    DevBuf<unsigned long long> best, d_scan;
-    int64_t best_cap = 0, blk_of_cap = 0, compactions = 0;
-    uint32_t scan_cap = 0, scan_epoch = 0, pin_next = 0;
-    DevBuf<uint8_t> d_tbl;
-    PinnedBuf<uint8_t> h_tbl_pin;
-    DevBuf<AsyncCounters> d_cnt;
-    PinnedBuf<AsyncCounters> h_cnt;
-  } async;
+  AsyncResident async;  // AsyncMPM<2> (async_api.h): the block scheduler + the device store of pool / backup containers
   SeedWork seed;  // mpmhip2d_seed_particles (seed_api.h): the tile and the work buffers of the candidate passes
 };
-static int a2_drop_view(mpmhip2d_ctx *m);
-static int a2_grow_particles(mpmhip2d_ctx *m, int64_t need);
+static int async_drop_view(mpmhip2d_ctx *m);
 int mpmhip2d_async_step(mpmhip2d_ctx *m, float dt);
 static void det2_free(mpmhip2d_ctx *m) {  // a failed det2_reserve leaves nothing half-allocated
   const bool on = m->det.on;
@@ -2871,6 +2913,33 @@ static int fail2d(mpmhip2d_ctx *m, int code, const std::string &msg) {
     hipError_t e_ = (call);                                                                                    \
     if (e_ != hipSuccess) return fail2d((m), MPMHIP_EHIP, std::string(#call " failed: ") + hipGetErrorString(e_)); \
   } while (0)
+
+// the particle arrays of the 2D object hold at least `need` particles (its first m->n stay)
+static int a2_grow_particles(mpmhip2d_ctx *m, int64_t need) {
+  if (need <= m->cap) return MPMHIP_OK;
+  HIPCHK2D(m, hipStreamSynchronize(m->stream));
+  const size_t cap = (size_t)need + (size_t)need / 2 + 1024, keep = (size_t)m->n;
+  hipError_t e = hipSuccess;
+  auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  A(m->x.regrow(2 * keep, 2 * cap, false)); A(m->v.regrow(2 * keep, 2 * cap, false)); A(m->F.regrow(4 * keep, 4 * cap, false));
+  A(m->B.regrow(4 * keep, 4 * cap, false)); A(m->aux.regrow(keep, cap, false)); A(m->gid.regrow(keep, cap, false));
+  A(m->pid.regrow(keep, cap, false));
+  if (e != hipSuccess) return fail2d(m, MPMHIP_ENOMEM, std::string("growing the particle arrays failed: ") + hipGetErrorString(e));
+  m->cap = (int64_t)cap;
+  return MPMHIP_OK;
+}
+// the same for any 2D object (a snapshot larger than max_particles): the per-particle arrays of the CPIC coupling grow with them
+static int a2_grow_particles_any(mpmhip2d_ctx *m, int64_t need) {
+  if (need <= m->cap) return MPMHIP_OK;
+  const size_t keep = (size_t)m->n;
+  if (int rc = a2_grow_particles(m, need)) return rc;
+  if (m->rigid_enabled) {
+    hipError_t e = m->d_states.regrow(keep, (size_t)m->cap, true);
+    if (e == hipSuccess) e = m->d_bnd.regrow(keep, (size_t)m->cap, true);
+    if (e != hipSuccess) return fail2d(m, MPMHIP_ENOMEM, std::string("growing the particle arrays failed: ") + hipGetErrorString(e));
+  }
+  return MPMHIP_OK;
+}
 
 const char *mpmhip2d_last_error(const mpmhip2d_ctx *m) { return m ? m->err.c_str() : g_2d_create_error.c_str(); }
 
@@ -3108,7 +3177,7 @@ int mpmhip2d_add_particles(mpmhip2d_ctx *m, int32_t group, int64_t n, const floa
   if (group < 0 || group >= (int)m->groups.size()) return fail2d(m, MPMHIP_EINVAL, "unknown group");
   if (n == 0) return MPMHIP_OK;
   HIPCHK2D(m, hipSetDevice(m->device));
-  if (int rc = a2_drop_view(m)) return rc;  // (resident async stepper: arrays that only mirror the pools go first)
+  if (int rc = async_drop_view(m)) return rc;  // (resident async stepper: arrays that only mirror the pools go first)
   if (m->n + n > m->cap) {
     if (!m->async.resident) return fail2d(m, MPMHIP_ECAPACITY, "particle capacity exceeded");
     if (int rc = a2_grow_particles(m, m->n + n)) return rc;  // (a resident stepper's arrays hold one batch or one working set)
@@ -3667,7 +3736,7 @@ int mpmhip2d_download_grid(mpmhip2d_ctx *m, float *grid) {  // (v.x, v.y, m) per
   return MPMHIP_OK;
 }
 
-#include "async2d_api.h"
+#include "async_api.h"
 #include "frame2d_api.h"
 #include "seed_api.h"
 

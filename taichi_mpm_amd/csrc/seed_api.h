@@ -1,5 +1,5 @@
 // taichi_mpm_amd/csrc/seed_api.h — host side of mpmhip_seed_particles, mpmhip2d_seed_particles and mpmhip2d_reserve (kernels: k_seed.h;
-// tiles: poisson_tile.h; rules: include/mpmhip.h).  Included by mpmhip.hip inside its extern "C" block, behind async2d_api.h and
+// tiles: poisson_tile.h; rules: include/mpmhip.h).  Included by mpmhip.hip inside its extern "C" block, behind async_api.h and
 // frame2d_api.h: both ctx types are complete here.  One driver (seed_particles) carries the call for both dimensions; what a ctx does
 // its own way is in its adapter (Seed3, Seed2).  A sampled region's lattice is judged by sdf_lattice.h and becomes the SdfDev of the
 // boundary's sampler (mpmhip.hip: sdf_fill; mpm_math.h).  A call synchronises twice for a few words each: the get-ready box (the number of

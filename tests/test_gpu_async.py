@@ -259,7 +259,7 @@ def test_async_snapshot_restart_continues_the_run(tm, tmp_path):
 def test_pooling_more_batches_than_the_ctx_holds_grows_the_records_before_the_gather(tm):
     """a C-ABI caller may pool several batches of up to `cap` particles each (mpmhip_async_pool_particles empties the
     slots, mpmhip_add_particles only checks slots + n <= cap): the working set of an advance can then exceed the ctx's
-    record arrays — they are grown BEFORE k_async_gather writes into them (async_api.h: async_advance)"""
+    record arrays — they are grown BEFORE k_async_gather writes into them (async_api.h: as_advance)"""
     res, dx, sa, sb = _two_stiffness_scene()
     total = len(sa.x) + len(sb.x)
     sim = tm.create_simulation3("async_mpm").initialize(dict(res=(res,) * 3, delta_x=dx, unit_delta_t=2e-6, max_units=1024,

@@ -117,6 +117,39 @@ def test_c_resident_async_stepper_begun_twice(tm):
     assert _live(tm) == base
 
 
+def test_c_resident_async_stepper_begun_again_after_use(tm):
+    """mpmhip_async_begin on a ctx whose store has been used starts from an EMPTY store (AsyncStore::reset): the containers, tags and
+    pending counters of the first session are gone, so the pools of the second session hold the second session's particles alone.
+    The store's size is bounded by what the second session can have appended: its pooled particles plus one container per particle
+    update (state[1], which begin resets), whether or not a compaction ran."""
+    base = _live(tm)
+    res, dx = 16, 1.0 / 16
+    kw = dict(unit_delta_t=2e-6, max_units=1024)
+    sim = tm.create_simulation3("async_mpm").initialize(dict(res=(res,) * 3, delta_x=dx, **kw))
+    x = _middle(res, 300, 3, seed=3)
+    x[:, 0] = (res / 2 - 0.9 + 0.85 * (x[:, 0] * res - (res / 2 - 0.9)) / 1.8) / res  # the lower of the two middle cells along x
+    sim.add_particles(dict(type="elastic", positions=x, velocities=np.zeros_like(x)))
+    for _ in range(3):
+        sim.step(1e-3)
+    assert set(np.unique(sim.get_pool_particles()["id"])) == set(range(len(x)))
+    from taichi_mpm_amd import _lib
+    again = _lib.AsyncConfig(kw["unit_delta_t"], kw["max_units"], 1.0, 1.0, 0)
+    sim._check(sim._L.mpmhip_async_begin(sim._ctx, C.byref(again)))
+    x2 = _middle(res, 100, 3, seed=4)
+    x2[:, 0] = (res / 2 + 0.05 + 0.85 * (x2[:, 0] * res - (res / 2 - 0.9)) / 1.8) / res  # the upper one
+    sim.add_particles(dict(type="elastic", positions=x2, velocities=np.zeros_like(x2)))
+    for _ in range(3):
+        sim.step(1e-3)
+    ids = set(np.unique(sim.get_pool_particles()["id"]).tolist())
+    st = sim._state()
+    print("second session: ids %d..%d (%d), state %s" % (min(ids), max(ids), len(ids), st))
+    assert ids and ids <= set(range(len(x), len(x) + len(x2))), sorted(ids)[:8]
+    assert st[4] <= st[5] <= len(x2) + st[1], st
+    assert _live(tm) > base
+    sim.close()
+    assert _live(tm) == base
+
+
 def test_d_local_tiled_job_of_two_virtual_ranks_with_a_migration(tm):
     """(the halo arena of each rank is allocated by one of two runtime calls and mapped by peers: the one array outside the counter)"""
     from taichi_mpm_amd import tiled
