@@ -532,6 +532,8 @@ class AsyncMPM3D : public MPM3D {
   std::string get_name() const override { return "async_mpm"; }  // src/async/async_mpm.h:251-253
   int64_t current_t_int() const { int64_t o[8]; check(mpmhip_async_state(ctx_, o), ctx_); return o[0]; }
   int64_t update_counter() const { int64_t o[8]; check(mpmhip_async_state(ctx_, o), ctx_); return o[1]; }
+  // {gather, file, load, export}: 1 = the ordered form of the deterministic mode ran last, 0 = the one that places by arrival, -1 = none yet
+  std::array<int32_t, 4> async_forms() const { std::array<int32_t, 4> o{}; check(mpmhip_async_forms(ctx_, o.data()), ctx_); return o; }
 
  protected:
   bool keep_apic_b_default() const override { return true; }  // (the P2G matrix is rebuilt from apic_b for every advance's dt)

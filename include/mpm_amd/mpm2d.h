@@ -398,6 +398,8 @@ class AsyncMPM2D : public MPM2D {
   std::string get_name() const override { return "async_mpm"; }  // src/async/async_mpm.h:251-253
   int64_t current_t_int() const { int64_t o[8]; check(mpmhip2d_async_state(ctx_, o), ctx_); return o[0]; }
   int64_t update_counter() const { int64_t o[8]; check(mpmhip2d_async_state(ctx_, o), ctx_); return o[1]; }
+  // {gather, file, load, export}: 1 = the ordered form of the deterministic mode ran last, 0 = the one that places by arrival, -1 = none yet
+  std::array<int32_t, 4> async_forms() const { std::array<int32_t, 4> o{}; check(mpmhip2d_async_forms(ctx_, o.data()), ctx_); return o; }
 };
 
 // the factory the reference reaches through `create_instance<Simulation2D>(name)`

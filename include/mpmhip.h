@@ -107,7 +107,8 @@ typedef struct {
                              * the slots) and calculate_energy (partial sums per node block / per sorted particle range, added in a fixed
                              * order; both grid walks give the same bits).  Switching the mode on takes effect from the next substep.
                              * The 2D solver has its own form of the mode (mpmhip2d_config.deterministic below: a cell sort and a
-                             * gather P2G).  Not covered: the asynchronous steppers, 2D and 3D.
+                             * gather P2G).  The asynchronous steppers, 2D and 3D, are covered: in the mode their containers are placed by
+                             * ordered stream compactions, not by order of arrival (mpmhip_async_forms).
                              * The reference's sort key is unique for the same purpose: (offset >> 5) << 25 | i, src/mpm.cpp:785-795.
                              * env MPMHIP_DETERMINISTIC=0/1 overrides */
   int32_t reserved[2];
@@ -610,6 +611,16 @@ int mpmhip_async_state(mpmhip_ctx *ctx, int64_t out[8]);
 double mpmhip_async_current_time(const mpmhip_ctx *ctx);
 int64_t mpmhip_async_block_times(mpmhip_ctx *ctx, int64_t capacity, int64_t *particle_t, int64_t *backup_t, int64_t *local_min);
 int64_t mpmhip_async_download_pools(mpmhip_ctx *ctx, int64_t capacity, float *rows, int32_t *block);
+/* test helper: which form of the four kernels that place containers ran last in this session — out = {gather (the working set of an
+ * advance), file (the appends behind the store's end), load (load_pools), export (download_pools)}: 0 = by order of arrival, 1 = the
+ * ordered form of the deterministic mode (csrc/k_async.h), -1 = not launched since mpmhip_async_begin.  Nothing is launched.
+ * With the mode on a resident stepper is a function of its configuration, its level set and the sequence of calls it receives:
+ * filed particles go behind the store's end in ascending working-set slot, working sets, views and exported rows come in ascending
+ * store position, so download_pools' raw rows, frames, snapshot blobs and counters are byte-identical between runs, whatever the
+ * launch sizes.  The mode may be switched between steps (mpmhip_set_deterministic): the next launch uses the new form, the order
+ * the store had until then stays.  TEST KNOB: env MPMHIP_ASYNC_WGS=n (read by mpmhip_async_begin / mpmhip2d_async_begin; results
+ * valid) caps the workgroups of every asynchronous launch, so that a small scene carries a scan across several chunks per workgroup. */
+int mpmhip_async_forms(mpmhip_ctx *ctx, int32_t out[4]);
 /* host wall time spent so far, ms: {update_dt_limits, of which the neighbour lists, advance, of which the substep (meaningful
  * with sync != 0: the stream is then synchronised behind every substep), store compaction, number of advances} */
 int mpmhip_async_profile(mpmhip_ctx *ctx, int32_t sync, double out[6]);
@@ -660,8 +671,8 @@ typedef struct {
                              * nine cells in a fixed order and is written with one plain store; the impulses particles hand to
                              * bodies are summed per workgroup in a fixed tree and the rows added in a fixed order.  No float atomic
                              * remains on the path.  With duplicate creation ids the run is still valid, but the order inside a cell
-                             * — and so the last bits — then depends on the slots.  Not covered: the asynchronous 2D stepper's pools,
-                             * gathers and appends. */
+                             * — and so the last bits — then depends on the slots.  The asynchronous 2D stepper is covered: its pools, gathers and
+                             * appends take the ordered forms (mpmhip_async_forms). */
   int32_t reserved[2];
 } mpmhip2d_config;
 int mpmhip2d_create(const mpmhip2d_config *cfg, mpmhip2d_ctx **out);
@@ -838,6 +849,9 @@ int mpmhip2d_snapshot_load(mpmhip2d_ctx *ctx, const void *src, size_t size);
  *                     pools become the object's particles (mpmhip2d_download / _num_particles then see the whole state, each
  *                     particle at its block's time; an id can occur more than once, as in the reference); returns their number.
  *                     _view_blocks: the pool block of each, in download order.
+ *   _download_pools   every container of every particle pool without touching the object's particles: rows of 16 floats — the
+ *                     container as stored, {x2, v2, F4, apic_b4, aux, gid bits, id bits, -} — + its block; rows == NULL: the count
+ *   _forms            as mpmhip_async_forms
  *   _state            {current_t_int, update_counter, min_delta_t_int, max_delta_t_int, live containers, store size,
  *                     compactions, steps}
  *   _table            dense block table (block b = bx nb[1] + by): limits, pool sizes, particle_t, backup_t, local_min_dt_limit;
@@ -847,6 +861,8 @@ int mpmhip2d_async_pool_particles(mpmhip2d_ctx *ctx);
 int mpmhip2d_async_step(mpmhip2d_ctx *ctx, float dt);
 int64_t mpmhip2d_async_load_pools(mpmhip2d_ctx *ctx);
 int64_t mpmhip2d_async_view_blocks(mpmhip2d_ctx *ctx, int64_t capacity, int32_t *block);
+int64_t mpmhip2d_async_download_pools(mpmhip2d_ctx *ctx, int64_t capacity, float *rows, int32_t *block);
+int mpmhip2d_async_forms(mpmhip2d_ctx *ctx, int32_t out[4]);
 int mpmhip2d_async_state(mpmhip2d_ctx *ctx, int64_t out[8]);
 double mpmhip2d_async_current_time(const mpmhip2d_ctx *ctx);
 int64_t mpmhip2d_async_table(mpmhip2d_ctx *ctx, int32_t nb[2], int64_t capacity, int64_t *strength, int64_t *cfl, int64_t *continuous,

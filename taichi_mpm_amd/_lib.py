@@ -188,10 +188,10 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip_tiled_reduce", "mpmhip_tiled_reduce_group", "mpmhip_calculate_energy_group", "mpmhip_tiled_totals", "mpmhip_tiled_totals_group",
             "mpmhip_import_particles", "mpmhip_active_bounds", "mpmhip_num_slots", "mpmhip_request_compaction", "mpmhip_reserve", "mpmhip_capacity", "mpmhip_mpm88_create", "mpmhip_mpm88_destroy", "mpmhip_mpm88_last_error", "mpmhip_mpm88_add",
             "mpmhip_mpm88_num_particles", "mpmhip_mpm88_advance", "mpmhip_mpm88_download", "mpmhip_mpm88_download_grid",
-            "mpmhip_async_enable", "mpmhip_async_begin", "mpmhip_async_pool_particles", "mpmhip_async_step", "mpmhip_async_load_pools", "mpmhip_async_state", "mpmhip_async_current_time", "mpmhip_async_block_times", "mpmhip_async_download_pools", "mpmhip_async_profile", "mpmhip_async_snapshot_size", "mpmhip_async_snapshot_save", "mpmhip_async_snapshot_load", "mpmhip_host_particle_bytes", "mpmhip_async_update_dt_limits", "mpmhip_async_blocks", "mpmhip_async_set_time_int", "mpmhip_async_table", "mpmhip_clear_particles", "mpmhip_set_dt", "mpmhip_set_time", "mpmhip_get_clock", "mpmhip_set_clock", "mpmhip_debug_allowed_dt",
+            "mpmhip_async_enable", "mpmhip_async_begin", "mpmhip_async_pool_particles", "mpmhip_async_step", "mpmhip_async_load_pools", "mpmhip_async_state", "mpmhip_async_current_time", "mpmhip_async_block_times", "mpmhip_async_download_pools", "mpmhip_async_forms", "mpmhip_async_profile", "mpmhip_async_snapshot_size", "mpmhip_async_snapshot_save", "mpmhip_async_snapshot_load", "mpmhip_host_particle_bytes", "mpmhip_async_update_dt_limits", "mpmhip_async_blocks", "mpmhip_async_set_time_int", "mpmhip_async_table", "mpmhip_clear_particles", "mpmhip_set_dt", "mpmhip_set_time", "mpmhip_get_clock", "mpmhip_set_clock", "mpmhip_debug_allowed_dt",
             "mpmhip2d_create", "mpmhip2d_destroy", "mpmhip2d_last_error", "mpmhip2d_set_deterministic", "mpmhip2d_upload_ids", "mpmhip2d_set_levelset", "mpmhip2d_add_group", "mpmhip2d_add_particles",
             "mpmhip2d_substep", "mpmhip2d_step", "mpmhip2d_current_time", "mpmhip2d_num_particles", "mpmhip2d_download", "mpmhip2d_download_grid",
-            "mpmhip2d_async_begin", "mpmhip2d_async_pool_particles", "mpmhip2d_async_step", "mpmhip2d_async_load_pools", "mpmhip2d_async_view_blocks",
+            "mpmhip2d_async_begin", "mpmhip2d_async_pool_particles", "mpmhip2d_async_step", "mpmhip2d_async_load_pools", "mpmhip2d_async_view_blocks", "mpmhip2d_async_download_pools", "mpmhip2d_async_forms",
             "mpmhip2d_async_state", "mpmhip2d_async_current_time", "mpmhip2d_async_table", "mpmhip2d_bgeo_size", "mpmhip2d_bgeo_encode", "mpmhip2d_write_bgeo", "mpmhip2d_snapshot_size", "mpmhip2d_snapshot_save", "mpmhip2d_snapshot_load",
             "mpmhip2d_set_rigid_coupling", "mpmhip2d_set_rigid_levelset_collision", "mpmhip2d_add_articulation", "mpmhip2d_set_articulation_iterations", "mpmhip2d_add_rigid_body", "mpmhip2d_rigid_get_state", "mpmhip2d_rigid_get_samples", "mpmhip2d_cdf_phase",
             "mpmhip2d_download_cdf", "mpmhip2d_download_colours", "mpmhip2d_poisson_tile", "mpmhip2d_seed_particles", "mpmhip2d_reserve", "mpmhip2d_num_slots", "mpmhip2d_capacity", "mpmhip2d_set_levelset_sdf", "mpmhip2d_delete_particles_inside_level_set", "mpmhip2d_debug_levelset_sample", "mpmhip2d_debug_force", "mpmhip2d_debug_plasticity", "mpmhip2d_debug_svd2",
@@ -339,6 +339,7 @@ def load():
     L.mpmhip_async_block_times.restype = C.c_int64
     L.mpmhip_async_download_pools.argtypes = [vp, C.c_int64, fp, ip]
     L.mpmhip_async_download_pools.restype = C.c_int64
+    L.mpmhip_async_forms.argtypes = [vp, P(C.c_int32)]
     L.mpmhip_async_profile.argtypes = [vp, C.c_int32, P(C.c_double)]
     L.mpmhip_async_snapshot_size.argtypes = [vp]
     L.mpmhip_async_snapshot_size.restype = C.c_int64
@@ -404,6 +405,9 @@ def load():
     L.mpmhip2d_async_load_pools.restype = C.c_int64
     L.mpmhip2d_async_view_blocks.argtypes = [vp, C.c_int64, ip]
     L.mpmhip2d_async_view_blocks.restype = C.c_int64
+    L.mpmhip2d_async_download_pools.argtypes = [vp, C.c_int64, fp, ip]
+    L.mpmhip2d_async_download_pools.restype = C.c_int64
+    L.mpmhip2d_async_forms.argtypes = [vp, P(C.c_int32)]
     L.mpmhip2d_async_state.argtypes = [vp, P(C.c_int64)]
     L.mpmhip2d_async_current_time.argtypes = [vp]
     L.mpmhip2d_async_current_time.restype = C.c_double

@@ -113,6 +113,23 @@ class AsyncSimulation3D(Simulation3D):
         self._ensure_ctx()
         return int(self._check(self._L.mpmhip_async_download_pools(self._ctx, 0, None, None)))
 
+    def async_forms(self):
+        """[gather, file, load, export] of the latest launch of each (mpmhip_async_forms): 1 = the ordered form of the
+        deterministic mode, 0 = the one that places by order of arrival, -1 = not launched in this session"""
+        self._ensure_ctx()
+        o = (C.c_int32 * 4)()
+        self._check(self._L.mpmhip_async_forms(self._ctx, o))
+        return list(o)
+
+    def download_pools(self):
+        """(rows [n, 27] float32, block [n] int32) exactly as mpmhip_async_download_pools hands them over: unsorted"""
+        n = self.get_num_pool_particles()
+        rows = np.zeros((max(n, 1), 27), np.float32)
+        blk = np.zeros(max(n, 1), np.int32)
+        got = int(self._check(self._L.mpmhip_async_download_pools(self._ctx, n, rows.ctypes.data_as(C.POINTER(C.c_float)),
+                                                                 blk.ctypes.data_as(C.POINTER(C.c_int32)))))
+        return rows[:got], blk[:got]
+
     def block_table(self):
         """dense block table (block b = (bx nb[1] + by) nb[2] + bz): continuous / strength / cfl limits, pool sizes,
         particle_t, backup_t, local_min_dt_limit"""
@@ -128,12 +145,7 @@ class AsyncSimulation3D(Simulation3D):
 
     def get_pool_particles(self):
         """every container of every particle pool (each at its block's particle_t) + its block's limits, sorted by id"""
-        n = self.get_num_pool_particles()
-        rows = np.zeros((max(n, 1), 27), np.float32)
-        blk = np.zeros(max(n, 1), np.int32)
-        got = int(self._check(self._L.mpmhip_async_download_pools(self._ctx, n, rows.ctypes.data_as(C.POINTER(C.c_float)),
-                                                                 blk.ctypes.data_as(C.POINTER(C.c_int32)))))
-        rows, blk = rows[:got], blk[:got]
+        rows, blk = self.download_pools()
         tab = self.block_table()
         out = dict(x=rows[:, 0:3].copy(), v=rows[:, 3:6].copy(), F=rows[:, 6:15].copy(), B=rows[:, 15:24].copy(), aux=rows[:, 24].copy(),
                    gid=rows[:, 25].copy().view(np.int32), id=rows[:, 26].copy().view(np.int32), block=blk.astype(np.int64),
@@ -294,6 +306,25 @@ class AsyncSimulation2D(Simulation2D):
         self._ensure_ctx()
         return int(self._check(self._L.mpmhip2d_async_load_pools(self._ctx)))
 
+    def async_forms(self):
+        """[gather, file, load, export] of the latest launch of each (mpmhip2d_async_forms): 1 = the ordered form of the
+        deterministic mode, 0 = the one that places by order of arrival, -1 = not launched in this session"""
+        self._ensure_ctx()
+        o = (C.c_int32 * 4)()
+        self._check(self._L.mpmhip2d_async_forms(self._ctx, o))
+        return list(o)
+
+    def download_pools(self):
+        """(rows [n, 16] float32 = {x2, v2, F4, apic_b4, aux, gid bits, id bits, -}, block [n] int32) exactly as
+        mpmhip2d_async_download_pools hands them over: unsorted; the object's particle arrays are not touched"""
+        self._ensure_ctx()
+        n = int(self._check(self._L.mpmhip2d_async_download_pools(self._ctx, 0, None, None)))
+        rows = np.zeros((max(n, 1), 16), np.float32)
+        blk = np.zeros(max(n, 1), np.int32)
+        got = int(self._check(self._L.mpmhip2d_async_download_pools(self._ctx, n, rows.ctypes.data_as(C.POINTER(C.c_float)),
+                                                                   blk.ctypes.data_as(C.POINTER(C.c_int32)))))
+        return rows[:got], blk[:got]
+
     def get_num_pool_particles(self):
         """containers in all particle pools (an id can sit in more than one, as in the reference)"""
         return self._load_pools()
@@ -310,12 +341,10 @@ class AsyncSimulation2D(Simulation2D):
 
     def get_pool_particles(self):
         """every container of every particle pool + its block and that block's limits, sorted by (id, block)"""
-        n = self._load_pools()
-        out = Simulation2D.get_particles(self, sort_by_id=False)
-        blk = np.zeros(max(n, 1), np.int32)
-        got = int(self._check(self._L.mpmhip2d_async_view_blocks(self._ctx, n, blk.ctypes.data_as(C.POINTER(C.c_int32)))))
-        assert got == n == len(out["id"])
-        blk = blk[:n].astype(np.int64)
+        rows, blk = self.download_pools()
+        out = dict(x=rows[:, 0:2].copy(), v=rows[:, 2:4].copy(), F=rows[:, 4:8].copy(), B=rows[:, 8:12].copy(), aux=rows[:, 12].copy(),
+                   gid=rows[:, 13].copy().view(np.int32), id=rows[:, 14].copy().view(np.int32))
+        blk = blk.astype(np.int64)
         tab = self.block_table()
         out.update(block=blk, continuous=tab["continuous"][blk], particle_t=tab["particle_t"][blk])
         o = np.lexsort((out["block"], out["id"]))

@@ -24,15 +24,19 @@ static int as_fail(mpmhip_ctx *c, int code, const std::string &msg) { return fai
 static int as_fail(mpmhip2d_ctx *m, int code, const std::string &msg) { return fail2d(m, code, msg); }
 static const char *as_begin_first(const mpmhip_ctx *) { return "mpmhip_async_begin first"; }
 static const char *as_begin_first(const mpmhip2d_ctx *) { return "mpmhip2d_async_begin first"; }
-// Launch caps, in workgroups of 256: of the passes over the store, of the filing pass over the working set, of the compaction
-// (a chained scan: every launched workgroup must be resident — scan_limit asks the occupancy API, 64 always are).  The values
+// Launch caps, in workgroups of 256: of the passes over the store, of the filing pass over the working set, of the chained scans
+// (the compaction and the ordered forms: every launched workgroup must be resident — scan_limit asks the occupancy API per kernel,
+// 64 always are).  The test knob MPMHIP_ASYNC_WGS lowers all of them (as_wgs).  The values
 // are each dimension's own from before the two steppers shared this file; whether any of them matters for speed has not been measured.
 static uint32_t as_store_wgs(const mpmhip_ctx *) { return 4096; }
 static uint32_t as_store_wgs(const mpmhip2d_ctx *) { return 2048; }
 static uint32_t as_file_wgs(const mpmhip_ctx *) { return 8192; }
 static uint32_t as_file_wgs(const mpmhip2d_ctx *) { return 2048; }
-static uint32_t as_compact_wgs(mpmhip_ctx *c) { return scan_limit(c, (const void *)k_async_compact<Store3>); }
-static uint32_t as_compact_wgs(mpmhip2d_ctx *) { return 64; }
+static uint32_t as_scan_wgs(mpmhip_ctx *c, const void *kernel) { return scan_limit(c, kernel); }
+static uint32_t as_scan_wgs(mpmhip2d_ctx *, const void *) { return 64; }
+// deterministic mode: the ordered forms of the kernels that place containers (k_async.h) instead of the ones that place by arrival
+static bool as_ordered(const mpmhip_ctx *c) { return c->deterministic; }
+static bool as_ordered(const mpmhip2d_ctx *m) { return m->det.on; }
 // the device views of the store (twin: the compaction's target) and of the working set
 static Store3 as_store(const mpmhip_ctx *c, bool twin = false) {
   const AsyncStore &S = c->async.store;
@@ -88,6 +92,18 @@ static AsTimer as_timer(mpmhip_ctx *c, int k) {
 }
 static int as_timer(mpmhip2d_ctx *, int) { return 0; }
 
+// the plain export of the pool containers: rows of Store::ROW floats in order of arrival
+static void as_export_plain(const mpmhip_ctx *c, dim3 grid, uint32_t size, float *rows, uint32_t *blk) {
+  const Store3 V = as_store(c);
+  hipLaunchKernelGGL(k_async_export, grid, dim3(256), 0, c->stream, size, (const uint32_t *)V.tag, (const float4 *)V.g, (const float4 *)V.w, rows, blk,
+                     c->async.store.d_cnt.get());
+}
+static void as_export_plain(const mpmhip2d_ctx *m, dim3 grid, uint32_t size, float *rows, uint32_t *blk) {
+  hipLaunchKernelGGL(k_async_export2, grid, dim3(256), 0, m->stream, size, as_store(m), rows, blk, m->async.store.d_cnt.get());
+}
+static void as_host_bytes(mpmhip_ctx *c, int64_t bytes) { c->host_particle_bytes += bytes; }
+static void as_host_bytes(mpmhip2d_ctx *, int64_t) {}
+
 extern "C++" {
 namespace {
 
@@ -102,8 +118,15 @@ namespace {
     if (e_ != hipSuccess) return as_fail(c, MPMHIP_EHIP, std::string("launch of " what " failed: ") + hipGetErrorString(e_)); \
   } while (0)
 
+// workgroups of an asynchronous launch that wants `want` and may have `limit`: TEST KNOB MPMHIP_ASYNC_WGS (read by as_begin) caps
+// every one of them, so that a scene of a few thousand containers makes one workgroup walk several chunks of a chained scan
 template <class Ctx>
-dim3 as_grid(const Ctx *c, uint32_t n) { return dim3(std::min<uint32_t>(std::max<uint32_t>((n + 255) / 256, 1), as_store_wgs(c))); }
+uint32_t as_wgs(const Ctx *c, uint32_t want, uint32_t limit) {
+  const uint32_t knob = c->async.test_wgs;
+  return std::max<uint32_t>(std::min(std::min(want, limit), knob ? knob : limit), 1);
+}
+template <class Ctx>
+dim3 as_grid(const Ctx *c, uint32_t n) { return dim3(as_wgs(c, (n + 255) / 256, as_store_wgs(c))); }
 
 template <class Ctx>
 int as_enter(Ctx *c) {  // every entry point of a resident stepper
@@ -120,6 +143,9 @@ int as_begin(Ctx *c, std::initializer_list<size_t> lane_bytes) {
   A.resident = false;
   A.sched_begin();  // block times, the reference's block order, cached_neighbours
   A.d_blk_of.reset(); A.blk_of_cap = 0;  // (the next load_pools allocates it again)
+  for (int32_t &f : A.forms) f = -1;
+  const char *knob = getenv("MPMHIP_ASYNC_WGS");
+  A.test_wgs = knob ? (uint32_t)std::max(atoi(knob), 0) : 0u;
   const hipError_t e = A.store.reset(lane_bytes, A.rank_of);
   if (e != hipSuccess) return as_fail(c, MPMHIP_ENOMEM, std::string("async store: tables of a new session: ") + hipGetErrorString(e));
   A.resident = true;
@@ -181,6 +207,23 @@ int as_settle(Ctx *c) {
   AsyncCounters h;
   return c->async.store.pending_counters ? as_counters(c, h) : MPMHIP_OK;
 }
+// the launch of a chained scan over n elements (the compaction, the ordered forms): its scan words sized and zeroed, a fresh epoch,
+// no more workgroups than stay resident
+struct AsScan { unsigned long long *slots; uint32_t epoch; dim3 grid; };
+template <class Ctx>
+int as_scan(Ctx *c, uint32_t n, const void *kernel, AsScan &out) {
+  auto &S = c->async.store;
+  const uint32_t nchunks = (n + 1023) / 1024;
+  if (nchunks + 1 > S.scan_cap) {
+    AS_CHK(hipStreamSynchronize(c->stream));  // (a pending launch may still read the old words)
+    AS_CHK(S.d_scan.alloc((size_t)nchunks + 1024));
+    AS_CHK(hipMemsetAsync(S.d_scan, 0, sizeof(unsigned long long) * ((size_t)nchunks + 1024), c->stream));
+    S.scan_cap = nchunks + 1024;
+  }
+  if (++S.scan_epoch == 0u) S.scan_epoch = 1u;  // (0 = never published)
+  out = AsScan{S.d_scan.get(), S.scan_epoch, dim3(as_wgs(c, nchunks, as_scan_wgs(c, kernel)))};
+  return MPMHIP_OK;
+}
 // (called with the counters settled: S.size and S.live are exact.)  The store holds exactly its live containers afterwards.
 template <class Ctx>
 int as_compact(Ctx *c) {
@@ -190,15 +233,10 @@ int as_compact(Ctx *c) {
   (void)whole;
   if (const hipError_t e = S.reserve_twins(); e != hipSuccess) return as_fail(c, MPMHIP_ENOMEM, std::string("async store: compaction buffers: ") + hipGetErrorString(e));
   AS_CHK(hipMemsetAsync(S.tag2, 0xFF, sizeof(uint32_t) * (size_t)S.cap, c->stream));
-  const uint32_t nchunks = (S.size + 1023) / 1024;
-  if (nchunks + 1 > S.scan_cap) {
-    AS_CHK(S.d_scan.alloc((size_t)nchunks + 1024));
-    AS_CHK(hipMemsetAsync(S.d_scan, 0, sizeof(unsigned long long) * ((size_t)nchunks + 1024), c->stream));
-    S.scan_cap = nchunks + 1024;
-  }
+  AsScan sc;
+  if (int rc = as_scan(c, S.size, (const void *)k_async_compact<decltype(as_store(c))>, sc)) return rc;
   const auto V = as_store(c), V2 = as_store(c, true);
-  hipLaunchKernelGGL(k_async_compact<decltype(as_store(c))>, dim3(std::min(nchunks, as_compact_wgs(c))), dim3(256), 0, c->stream, S.size, V, V2,
-                     S.d_scan.get(), ++S.scan_epoch, S.d_cnt.get());
+  hipLaunchKernelGGL(k_async_compact<decltype(as_store(c))>, sc.grid, dim3(256), 0, c->stream, S.size, V, V2, sc.slots, sc.epoch, S.d_cnt.get());
   AS_LAUNCHED("async_compact");
   S.swap_twins();
   AsyncCounters h;
@@ -223,9 +261,15 @@ int as_file(Ctx *c, uint32_t n, int all_to_pool) {
   auto &A = c->async;
   auto &S = A.store;
   if (int rc = as_store_reserve(c, AsyncStore::sum(S.size, n))) return rc;
-  const uint32_t wgs = std::min<uint32_t>(std::max<uint32_t>((n + 255) / 256, 1), as_file_wgs(c));
-  hipLaunchKernelGGL(k_async_file<decltype(as_work(c))>, dim3(wgs), dim3(256), 0, c->stream, c->P.idx, n, as_work(c), (const uint8_t *)S.d_tbl,
-                     all_to_pool, A.nb[0], A.nb[1], A.nb[2], S.cap, as_store(c), S.d_cnt.get());
+  if ((A.forms[1] = as_ordered(c))) {
+    AsScan sc;
+    if (int rc = as_scan(c, n, (const void *)k_async_file_ordered<decltype(as_work(c))>, sc)) return rc;
+    hipLaunchKernelGGL(k_async_file_ordered<decltype(as_work(c))>, sc.grid, dim3(256), 0, c->stream, c->P.idx, n, as_work(c),
+                       (const uint8_t *)S.d_tbl, all_to_pool, A.nb[0], A.nb[1], A.nb[2], S.cap, as_store(c), sc.slots, sc.epoch, S.d_cnt.get());
+  } else {
+    hipLaunchKernelGGL(k_async_file<decltype(as_work(c))>, dim3(as_wgs(c, (n + 255) / 256, as_file_wgs(c))), dim3(256), 0, c->stream, c->P.idx, n,
+                       as_work(c), (const uint8_t *)S.d_tbl, all_to_pool, A.nb[0], A.nb[1], A.nb[2], S.cap, as_store(c), S.d_cnt.get());
+  }
   AS_LAUNCHED("async_file");
   return MPMHIP_OK;
 }
@@ -283,8 +327,15 @@ int as_advance(Ctx *c, int64_t limit) {
   if (int rc = as_make_room(c, std::min<int64_t>((int64_t)S.size_ub, (int64_t)c->next_pid))) return rc;
   hipLaunchKernelGGL(k_async_mark<decltype(as_store(c))>, as_grid(c, S.size_ub), dim3(256), 0, c->stream, S.size_ub, as_store(c),
                      (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best.get());
-  hipLaunchKernelGGL(k_async_gather<decltype(as_work(c))>, as_grid(c, S.size_ub), dim3(256), 0, c->stream, S.size_ub, as_store(c),
-                     (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best.get(), as_work(c), S.d_cnt.get());
+  if ((A.forms[0] = as_ordered(c))) {
+    AsScan sc;
+    if (int rc = as_scan(c, S.size_ub, (const void *)k_async_gather_ordered<decltype(as_work(c))>, sc)) return rc;
+    hipLaunchKernelGGL(k_async_gather_ordered<decltype(as_work(c))>, sc.grid, dim3(256), 0, c->stream, S.size_ub, as_store(c),
+                       (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best.get(), as_work(c), sc.slots, sc.epoch, S.d_cnt.get());
+  } else {
+    hipLaunchKernelGGL(k_async_gather<decltype(as_work(c))>, as_grid(c, S.size_ub), dim3(256), 0, c->stream, S.size_ub, as_store(c),
+                       (const uint8_t *)S.d_tbl, (const uint32_t *)S.d_rank, S.best.get(), as_work(c), S.d_cnt.get());
+  }
   AS_LAUNCHED("async_gather");
   AsyncCounters h;
   if (int rc = as_counters(c, h)) return rc;  // the one read-back of an advance (also settles the previous one's appends)
@@ -361,13 +412,62 @@ int as_load_pools(Ctx *c) {
   if (int rc = as_settle(c)) return rc;
   if (int rc = as_make_room(c, (int64_t)S.live)) return rc;
   if (int rc = as_ensure_blk_of(c)) return rc;
-  hipLaunchKernelGGL(k_async_load<decltype(as_work(c))>, as_grid(c, S.size), dim3(256), 0, c->stream, S.size, as_store(c), as_work(c),
-                     A.d_blk_of.get(), S.d_cnt.get());
+  if ((A.forms[2] = as_ordered(c))) {
+    AsScan sc;
+    if (int rc = as_scan(c, S.size, (const void *)k_async_load_ordered<decltype(as_work(c))>, sc)) return rc;
+    hipLaunchKernelGGL(k_async_load_ordered<decltype(as_work(c))>, sc.grid, dim3(256), 0, c->stream, S.size, as_store(c), as_work(c),
+                       A.d_blk_of.get(), sc.slots, sc.epoch, S.d_cnt.get());
+  } else {
+    hipLaunchKernelGGL(k_async_load<decltype(as_work(c))>, as_grid(c, S.size), dim3(256), 0, c->stream, S.size, as_store(c), as_work(c),
+                       A.d_blk_of.get(), S.d_cnt.get());
+  }
   AS_LAUNCHED("async_load");
   AsyncCounters h;
   if (int rc = as_counters(c, h)) return rc;
   if (int rc = as_working_set(c, h.n_work)) return rc;  // k_async_load replaced the ctx's particles by the view
   S.view = true;
+  return MPMHIP_OK;
+}
+
+// Every container of every particle pool as rows of Store::ROW floats + the container's block (mpmhip_async_download_pools,
+// mpmhip2d_async_download_pools).  rows == NULL: only the count.
+template <class Ctx>
+int64_t as_download_pools(Ctx *c, int64_t capacity, float *rows, int32_t *block) {
+  using Store = decltype(as_store(c));
+  auto &A = c->async;
+  auto &S = A.store;
+  if (int rc = as_enter(c)) return rc;
+  if (int rc = as_settle(c)) return rc;
+  DevBuf<float> d_rows;
+  DevBuf<uint32_t> d_blk;
+  const size_t m = std::max<size_t>(S.size, 1);
+  AS_CHK(d_rows.alloc(m * Store::ROW));
+  AS_CHK(d_blk.alloc(m));
+  if ((A.forms[3] = as_ordered(c))) {
+    AsScan sc;
+    if (int rc = as_scan(c, S.size, (const void *)k_async_export_ordered<Store>, sc)) return rc;
+    hipLaunchKernelGGL(k_async_export_ordered<Store>, sc.grid, dim3(256), 0, c->stream, S.size, as_store(c), d_rows.get(), d_blk.get(), sc.slots,
+                       sc.epoch, S.d_cnt.get());
+  } else {
+    as_export_plain(c, as_grid(c, S.size), S.size, d_rows.get(), d_blk.get());
+  }
+  AS_LAUNCHED("async_export");
+  AsyncCounters h;
+  if (int rc = as_counters(c, h)) return rc;
+  const int64_t n = (int64_t)h.n_work;
+  if (!rows || !block || !n) return n;
+  if (capacity < n)
+    return as_fail(c, MPMHIP_ECAPACITY, "async download: " + std::to_string(n) + " containers, room for " + std::to_string(capacity));
+  AS_CHK(hipMemcpy(rows, d_rows, sizeof(float) * Store::ROW * (size_t)n, hipMemcpyDeviceToHost));
+  AS_CHK(hipMemcpy(block, d_blk, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  as_host_bytes(c, n * Store::ROW * 4);
+  return n;
+}
+// {gather, file, load, export} of the most recent launch of each in this session: 0 arrival order, 1 ordered, -1 not launched yet
+template <class Ctx>
+int as_forms(Ctx *c, int32_t out[4]) {
+  if (!c->async.resident) return as_fail(c, MPMHIP_EINVAL, as_begin_first(c));
+  for (int k = 0; k < 4; k++) out[k] = c->async.forms[k];
   return MPMHIP_OK;
 }
 
@@ -435,29 +535,9 @@ int64_t mpmhip_async_block_times(mpmhip_ctx *c, int64_t capacity, int64_t *parti
 // reference) as rows of 27 floats {x3, v3, F9, apic_b9, aux, gid bits, id bits} + the container's block.  rows == NULL:
 // only the count.  (Tests and host-side inspection: the stepping itself never calls this.)
 int64_t mpmhip_async_download_pools(mpmhip_ctx *c, int64_t capacity, float *rows, int32_t *block) {
-  if (!c) return MPMHIP_EINVAL;
-  auto &S = c->async.store;
-  if (int rc = as_enter(c)) return rc;
-  if (int rc = as_settle(c)) return rc;
-  DevBuf<float> d_rows;
-  DevBuf<uint32_t> d_blk;
-  const size_t m = std::max<size_t>(S.size, 1);
-  HIPCHK(c, d_rows.alloc(m * 27));
-  HIPCHK(c, d_blk.alloc(m));
-  const Store3 V = as_store(c);
-  hipLaunchKernelGGL(k_async_export, as_grid(c, S.size), dim3(256), 0, c->stream, S.size, (const uint32_t *)V.tag, (const float4 *)V.g,
-                     (const float4 *)V.w, d_rows.get(), d_blk.get(), S.d_cnt.get());
-  AsyncCounters h;
-  if (int rc = launch_check(c, "async_export")) return rc;
-  if (int rc = as_counters(c, h)) return rc;
-  const int64_t n = (int64_t)h.n_work;
-  if (!rows || !block || !n) return n;
-  if (capacity < n) return fail(c, MPMHIP_ECAPACITY, "async download: %lld containers, room for %lld", (long long)n, (long long)capacity);
-  HIPCHK(c, hipMemcpy(rows, d_rows, sizeof(float) * 27 * (size_t)n, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(block, d_blk, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
-  c->host_particle_bytes += n * 27 * 4;
-  return n;
+  return c ? as_download_pools(c, capacity, rows, block) : MPMHIP_EINVAL;
 }
+int mpmhip_async_forms(mpmhip_ctx *c, int32_t out[4]) { return c && out ? as_forms(c, out) : MPMHIP_EINVAL; }
 
 // as_load_pools, and each particle of the view gets its pool block's (continuous, strength, cfl) limits for the frame's `limit` attribute
 int mpmhip_async_load_pools(mpmhip_ctx *c) {
@@ -621,6 +701,13 @@ int64_t mpmhip2d_async_load_pools(mpmhip2d_ctx *m) {
   if (int rc = as_load_pools(m)) return rc;
   return m->n;
 }
+
+// every container of every particle pool as rows of 16 floats — the container as stored: {x2, v2, F4, apic_b4, aux, gid bits, id bits, -}
+// — + its block; rows == NULL: only the count.  (Tests and host-side inspection.)
+int64_t mpmhip2d_async_download_pools(mpmhip2d_ctx *m, int64_t capacity, float *rows, int32_t *block) {
+  return m ? as_download_pools(m, capacity, rows, block) : MPMHIP_EINVAL;
+}
+int mpmhip2d_async_forms(mpmhip2d_ctx *m, int32_t out[4]) { return m && out ? as_forms(m, out) : MPMHIP_EINVAL; }
 
 // dense view of the block table: nb[2] blocks per axis (block b = bx nb[1] + by, 8 x 16 nodes each); any output may be NULL.
 // capacity < number of blocks: only the number is returned.

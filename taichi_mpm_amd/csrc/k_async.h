@@ -51,6 +51,15 @@ struct Store3 {
     v[0] = w0.x; v[1] = w0.y; v[2] = w0.z;
     aux = g0.w; gid = __float_as_uint(g3.y);
   }
+  static constexpr int ROW = 27;  // floats of an export row {x3, v3, F9, apic_b9, aux, gid bits, id bits} (k_async_export's)
+  __device__ __forceinline__ void row(uint32_t e, float *__restrict__ r) const {
+    const float *sg = reinterpret_cast<const float *>(g + (size_t)e * 4), *sw = reinterpret_cast<const float *>(w + (size_t)e * 4);
+    r[0] = sg[0]; r[1] = sg[1]; r[2] = sg[2];
+    r[3] = sw[0]; r[4] = sw[1]; r[5] = sw[2];
+#pragma unroll
+    for (int k = 0; k < 9; k++) { r[6 + k] = sg[4 + k]; r[15 + k] = sw[4 + k]; }
+    r[24] = sg[3]; r[25] = sg[13]; r[26] = sg[14];
+  }
 };
 // A 2D container: ONE 64-byte record {x2, v2}, {F4}, {apic_b4}, {aux, gid bits, id bits, -}.
 struct Store2 {
@@ -70,6 +79,13 @@ struct Store2 {
     F.m[0] = r1.x; F.m[1] = r1.y; F.m[2] = 0.0f; F.m[3] = r1.z; F.m[4] = r1.w; F.m[5] = 0.0f; F.m[6] = 0.0f; F.m[7] = 0.0f; F.m[8] = 1.0f;
     v[0] = r0.z; v[1] = r0.w; v[2] = 0.0f;
     aux = r3.x; gid = __float_as_uint(r3.y);
+  }
+  static constexpr int ROW = 16;  // an export row is the record itself: {x2, v2, F4, apic_b4, aux, gid bits, id bits, -}
+  __device__ __forceinline__ void row(uint32_t e, float *__restrict__ r) const {
+    const float4 *s = rec + (size_t)e * 4;
+    const float4 r0 = s[0], r1 = s[1], r2 = s[2], r3 = s[3];
+    float4 *d = reinterpret_cast<float4 *>(r);  // (rows of 64 bytes in a hipMalloc'ed array: aligned)
+    d[0] = r0; d[1] = r1; d[2] = r2; d[3] = r3;
   }
 };
 
@@ -293,7 +309,8 @@ __global__ __launch_bounds__(256) void k_async_load(uint32_t size, typename Work
   }
 }
 
-// pool containers -> flat arrays (tests, frame output): one row per container, in store order
+// pool containers -> flat arrays (tests, frame output): one row per container, in order of arrival (in store order:
+// k_async_export_ordered below)
 __global__ __launch_bounds__(256) void k_async_export(uint32_t size, const uint32_t *__restrict__ tag, const float4 *__restrict__ sg,
                                                       const float4 *__restrict__ sw, float *__restrict__ out27, uint32_t *__restrict__ blk,
                                                       AsyncCounters *cnt) {
@@ -309,6 +326,194 @@ __global__ __launch_bounds__(256) void k_async_export(uint32_t size, const uint3
     for (int k = 0; k < 9; k++) { r[6 + k] = g[4 + k]; r[15 + k] = w[4 + k]; }  // F, apic_b
     r[24] = g[3]; r[25] = g[13]; r[26] = g[14];                 // aux, gid (bits), id (bits)
     blk[o] = t;
+  }
+}
+
+// the 2D store's export (mpmhip2d_async_download_pools): one row of Store2::ROW floats per pool container, in order of arrival
+__global__ __launch_bounds__(256) void k_async_export2(uint32_t size, Store2 S, float *__restrict__ out, uint32_t *__restrict__ blk,
+                                                       AsyncCounters *cnt) {
+  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < size; e += gridDim.x * blockDim.x) {
+    const uint32_t t = S.tag[e];
+    if (t == AS_FREE || (t & AS_BACKUP)) continue;
+    const uint32_t o = atomicAdd(&cnt->n_work, 1u);
+    S.row(e, out + (size_t)o * Store2::ROW);
+    blk[o] = t;
+  }
+}
+
+// ---- deterministic mode (mpmhip_config.deterministic / mpmhip2d_config.deterministic): the ORDERED forms of the four kernels above
+// that take a destination from a global counter.  There the order of the working set, of the store and of everything read from the
+// store is the order in which lanes arrived.  Here each kernel is a stream compaction like k_async_compact: chunks of 1024 elements
+// per workgroup, four consecutive ones per lane, flag = "this element is written", slot = exclusive prefix of the flags in element
+// order (chained single-pass scan of k_sort.h over the store's scan words, a fresh epoch per launch; the host launches no more
+// workgroups than stay resident; a wait that expires sets the sticky bit of cnt->pad[0] and counts the missing sums as zero: every
+// slot is then too small, i.e. inside its array).  What comes out is a function of the input arrays alone, whatever the launch size.
+//
+// where a chunk's written elements go: `slot` of this lane's first one, [begin, end) of the whole chunk.  `fold` is added to what the
+// chunk publishes: k_async_file_ordered's chunk 0 hands the append cursor on that way (every other caller and chunk: 0).
+struct OrderedSlots { uint32_t slot, begin, end; };
+__device__ __forceinline__ OrderedSlots async_ordered_slots(uint32_t mine, uint32_t chunk, uint32_t fold, unsigned long long *__restrict__ slots,
+                                                            uint32_t epoch, uint32_t *lds, uint32_t *err) {
+  uint32_t total;
+  const uint32_t excl = wg_exclusive_scan_256(mine, lds, total);
+  if (threadIdx.x == 0) publish(slots + chunk, epoch, total + fold);
+  const uint32_t pre = sum_predecessors(slots, chunk, epoch, lds, err) + fold;
+  return OrderedSlots{pre + excl, pre, pre + total};
+}
+
+// k_async_gather with the winners in ascending store position
+template <class Work>
+__global__ __launch_bounds__(256) void k_async_gather_ordered(uint32_t size, typename Work::Store S, const uint8_t *__restrict__ tbl,
+                                                              const uint32_t *__restrict__ rank_of, unsigned long long *__restrict__ best,
+                                                              Work W, unsigned long long *__restrict__ slots, uint32_t epoch,
+                                                              AsyncCounters *cnt) {
+  __shared__ uint32_t lds[8];
+  const uint32_t nchunks = (size + 1023u) / 1024u;
+  uint32_t round = 0;
+  while (true) {
+    const uint32_t chunk = next_chunk(round);
+    if (chunk >= nchunks) return;
+    const uint32_t e0 = chunk * 1024u + threadIdx.x * 4u;
+    uint32_t win = 0, nwin = 0, freed = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t e = e0 + j;
+      const uint32_t t = e < size ? S.tag[e] : AS_FREE;
+      if (t == AS_FREE) continue;
+      const uint32_t b = t & ~AS_BACKUP;
+      const uint8_t act = tbl[b];
+      const int cat = async_category(t, act);
+      if (cat >= 0) {
+        const int32_t id = S.id(e);
+        if (best[id] == async_key((uint32_t)cat, rank_of[b], e)) {
+          best[id] = ~0ull;  // (one winner per id: the table is clean again after the pass)
+          win |= 1u << j;
+          nwin++;
+        }
+      }
+      if (act & AT_SWAP) {
+        if (t & AS_BACKUP) { S.tag[e] = AS_FREE; freed++; }
+        else S.tag[e] = t | AS_BACKUP;
+      }
+    }
+    if (freed) atomicAdd(&cnt->n_freed, freed);  // (an integer sum: the same whatever the order)
+    const OrderedSlots R = async_ordered_slots(nwin, chunk, 0u, slots, epoch, lds, &cnt->pad[0]);
+    uint32_t o = R.slot;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if ((win >> j) & 1u) W.from_store(o++, S, e0 + j);
+    if (chunk == nchunks - 1 && threadIdx.x == 255) cnt->n_work = R.end;
+  }
+}
+
+// k_async_file with the filed particles behind the store's end in ascending working-set slot.  The base of the append is the
+// device's cnt->size (the host knows an upper bound while an earlier advance's appends are pending): chunk 0 — nobody else —
+// reads it and folds it into what it publishes, every later chunk gets it with the sum of its predecessors, and the last chunk —
+// nobody else — writes the new cursor, which it can only know after chunk 0 has read the old one.
+template <class Work>
+__global__ __launch_bounds__(256) void k_async_file_ordered(float idx, uint32_t n, Work W, const uint8_t *__restrict__ tbl, int all_to_pool,
+                                                            int nbx, int nby, int nbz, uint32_t cap, typename Work::Store S,
+                                                            unsigned long long *__restrict__ slots, uint32_t epoch, AsyncCounters *cnt) {
+  __shared__ uint32_t lds[8];
+  const uint32_t nchunks = (n + 1023u) / 1024u;
+  uint32_t round = 0;
+  while (true) {
+    const uint32_t chunk = next_chunk(round);
+    if (chunk >= nchunks) return;
+    const uint32_t i0 = chunk * 1024u + threadIdx.x * 4u;
+    uint32_t tag[4], nfiled = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t i = i0 + j;
+      tag[j] = AS_FREE;
+      if (i >= n || W.id(i) < 0) continue;  // deleted by the substep (clear_boundary_particles): not filed back, as in the reference
+      float x[3];
+      W.pos(i, x);
+      const uint32_t b = async_block_of<Work::Store::D>(idx, x, nbx, nby, nbz);
+      if (b == INVALID) continue;
+      const uint8_t act = all_to_pool ? (uint8_t)AT_DEST_POOL : tbl[b];
+      if (!(act & (AT_DEST_POOL | AT_DEST_BACKUP))) continue;
+      tag[j] = (act & AT_DEST_POOL) ? b : (b | AS_BACKUP);
+      nfiled++;
+    }
+    const uint32_t base = chunk == 0u ? cnt->size : 0u;
+    const OrderedSlots R = async_ordered_slots(nfiled, chunk, base, slots, epoch, lds, &cnt->pad[0]);
+    uint32_t e = R.slot;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (tag[j] == AS_FREE) continue;
+      if (e < cap) {  // (the host sized the store for the whole working set: cannot happen)
+        W.to_store(i0 + j, S, e);
+        S.tag[e] = tag[j];
+      }
+      e++;
+    }
+    if (threadIdx.x == 255) {
+      atomicAdd(&cnt->n_append, min(R.end, cap) - min(R.begin, cap));  // (an integer sum: the same whatever the order)
+      if (chunk == nchunks - 1) cnt->size = min(R.end, cap);
+    }
+  }
+}
+
+// k_async_load with the view in store order
+template <class Work>
+__global__ __launch_bounds__(256) void k_async_load_ordered(uint32_t size, typename Work::Store S, Work W, uint32_t *__restrict__ blk_of,
+                                                            unsigned long long *__restrict__ slots, uint32_t epoch, AsyncCounters *cnt) {
+  __shared__ uint32_t lds[8];
+  const uint32_t nchunks = (size + 1023u) / 1024u;
+  uint32_t round = 0;
+  while (true) {
+    const uint32_t chunk = next_chunk(round);
+    if (chunk >= nchunks) return;
+    const uint32_t e0 = chunk * 1024u + threadIdx.x * 4u;
+    uint32_t t[4], npool = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      t[j] = (e0 + j < size) ? S.tag[e0 + j] : AS_FREE;
+      if (t[j] & AS_BACKUP) t[j] = AS_FREE;  // (AS_FREE has the bit too: what stays is a pool container)
+      npool += t[j] != AS_FREE;
+    }
+    const OrderedSlots R = async_ordered_slots(npool, chunk, 0u, slots, epoch, lds, &cnt->pad[0]);
+    uint32_t s = R.slot;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (t[j] == AS_FREE) continue;
+      W.from_store(s, S, e0 + j);
+      blk_of[s] = t[j];
+      s++;
+    }
+    if (chunk == nchunks - 1 && threadIdx.x == 255) cnt->n_work = R.end;
+  }
+}
+
+// k_async_export / k_async_export2 with the rows in store order
+template <class Store>
+__global__ __launch_bounds__(256) void k_async_export_ordered(uint32_t size, Store S, float *__restrict__ out, uint32_t *__restrict__ blk,
+                                                              unsigned long long *__restrict__ slots, uint32_t epoch, AsyncCounters *cnt) {
+  __shared__ uint32_t lds[8];
+  const uint32_t nchunks = (size + 1023u) / 1024u;
+  uint32_t round = 0;
+  while (true) {
+    const uint32_t chunk = next_chunk(round);
+    if (chunk >= nchunks) return;
+    const uint32_t e0 = chunk * 1024u + threadIdx.x * 4u;
+    uint32_t t[4], npool = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      t[j] = (e0 + j < size) ? S.tag[e0 + j] : AS_FREE;
+      if (t[j] & AS_BACKUP) t[j] = AS_FREE;
+      npool += t[j] != AS_FREE;
+    }
+    const OrderedSlots R = async_ordered_slots(npool, chunk, 0u, slots, epoch, lds, &cnt->pad[0]);
+    uint32_t o = R.slot;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (t[j] == AS_FREE) continue;
+      S.row(e0 + j, out + (size_t)o * Store::ROW);
+      blk[o] = t[j];
+      o++;
+    }
+    if (chunk == nchunks - 1 && threadIdx.x == 255) cnt->n_work = R.end;
   }
 }
 

@@ -322,6 +322,8 @@ struct AsyncResident : AsyncSched {
   PinnedBuf<uint32_t> h_tab;
   size_t h_tab_cap = 0;
   AsyncStore store;
+  int32_t forms[4] = {-1, -1, -1, -1};  // {gather, file, load, export} of the latest launch: 0 by arrival, 1 ordered (mpmhip_async_forms)
+  uint32_t test_wgs = 0;                // TEST KNOB (env MPMHIP_ASYNC_WGS, results valid): workgroups of every asynchronous launch at most; 0 = off
 };
 
 struct mpmhip_ctx {
@@ -796,7 +798,9 @@ int mpmhip_create(const mpmhip_config *cfg, mpmhip_ctx **out) {
   {
 #define MPM_CT_ALL(K) (const void *)K<16, false>, (const void *)K<32, false>, (const void *)K<64, false>, (const void *)K<16, true>, (const void *)K<32, true>, (const void *)K<64, true>
     const void *scans[] = {(const void *)k_sort_front, (const void *)k_block_table, MPM_CT_ALL(k_cell_table), MPM_CT_ALL(k_cell_table_plain),
-                           (const void *)k_async_compact<Store3>};
+                           (const void *)k_async_compact<Store3>, (const void *)k_async_gather_ordered<Work3>,
+                           (const void *)k_async_file_ordered<Work3>, (const void *)k_async_load_ordered<Work3>,
+                           (const void *)k_async_export_ordered<Store3>};
 #undef MPM_CT_ALL
     for (const void *k : scans) {
       int per_cu = 0;
