@@ -104,8 +104,29 @@ class RigidConfig2D(C.Structure):
                 ("scripted_rotation", SCRIPT_FN), ("rotation_user", C.c_void_p)]
 
 
+class GroupParams(C.Structure):
+    """mirror of a row of the group table (csrc/group_params.h: GroupParams), as the snapshot blobs hold it"""
+    _fields_ = [("p", C.c_float * NPARAM), ("type", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
+# mirrors of the headers of the three snapshot blobs (csrc/snapshot_blob.h); the group table follows each
+class SnapHeader(C.Structure):
+    """3D, synchronous ("MPMHIP01")"""
+    _fields_ = [("magic", C.c_char * 8), ("abi", C.c_uint32), ("n_groups", C.c_uint32), ("n_slots", C.c_int64), ("substeps", C.c_int64),
+                ("next_pid", C.c_int32), ("b_stale", C.c_int32), ("store_b", C.c_int32), ("res", C.c_int32 * 3), ("t", C.c_float),
+                ("request_t", C.c_float), ("dx", C.c_float), ("dt", C.c_float), ("n_dead", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SnapAsync(C.Structure):
+    """3D, asynchronous ("MPMASYNC")"""
+    _fields_ = [("magic", C.c_char * 8), ("abi", C.c_uint32), ("n_groups", C.c_uint32), ("res", C.c_int32 * 3), ("nb", C.c_int32 * 3),
+                ("dx", C.c_float), ("unit_delta_t", C.c_float), ("nblk", C.c_int64), ("containers", C.c_int64), ("current_t_int", C.c_int64),
+                ("min_delta_t_int", C.c_int64), ("max_delta_t_int", C.c_int64), ("update_counter", C.c_int64), ("step_counter", C.c_int64),
+                ("next_pid", C.c_int32), ("pad", C.c_int32), ("request_t", C.c_float), ("current_t", C.c_float)]
+
+
 class Snap2DHeader(C.Structure):
-    """mirror of the header of a 2D snapshot blob (csrc/frame2d_api.h: Snap2D) — only its size and the first fields are used"""
+    """2D ("MPM2DSNP"; Snap2D in the header)"""
     _fields_ = [("magic", C.c_char * 8), ("abi", C.c_uint32), ("n_groups", C.c_uint32), ("res", C.c_int32 * 2), ("next_pid", C.c_int32),
                 ("n_bodies", C.c_int32), ("n_joints", C.c_int32), ("has_async", C.c_int32), ("n", C.c_int64), ("dx", C.c_float),
                 ("base_dt", C.c_float), ("t", C.c_float), ("request_t", C.c_float), ("n_dead", C.c_uint32), ("n_ranked", C.c_uint32),

@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .mpm import MPMError, Simulation3D
+from .mpm import MPMError, Simulation3D, read_snapshot, snapshot_groups
 from .mpm2d import Simulation2D
 
 _LP = C.POINTER(C.c_int64)
@@ -196,15 +196,10 @@ class AsyncSimulation3D(Simulation3D):
 
     def load_snapshot(self, path):
         """into a simulation initialised with the same grid and unit_delta_t; replaces all particles and groups"""
-        raw = np.fromfile(path, np.uint8)
-        self.frame = int(raw[:8].view(np.int64)[0])
-        blob = np.ascontiguousarray(raw[8:])
-        n_groups = int(blob[12:16].view(np.uint32)[0])
+        (self.frame,), blob, h = read_snapshot(path, _lib.SnapAsync)
         self._ensure_ctx()
         self._check(self._L.mpmhip_async_snapshot_load(self._ctx, blob.ctypes.data_as(C.c_void_p), len(blob)))
-        off = 8 + 4 + 4 + 24 + 8 + 7 * 8 + 8 + 8  # sizeof(SnapAsync)
-        rows = blob[off:off + 80 * n_groups].view(np.float32).reshape(n_groups, 20)
-        self._groups = [(int(r[16:17].view(np.int32)[0]), r[:16].copy()) for r in rows]
+        self._groups = snapshot_groups(blob, h)
         self._n_added = max(self._n_added, self.get_num_pool_particles())
 
 

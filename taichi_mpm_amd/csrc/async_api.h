@@ -558,126 +558,6 @@ int mpmhip_async_load_pools(mpmhip_ctx *c) {
   return MPMHIP_OK;
 }
 
-// ---- snapshots of the asynchronous stepper (the reference serialises every pool and the block table: TC_IO of
-// particle_pool_tmp / backup_pool_tmp / blocks, src/async/async_mpm.h:120-172).  Blob: header, group table, the per-block
-// integers, the store's live containers (compacted: tags, ids, g, w).  Loaded into a ctx of the same grid on which
-// mpmhip_async_begin has run with the same unit_delta_t; level set and configuration come from the scene, as for the
-// synchronous snapshots.
-struct SnapAsync {
-  char magic[8];  // "MPMASYNC"
-  uint32_t abi, n_groups;
-  int32_t res[3], nb[3];
-  float dx, unit_delta_t;
-  int64_t nblk, containers, current_t_int, min_delta_t_int, max_delta_t_int, update_counter, step_counter;
-  int32_t next_pid, pad;
-  float request_t, current_t;
-};
-static size_t async_snapshot_bytes(const mpmhip_ctx *c, size_t containers) {
-  return sizeof(SnapAsync) + sizeof(GroupParams) * c->groups.size() + sizeof(int64_t) * 6 * c->async.continuous.size() +
-         containers * (sizeof(uint32_t) + sizeof(int32_t) + 2 * 4 * sizeof(float4));
-}
-int64_t mpmhip_async_snapshot_size(mpmhip_ctx *c) {
-  if (!c || !c->async.resident) return MPMHIP_EINVAL;
-  if (int rc = as_pool_particles(c)) return rc;
-  if (int rc = as_settle(c)) return rc;
-  if (int rc = as_compact(c)) return rc;  // the store holds exactly its live containers afterwards
-  return (int64_t)async_snapshot_bytes(c, c->async.store.size);
-}
-int mpmhip_async_snapshot_save(mpmhip_ctx *c, void *dst, size_t cap) {
-  if (!c || !dst) return MPMHIP_EINVAL;
-  auto &A = c->async;
-  auto &S = A.store;
-  if (!A.resident) return fail(c, MPMHIP_EINVAL, "mpmhip_async_begin first");
-  const int64_t need = mpmhip_async_snapshot_size(c);
-  if (need < 0) return (int)need;
-  if (cap < (size_t)need) return fail(c, MPMHIP_ECAPACITY, "snapshot buffer too small: %zu < %lld", cap, (long long)need);
-  SnapAsync h;
-  memset(&h, 0, sizeof h);
-  memcpy(h.magic, "MPMASYNC", 8);
-  h.abi = MPMHIP_ABI_VERSION; h.n_groups = (uint32_t)c->groups.size();
-  for (int k = 0; k < 3; k++) { h.res[k] = c->P.res[k]; h.nb[k] = A.nb[k]; }
-  h.dx = c->P.dx; h.unit_delta_t = A.cfg.unit_delta_t;
-  h.nblk = (int64_t)A.continuous.size(); h.containers = S.size;
-  h.current_t_int = A.current_t_int; h.min_delta_t_int = A.min_delta_t_int; h.max_delta_t_int = A.max_delta_t_int;
-  h.update_counter = A.update_counter; h.step_counter = A.step_counter; h.next_pid = c->next_pid;
-  h.request_t = A.request_t; h.current_t = A.current_t;
-  char *p = (char *)dst;
-  memcpy(p, &h, sizeof h); p += sizeof h;
-  memcpy(p, c->groups.data(), sizeof(GroupParams) * c->groups.size()); p += sizeof(GroupParams) * c->groups.size();
-  const size_t nb = sizeof(int64_t) * (size_t)h.nblk;
-  for (const std::vector<int64_t> *v : {&A.continuous, &A.strength, &A.cfl, &A.particle_t, &A.backup_t, &A.local_min}) { memcpy(p, v->data(), nb); p += nb; }
-  HIPCHK(c, S.save(p, S.size));
-  c->host_particle_bytes += (int64_t)S.size * 136;
-  return MPMHIP_OK;
-}
-int mpmhip_async_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
-  if (!c || !src || size < sizeof(SnapAsync)) return MPMHIP_EINVAL;
-  auto &A = c->async;
-  auto &S = A.store;
-  if (!A.resident) return fail(c, MPMHIP_EINVAL, "mpmhip_async_begin first");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  SnapAsync h;
-  memcpy(&h, src, sizeof h);
-  if (memcmp(h.magic, "MPMASYNC", 8) != 0 || h.abi != MPMHIP_ABI_VERSION) return fail(c, MPMHIP_EINVAL, "not an asynchronous-stepper snapshot of this ABI version");
-  for (int k = 0; k < 3; k++)
-    if (h.res[k] != c->P.res[k] || h.nb[k] != A.nb[k]) return fail(c, MPMHIP_EINVAL, "snapshot is of a %dx%dx%d grid", h.res[0], h.res[1], h.res[2]);
-  if (h.dx != c->P.dx || h.unit_delta_t != A.cfg.unit_delta_t) return fail(c, MPMHIP_EINVAL, "snapshot has delta_x = %g, unit_delta_t = %g", h.dx, h.unit_delta_t);
-  if ((int)h.n_groups > c->groups_cap || h.nblk != (int64_t)A.continuous.size() || h.containers < 0) return fail(c, MPMHIP_EINVAL, "snapshot header inconsistent with this ctx");
-  if (h.n_groups < 0) return fail(c, MPMHIP_EINVAL, "snapshot header inconsistent with this ctx");
-  if ((uint64_t)h.containers > size / 136) return fail(c, MPMHIP_EINVAL, "snapshot size mismatch");  // (bounded before it is multiplied)
-  if (size != sizeof(SnapAsync) + sizeof(GroupParams) * (size_t)h.n_groups + sizeof(int64_t) * 6 * (size_t)h.nblk +
-                  (size_t)h.containers * (sizeof(uint32_t) + sizeof(int32_t) + 2 * 4 * sizeof(float4)))
-    return fail(c, MPMHIP_EINVAL, "snapshot size mismatch");
-  const char *containers = (const char *)src + sizeof h + sizeof(GroupParams) * h.n_groups + 6 * sizeof(int64_t) * (size_t)h.nblk;
-  {  // the container arrays index the block table (tag), the block order and the per-id bids (id) on the device: a truncated
-     // or foreign blob must not get that far
-    const size_t n = (size_t)h.containers;
-    const char *q = containers;
-    const uint32_t *tags = reinterpret_cast<const uint32_t *>(q);
-    const int32_t *ids = reinterpret_cast<const int32_t *>(q + sizeof(uint32_t) * n);
-    if (h.next_pid < 0) return fail(c, MPMHIP_EINVAL, "snapshot header inconsistent with this ctx (next id %d)", h.next_pid);
-    // the scheduler's limits (first of the six block tables): powers of two in [1, 2^31], or update_dt_limits cannot use them
-    if (!AsyncSched::limits_are_sane((const char *)src + sizeof h + sizeof(GroupParams) * h.n_groups, (size_t)h.nblk))
-      return fail(c, MPMHIP_EINVAL, "snapshot block table holds a time-step limit that is not a power of two in [1, 2^31]");
-    const char *recg = q + (sizeof(uint32_t) + sizeof(int32_t)) * n;  // RecG per container: the group id at byte 52
-    for (size_t i = 0; i < n; i++) {
-      uint32_t tg; int32_t id;
-      memcpy(&tg, tags + i, 4); memcpy(&id, ids + i, 4);
-      if (tg == AS_FREE) continue;
-      uint32_t gid;
-      memcpy(&gid, recg + 64 * i + 52, 4);
-      if (gid >= (uint32_t)h.n_groups) return fail(c, MPMHIP_EINVAL, "snapshot container %zu names group %u of %d", i, gid, h.n_groups);
-      if ((int64_t)(tg & ~AS_BACKUP) >= h.nblk) return fail(c, MPMHIP_EINVAL, "snapshot container %zu names block %u of %lld", i, tg & ~AS_BACKUP, (long long)h.nblk);
-      if (id < 0 || id >= h.next_pid) return fail(c, MPMHIP_EINVAL, "snapshot container %zu has id %d outside [0, %d)", i, id, h.next_pid);
-    }
-  }
-  const char *p = (const char *)src + sizeof h;
-  {  // (nothing of the ctx is touched before the whole blob has been checked)
-    std::vector<GroupParams> gs((size_t)h.n_groups);
-    memcpy(gs.data(), p, sizeof(GroupParams) * h.n_groups); p += sizeof(GroupParams) * h.n_groups;
-    for (const GroupParams &g : gs)
-      if (g.type < MPMHIP_VISCO || g.type > MPMHIP_ELASTIC) return fail(c, MPMHIP_EINVAL, "snapshot holds an unknown material id %d", g.type);
-    c->groups.swap(gs);
-  }
-  if (h.n_groups) HIPCHK(c, hipMemcpy(c->d_groups, c->groups.data(), sizeof(GroupParams) * h.n_groups, hipMemcpyHostToDevice));
-  const size_t nb = sizeof(int64_t) * (size_t)h.nblk;
-  for (std::vector<int64_t> *v : {&A.continuous, &A.strength, &A.cfl, &A.particle_t, &A.backup_t, &A.local_min}) { memcpy(v->data(), p, nb); p += nb; }
-  const size_t n = (size_t)h.containers;
-  S.size = S.size_ub = S.live = 0;
-  if (int rc = as_store_reserve(c, (uint32_t)n + 1024)) return rc;
-  HIPCHK(c, S.load(containers, n));
-  c->host_particle_bytes += (int64_t)n * 136;
-  A.current_t_int = h.current_t_int; A.min_delta_t_int = h.min_delta_t_int; A.max_delta_t_int = h.max_delta_t_int;
-  A.update_counter = h.update_counter; A.step_counter = h.step_counter;
-  A.request_t = h.request_t; A.current_t = h.current_t;
-  A.limits_version++;  // (the neighbour lists are rebuilt from the loaded limits at the next update)
-  c->next_pid = h.next_pid;
-  c->t = A.current_t;
-  // (the one drop that leaves n_dead alone: a count left by the last working set stays until the next advance zeroes it)
-  return drop_records(c, DEAD_KEEP);
-}
-
 // ------------------------------------------------------------------------------------------------ the 2D entry points
 // AsyncMPM<2>::initialize (src/async/async_mpm.cpp:13-55) on top of mpmhip2d_create
 int mpmhip2d_async_begin(mpmhip2d_ctx *m, const mpmhip_async_config *cfg) {

@@ -83,6 +83,7 @@
 #include "record_state.h"
 #include "launch_plan.h"
 #include "sdf_lattice.h"
+#include "snapshot_blob.h"
 #include "mpm_common.h"
 #include "k_sort.h"
 #include "k_particles.h"
@@ -292,18 +293,19 @@ struct AsyncStore : AsyncStoreCount {
     std::swap(tag, tag2);
     for (int l = 0; l < n_lanes; l++) std::swap(lane[l].a, lane[l].b);
   }
-  // the first n containers <-> a host image: the tags, then lane after lane (the container part of both snapshot formats)
-  hipError_t save(char *dst, size_t n) const {
-    hipError_t e = n ? hipMemcpy(dst, tag, sizeof(uint32_t) * n, hipMemcpyDeviceToHost) : hipSuccess;
-    dst += sizeof(uint32_t) * n;
-    for (int l = 0; l < n_lanes && e == hipSuccess && n; dst += lane[l].bytes * n, l++) e = hipMemcpy(dst, lane[l].a, lane[l].bytes * n, hipMemcpyDeviceToHost);
+  // the containers of a snapshot blob <-> the store, section by section (snapshot_blob.h: LayoutStore — the tags, then lane after lane)
+  hipError_t save(char *blob, const snap::LayoutStore &L) const {
+    if (!fits(L) || L.tags.len > sizeof(uint32_t) * (size_t)size) return hipErrorInvalidValue;
+    hipError_t e = L.tags.len ? hipMemcpy(blob + L.tags.off, tag, L.tags.len, hipMemcpyDeviceToHost) : hipSuccess;
+    for (int l = 0; l < n_lanes && e == hipSuccess && L.lane[l].len; l++) e = hipMemcpy(blob + L.lane[l].off, lane[l].a, L.lane[l].len, hipMemcpyDeviceToHost);
     return e;
   }
-  hipError_t load(const char *src, size_t n) {  // (into a store reserved for at least n: the store then holds exactly these, all counted live)
+  hipError_t load(const char *blob, const snap::LayoutStore &L) {  // (into a store reserved for them: it then holds exactly these, all counted live)
+    const size_t n = L.tags.len / sizeof(uint32_t);
+    if (!fits(L) || n > cap) return hipErrorInvalidValue;
     hipError_t e = hipMemset(tag, 0xFF, sizeof(uint32_t) * (size_t)cap);
-    if (e == hipSuccess && n) e = hipMemcpy(tag, src, sizeof(uint32_t) * n, hipMemcpyHostToDevice);
-    src += sizeof(uint32_t) * n;
-    for (int l = 0; l < n_lanes && e == hipSuccess && n; src += lane[l].bytes * n, l++) e = hipMemcpy(lane[l].a, src, lane[l].bytes * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(tag, blob + L.tags.off, L.tags.len, hipMemcpyHostToDevice);
+    for (int l = 0; l < n_lanes && e == hipSuccess && n; l++) e = hipMemcpy(lane[l].a, blob + L.lane[l].off, L.lane[l].len, hipMemcpyHostToDevice);
     AsyncCounters z;
     memset(&z, 0, sizeof z);
     z.size = (uint32_t)n;
@@ -311,6 +313,11 @@ struct AsyncStore : AsyncStoreCount {
     size = size_ub = live = (uint32_t)n;
     pending_counters = false; view = false;
     return e;
+  }
+  bool fits(const snap::LayoutStore &L) const {  // the layout's lanes are this store's, for one number of containers
+    bool ok = L.n_lanes == n_lanes;
+    for (int l = 0; l < n_lanes && ok; l++) ok = L.lane[l].len == lane[l].bytes * (L.tags.len / sizeof(uint32_t));
+    return ok;
   }
 };
 // what both ctx types keep for the asynchronous stepper: the block scheduler (async_sched.h), the reduction table of
@@ -1784,167 +1791,6 @@ int mpmhip_upload_grid(mpmhip_ctx *c, const float *src) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(c->dense, src, nodes * sizeof(float4), hipMemcpyHostToDevice));
   return do_grid(c, 2);
-}
-
-// ------------------------------------------------------------------------------------------------ snapshots
-// Whole-state save / load (reference: TC_IO serialization of MPM<dim> + ParticleAllocator, src/mpm.h:38-54,134-169,
-// general_action "save"/"load" src/mpm.cpp:940-960).  The blob holds the raw records — including the P2G affine
-// matrices — so a restart continues exactly where the run stopped (up to the in-cell summation order).
-struct SnapHeader {
-  char magic[8];  // "MPMHIP01"
-  uint32_t abi, n_groups;
-  int64_t n_slots, substeps;
-  int32_t next_pid, b_stale, store_b, res[3];
-  float t, request_t, dx, dt;
-  uint32_t n_dead, pad;
-};
-
-// scenes with rigid bodies append the bodies' records (pose, velocities, mass properties) and the joints: meshes, boundary
-// particles and scripts come from the scene again (the script adds the same bodies before it loads), like the level set
-struct SnapRigid {
-  char magic[8];  // "MPMRIGID"
-  uint32_t n_bodies, n_joints, sizeof_body, sizeof_joint;
-};
-// ... and, behind the joints, the settings of the rigid-rigid collision pass (a blob that ends before it keeps the ctx's own)
-struct SnapRigidCollide {
-  char magic[8];  // "MPMRRCOL"
-  int32_t on, iterations, position_iterations;
-  float penalty;
-};
-static size_t snapshot_rigid_bytes(const mpmhip_ctx *c) {
-  return rigid_active(c) ? sizeof(SnapRigid) + sizeof(RigidBodyDev) * c->rigid.bodies.size() + sizeof(JointDev) * c->rigid.joints.size() +
-                               sizeof(SnapRigidCollide)
-                         : 0;
-}
-static size_t snapshot_bytes(const mpmhip_ctx *c) {
-  return sizeof(SnapHeader) + sizeof(GroupParams) * c->groups.size() +
-         (size_t)c->n_slots * (sizeof(RecG) + sizeof(RecP) + sizeof(float) * BW) + snapshot_rigid_bytes(c);
-}
-
-int64_t mpmhip_snapshot_size(mpmhip_ctx *c) { return c ? (int64_t)snapshot_bytes(c) : MPMHIP_EINVAL; }
-
-int mpmhip_snapshot_save(mpmhip_ctx *c, void *dst, size_t cap) {
-  if (!c || !dst) return MPMHIP_EINVAL;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->in_substep) return fail(c, MPMHIP_EINVAL, "snapshot inside a substep");
-  if (cap < snapshot_bytes(c)) return fail(c, MPMHIP_ECAPACITY, "snapshot buffer too small: %zu < %zu", cap, snapshot_bytes(c));
-  Counters hc;
-  int rc = read_counters(c, hc);
-  if (rc) return rc;
-  if (!c->rec.affine_valid()) {  // make A current first (fresh uploads), so that the blob is self-consistent
-    hipLaunchKernelGGL(k_affine, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, c->rg, c->rp, c->rb, c->d_groups);
-    c->rec.affine_rebuilt();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  SnapHeader h;
-  memset(&h, 0, sizeof h);
-  memcpy(h.magic, "MPMHIP01", 8);
-  h.abi = MPMHIP_ABI_VERSION; h.n_groups = (uint32_t)c->groups.size();
-  h.n_slots = c->n_slots; h.substeps = c->substeps; h.next_pid = c->next_pid;
-  h.b_stale = c->rec.b_stale(); h.store_b = c->P.store_b;
-  for (int k = 0; k < 3; k++) h.res[k] = c->P.res[k];
-  h.t = c->t; h.request_t = c->request_t; h.dx = c->P.dx; h.dt = c->P.dt; h.n_dead = hc.n_dead;
-  char *p = (char *)dst;
-  memcpy(p, &h, sizeof h); p += sizeof h;
-  memcpy(p, c->groups.data(), sizeof(GroupParams) * c->groups.size()); p += sizeof(GroupParams) * c->groups.size();
-  const size_t n = (size_t)c->n_slots;
-  if (n) {
-    HIPCHK(c, hipMemcpy(p, c->rg, sizeof(RecG) * n, hipMemcpyDeviceToHost)); p += sizeof(RecG) * n;
-    HIPCHK(c, hipMemcpy(p, c->rp, sizeof(RecP) * n, hipMemcpyDeviceToHost)); p += sizeof(RecP) * n;
-    HIPCHK(c, hipMemcpy(p, c->rb, sizeof(float) * BW * n, hipMemcpyDeviceToHost)); p += sizeof(float) * BW * n;
-  }
-  if (rigid_active(c)) {
-    SnapRigid r;
-    memcpy(r.magic, "MPMRIGID", 8);
-    r.n_bodies = (uint32_t)c->rigid.bodies.size(); r.n_joints = (uint32_t)c->rigid.joints.size();
-    r.sizeof_body = (uint32_t)sizeof(RigidBodyDev); r.sizeof_joint = (uint32_t)sizeof(JointDev);
-    memcpy(p, &r, sizeof r); p += sizeof r;
-    HIPCHK(c, hipMemcpy(p, c->rigid.d_rb, sizeof(RigidBodyDev) * r.n_bodies, hipMemcpyDeviceToHost)); p += sizeof(RigidBodyDev) * r.n_bodies;
-    if (r.n_joints) memcpy(p, c->rigid.joints.data(), sizeof(JointDev) * r.n_joints);
-    p += sizeof(JointDev) * r.n_joints;
-    SnapRigidCollide k;
-    memcpy(k.magic, "MPMRRCOL", 8);
-    k.on = c->rigid.col.on; k.iterations = c->rigid.col.iterations; k.position_iterations = c->rigid.col.position_iterations;
-    k.penalty = c->rigid.col.penalty;
-    memcpy(p, &k, sizeof k);
-  }
-  return MPMHIP_OK;
-}
-
-int mpmhip_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
-  if (!c || !src || size < sizeof(SnapHeader)) return MPMHIP_EINVAL;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  SnapHeader h;
-  memcpy(&h, src, sizeof h);
-  if (memcmp(h.magic, "MPMHIP01", 8) != 0 || h.abi != MPMHIP_ABI_VERSION) return fail(c, MPMHIP_EINVAL, "not a libmpmhip snapshot of this ABI version");
-  for (int k = 0; k < 3; k++)
-    if (h.res[k] != c->P.res[k]) return fail(c, MPMHIP_EINVAL, "snapshot is of a %dx%dx%d grid", h.res[0], h.res[1], h.res[2]);
-  if (h.dx != c->P.dx) return fail(c, MPMHIP_EINVAL, "snapshot has delta_x = %g, the ctx %g", h.dx, c->P.dx);
-  // the stored P2G affine matrices carry the factor -4 inv_dx dt of the saving ctx (and apic_b is recovered with it)
-  if (h.dt != c->P.dt) return fail(c, MPMHIP_EINVAL, "snapshot has base_delta_t = %g, the ctx %g", h.dt, c->P.dt);
-  if (h.n_slots < 0 || h.n_slots > c->cap) return fail(c, MPMHIP_ECAPACITY, "snapshot holds %lld particle slots, capacity is %lld", (long long)h.n_slots, (long long)c->cap);
-  if ((int)h.n_groups > c->groups_cap) return fail(c, MPMHIP_ECAPACITY, "snapshot holds %u groups", h.n_groups);
-  const size_t n = (size_t)h.n_slots;
-  const size_t base = sizeof h + sizeof(GroupParams) * h.n_groups + n * (sizeof(RecG) + sizeof(RecP) + sizeof(float) * BW);
-  if (size < base) return fail(c, MPMHIP_EINVAL, "snapshot is truncated");
-  // the rigid section: the scene must have added the same bodies (meshes, scripts) before it loads
-  SnapRigid sr;
-  memset(&sr, 0, sizeof sr);
-  const bool has_rigid = size >= base + sizeof sr && memcmp((const char *)src + base, "MPMRIGID", 8) == 0;
-  if (has_rigid) {
-    memcpy(&sr, (const char *)src + base, sizeof sr);
-    if (sr.sizeof_body != sizeof(RigidBodyDev) || sr.sizeof_joint != sizeof(JointDev) || sr.n_joints > (uint32_t)MAX_JOINTS ||
-        size < base + sizeof sr + (size_t)sr.sizeof_body * sr.n_bodies + (size_t)sr.sizeof_joint * sr.n_joints)
-      return fail(c, MPMHIP_EINVAL, "snapshot: the rigid-body section is damaged or of another build");
-    if (!rigid_active(c) || c->rigid.bodies.size() != sr.n_bodies)
-      return fail(c, MPMHIP_EINVAL, "snapshot holds %u rigid bodies: add the scene's bodies (same meshes, same order) before loading",
-                  sr.n_bodies - 1);
-  } else if (rigid_active(c)) {
-    return fail(c, MPMHIP_EINVAL, "snapshot holds no rigid bodies, this simulation has %d", (int)c->rigid.bodies.size() - 1);
-  }
-  {
-    const RecG *srg = reinterpret_cast<const RecG *>((const char *)src + sizeof h + sizeof(GroupParams) * h.n_groups);
-    for (size_t i = 0; i < n; i++)
-      if (srg[i].pid >= 0 && srg[i].gid >= h.n_groups)
-        return fail(c, MPMHIP_EINVAL, "snapshot record %zu refers to group %u of %u", i, srg[i].gid, h.n_groups);
-  }
-  const char *p = (const char *)src + sizeof h;
-  c->groups.assign((const GroupParams *)p, (const GroupParams *)p + h.n_groups); p += sizeof(GroupParams) * h.n_groups;
-  if (h.n_groups) HIPCHK(c, hipMemcpy(c->d_groups, c->groups.data(), sizeof(GroupParams) * h.n_groups, hipMemcpyHostToDevice));
-  if (n) {
-    HIPCHK(c, hipMemcpy(c->rg, p, sizeof(RecG) * n, hipMemcpyHostToDevice)); p += sizeof(RecG) * n;
-    HIPCHK(c, hipMemcpy(c->rp, p, sizeof(RecP) * n, hipMemcpyHostToDevice)); p += sizeof(RecP) * n;
-    HIPCHK(c, hipMemcpy(c->rb, p, sizeof(float) * BW * n, hipMemcpyHostToDevice));
-  }
-  set_slots(c, h.n_slots);
-  c->substeps = h.substeps; c->next_pid = h.next_pid;
-  c->t = h.t; c->request_t = h.request_t;
-  // A travels in the records; apic_b is current only if the saving ctx kept it up to date
-  // (keys and block flags are rebuilt by the next sort)
-  if (int rc = clear_block_flags(c, c->rec.snapshot_loaded(h.b_stale != 0 || h.store_b == 0))) return rc;
-  if (c->P.store_b && c->rec.b_stale()) {  // this ctx keeps apic_b: rebuild it from A once
-    int rc = ensure_b_current(c);
-    if (rc) return rc;
-  }
-  Counters hc;
-  memset(&hc, 0, sizeof hc);
-  hc.n_dead = h.n_dead;
-  HIPCHK(c, hipMemcpy(c->cnt, &hc, sizeof hc, hipMemcpyHostToDevice));
-  if (has_rigid) {  // poses, velocities and joints of the saved run; colours travel in the records, the CDF is rebuilt every substep
-    const char *q = (const char *)src + base + sizeof sr;
-    HIPCHK(c, hipMemcpy(c->rigid.d_rb, q, sizeof(RigidBodyDev) * sr.n_bodies, hipMemcpyHostToDevice)); q += sizeof(RigidBodyDev) * sr.n_bodies;
-    c->rigid.joints.assign((const JointDev *)q, (const JointDev *)q + sr.n_joints);
-    if (sr.n_joints) HIPCHK(c, hipMemcpy(c->rigid.d_joints, c->rigid.joints.data(), sizeof(JointDev) * sr.n_joints, hipMemcpyHostToDevice));
-    q += sizeof(JointDev) * sr.n_joints;
-    SnapRigidCollide k;
-    if ((size_t)(q - (const char *)src) + sizeof k <= size && memcmp(q, "MPMRRCOL", 8) == 0) {
-      memcpy(&k, q, sizeof k);
-      c->rigid.col.on = k.on != 0; c->rigid.col.iterations = k.iterations; c->rigid.col.position_iterations = k.position_iterations != 0;
-      c->rigid.col.penalty = k.penalty;
-    }
-  }
-  return MPMHIP_OK;
 }
 
 int mpmhip_delete_particles_inside_level_set(mpmhip_ctx *c, int64_t *deleted) {
@@ -3742,6 +3588,26 @@ int mpmhip2d_download_grid(mpmhip2d_ctx *m, float *grid) {  // (v.x, v.y, m) per
 
 #include "async_api.h"
 #include "frame2d_api.h"
+// snapshot_blob.h: its copies of the device-side record geometry
+static_assert(snap::RECG_BYTES == sizeof(RecG) && snap::RECP_BYTES == sizeof(RecP) && snap::BROW_BYTES == sizeof(float) * BW, "snapshot_blob.h: records");
+static_assert(snap::RECG_GID == offsetof(RecG, gid) && snap::RECG_PID == offsetof(RecG, pid), "snapshot_blob.h: ids of a RecG");
+static_assert(snap::REC2_BYTES == 4 * sizeof(float4) && snap::REC2_GID == 3 * sizeof(float4) + offsetof(float4, y) &&
+              snap::REC2_ID == 3 * sizeof(float4) + offsetof(float4, z), "snapshot_blob.h: the 2D container record (k_async.h: Store2)");
+static_assert(snap::TAG_BYTES == sizeof(uint32_t) && snap::ID_BYTES == sizeof(int32_t) && snap::W3_BYTES == 4 * sizeof(float4) &&
+              snap::CONTAINER3_BYTES == sizeof(uint32_t) + sizeof(int32_t) + 2 * 4 * sizeof(float4) &&
+              snap::CONTAINER2_BYTES == sizeof(uint32_t) + 4 * sizeof(float4), "snapshot_blob.h: containers (k_async.h: Store3, Store2)");
+static_assert(snap::TAG_FREE == AS_FREE && snap::TAG_BACKUP == AS_BACKUP, "snapshot_blob.h: container tags");
+static_assert(snap::BODY3_BYTES == sizeof(RigidBodyDev) && snap::JOINT3_BYTES == sizeof(JointDev) && snap::JOINT3_OBJ0 == offsetof(JointDev, obj0) &&
+              snap::JOINT3_OBJ1 == offsetof(JointDev, obj1) && snap::MAX_JOINTS3 == (uint32_t)MAX_JOINTS, "snapshot_blob.h: 3D bodies and joints");
+static_assert(snap::BODY2_BYTES == sizeof(mpm2d::Rigid2) && snap::JOINTS2_BYTES == sizeof(mpm2d::Joints2) && snap::JOINTS2_N == offsetof(mpm2d::Joints2, n) &&
+              snap::JOINTS2_FIRST == offsetof(mpm2d::Joints2, j) && snap::JOINT2_BYTES == sizeof(mpm2d::Joint2) &&
+              snap::JOINT2_OBJ0 == offsetof(mpm2d::Joint2, obj0) && snap::JOINT2_OBJ1 == offsetof(mpm2d::Joint2, obj1) &&
+              snap::MAX_JOINTS2 == mpm2d::MAX_JOINTS2, "snapshot_blob.h: 2D bodies and joints");
+static_assert(snap::P2_BYTES[snap::P2_X] == 2 * sizeof(float) && snap::P2_BYTES[snap::P2_V] == 2 * sizeof(float) && snap::P2_BYTES[snap::P2_F] == 4 * sizeof(float) &&
+              snap::P2_BYTES[snap::P2_B] == 4 * sizeof(float) && snap::P2_BYTES[snap::P2_AUX] == sizeof(float) && snap::P2_BYTES[snap::P2_GID] == sizeof(int32_t) &&
+              snap::P2_BYTES[snap::P2_PID] == sizeof(int32_t) && snap::RANK_BYTES == sizeof(uint32_t) && snap::COLOUR_BYTES == sizeof(uint32_t) &&
+              snap::TABLE_WORD == sizeof(int64_t), "snapshot_blob.h: the 2D object's arrays, the block tables");
+#include "snapshot_api.h"
 #include "seed_api.h"
 
 // ------------------------------------------------------------------------------------------------ debug math

@@ -34,6 +34,23 @@ class MPMError(RuntimeError):
     pass
 
 
+def read_snapshot(path, header, frame_words=1):
+    """(the Python layer's int64 words in front, the library's blob, the blob's header) of a snapshot file; `header` is the ctypes
+    mirror of the blob's header (_lib.SnapHeader, SnapAsync, Snap2DHeader)"""
+    raw = np.fromfile(path, np.uint8)
+    lead = 8 * frame_words
+    if len(raw) < lead + C.sizeof(header):
+        raise MPMError("%s is no snapshot: %d bytes, less than the header of one" % (path, len(raw)))
+    blob = np.ascontiguousarray(raw[lead:])
+    return [int(v) for v in raw[:lead].view(np.int64)], blob, header.from_buffer_copy(blob[:C.sizeof(header)].tobytes())
+
+
+def snapshot_groups(blob, h):
+    """[(material id, parameter row)] of the group table behind header `h` of a blob the library has accepted"""
+    rows = (_lib.GroupParams * int(h.n_groups)).from_buffer_copy(blob[C.sizeof(h):C.sizeof(h) + C.sizeof(_lib.GroupParams) * int(h.n_groups)].tobytes())
+    return [(int(g.type), np.array(g.p[:], np.float32)) for g in rows]
+
+
 class LevelSet:
     """Analytic stand-in for taichi's LevelSet (scripts/async/async_mpm.py:129-137 `create_levelset`): a union of
     solids — half-spaces, spheres, axis-aligned cuboids — with one friction code (README.md:326-330).  Method names
@@ -1217,11 +1234,8 @@ class Simulation3D:
     def load_snapshot(self, path):
         """into a simulation initialised with the same grid; level set and config come from the script, as in the
         reference.  Replaces all particles and groups."""
-        raw = np.fromfile(path, np.uint8)
-        self.frame = int(raw[:8].view(np.int64)[0])
-        blob = np.ascontiguousarray(raw[8:])
-        n_groups = int(blob[12:16].view(np.uint32)[0])
-        n_slots = int(blob[16:24].view(np.int64)[0])
+        (self.frame,), blob, h = read_snapshot(path, _lib.SnapHeader)
+        n_slots = int(h.n_slots)
         if self._ctx is None:
             self._staged, self._groups = [], []
             self._create(max(self.max_particles, int(n_slots * 1.25) + 1024))
@@ -1230,8 +1244,7 @@ class Simulation3D:
             self._check(self._L.mpmhip_reserve(self._ctx, cap))
             self._capacity = cap
         self._check(self._L.mpmhip_snapshot_load(self._ctx, blob.ctypes.data_as(C.c_void_p), len(blob)))
-        rows = blob[80:80 + 80 * n_groups].view(np.float32).reshape(n_groups, 20)
-        self._groups = [(int(r[16:17].view(np.int32)[0]), r[:16].copy()) for r in rows]
+        self._groups = snapshot_groups(blob, h)
         self._n_added = n_slots
         self._time_offset = 0.0
 

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from .materials import MATERIAL_IDS, group_params, initial_aux
-from .mpm import DynamicLevelSet, LevelSet, MPMError, _SampledField, check_unsupported_keys, eval_shapes
+from .mpm import DynamicLevelSet, LevelSet, MPMError, _SampledField, check_unsupported_keys, eval_shapes, read_snapshot, snapshot_groups
 
 
 def lattice_square(lower, higher, dx):
@@ -626,17 +626,12 @@ class Simulation2D:
     def load_snapshot(self, path):
         """into a simulation set up with the same grid and scene (level set, configuration, the rigid bodies — added before the
         load — come from the script, as in the reference); replaces all particles and groups"""
-        raw = np.fromfile(path, np.uint8)
-        self.frame, self.frame_count = (int(v) for v in raw[:16].view(np.int64))
-        blob = np.ascontiguousarray(raw[16:])
+        (self.frame, self.frame_count), blob, h = read_snapshot(path, _lib.Snap2DHeader, frame_words=2)
         self._ensure_ctx()
         self._check(self._L.mpmhip2d_snapshot_load(self._ctx, blob.ctypes.data_as(C.c_void_p), len(blob)))
-        n_groups = int(blob[12:16].view(np.uint32)[0])
-        off = C.sizeof(_lib.Snap2DHeader)
-        rows = blob[off:off + 80 * n_groups].view(np.float32).reshape(n_groups, 20)
-        self._groups = [(int(r[16:17].view(np.int32)[0]), r[:16].copy()) for r in rows]
+        self._groups = snapshot_groups(blob, h)
         self._staged = []
-        self._n_added = max(self._n_added, int(blob[40:48].view(np.int64)[0]))
+        self._n_added = max(self._n_added, int(h.n))
 
     def write_partio(self, file_name):
         """MPM<2>::write_partio (src/visualize.cpp:17-100): the same Houdini .bgeo as the 3D simulation writes, z = 0

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from taichi_mpm_amd import _lib
 from tests.common import lattice_cube, make_state
 
 pytestmark = pytest.mark.gpu
@@ -286,7 +287,7 @@ def test_a_snapshot_with_a_container_array_out_of_range_is_refused_before_anythi
     a.save_snapshot(path)
     raw = np.fromfile(path, np.uint8)
     n_cont = a.get_num_pool_particles()
-    hdr = 8 + (8 + 4 + 4 + 24 + 8 + 7 * 8 + 8 + 8) + 80 * 1 + 6 * 8 * int(np.prod(a.nb))  # frame word, SnapAsync, one group, six block arrays
+    hdr = 8 + C.sizeof(_lib.SnapAsync) + 80 * 1 + 6 * 8 * int(np.prod(a.nb))  # frame word, SnapAsync, one group, six block arrays
     for what, word in (("tag", 0x7FFFFFF0), ("id", -5)):
         bad = raw.copy()
         if what == "tag":
