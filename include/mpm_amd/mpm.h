@@ -319,6 +319,11 @@ class MPM<3> {
     d.phi = phi.data();
     return seed(config, d);
   }
+  // ... the region as an expression (include/mpmhip.h, "Region expressions": leaves, a postfix program, the phi arrays)
+  int64_t add_particles_region(const Config &config, const mpmhip_region_desc &region) {
+    mpmhip_seed_desc d{};
+    return seed(config, d, &region);
+  }
 
   // --- time stepping
   virtual void step(real dt) { check(mpmhip_step(ctx_, dt), ctx_); frame++; }  // src/mpm.cpp:428-439 (dt < 0: one substep)
@@ -450,7 +455,7 @@ class MPM<3> {
   }
   // the group of a seeding call (vol = dx^3 / ppc, mass = vol * density: create_particle(coord, maximum, config), :134-135) and
   // the call; a ctx that is too small is grown once and the call repeated
-  int64_t seed(const Config &config, mpmhip_seed_desc &d) {
+  int64_t seed(const Config &config, mpmhip_seed_desc &d, const mpmhip_region_desc *region = nullptr) {
     const std::string type = config.get("type", "");
     const float ppc = config.get("ppc", config.get("maximum", 8.0f));
     if (!(ppc > 0)) throw std::runtime_error("add_particles_region: ppc must be > 0");
@@ -467,10 +472,11 @@ class MPM<3> {
     d.source_delta_t = config.get("delta_t", 1e-3f);  // src/mpm.cpp:224
     d.initial_dg = t.initial_dg;
     int64_t n = 0;
-    int rc = mpmhip_seed_particles(ctx_, gid, &d, &n);
+    auto call = [&] { return region ? mpmhip_seed_particles_region(ctx_, gid, &d, region, &n) : mpmhip_seed_particles(ctx_, gid, &d, &n); };
+    int rc = call();
     if (rc == MPMHIP_ECAPACITY) {
       check(mpmhip_reserve(ctx_, (mpmhip_num_slots(ctx_) + n) * 5 / 4), ctx_);
-      rc = mpmhip_seed_particles(ctx_, gid, &d, &n);
+      rc = call();
     }
     check(rc, ctx_);
     return n;

@@ -176,6 +176,11 @@ class MPM<2> {
     d.phi = phi.data();
     return seed(config, d);
   }
+  // ... the region as an expression (include/mpmhip.h, "Region expressions"), read in the plane
+  int64_t add_particles_region(const Config &config, const mpmhip_region_desc &region) {
+    mpmhip2d_seed_desc d{};
+    return seed(config, d, &region);
+  }
 
   // --- add_particles(type='rigid') in 2D: the outline as n_segments x 4 floats (two end points each); keys as in 3D
   virtual std::string add_rigid_body(const Config &config, int64_t n_segments, const float *segments, ScriptPosition scripted_position = nullptr,
@@ -320,7 +325,7 @@ class MPM<2> {
   }
   // the group of a seeding call (vol = dx^2 / ppc, mass = vol * density: create_particle(coord, maximum, config), :134) and the
   // call; a ctx that is too small is grown once and the call repeated
-  int64_t seed(const Config &config, mpmhip2d_seed_desc &d) {
+  int64_t seed(const Config &config, mpmhip2d_seed_desc &d, const mpmhip_region_desc *region = nullptr) {
     const std::string type = config.get("type", "");
     const float ppc = config.get("ppc", config.get("maximum", 4.0f));
     if (!(ppc > 0)) throw std::runtime_error("add_particles_region: ppc must be > 0");
@@ -336,10 +341,11 @@ class MPM<2> {
     d.source_delta_t = config.get("delta_t", 1e-3f);  // src/mpm.cpp:224
     d.initial_dg = t.initial_dg;
     int64_t n = 0;
-    int rc = mpmhip2d_seed_particles(ctx_, gid, &d, &n);
+    auto call = [&] { return region ? mpmhip2d_seed_particles_region(ctx_, gid, &d, region, &n) : mpmhip2d_seed_particles(ctx_, gid, &d, &n); };
+    int rc = call();
     if (rc == MPMHIP_ECAPACITY) {
       check(mpmhip2d_reserve(ctx_, (mpmhip2d_num_slots(ctx_) + n) * 3 / 2), ctx_);
-      rc = mpmhip2d_seed_particles(ctx_, gid, &d, &n);
+      rc = call();
     }
     check(rc, ctx_);
     return n;

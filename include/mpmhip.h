@@ -820,6 +820,82 @@ int mpmhip2d_debug_plasticity(mpmhip2d_ctx *ctx, int32_t material, const float p
 int mpmhip2d_debug_svd2(mpmhip2d_ctx *ctx, int64_t n, const float *F /* [n][4] */, float *cu /* [n] */, float *su /* [n] */,
                         float *S /* [n][2] */);
 
+/* Region expressions — CSG combinations of level sets, evaluated per point on the device (csrc/k_region.h: RegionExpr<D>; checks:
+ * csrc/region_program.h; host side: csrc/region_api.h).  A region is "where phi < 0", phi in GRID units (what the samplers and the
+ * shape evaluator return).  One description serves D = 3 and D = 2.
+ *   leaf       one mpmhip_shape (kind 0; for D = 2 read in the plane exactly as mpmhip2d_seed_particles reads it: z ignored, a box
+ *              unbounded along z) or one sampled field (kind 1): a lattice plus `field`, an index into the description's list of phi
+ *              arrays (several leaves may share one array; D = 2 uses res[0..1], origin[0..1]).  A sampled leaf evaluated OUTSIDE
+ *              its lattice has no level set there: phi = +inf.  That point is not in the leaf — and it IS in the leaf's complement.
+ *   placement  (placed != 0) maps the leaf's own space to the world: world = t + s R (local - p), R a rotation (D = 3: rot is the
+ *              3x3 matrix, row-major, checked for orthonormality to 1e-4 per entry of R^T R and for a positive determinant — a
+ *              reflection is refused; D = 2: rot[0] is the angle in radians
+ *              and R = [c -s; s c] with c = (float)cos((double)angle), s = (float)sin((double)angle)), s = scale > 0, t = translate,
+ *              p = pivot.  The device goes the other way in fp32, in this order, nothing contracted:
+ *                d = x - t;   y_k = ((R_0k d_0 + R_1k d_1) + R_2k d_2)   (D = 2: R_0k d_0 + R_1k d_1);
+ *                local_k = fl(fl(y_k * fl(1 / s)) + p_k);   phi = fl(phi_leaf(local) * s).
+ *              A leaf without a placement takes no arithmetic on x: the bits of the plain region.
+ *   band       (banded != 0) with lo < hi in grid units: phi' = max(lo - phi, phi - hi), the shell lo < phi < hi.
+ *   operators  on phi, exact in fp32: UNION = min, INTERSECT = max, NEG = -phi.  A difference a - b is INTERSECT(a, NEG b).
+ *   program    postfix: PUSH leaf, UNION, INTERSECT, NEG.  At most MPMHIP_REGION_MAX_LEAVES leaves, _MAX_FIELDS arrays, _MAX_OPS
+ *              operations, stack depth _MAX_DEPTH (enough for every tree over 8 leaves when the deeper operand of each operator is
+ *              evaluated first).
+ * The host validates before anything is uploaded or launched; MPMHIP_EINVAL with a message for: an empty program, more than the
+ * limits, an unknown opcode, leaf kind or shape type, a shape leaf the level set would refuse (sphere radius <= 0, cuboid without
+ * lo < hi on an axis that is read) or with a non-finite parameter, a leaf or field index out of range, stack underflow, depth above 4, a stack that
+ * does not end at exactly one value, a rotation that is not finite, not orthonormal or a reflection, scale <= 0 or not finite, a non-finite
+ * translation or pivot, lo >= hi or a NaN band edge, a lattice mpmhip_set_levelset_sdf would refuse, a missing phi array.
+ *
+ * mpmhip_seed_particles_region / mpmhip2d_seed_particles_region: mpmhip_seed_particles with the region given as an expression.  `how`
+ * supplies ppc, velocity, source, source_delta_t, initial_dg; its own region fields must be empty (n_shapes == 0, sdf == NULL).
+ * Everything else — the candidate arithmetic, the order, refusals, ECAPACITY, ids — is the existing call's; the phi arrays are
+ * uploaded back to back into the ctx's seed buffer.  source = 1 keeps a candidate inside the region whose advected position is not.
+ * mpmhip_region_sample: no ctx; the device's phi (grid units, +-inf possible) at n host-given points [n][dim] for a grid of cell
+ * size delta_x, on `device`.  mpmhip_region_bake: no ctx; phi at the nodes of `lattice` (node index i sits at
+ * fl(origin + fl(i * spacing)) per axis, as the mesh voxeliser defines it; dim = 2: res[0..1], origin[0..1]) in WORLD units,
+ * fl(phi * delta_x) clamped to +-band (band > 0 finite, world units: the +inf of a sampled leaf cannot reach the array), C order —
+ * an array mpmhip_set_levelset_sdf / mpmhip2d_set_levelset_sdf installs as a composite boundary.  min / max composition keeps the
+ * zero set and the sign exact and |grad phi| <= 1; away from the surface it is a lower bound of the true distance, not the distance —
+ * what the analytic level set already does with several shapes.  Errors of the two: mpmhip_last_error(NULL). */
+#define MPMHIP_REGION_MAX_LEAVES 8
+#define MPMHIP_REGION_MAX_FIELDS 4
+#define MPMHIP_REGION_MAX_OPS 24
+#define MPMHIP_REGION_MAX_DEPTH 4
+enum { MPMHIP_REGION_PUSH = 0, MPMHIP_REGION_UNION = 1, MPMHIP_REGION_INTERSECT = 2, MPMHIP_REGION_NEG = 3 };
+typedef struct {
+  int32_t kind;   /* 0 shape, 1 sampled field */
+  int32_t field;  /* kind 1: index into fields */
+  mpmhip_shape shape;
+  int32_t placed, banded;
+  float rot[9];
+  float scale, translate[3], pivot[3];
+  float lo, hi;
+} mpmhip_region_leaf;
+typedef struct {
+  int32_t op, leaf; /* leaf: of a PUSH */
+} mpmhip_region_op;
+typedef struct {
+  int32_t res[3];
+  float origin[3];
+  float spacing;
+  int32_t reserved;
+  const float *phi; /* host array, world units, C order */
+} mpmhip_region_field;
+typedef struct {
+  int32_t n_leaves, n_ops, n_fields, reserved;
+  mpmhip_region_leaf leaves[MPMHIP_REGION_MAX_LEAVES];
+  mpmhip_region_op ops[MPMHIP_REGION_MAX_OPS];
+  mpmhip_region_field fields[MPMHIP_REGION_MAX_FIELDS];
+} mpmhip_region_desc;
+int mpmhip_seed_particles_region(mpmhip_ctx *ctx, int32_t group, const mpmhip_seed_desc *how, const mpmhip_region_desc *region,
+                                 int64_t *n_added);
+int mpmhip2d_seed_particles_region(mpmhip2d_ctx *ctx, int32_t group, const mpmhip2d_seed_desc *how, const mpmhip_region_desc *region,
+                                   int64_t *n_added);
+int mpmhip_region_sample(int32_t device, int32_t dim, float delta_x, const mpmhip_region_desc *region, int64_t n,
+                         const float *pos /* [n][dim] */, float *phi_out /* [n] */);
+int mpmhip_region_bake(int32_t device, int32_t dim, float delta_x, const mpmhip_region_desc *region, const mpmhip_sdf_desc *lattice,
+                       float band, float *phi_out);
+
 /* frame output of the 2D simulation — replaces MPM<2>::write_partio (src/visualize.cpp:17-100): the same .bgeo as the 3D
  * entry points above (z = 0), boundary particles of rigid bodies as rows of type 1; with a resident asynchronous stepper the rows
  * are the containers of every particle pool with their block's limits (src/async/async_visualize.cpp:17-26,86-96) */

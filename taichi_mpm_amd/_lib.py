@@ -65,6 +65,34 @@ class SeedDesc2D(C.Structure):
                 ("initial_dg", C.c_float), ("reserved", C.c_int32)]
 
 
+REGION_MAX_LEAVES, REGION_MAX_FIELDS, REGION_MAX_OPS, REGION_MAX_DEPTH = 8, 4, 24, 4
+REGION_PUSH, REGION_UNION, REGION_INTERSECT, REGION_NEG = 0, 1, 2, 3
+
+
+class RegionLeaf(C.Structure):
+    """mirror of mpmhip_region_leaf"""
+    _fields_ = [("kind", C.c_int32), ("field", C.c_int32), ("shape", Shape), ("placed", C.c_int32), ("banded", C.c_int32),
+                ("rot", C.c_float * 9), ("scale", C.c_float), ("translate", C.c_float * 3), ("pivot", C.c_float * 3),
+                ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class RegionOp(C.Structure):
+    """mirror of mpmhip_region_op"""
+    _fields_ = [("op", C.c_int32), ("leaf", C.c_int32)]
+
+
+class RegionField(C.Structure):
+    """mirror of mpmhip_region_field"""
+    _fields_ = [("res", C.c_int32 * 3), ("origin", C.c_float * 3), ("spacing", C.c_float), ("reserved", C.c_int32),
+                ("phi", C.POINTER(C.c_float))]
+
+
+class RegionDesc(C.Structure):
+    """mirror of mpmhip_region_desc"""
+    _fields_ = [("n_leaves", C.c_int32), ("n_ops", C.c_int32), ("n_fields", C.c_int32), ("reserved", C.c_int32),
+                ("leaves", RegionLeaf * REGION_MAX_LEAVES), ("ops", RegionOp * REGION_MAX_OPS), ("fields", RegionField * REGION_MAX_FIELDS)]
+
+
 class AsyncConfig(C.Structure):
     """mirror of mpmhip_async_config"""
     _fields_ = [("unit_delta_t", C.c_float), ("max_units", C.c_int64), ("cfl_dt_mul", C.c_float), ("strength_dt_mul", C.c_float),
@@ -215,7 +243,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip2d_async_begin", "mpmhip2d_async_pool_particles", "mpmhip2d_async_step", "mpmhip2d_async_load_pools", "mpmhip2d_async_view_blocks", "mpmhip2d_async_download_pools", "mpmhip2d_async_forms",
             "mpmhip2d_async_state", "mpmhip2d_async_current_time", "mpmhip2d_async_table", "mpmhip2d_bgeo_size", "mpmhip2d_bgeo_encode", "mpmhip2d_write_bgeo", "mpmhip2d_snapshot_size", "mpmhip2d_snapshot_save", "mpmhip2d_snapshot_load",
             "mpmhip2d_set_rigid_coupling", "mpmhip2d_set_rigid_levelset_collision", "mpmhip2d_add_articulation", "mpmhip2d_set_articulation_iterations", "mpmhip2d_add_rigid_body", "mpmhip2d_rigid_get_state", "mpmhip2d_rigid_get_samples", "mpmhip2d_cdf_phase",
-            "mpmhip2d_download_cdf", "mpmhip2d_download_colours", "mpmhip2d_poisson_tile", "mpmhip2d_seed_particles", "mpmhip2d_reserve", "mpmhip2d_num_slots", "mpmhip2d_capacity", "mpmhip2d_set_levelset_sdf", "mpmhip2d_delete_particles_inside_level_set", "mpmhip2d_debug_levelset_sample", "mpmhip2d_debug_force", "mpmhip2d_debug_plasticity", "mpmhip2d_debug_svd2",
+            "mpmhip2d_download_cdf", "mpmhip2d_download_colours", "mpmhip2d_poisson_tile", "mpmhip2d_seed_particles", "mpmhip2d_reserve", "mpmhip_seed_particles_region", "mpmhip2d_seed_particles_region", "mpmhip_region_sample", "mpmhip_region_bake", "mpmhip2d_num_slots", "mpmhip2d_capacity", "mpmhip2d_set_levelset_sdf", "mpmhip2d_delete_particles_inside_level_set", "mpmhip2d_debug_levelset_sample", "mpmhip2d_debug_force", "mpmhip2d_debug_plasticity", "mpmhip2d_debug_svd2",
             "mpmhip_set_rigid_coupling", "mpmhip_add_rigid_body", "mpmhip_num_rigid_bodies", "mpmhip_rigid_get_state", "mpmhip_rigid_set_velocity",
             "mpmhip_rigid_get_samples", "mpmhip_rigid_get_mesh", "mpmhip2d_rigid_get_mesh", "mpmhip_rasterize_rigid_boundary", "mpmhip_gather_cdf", "mpmhip_advect_rigid_bodies", "mpmhip_download_cdf",
             "mpmhip_add_articulation", "mpmhip_num_articulations", "mpmhip_set_articulation_iterations", "mpmhip_articulate",
@@ -401,6 +429,10 @@ def load():
     L.mpmhip2d_poisson_tile.argtypes = [fp, C.c_int64]
     L.mpmhip2d_poisson_tile.restype = C.c_int64
     L.mpmhip2d_seed_particles.argtypes = [vp, C.c_int32, P(SeedDesc2D), P(C.c_int64)]
+    L.mpmhip_seed_particles_region.argtypes = [vp, C.c_int32, P(SeedDesc), P(RegionDesc), P(C.c_int64)]
+    L.mpmhip2d_seed_particles_region.argtypes = [vp, C.c_int32, P(SeedDesc2D), P(RegionDesc), P(C.c_int64)]
+    L.mpmhip_region_sample.argtypes = [C.c_int32, C.c_int32, C.c_float, P(RegionDesc), C.c_int64, fp, fp]
+    L.mpmhip_region_bake.argtypes = [C.c_int32, C.c_int32, C.c_float, P(RegionDesc), P(SdfDesc), C.c_float, fp]
     L.mpmhip2d_reserve.argtypes = [vp, C.c_int64]
     L.mpmhip2d_num_slots.argtypes = [vp]
     L.mpmhip2d_num_slots.restype = C.c_int64

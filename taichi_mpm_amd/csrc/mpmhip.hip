@@ -3,6 +3,7 @@
 //   mpm_common.h (records, parameter blocks, Morton keys)   mpm_math.h (3x3 math, constitutive models, level set)
 //   k_sort.h  k_p2g.h  k_grid.h  k_g2p.h  k_tiling.h  k_particles.h  k_debug.h
 //   k_seed.h (particle seeding from the periodic Poisson-disk tiles, poisson_tile.h; both dimensions)
+//   k_region.h (region expressions: CSG programs over level-set leaves, the region of a seeding call or sampled on a lattice)
 //   k_bgeo.h (.bgeo frame rows)   k_mpm88.h (the 2D dense-grid demo, its own small object)
 // host_mem.h: DevBuf / PinnedBuf, the owners of every device and pinned array of the objects below (a new array needs a field and
 // its allocation, nothing else); what a kernel takes by value keeps raw pointers into them.
@@ -83,6 +84,7 @@
 #include "record_state.h"
 #include "launch_plan.h"
 #include "sdf_lattice.h"
+#include "region_program.h"
 #include "snapshot_blob.h"
 #include "mpm_common.h"
 #include "k_sort.h"
@@ -99,6 +101,7 @@
 #include "k_sdf.h"
 #include "k_mesh_sdf.h"
 #include "k_seed.h"
+#include "k_region.h"
 #include "poisson_tile.h"
 #include "k_bgeo.h"
 #include "k_mpm88.h"
@@ -3609,6 +3612,7 @@ static_assert(snap::P2_BYTES[snap::P2_X] == 2 * sizeof(float) && snap::P2_BYTES[
               snap::TABLE_WORD == sizeof(int64_t), "snapshot_blob.h: the 2D object's arrays, the block tables");
 #include "snapshot_api.h"
 #include "seed_api.h"
+#include "region_api.h"
 
 // ------------------------------------------------------------------------------------------------ debug math
 int mpmhip_debug_cond_census(mpmhip_ctx *c, double out[MPMHIP_COND_CENSUS_WORDS]) {

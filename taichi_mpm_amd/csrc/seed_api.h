@@ -188,8 +188,10 @@ double seed_get_ready(const typename A::Ctx *c, float ppc, const int *box, SeedP
   return n_rep;
 }
 
-template <class A>
-int seed_particles(typename A::Ctx *c, int32_t group, const typename A::Desc *d, int64_t *n_added) {
+// `make(R)` builds the region the kernels take (a plain one: seed_region; an expression: region_api.h) once the call's other
+// arguments have passed; the kernels are instantiated for its type
+template <class A, class Region, class Make>
+int seed_particles_as(typename A::Ctx *c, int32_t group, const typename A::Desc *d, int64_t *n_added, Make make) {
   SEED_NO_CONTRACT
   constexpr int D = A::D;
   if (!c) return MPMHIP_EINVAL;
@@ -204,8 +206,8 @@ int seed_particles(typename A::Ctx *c, int32_t group, const typename A::Desc *d,
   if (d->source && !std::isfinite(d->source_delta_t)) SEED_FAIL("seed_particles: source_delta_t is not finite");
   SEED_HIP(hipSetDevice(c->device));
   SEED_HIP(hipStreamSynchronize(c->stream));
-  typename A::Region R;
-  if (int rc = seed_region<A>(c, d, R)) return rc;
+  Region R;
+  if (int rc = make(R)) return rc;
   SeedWork &W = c->seed;
   if (!W.d_tile) {
     const std::vector<float> &t = poisson_tile::tile<D>();
@@ -225,7 +227,7 @@ int seed_particles(typename A::Ctx *c, int32_t group, const typename A::Desc *d,
   for (int k = 0; k < D; k++) { box[k] = 0x7fffffff; box[D + k] = -1; }
   SEED_HIP(hipMemcpyAsync(W.d_box, box, sizeof box, hipMemcpyHostToDevice, c->stream));
   const uint32_t bounds_wgs = (uint32_t)std::min<uint64_t>((cells + SEED_WG - 1) / SEED_WG, A::max_bounds_wgs(c));
-  hipLaunchKernelGGL((k_seed_bounds<D, typename A::Region>), dim3(bounds_wgs), dim3(SEED_WG), 0, c->stream, R, S, W.d_box.get());
+  hipLaunchKernelGGL((k_seed_bounds<D, Region>), dim3(bounds_wgs), dim3(SEED_WG), 0, c->stream, R, S, W.d_box.get());
   SEED_LAUNCHED("seed_bounds");
   SEED_HIP(hipMemcpyAsync(box, W.d_box, sizeof box, hipMemcpyDeviceToHost, c->stream));
   SEED_HIP(hipStreamSynchronize(c->stream));
@@ -262,7 +264,7 @@ int seed_particles(typename A::Ctx *c, int32_t group, const typename A::Desc *d,
     W.wg_cap = wgs;
   }
   uint32_t *d_total = reinterpret_cast<uint32_t *>(W.d_box + 2 * D);
-  hipLaunchKernelGGL((k_seed_count<D, typename A::Region>), dim3(wgs), dim3(SEED_WG), 0, c->stream, R, S, (const float *)W.d_tile,
+  hipLaunchKernelGGL((k_seed_count<D, Region>), dim3(wgs), dim3(SEED_WG), 0, c->stream, R, S, (const float *)W.d_tile,
                      W.d_words.get(), W.d_totals.get());
   hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(SEED_SCAN_WG), 0, c->stream, W.d_totals.get(), wgs, d_total);
   SEED_LAUNCHED("seed_count");
@@ -279,6 +281,11 @@ int seed_particles(typename A::Ctx *c, int32_t group, const typename A::Desc *d,
     SEED_LAUNCHED("seed_write");
     return (int)MPMHIP_OK;
   });
+}
+
+template <class A>
+int seed_particles(typename A::Ctx *c, int32_t group, const typename A::Desc *d, int64_t *n_added) {
+  return seed_particles_as<A, typename A::Region>(c, group, d, n_added, [&](typename A::Region &R) { return seed_region<A>(c, d, R); });
 }
 
 #undef SEED_FAIL

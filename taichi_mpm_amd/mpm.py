@@ -315,6 +315,292 @@ class MeshLevelSet:
         return MeshLevelSet(moved, self.res, self.origin, self.spacing, self.band, self.friction)
 
 
+class _Placement:
+    """world = t + s R (local - p), float64.  R is kept as a 3x3 matrix (a rotation in the plane: about z); `angle` is the plane's
+    angle in radians while every factor was one (what the 2D description carries), `dim` 2 or 3 once a rotation has fixed it."""
+
+    def __init__(self, R, s, t, p, angle, dim):
+        self.R, self.s, self.t, self.p, self.angle, self.dim = R, s, t, p, angle, dim
+
+    @staticmethod
+    def parse(rotate, scale, translate, about):
+        dim, angle = None, 0.0
+        if rotate is None:
+            R = np.eye(3)
+        elif np.isscalar(rotate):  # the plane: degrees
+            dim, angle = 2, float(np.radians(float(rotate)))
+            c, s_ = np.cos(angle), np.sin(angle)
+            R = np.array([[c, -s_, 0.0], [s_, c, 0.0], [0.0, 0.0, 1.0]])
+        elif len(rotate) == 2 and np.ndim(rotate[0]) == 1:  # (axis, degrees)
+            dim, angle = 3, None
+            a = np.asarray(rotate[0], np.float64)
+            if a.shape != (3,) or not np.all(np.isfinite(a)) or not np.linalg.norm(a) > 0:
+                raise MPMError("Region.placed: the rotation axis must be a finite, non-zero 3-vector")
+            a = a / np.linalg.norm(a)
+            th = np.radians(float(rotate[1]))
+            K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+            R = np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)
+        else:
+            dim, angle = 3, None
+            R = np.asarray(rotate, np.float64)
+            if R.shape != (3, 3) or not np.all(np.isfinite(R)) or np.abs(R.T @ R - np.eye(3)).max() > 1e-5 or np.linalg.det(R) < 0:
+                raise MPMError("Region.placed: rotate must be an orthonormal 3x3 matrix of determinant +1 (no reflection), (axis, degrees), "
+                               "or degrees in the plane")
+        if not (np.isfinite(scale) and float(scale) > 0):
+            raise MPMError("Region.placed: scale must be a finite number > 0, got %r" % (scale,))
+
+        def vec(v, what):
+            v = np.asarray(v, np.float64).reshape(-1)
+            if len(v) not in (2, 3) or not np.all(np.isfinite(v)):
+                raise MPMError("Region.placed: %s must be 2 or 3 finite numbers" % what)
+            return np.concatenate([v, np.zeros(3 - len(v))])
+        return _Placement(R, float(scale), vec(translate, "translate"), vec(about, "about"), angle, dim)
+
+    def after(self, inner):
+        """self applied to what `inner` has placed: t2 + s2 R2 ((t1 + s1 R1 (x - p1)) - p2)"""
+        if inner is None:
+            return self
+        if self.dim and inner.dim and self.dim != inner.dim:
+            raise MPMError("Region.placed: a rotation in the plane and one in space cannot be composed")
+        angle = None if self.angle is None or inner.angle is None else self.angle + inner.angle
+        return _Placement(self.R @ inner.R, self.s * inner.s, self.t + self.s * (self.R @ (inner.t - self.p)), inner.p, angle,
+                          self.dim or inner.dim)
+
+
+class _Leaf:
+    """one shape (obj None) or one sampled object of a Region, with its placement and band"""
+
+    def __init__(self, obj, shape, place=None, band=None):
+        self.obj, self.shape, self.place, self.band = obj, shape, place, band
+
+
+class Region:
+    """A CSG expression over level sets (include/mpmhip.h, "Region expressions"): where phi < 0, phi in grid units.
+    Region(x) wraps a LevelSet (k shapes: the union of k shape leaves), a SampledLevelSet, a MeshLevelSet (voxelised once, when the
+    expression is first compiled) or a SampledLevelSet2D.  a | b union (min), a & b intersection (max), a - b difference, ~a
+    complement; .band(lo, hi) (a leaf only): the shell lo < phi < hi in grid units; .placed(...) a rotated, scaled, translated copy.
+    A sampled leaf has phi = +inf outside its lattice: such a point is not in the leaf and IS in its complement.
+    add_particles(region=<Region>) seeds it on the device; to_sampled / to_sampled2d bake it into a sampled level set (a composite
+    boundary); sample() returns the device's phi.  Limits: 8 leaves, 4 distinct arrays, 24 operations, stack depth 4."""
+
+    def __init__(self, x=None, _node=None):
+        if _node is not None:
+            self._node = _node
+            return
+        if isinstance(x, Region):
+            self._node = x._node
+        elif isinstance(x, LevelSet):
+            if not x.shapes:
+                raise MPMError("Region: the LevelSet has no shapes")
+            node = None
+            for sh in x.shapes:
+                leaf = ("leaf", _Leaf(None, (int(sh[0]), int(sh[1]), [float(v) for v in sh[2]])))
+                node = leaf if node is None else ("or", node, leaf)
+            self._node = node
+        elif isinstance(x, (MeshLevelSet, _SampledField)):
+            self._node = ("leaf", _Leaf(x, None))
+        else:
+            raise MPMError("Region takes a LevelSet, a SampledLevelSet, a MeshLevelSet or a SampledLevelSet2D, got %r" % type(x).__name__)
+
+    @staticmethod
+    def _of(x):
+        return x if isinstance(x, Region) else Region(x)
+
+    def __or__(self, o):
+        return Region(_node=("or", self._node, Region._of(o)._node))
+
+    def __and__(self, o):
+        return Region(_node=("and", self._node, Region._of(o)._node))
+
+    def __sub__(self, o):
+        return Region(_node=("and", self._node, ("not", Region._of(o)._node)))
+
+    def __invert__(self):
+        return Region(_node=self._node[1] if self._node[0] == "not" else ("not", self._node))
+
+    def band(self, lo, hi):
+        """the shell lo < phi < hi (grid units) of a leaf"""
+        if self._node[0] != "leaf":
+            raise MPMError("Region.band is defined on a leaf (one shape or one sampled field), not on a composite: band the leaves")
+        l = self._node[1]
+        if l.band is not None:
+            raise MPMError("Region.band: the leaf already has a band")
+        lo, hi = float(lo), float(hi)
+        if not lo < hi:
+            raise MPMError("Region.band needs lo < hi, got %r, %r" % (lo, hi))
+        return Region(_node=("leaf", _Leaf(l.obj, l.shape, l.place, (lo, hi))))
+
+    def placed(self, rotate=None, scale=1.0, translate=(0.0, 0.0, 0.0), about=(0.0, 0.0, 0.0)):
+        """the copy world = translate + scale * R (x - about); on a composite the placement goes down to the leaves and composes
+        with what they carry.  rotate: a 3x3 matrix or (axis, degrees) in 3D, degrees in 2D."""
+        P = _Placement.parse(rotate, scale, translate, about)
+
+        def go(n):
+            if n[0] == "leaf":
+                l = n[1]
+                band = None if l.band is None else (l.band[0] * P.s, l.band[1] * P.s)  # (the shell scales with its leaf)
+                return ("leaf", _Leaf(l.obj, l.shape, P.after(l.place), band))
+            return (n[0],) + tuple(go(c) for c in n[1:])
+        return Region(_node=go(self._node))
+
+    # ---- the postfix program
+    def postfix(self):
+        """[("push", leaf) | ("or",) | ("and",) | ("not",)] with the deeper operand of every binary operator first, and the stack
+        depth the program needs"""
+        def need(n):
+            if n[0] == "leaf":
+                return 1
+            if n[0] == "not":
+                return need(n[1])
+            a, b = need(n[1]), need(n[2])
+            return a + 1 if a == b else max(a, b)
+        out = []
+
+        def emit(n):
+            if n[0] == "leaf":
+                out.append(("push", n[1]))
+            elif n[0] == "not":
+                emit(n[1])
+                out.append(("not",))
+            else:
+                first, second = (n[1], n[2]) if need(n[1]) >= need(n[2]) else (n[2], n[1])
+                emit(first)
+                emit(second)
+                out.append((n[0],))
+        emit(self._node)
+        return out, need(self._node)
+
+    def dim(self):
+        """2 or 3 when a sampled object or a rotation fixes it, else None (shapes alone serve both)"""
+        dims = set()
+        for op in self.postfix()[0]:
+            if op[0] == "push":
+                l = op[1]
+                if l.obj is not None:
+                    dims.add(3 if isinstance(l.obj, MeshLevelSet) else l.obj._DIM)
+                if l.place is not None and l.place.dim:
+                    dims.add(l.place.dim)
+        if len(dims) > 1:
+            raise MPMError("Region: objects or rotations of the plane and of space are mixed in one expression")
+        return dims.pop() if dims else None
+
+    def compile(self, dim, delta_x, device=0):
+        """(the mpmhip_region_desc of this expression for a solver of `dim` axes and cell size delta_x, the objects its pointers
+        need alive)"""
+        own = self.dim()
+        if own is not None and own != dim:
+            raise MPMError("Region: the expression is %dD, the call is %dD" % (own, dim))
+        prog, depth = self.postfix()
+        n_leaves = sum(1 for op in prog if op[0] == "push")
+        if depth > _lib.REGION_MAX_DEPTH:  # (first: only a tree of more than 8 leaves can need it)
+            raise MPMError("Region: the expression needs stack depth %d, at most depth %d is supported" % (depth, _lib.REGION_MAX_DEPTH))
+        if n_leaves > _lib.REGION_MAX_LEAVES:
+            raise MPMError("Region: %d leaves, at most %d leaves are supported" % (n_leaves, _lib.REGION_MAX_LEAVES))
+        if len(prog) > _lib.REGION_MAX_OPS:
+            raise MPMError("Region: %d operations, at most %d operations are supported" % (len(prog), _lib.REGION_MAX_OPS))
+        d = _lib.RegionDesc()
+        keep, fields = [], {}
+        code = {"or": _lib.REGION_UNION, "and": _lib.REGION_INTERSECT, "not": _lib.REGION_NEG}
+        for i, op in enumerate(prog):
+            if op[0] != "push":
+                d.ops[i].op = code[op[0]]
+                continue
+            l, k = op[1], d.n_leaves
+            d.ops[i].op, d.ops[i].leaf = _lib.REGION_PUSH, k
+            d.n_leaves += 1
+            L = d.leaves[k]
+            if l.obj is None:
+                L.kind = 0
+                L.shape.type, L.shape.inside_out = l.shape[0], l.shape[1]
+                L.shape.p[:] = l.shape[2]
+            else:
+                obj = l.obj
+                if id(obj) not in fields and len(fields) >= _lib.REGION_MAX_FIELDS:  # (before a mesh is voxelised for nothing)
+                    raise MPMError("Region: more than %d distinct arrays, at most %d arrays are supported" % ((_lib.REGION_MAX_FIELDS,) * 2))
+                if isinstance(obj, MeshLevelSet):
+                    # voxelised once per (device, lattice, band, triangle array): an object whose res, origin, spacing, band or
+                    # triangles are replaced afterwards is voxelised again.  Vertices edited in place are not noticed.
+                    spacing = obj.spacing or float(delta_x)
+                    key = (int(device), spacing, tuple(obj.res), tuple(obj.origin), obj.band, obj.triangles.ctypes.data, obj.triangles.shape)
+                    cache = obj.__dict__.setdefault("_region_baked", {})
+                    if key not in cache:
+                        cache.clear()
+                        cache[key] = SampledLevelSet.from_mesh(obj.triangles, obj.res, obj.origin, spacing, obj.band, device=device)
+                    obj = cache[key]
+                if id(l.obj) not in fields:
+                    f = d.fields[len(fields)]
+                    f.res[:len(obj.res)] = obj.res
+                    f.origin[:len(obj.origin)] = obj.origin
+                    f.spacing = float(delta_x) if obj.spacing is None else obj.spacing
+                    f.phi = obj.phi.ctypes.data_as(C.POINTER(C.c_float))
+                    keep.append(obj.phi)
+                    fields[id(l.obj)] = len(fields)
+                L.kind, L.field = 1, fields[id(l.obj)]
+            if l.place is not None:
+                P = l.place
+                if dim == 2 and P.angle is None:
+                    raise MPMError("Region: a rotation in space cannot place a leaf of a 2D expression")
+                L.placed = 1
+                if dim == 2:
+                    L.rot[0] = P.angle
+                else:
+                    L.rot[:] = [float(v) for v in P.R.reshape(-1)]
+                L.scale = P.s
+                L.translate[:] = [float(v) for v in P.t]
+                L.pivot[:] = [float(v) for v in P.p]
+            if l.band is not None:
+                L.banded, L.lo, L.hi = 1, l.band[0], l.band[1]
+        d.n_ops, d.n_fields = len(prog), len(fields)
+        return d, keep
+
+    # ---- the ctx-free entries
+    def sample(self, points, delta_x, device=0):
+        """the device's phi (grid units; +-inf where a sampled leaf has no lattice) at points (n, 2) or (n, 3)"""
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] not in (2, 3):
+            raise MPMError("Region.sample: points must be an (n, 2) or (n, 3) array, got shape %r" % (pts.shape,))
+        d, keep = self.compile(pts.shape[1], delta_x, device)
+        out = np.empty(len(pts), np.float32)
+        fp = C.POINTER(C.c_float)
+        L = _lib.load()
+        if L.mpmhip_region_sample(int(device), pts.shape[1], float(delta_x), C.byref(d), len(pts), pts.ctypes.data_as(fp), out.ctypes.data_as(fp)) != 0:
+            raise MPMError(L.mpmhip_last_error(None).decode())
+        return out
+
+    def _bake(self, dim, res, origin, spacing, band, device, delta_x):
+        res = tuple(int(r) for r in res)
+        if len(res) != dim or min(res) < 2:
+            raise MPMError("Region.to_sampled: res must be %d numbers >= 2, got %r" % (dim, res))
+        if spacing is None or not (np.isfinite(spacing) and float(spacing) > 0):
+            raise MPMError("Region.to_sampled: spacing must be a finite number > 0, got %r" % (spacing,))
+        dx = float(spacing) if delta_x is None else float(delta_x)
+        band = 3.0 * dx + 2.0 * float(spacing) if band is None else float(band)
+        if not (np.isfinite(band) and band > 0):
+            raise MPMError("Region.to_sampled: band must be a finite number > 0 (world units), got %r" % (band,))
+        d, keep = self.compile(dim, dx, device)
+        lat = _lib.SdfDesc()
+        lat.res[:dim] = res
+        lat.origin[:dim] = [float(origin[k]) for k in range(dim)]
+        lat.spacing = float(spacing)
+        phi = np.empty(res, np.float32)
+        L = _lib.load()
+        if L.mpmhip_region_bake(int(device), dim, dx, C.byref(d), C.byref(lat), band, phi.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+            raise MPMError(L.mpmhip_last_error(None).decode())
+        return phi
+
+    def to_sampled(self, res, origin, spacing, band=None, device=0, delta_x=None, friction=-1.0):
+        """bake the expression on the device into a SampledLevelSet (world units, clamped to +-band; band in world units, None =
+        3 delta_x + 2 spacing: what the grid pass reads, include/mpmhip.h: mpmhip_mesh_to_sdf).  delta_x: the cell size the
+        expression's bands (grid units) refer to, None = spacing.  min / max composition keeps the zero set, the sign and
+        |grad phi| <= 1; away from the surface it is a lower bound of the distance."""
+        return SampledLevelSet(self._bake(3, res, origin, spacing, band, device, delta_x), tuple(float(v) for v in origin), float(spacing), friction)
+
+    def to_sampled2d(self, res, origin, spacing, band=None, device=0, delta_x=None):
+        """to_sampled in the plane -> SampledLevelSet2D; its as_boundary(friction=...) is the composite boundary"""
+        from .mpm2d import SampledLevelSet2D
+        return SampledLevelSet2D(self._bake(2, res, origin, spacing, band, device, delta_x), tuple(float(v) for v in origin), float(spacing))
+
+
 class DynamicLevelSet:
     """taichi's DynamicLevelSet as the python driver builds it every frame (scripts/async/async_mpm.py:119-127):
     `initialize(t0, t1, levelset(t0), levelset(t1))`; the two key frames are blended linearly in time on the device
@@ -659,8 +945,8 @@ class Simulation3D:
             for i, (t_, io, p) in enumerate(region.shapes):
                 d.shapes[i].type, d.shapes[i].inside_out = t_, io
                 d.shapes[i].p[:] = p
-        else:
-            raise MPMError("add_particles(region=) takes a LevelSet, a SampledLevelSet or a MeshLevelSet, got %r" % type(region).__name__)
+        elif not isinstance(region, Region):  # (an expression travels beside the description: _seed_region)
+            raise MPMError("add_particles(region=) takes a LevelSet, a SampledLevelSet or a MeshLevelSet, or a Region over them, got %r" % type(region).__name__)
         d.ppc = ppc
         d.velocity[:] = _vec3(cfg.get("initial_velocity"), (0, 0, 0))
         d.source = int(bool(cfg.get("pd_source", False)))
@@ -671,10 +957,16 @@ class Simulation3D:
     def _seed_region(self, cfg, ptype, ppc):
         """add_particles(region=...): the reference's default fill, add_particles(density_tex=...) with the periodic Poisson-disk
         tile (src/mpm.cpp:205-251), on the device (include/mpmhip.h: mpmhip_seed_particles).  region: a LevelSet (where its shapes
-        are negative), a SampledLevelSet, or a MeshLevelSet (voxelised through SampledLevelSet.from_mesh).  Keys: ppc (8),
-        initial_velocity, pd_source, delta_t (1e-3), initial_dg, density and the material keys."""
+        are negative), a SampledLevelSet, a MeshLevelSet (voxelised through SampledLevelSet.from_mesh), or a Region expression
+        over these (mpmhip_seed_particles_region).  Keys: ppc (8), initial_velocity, pd_source, delta_t (1e-3), initial_dg, density
+        and the material keys."""
         dx = self.delta_x
         d, keep = self._seed_desc(cfg, ptype, ppc)
+        if isinstance(cfg["region"], Region):
+            rd, rkeep = cfg["region"].compile(3, dx, self.device)
+            seed = lambda: self._L.mpmhip_seed_particles_region(self._ctx, gi, C.byref(d), C.byref(rd), C.byref(n))
+        else:
+            seed = lambda: self._L.mpmhip_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
         vol = dx ** 3 / ppc  # create_particle(coord, maximum, config), src/mpm.cpp:134-135
         mass = vol * float(cfg.get("density", 400.0))
         params, mat = group_params(ptype, mass, vol, **{k: v for k, v in cfg.items() if isinstance(v, (int, float))})
@@ -687,13 +979,13 @@ class Simulation3D:
             self._groups.append((mat, params))
             self._check(self._L.mpmhip_add_group(self._ctx, mat, params.ctypes.data_as(C.POINTER(C.c_float))))
         n = C.c_int64(0)
-        rc = self._L.mpmhip_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+        rc = seed()
         if rc == -4:  # MPMHIP_ECAPACITY: n is what the call needs; nothing was written
             need = int(self._L.mpmhip_num_slots(self._ctx)) + n.value
             cap = max(int(need * 1.25), self.max_particles)
             self._check(self._L.mpmhip_reserve(self._ctx, cap))
             self._capacity = cap
-            rc = self._L.mpmhip_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+            rc = seed()
         self._check(rc)
         self._n_added += n.value
         return ""

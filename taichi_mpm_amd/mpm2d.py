@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from .materials import MATERIAL_IDS, group_params, initial_aux
-from .mpm import DynamicLevelSet, LevelSet, MPMError, _SampledField, check_unsupported_keys, eval_shapes, read_snapshot, snapshot_groups
+from .mpm import DynamicLevelSet, LevelSet, MPMError, Region, _SampledField, check_unsupported_keys, eval_shapes, read_snapshot, snapshot_groups
 
 
 def lattice_square(lower, higher, dx):
@@ -303,8 +303,8 @@ class Simulation2D:
             for i, (t_, io, p) in enumerate(region.shapes):
                 d.shapes[i].type, d.shapes[i].inside_out = t_, io
                 d.shapes[i].p[:] = p
-        else:
-            raise MPMError("add_particles(region=) takes a LevelSet or a SampledLevelSet2D, got %r" % type(region).__name__)
+        elif not isinstance(region, Region):  # (an expression travels beside the description: _seed_region)
+            raise MPMError("add_particles(region=) takes a LevelSet or a SampledLevelSet2D, or a Region over them, got %r" % type(region).__name__)
         d.ppc = ppc
         v0 = cfg.get("initial_velocity", (0.0, 0.0))
         d.velocity[:] = (float(v0[0]), float(v0[1]))
@@ -316,10 +316,16 @@ class Simulation2D:
     def _seed_region(self, cfg, ptype, ppc):
         """add_particles(region=...): the reference's default fill, add_particles(density_tex=...) with the periodic Poisson-disk
         tile (src/mpm.cpp:205-251), on the device (include/mpmhip.h: mpmhip2d_seed_particles).  region: a LevelSet (where its shapes,
-        read in the plane, are negative) or a SampledLevelSet2D.  Keys: ppc (4), initial_velocity, pd_source, delta_t (1e-3),
-        initial_dg, density and the material keys."""
+        read in the plane, are negative), a SampledLevelSet2D, or a Region expression over these
+        (mpmhip2d_seed_particles_region).  Keys: ppc (4), initial_velocity, pd_source, delta_t (1e-3), initial_dg, density and the
+        material keys."""
         dx = self.delta_x
         d, keep = self._seed_desc(cfg, ptype, ppc)
+        if isinstance(cfg["region"], Region):
+            rd, rkeep = cfg["region"].compile(2, dx)  # (no mesh leaf in the plane: nothing is voxelised)
+            seed = lambda: self._L.mpmhip2d_seed_particles_region(self._ctx, gi, C.byref(d), C.byref(rd), C.byref(n))
+        else:
+            seed = lambda: self._L.mpmhip2d_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
         vol = dx ** 2 / ppc  # pow<dim>(delta_x) / maximum, src/mpm.cpp:134
         mass = vol * float(cfg.get("density", 400.0))
         params, mat = group_params(ptype, mass, vol, **{k: v for k, v in cfg.items() if isinstance(v, (int, float))})
@@ -332,12 +338,12 @@ class Simulation2D:
             self._groups.append((mat, params))
             self._check(self._L.mpmhip2d_add_group(self._ctx, mat, params.ctypes.data_as(C.POINTER(C.c_float))))
         n = C.c_int64(0)
-        rc = self._L.mpmhip2d_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+        rc = seed()
         if rc == -4:  # MPMHIP_ECAPACITY: n is what the call needs; nothing was written
             cap = max(int((int(self._L.mpmhip2d_num_slots(self._ctx)) + n.value) * 1.5), self.max_particles)
             self._check(self._L.mpmhip2d_reserve(self._ctx, cap))
             self._capacity = int(self._L.mpmhip2d_capacity(self._ctx))  # (what the library has: it may give more than it was asked for)
-            rc = self._L.mpmhip2d_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+            rc = seed()
         self._check(rc)
         self._n_added += n.value
         return ""
