@@ -287,8 +287,8 @@ int mpmhip_add_particles(mpmhip_ctx *ctx, int32_t group, int64_t n, const float 
  *   order       the survivors are appended in ascending c with creation ids next_id + rank (the reference's order).
  *   records     velocity as given, F = initial_dg * I, B = 0, aux the material default, mass from the group row.
  * *n_added = the number of new particles.  If they do not fit the ctx, nothing is written, *n_added is the number needed and the
- * call returns MPMHIP_ECAPACITY: mpmhip_reserve and call again.  MPMHIP_EINVAL with a message: inside a substep, on a tiled ctx,
- * an unknown group, ppc <= 0, a lattice mpmhip_set_levelset_sdf would refuse, more than 2^31 candidates.
+ * call returns MPMHIP_ECAPACITY: mpmhip_reserve and call again.  MPMHIP_EINVAL with a message: inside a substep, on a tiled ctx
+ * (there: mpmhip_seed_particles_brick, below the region expressions), an unknown group, ppc <= 0, a lattice mpmhip_set_levelset_sdf would refuse, more than 2^31 candidates.
  * The 2D solver has the same call: mpmhip2d_seed_particles below.  Out of scope: pd_packed, non-uniform densities, pd = False,
  * point_cloud. */
 typedef struct {
@@ -891,6 +891,48 @@ int mpmhip_seed_particles_region(mpmhip_ctx *ctx, int32_t group, const mpmhip_se
                                  int64_t *n_added);
 int mpmhip2d_seed_particles_region(mpmhip2d_ctx *ctx, int32_t group, const mpmhip2d_seed_desc *how, const mpmhip_region_desc *region,
                                    int64_t *n_added);
+/* Seeding a tiled job — every rank fills its own brick on the device (3D; the 2D solver has no tiling).
+ *
+ * mpmhip_seed_particles_brick: mpmhip_seed_particles (region == NULL: the plain region of `desc`) or mpmhip_seed_particles_region
+ * (region != NULL, and `desc` carries no region of its own) on a ctx with a partition (mpmhip_set_partition, or mpmhip_tiled_setup, which
+ * calls it); on a ctx without one: MPMHIP_EINVAL.  A COLLECTIVE BY CONVENTION: every rank of the job makes the same call with the same
+ * description, at the same ctx time and with the same next id.  No message is passed.  Every rank evaluates ALL candidates — the price of
+ * one call on one ctx — and keeps the survivors whose base cell lies in its brick:
+ *   owner      the brick that holds the base cell b[k] = (int)fl(fl(x[k] * fl(1 / dx)) - 0.5f) under the cuts of the partition: what the
+ *              migration computes, here with nothing contracted (tiled.base_cells / Partition.rank_of_cells restate it to the bit).
+ *              Should the migration's own expression round differently for a particle at an exact cell face, that particle simply
+ *              migrates at the next check.
+ *   ids        a survivor's id is next_id + (the survivors of the JOB with a smaller c): the id it gets on one ctx.
+ *   slots      it is appended behind the resident records at (the survivors of THIS brick with a smaller c): a rank's new records
+ *              ascend in id, as on one ctx.
+ *   counts     counts[0] = added on this rank, counts[1] = accepted job-wide.  On EVERY rank the next id advances by counts[1], so
+ *              the ranks stay in step.  The job-wide set, the ids and the positions are exactly those of the one-ctx calls.
+ *   capacity   MPMHIP_ECAPACITY: nothing was written on this rank, its next id has not moved, counts[0] = the particles needed
+ *              HERE.  mpmhip_reserve and repeat the call on this rank alone: the call is pure, the repeat gives the same particles.
+ * Everything else is the existing calls': the refusals (inside a substep, an unknown group, ppc, the lattice, more than 2^31 candidates),
+ * source, initial_dg, the velocity; mpmhip_host_particle_bytes does not change.
+ * On a ctx with a native plan (mpmhip_tiled_setup) the call may come between two mpmhip_tiled_advance[_group] calls — an emitter.  It
+ * marks the plan stale: the next advance begins with the planning scan of a job's first substep (one scan + table exchange on every
+ * rank), which cuts the halo boxes around the new particles; until then the clip box is widened to hold every candidate of the call.
+ * On the callback path (mpmhip_set_halo) the plan is the caller's: the call is allowed, planning again is the caller's business.
+ * mpmhip_seed_particles and mpmhip_seed_particles_region keep refusing a tiled ctx.
+ *
+ * mpmhip_seed_histogram: what the partition of such a job is cut from, on any ctx, tiled or not.  hist_a[i] = the survivors of the
+ * call whose base cell has index i along axis a (res[a] entries each, NULL allowed), *total their number, cell_bounds = lo3, hi3
+ * (exclusive) of their base cells (all 0 without survivors).  Integer counts: exact, whatever the order.  Nothing is written, no
+ * counter moves; the ctx's time, gravity and base_delta_t enter as in the seeding call (source = 1).  An empty region: MPMHIP_EINVAL
+ * "region is empty".
+ *
+ * mpmhip_set_next_id raises the creation-id counter to `id`, never lowers it, and returns the counter (>= 0; id = 0 reads it) or a
+ * negative error.  A job whose first particles came through mpmhip_upload(MPMHIP_F_ID) — which leaves each rank's counter behind
+ * its own largest id — levels its ranks' counters with it before the first collective seeding call. */
+int mpmhip_seed_particles_brick(mpmhip_ctx *ctx, int32_t group, const mpmhip_seed_desc *desc,
+                                const mpmhip_region_desc *region /* NULL: the plain region of the desc */,
+                                int64_t counts[2] /* [0] added on this rank (ECAPACITY: needed here), [1] accepted job-wide */);
+int mpmhip_seed_histogram(mpmhip_ctx *ctx, const mpmhip_seed_desc *desc, const mpmhip_region_desc *region /* or NULL */,
+                          int64_t *hist_x, int64_t *hist_y, int64_t *hist_z /* res[a] bins each */, int64_t *total,
+                          int32_t cell_bounds[6] /* lo3, hi3 (exclusive) of the survivors' base cells */);
+int mpmhip_set_next_id(mpmhip_ctx *ctx, int32_t id);
 int mpmhip_region_sample(int32_t device, int32_t dim, float delta_x, const mpmhip_region_desc *region, int64_t n,
                          const float *pos /* [n][dim] */, float *phi_out /* [n] */);
 int mpmhip_region_bake(int32_t device, int32_t dim, float delta_x, const mpmhip_region_desc *region, const mpmhip_sdf_desc *lattice,

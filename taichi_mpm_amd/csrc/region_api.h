@@ -1,6 +1,8 @@
 // taichi_mpm_amd/csrc/region_api.h — host side of the region expressions (kernels: k_region.h; checks: region_program.h; rules:
 // include/mpmhip.h).  Included by mpmhip.hip inside its extern "C" block, behind seed_api.h.  The seeding entries go through the one
 // driver of seed_api.h with RegionExpr<D> as the region; the two ctx-free entries keep their arrays for the length of the call.
+// mpmhip_seed_particles_brick and mpmhip_seed_histogram take either kind of region (NULL: the plain one of the seed description) and
+// stand here for that reason; mpmhip_set_next_id beside them.
 #pragma once
 
 extern "C++" {
@@ -58,18 +60,29 @@ int region_build(const mpmhip_region_desc *r, DevBuf<float> &buf, size_t &cap, h
   return MPMHIP_OK;
 }
 
-template <class A>
-int seed_particles_region(typename A::Ctx *c, int32_t group, const typename A::Desc *how, const mpmhip_region_desc *region, int64_t *n_added) {
-  if (c && how && (how->n_shapes != 0 || how->sdf)) {
-    if (n_added) *n_added = 0;
+// `region` == NULL: the plain region of `how` (seed_region); else the expression, and `how` must carry no region of its own
+template <class A, SeedCall CALL>
+int seed_particles_either(typename A::Ctx *c, int32_t group, const typename A::Desc *how, const mpmhip_region_desc *region, SeedOut &out) {
+  if (!region)
+    return seed_particles_as<A, typename A::Region, CALL>(c, group, how, out, [&](typename A::Region &R) { return seed_region<A>(c, how, R); });
+  if (c && how && (how->n_shapes != 0 || how->sdf))
     return A::fail(c, MPMHIP_EINVAL, "seed_particles_region: the seed description's own region must be empty (n_shapes == 0, sdf == NULL)");
-  }
-  return seed_particles_as<A, RegionExpr<A::D>>(c, group, how, n_added, [&](RegionExpr<A::D> &R) {
+  return seed_particles_as<A, RegionExpr<A::D>, CALL>(c, group, how, out, [&](RegionExpr<A::D> &R) {
     std::string why;
     SeedWork &W = c->seed;
     const int rc = region_build<A::D>(region, W.d_phi, W.phi_cap, c->stream, R, why);
     return rc ? A::fail(c, rc, ("seed_particles_region: " + why).c_str()) : (int)MPMHIP_OK;
   });
+}
+
+template <class A>
+int seed_particles_region(typename A::Ctx *c, int32_t group, const typename A::Desc *how, const mpmhip_region_desc *region, int64_t *n_added) {
+  if (n_added) *n_added = 0;
+  if (c && !region) return A::fail(c, MPMHIP_EINVAL, "seed_particles_region: the region description is required");
+  SeedOut out;
+  const int rc = seed_particles_either<A, SEED_WHOLE>(c, group, how, region, out);
+  if (n_added) *n_added = out.here;
+  return rc;
 }
 
 // what the two ctx-free entries share: the arguments, the device, the description checked (region_build) and on the device
@@ -134,6 +147,26 @@ int mpmhip_seed_particles_region(mpmhip_ctx *c, int32_t group, const mpmhip_seed
 int mpmhip2d_seed_particles_region(mpmhip2d_ctx *m, int32_t group, const mpmhip2d_seed_desc *how, const mpmhip_region_desc *region,
                                    int64_t *n_added) {
   return seed_particles_region<Seed2>(m, group, how, region, n_added);
+}
+int mpmhip_seed_particles_brick(mpmhip_ctx *c, int32_t group, const mpmhip_seed_desc *how, const mpmhip_region_desc *region, int64_t counts[2]) {
+  SeedOut out;
+  const int rc = seed_particles_either<Seed3, SEED_BRICK>(c, group, how, region, out);
+  if (counts) { counts[0] = out.here; counts[1] = out.job; }
+  return rc;
+}
+int mpmhip_seed_histogram(mpmhip_ctx *c, const mpmhip_seed_desc *how, const mpmhip_region_desc *region, int64_t *hist_x, int64_t *hist_y,
+                          int64_t *hist_z, int64_t *total, int32_t cell_bounds[6]) {
+  SeedOut out;
+  out.hist[0] = hist_x; out.hist[1] = hist_y; out.hist[2] = hist_z;
+  out.total = total; out.cell_bounds = cell_bounds;
+  if (total) *total = 0;
+  return seed_particles_either<Seed3, SEED_HIST>(c, -1, how, region, out);
+}
+int mpmhip_set_next_id(mpmhip_ctx *c, int32_t id) {
+  if (!c) return MPMHIP_EINVAL;
+  if (c->in_substep) return fail(c, MPMHIP_EINVAL, "set_next_id inside a substep");
+  if (id > c->next_pid) c->next_pid = id;
+  return c->next_pid;
 }
 int mpmhip_region_sample(int32_t device, int32_t dim, float delta_x, const mpmhip_region_desc *region, int64_t n, const float *pos, float *phi_out) {
   if (dim == 3) return region_sample<3>(device, delta_x, region, n, pos, phi_out);

@@ -4,6 +4,8 @@
 // its own way is in its adapter (Seed3, Seed2).  A sampled region's lattice is judged by sdf_lattice.h and becomes the SdfDev of the
 // boundary's sampler (mpmhip.hip: sdf_fill; mpm_math.h).  A call synchronises twice for a few words each: the get-ready box (the number of
 // replicas sizes the candidate passes) and the survivors' count (the capacity check comes before anything is written).
+// The same driver carries a rank of a tiled job filling its own brick and the histogram call (SeedCall; their entry points stand in
+// region_api.h, where both kinds of region are known): what differs is the passes behind the get-ready box.
 #pragma once
 
 // the particle arrays hold at least `capacity` particles; what they hold stays.  The per-particle arrays of the CPIC coupling grow
@@ -23,6 +25,10 @@ extern "C++" {
 namespace {
 
 #define SEED_NO_CONTRACT _Pragma("clang fp contract(off)")
+
+// which call the driver carries: the whole region on one ctx, this rank's brick of it (mpmhip_seed_particles_brick), or only the
+// histograms of the survivors' base cells (mpmhip_seed_histogram: no group, nothing written)
+enum SeedCall { SEED_WHOLE, SEED_BRICK, SEED_HIST };
 
 template <int D>
 int64_t seed_tile_out(float *out, int64_t capacity) {
@@ -52,9 +58,13 @@ struct Seed3 {
   using Desc = mpmhip_seed_desc;
   using Region = SeedRegion;
   static int fail(Ctx *c, int code, const char *msg) { return ::fail(c, code, "%s", msg); }
-  static const char *refused(const Ctx *c) {
+  static const char *refused(const Ctx *c, SeedCall call) {
     if (c->in_substep) return "seed_particles inside a substep";
-    if (c->T.enabled || c->tn.on) return "seed_particles on a tiled ctx: seed before the partition is set, or give each rank its positions";
+    const bool tiled = c->T.enabled || c->tn.on;
+    if (call == SEED_WHOLE && tiled)
+      return "seed_particles on a tiled ctx: mpmhip_seed_particles_brick fills every rank's own brick (or seed before the partition is set, or give "
+             "each rank its positions)";
+    if (call == SEED_BRICK && !tiled) return "seed_particles_brick needs a ctx with a partition (mpmhip_set_partition or mpmhip_tiled_setup)";
     return nullptr;
   }
   static int shapes(Ctx *c, const Desc *d, Region &R) {
@@ -65,19 +75,37 @@ struct Seed3 {
   static float min_distance(double v) { return (float)std::cbrt(v * 13.0 / 18.0); }
   static uint32_t max_bounds_wgs(const Ctx *c) { return (uint32_t)c->n_cus * 32u; }
   static float base_dt(const Ctx *c) { return c->P.dt; }
+  // n particles are appended here and n_ids creation ids are used up (a rank of a tiled job: the job's count, n only its brick's)
   template <class Write>
-  static int commit(Ctx *c, int32_t group, int64_t n, Write write) {
+  static int commit(Ctx *c, int32_t group, int64_t n, int64_t n_ids, Write write) {
     if (int rc = async_drop_view(c)) return rc;  // (resident async stepper: records that only mirror the pools go first)
     if (c->n_slots + n > c->cap)
       return ::fail(c, MPMHIP_ECAPACITY, "particle capacity exceeded: %lld + %lld > %lld", (long long)c->n_slots, (long long)n, (long long)c->cap);
-    if ((int64_t)c->next_pid + n > 0x7fffffffll) return ::fail(c, MPMHIP_ECAPACITY, "seed_particles: creation ids exceed 2^31");
+    if ((int64_t)c->next_pid + n_ids > 0x7fffffffll) return ::fail(c, MPMHIP_ECAPACITY, "seed_particles: creation ids exceed 2^31");
+    if (n == 0) { c->next_pid += (int32_t)n_ids; return MPMHIP_OK; }  // (every survivor lies in another rank's brick)
     if (int rc = ensure_b_current(c)) return rc;  // A of every particle is recomputed from apic_b
     if (int rc = write(SeedSink3{reinterpret_cast<float4 *>(c->rg + c->n_slots), reinterpret_cast<float4 *>(c->rp + c->n_slots),
                                  reinterpret_cast<float4 *>(c->rb + (size_t)c->n_slots * BW), c->groups[group].p[0]}))
       return rc;
-    c->next_pid += (int32_t)n;
+    c->next_pid += (int32_t)n_ids;
     set_slots(c, c->n_slots + n);
     return clear_block_flags(c, c->rec.particles_appended());
+  }
+  // A ctx with a native plan (mpmhip_tiled_setup) between two advances: the halo boxes were cut to the particles of the last check and know
+  // nothing of the new ones.  The plan goes stale — the next advance begins with the planning scan of a job's first substep, on every
+  // rank, since every rank made this call — and until that scan has cut fresh boxes the clip box also holds every node a candidate of
+  // this call can touch: the look-back test of tn_mig_c compares against the clip box while there are no occupancy boxes.  (The
+  // candidates lie in [min_corner, min_corner + replicas * region_size) per axis; their base cells b reach the nodes b .. b + 2.)
+  static void appended_to_job(Ctx *c, const SeedParams<3> &S) {
+    if (!c->tn.on) return;  // (the callback path: the plan is the caller's, and so is planning again)
+    auto &N = c->tn;
+    for (int a = 0; a < 3; a++) {
+      const double lo = (double)S.min_corner[a], hi = lo + (double)S.nrep[a] * (double)S.region_size;
+      const int blo = (int)std::floor(lo * (double)S.idx - 0.5) - 1, bhi = (int)std::ceil(hi * (double)S.idx - 0.5) + 1;
+      N.clip_lo[a] = std::max(0, std::min(N.clip_lo[a], blo));
+      N.clip_hi[a] = std::min(c->P.res[a] + 1, std::max(N.clip_hi[a], bhi + 3));
+    }
+    N.occ_valid = false;
   }
 };
 
@@ -87,7 +115,7 @@ struct Seed2 {
   using Desc = mpmhip2d_seed_desc;
   using Region = SeedRegion2;
   static int fail(Ctx *m, int code, const char *msg) { return fail2d(m, code, msg); }
-  static const char *refused(const Ctx *m) {
+  static const char *refused(const Ctx *m, SeedCall) {
     return m->async.resident ? "seed_particles: not on a resident asynchronous stepper (seed before mpmhip2d_async_begin)" : nullptr;
   }
   static int shapes(Ctx *m, const Desc *d, Region &R) {
@@ -105,7 +133,7 @@ struct Seed2 {
   static uint32_t max_bounds_wgs(const Ctx *) { return 8192u; }
   static float base_dt(const Ctx *m) { return m->base_dt; }
   template <class Write>
-  static int commit(Ctx *m, int32_t, int64_t n, Write write) {
+  static int commit(Ctx *m, int32_t, int64_t n, int64_t, Write write) {
     if ((int64_t)m->next_pid + n > 0x7fffffffll) return fail2d(m, MPMHIP_EINVAL, "seed_particles: creation ids exceed 2^31");
     if (m->n + n > m->cap)
       return fail2d(m, MPMHIP_ECAPACITY, "particle capacity exceeded: " + std::to_string(m->n) + " + " + std::to_string(n) + " > " + std::to_string(m->cap));
@@ -188,17 +216,28 @@ double seed_get_ready(const typename A::Ctx *c, float ppc, const int *box, SeedP
   return n_rep;
 }
 
+// what a call reports beside its code: the particles added here and job-wide (SEED_WHOLE: the same number; on MPMHIP_ECAPACITY what
+// is needed here), and for SEED_HIST where the histograms go
+struct SeedOut {
+  int64_t here = 0, job = 0;
+  int64_t *hist[3] = {nullptr, nullptr, nullptr}, *total = nullptr;
+  int32_t *cell_bounds = nullptr;
+};
+
 // `make(R)` builds the region the kernels take (a plain one: seed_region; an expression: region_api.h) once the call's other
-// arguments have passed; the kernels are instantiated for its type
-template <class A, class Region, class Make>
-int seed_particles_as(typename A::Ctx *c, int32_t group, const typename A::Desc *d, int64_t *n_added, Make make) {
+// arguments have passed; the kernels are instantiated for its type.  CALL picks what follows the get-ready pass, which all share:
+//   SEED_WHOLE  k_seed_count, k_seed_scan, k_seed_write: every survivor becomes a particle of this ctx
+//   SEED_BRICK  k_seed_count_brick, k_seed_scan2, k_seed_write_brick: the survivors of this rank's brick do, with the ids all ranks agree on
+//   SEED_HIST   k_seed_hist: nothing is written, no group is read, no counter moves
+template <class A, class Region, SeedCall CALL, class Make>
+int seed_particles_as(typename A::Ctx *c, int32_t group, const typename A::Desc *d, SeedOut &out, Make make) {
   SEED_NO_CONTRACT
   constexpr int D = A::D;
+  static_assert(CALL == SEED_WHOLE || D == 3, "bricks and their histograms: the 3D ctx only");
   if (!c) return MPMHIP_EINVAL;
-  if (n_added) *n_added = 0;
   if (!d) SEED_FAIL("seed_particles: the description is required");
-  if (const char *why = A::refused(c)) return A::fail(c, MPMHIP_EINVAL, why);
-  if (group < 0 || group >= (int)c->groups.size()) SEED_FAIL("unknown group %d", group);
+  if (const char *why = A::refused(c, CALL)) return A::fail(c, MPMHIP_EINVAL, why);
+  if (CALL != SEED_HIST && (group < 0 || group >= (int)c->groups.size())) SEED_FAIL("unknown group %d", group);
   if (!(d->ppc > 0.0f) || !std::isfinite(d->ppc)) SEED_FAIL("seed_particles: ppc must be a finite number > 0");
   for (int k = 0; k < D; k++)
     if (!std::isfinite(d->velocity[k])) SEED_FAIL("seed_particles: velocity[%d] is not finite", k);
@@ -240,7 +279,7 @@ int seed_particles_as(typename A::Ctx *c, int32_t group, const typename A::Desc 
   for (int k = 0; k < D; k++) S.nrep[k] = (uint32_t)nrep[k];
   S.n_rep = (uint32_t)n_rep; S.n_tile = W.n_tile; S.n_cand = (uint32_t)n_cand;
   S.source = d->source != 0;
-  const int mat = c->groups[group].type;
+  const int mat = CALL == SEED_HIST ? 0 : c->groups[group].type;
   for (int k = 0; k < D; k++) {
     S.velocity[k] = d->velocity[k];
     if (S.source) {  // src/mpm.cpp:222-227
@@ -255,37 +294,121 @@ int seed_particles_as(typename A::Ctx *c, int32_t group, const typename A::Desc 
   S.aux = (mat == MPMHIP_SNOW || mat == MPMHIP_WATER) ? 1.0f : (mat == MPMHIP_VISCO ? 1000.0f : 0.0f);  // as the ctx's add_particles
   S.gid = group;
   S.pid0 = c->next_pid;
-  // ---- count + scan
-  const uint32_t wgs = (uint32_t)(((uint64_t)S.n_cand + SEED_PER_WG - 1) / SEED_PER_WG);
-  if (wgs > W.wg_cap || !W.d_words) {
-    W.wg_cap = 0;
-    if (W.d_words.alloc((size_t)wgs * SEED_WORDS) != hipSuccess || W.d_totals.alloc(wgs) != hipSuccess)
-      return seed_fail<A>(c, MPMHIP_ENOMEM, "seed_particles: device allocation for %u candidates failed", S.n_cand);
-    W.wg_cap = wgs;
+  if constexpr (CALL == SEED_HIST) {
+    // ---- the histograms: rows of res[a] words per axis, zeroed, counted on the device, widened on the way out
+    uint32_t sum = 0;
+    for (int k = 0; k < D; k++) sum += (uint32_t)S.res[k];
+    if (sum > W.hist_cap || !W.d_hist) {
+      W.hist_cap = 0;
+      if (W.d_hist.alloc(sum) != hipSuccess) return seed_fail<A>(c, MPMHIP_ENOMEM, "seed_histogram: device allocation of %u words failed", sum);
+      W.hist_cap = sum;
+    }
+    SEED_HIP(hipMemsetAsync(W.d_hist, 0, sizeof(uint32_t) * sum, c->stream));
+    const uint32_t chunks = (uint32_t)(((uint64_t)S.n_cand + SEED_WG - 1) / SEED_WG);
+    const size_t lds = sizeof(uint32_t) * sum;
+    const int use_lds = lds <= 65536;  // (what a workgroup may ask for without more ado)
+    const uint32_t wgs = std::min<uint32_t>(chunks, (uint32_t)c->n_cus * 8u);
+    hipLaunchKernelGGL((k_seed_hist<D, Region>), dim3(wgs), dim3(SEED_WG), use_lds ? lds : 0, c->stream, R, S, (const float *)W.d_tile, chunks,
+                       use_lds, W.d_hist.get());
+    SEED_LAUNCHED("seed_hist");
+    std::vector<uint32_t> h(sum);
+    SEED_HIP(hipMemcpyAsync(h.data(), W.d_hist, sizeof(uint32_t) * sum, hipMemcpyDeviceToHost, c->stream));
+    SEED_HIP(hipStreamSynchronize(c->stream));
+    uint32_t at = 0;
+    for (int k = 0; k < D; k++) {
+      int64_t row = 0;
+      int lo = 0x7fffffff, hi = -1;
+      for (int i = 0; i < S.res[k]; i++) {
+        const uint32_t v = h[at + (uint32_t)i];
+        if (out.hist[k]) out.hist[k][i] = (int64_t)v;
+        if (v) { lo = std::min(lo, i); hi = i + 1; }
+        row += v;
+      }
+      if (out.cell_bounds) { out.cell_bounds[k] = hi < 0 ? 0 : lo; out.cell_bounds[D + k] = hi < 0 ? 0 : hi; }
+      out.here = out.job = row;  // (every survivor counts once per axis)
+      at += (uint32_t)S.res[k];
+    }
+    if (out.total) *out.total = out.job;
+    return MPMHIP_OK;
+  } else {
+    // ---- count + scan
+    const uint32_t wgs = (uint32_t)(((uint64_t)S.n_cand + SEED_PER_WG - 1) / SEED_PER_WG);
+    if (wgs > W.wg_cap || !W.d_words) {
+      W.wg_cap = 0;
+      if (W.d_words.alloc((size_t)wgs * SEED_WORDS) != hipSuccess || W.d_totals.alloc(wgs) != hipSuccess)
+        return seed_fail<A>(c, MPMHIP_ENOMEM, "seed_particles: device allocation for %u candidates failed", S.n_cand);
+      W.wg_cap = wgs;
+    }
+    if constexpr (CALL == SEED_BRICK) {
+      if (wgs > W.wg_cap2 || !W.d_words_mine) {
+        W.wg_cap2 = 0;
+        if (W.d_words_mine.alloc((size_t)wgs * SEED_WORDS) != hipSuccess || W.d_totals2.alloc((size_t)wgs + 1) != hipSuccess)
+          return seed_fail<A>(c, MPMHIP_ENOMEM, "seed_particles: device allocation for %u candidates failed", S.n_cand);
+        W.wg_cap2 = wgs;
+      }
+      SeedBricks K;
+      memset(&K, 0, sizeof K);
+      K.rank = c->T.rank;
+      for (int a = 0; a < 3; a++) {
+        K.dims[a] = c->T.dims[a];
+        for (int k = 0; k <= c->T.dims[a]; k++) K.cuts[a][k] = c->T.cuts[a][k];
+      }
+      unsigned long long *d_total = W.d_totals2 + wgs;
+      hipLaunchKernelGGL((k_seed_count_brick<D, Region>), dim3(wgs), dim3(SEED_WG), 0, c->stream, R, S, K, (const float *)W.d_tile,
+                         W.d_words.get(), W.d_words_mine.get(), W.d_totals2.get());
+      hipLaunchKernelGGL(k_seed_scan2, dim3(1), dim3(SEED_SCAN_WG), 0, c->stream, W.d_totals2.get(), wgs, d_total);
+      SEED_LAUNCHED("seed_count_brick");
+      unsigned long long total = 0;
+      SEED_HIP(hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
+      SEED_HIP(hipStreamSynchronize(c->stream));
+      out.job = (int64_t)(total & 0xffffffffull);
+      out.here = (int64_t)(total >> 32);
+      if (out.job == 0) return MPMHIP_OK;
+      // ---- the ctx's checks, then this brick's survivors go to its sink
+      const int rc = A::commit(c, group, out.here, out.job, [&](auto sink) {
+        hipLaunchKernelGGL((k_seed_write_brick<D, decltype(sink)>), dim3(wgs), dim3(SEED_WG), 0, c->stream, S, (const float *)W.d_tile,
+                           (const unsigned long long *)W.d_words, (const unsigned long long *)W.d_words_mine,
+                           (const unsigned long long *)W.d_totals2, sink);
+        SEED_LAUNCHED("seed_write_brick");
+        return (int)MPMHIP_OK;
+      });
+      if (!rc) A::appended_to_job(c, S);
+      return rc;
+    } else {
+      uint32_t *d_total = reinterpret_cast<uint32_t *>(W.d_box + 2 * D);
+      hipLaunchKernelGGL((k_seed_count<D, Region>), dim3(wgs), dim3(SEED_WG), 0, c->stream, R, S, (const float *)W.d_tile,
+                         W.d_words.get(), W.d_totals.get());
+      hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(SEED_SCAN_WG), 0, c->stream, W.d_totals.get(), wgs, d_total);
+      SEED_LAUNCHED("seed_count");
+      uint32_t total = 0;
+      SEED_HIP(hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
+      SEED_HIP(hipStreamSynchronize(c->stream));
+      const int64_t n = (int64_t)total;
+      out.here = out.job = n;
+      if (n == 0) return MPMHIP_OK;
+      // ---- the ctx's checks, then the survivors go to its sink
+      return A::commit(c, group, n, n, [&](auto sink) {
+        hipLaunchKernelGGL((k_seed_write<D, decltype(sink)>), dim3(wgs), dim3(SEED_WG), 0, c->stream, S, (const float *)W.d_tile,
+                           (const unsigned long long *)W.d_words, (const uint32_t *)W.d_totals, sink);
+        SEED_LAUNCHED("seed_write");
+        return (int)MPMHIP_OK;
+      });
+    }
   }
-  uint32_t *d_total = reinterpret_cast<uint32_t *>(W.d_box + 2 * D);
-  hipLaunchKernelGGL((k_seed_count<D, Region>), dim3(wgs), dim3(SEED_WG), 0, c->stream, R, S, (const float *)W.d_tile,
-                     W.d_words.get(), W.d_totals.get());
-  hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(SEED_SCAN_WG), 0, c->stream, W.d_totals.get(), wgs, d_total);
-  SEED_LAUNCHED("seed_count");
-  uint32_t total = 0;
-  SEED_HIP(hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-  SEED_HIP(hipStreamSynchronize(c->stream));
-  const int64_t n = (int64_t)total;
-  if (n_added) *n_added = n;
-  if (n == 0) return MPMHIP_OK;
-  // ---- the ctx's checks, then the survivors go to its sink
-  return A::commit(c, group, n, [&](auto sink) {
-    hipLaunchKernelGGL((k_seed_write<D, decltype(sink)>), dim3(wgs), dim3(SEED_WG), 0, c->stream, S, (const float *)W.d_tile,
-                       (const unsigned long long *)W.d_words, (const uint32_t *)W.d_totals, sink);
-    SEED_LAUNCHED("seed_write");
-    return (int)MPMHIP_OK;
-  });
+}
+
+// the existing calls' shape: one count out, zero until the call knows better
+template <class A, class Region, class Make>
+int seed_particles_whole(typename A::Ctx *c, int32_t group, const typename A::Desc *d, int64_t *n_added, Make make) {
+  SeedOut out;
+  const int rc = seed_particles_as<A, Region, SEED_WHOLE>(c, group, d, out, make);
+  if (n_added) *n_added = out.here;
+  return rc;
 }
 
 template <class A>
 int seed_particles(typename A::Ctx *c, int32_t group, const typename A::Desc *d, int64_t *n_added) {
-  return seed_particles_as<A, typename A::Region>(c, group, d, n_added, [&](typename A::Region &R) { return seed_region<A>(c, d, R); });
+  return seed_particles_whole<A, typename A::Region>(c, group, d, n_added, [&](typename A::Region &R) { return seed_region<A>(c, d, R); });
 }
 
 #undef SEED_FAIL

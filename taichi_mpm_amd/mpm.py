@@ -705,6 +705,7 @@ class Simulation3D:
         self.frame = 0
         self.config = {}
         self._n_added = 0
+        self.seed_counts = (0, 0)  # (added here, added in the job) of the last add_particles(region=, brick=True)
         self._rigids = []  # ctypes keep-alives (config struct, script callbacks) of the rigid bodies, index = body id - 1
         self._free_bodies = 0  # bodies that move under impulses (not scripted, density > 0)
         self._script_error = None  # first exception raised by a scripted_position / scripted_rotation callback
@@ -959,17 +960,25 @@ class Simulation3D:
         tile (src/mpm.cpp:205-251), on the device (include/mpmhip.h: mpmhip_seed_particles).  region: a LevelSet (where its shapes
         are negative), a SampledLevelSet, a MeshLevelSet (voxelised through SampledLevelSet.from_mesh), or a Region expression
         over these (mpmhip_seed_particles_region).  Keys: ppc (8), initial_velocity, pd_source, delta_t (1e-3), initial_dg, density
-        and the material keys."""
+        and the material keys.  brick=True, on a ctx with a partition (a rank of a tiled job): mpmhip_seed_particles_brick — every
+        rank makes the same call and keeps the particles of its own brick, with the ids of the one-ctx call; `seed_counts` is then
+        (added here, added in the job).  Without it a tiled ctx refuses the call, as before."""
         dx = self.delta_x
+        brick = bool(cfg.get("brick", False))
         d, keep = self._seed_desc(cfg, ptype, ppc)
+        rd = None
         if isinstance(cfg["region"], Region):
             rd, rkeep = cfg["region"].compile(3, dx, self.device)
-            seed = lambda: self._L.mpmhip_seed_particles_region(self._ctx, gi, C.byref(d), C.byref(rd), C.byref(n))
+        n = (C.c_int64 * 2)()
+        if brick:  # this rank's brick of the region: n[0] particles here of n[1] in the job
+            seed = lambda: self._L.mpmhip_seed_particles_brick(self._ctx, gi, C.byref(d), C.byref(rd) if rd is not None else None, n)
+        elif rd is not None:
+            seed = lambda: self._L.mpmhip_seed_particles_region(self._ctx, gi, C.byref(d), C.byref(rd), n)
         else:
-            seed = lambda: self._L.mpmhip_seed_particles(self._ctx, gi, C.byref(d), C.byref(n))
+            seed = lambda: self._L.mpmhip_seed_particles(self._ctx, gi, C.byref(d), n)
         vol = dx ** 3 / ppc  # create_particle(coord, maximum, config), src/mpm.cpp:134-135
         mass = vol * float(cfg.get("density", 400.0))
-        params, mat = group_params(ptype, mass, vol, **{k: v for k, v in cfg.items() if isinstance(v, (int, float))})
+        params, mat = group_params(ptype, mass, vol, **{k: v for k, v in cfg.items() if isinstance(v, (int, float)) and k != "brick"})
         if "params" in cfg:
             params = np.ascontiguousarray(cfg["params"], np.float32).reshape(16).copy()
         self._ensure_ctx()  # (a call before the ctx exists creates it)
@@ -978,17 +987,37 @@ class Simulation3D:
         if gi == len(self._groups):
             self._groups.append((mat, params))
             self._check(self._L.mpmhip_add_group(self._ctx, mat, params.ctypes.data_as(C.POINTER(C.c_float))))
-        n = C.c_int64(0)
         rc = seed()
-        if rc == -4:  # MPMHIP_ECAPACITY: n is what the call needs; nothing was written
-            need = int(self._L.mpmhip_num_slots(self._ctx)) + n.value
+        if rc == -4:  # MPMHIP_ECAPACITY: n[0] is what the call needs here; nothing was written
+            need = int(self._L.mpmhip_num_slots(self._ctx)) + n[0]
             cap = max(int(need * 1.25), self.max_particles)
             self._check(self._L.mpmhip_reserve(self._ctx, cap))
             self._capacity = cap
             rc = seed()
         self._check(rc)
-        self._n_added += n.value
+        self._n_added += n[0]
+        if brick:
+            self.seed_counts = (int(n[0]), int(n[1]))
         return ""
+
+    def seed_histograms(self, config):
+        """mpmhip_seed_histogram for an add_particles(region=...) config: (hists, cell_lo, cell_hi, total) — per axis the number of
+        particles the call would create with their base cell at each index, the bounds of those cells (hi exclusive) and their
+        number.  Nothing is added; the arguments of tiled.Partition.from_histograms."""
+        cfg = dict(config)
+        ppc = float(cfg.get("ppc", cfg.get("maximum", 8)))
+        d, keep = self._seed_desc(cfg, cfg.get("type"), ppc)
+        rd = None
+        if isinstance(cfg["region"], Region):
+            rd, rkeep = cfg["region"].compile(3, self.delta_x, self.device)
+        self._ensure_ctx()
+        hists = [np.zeros(r, np.int64) for r in self.res]
+        total, bounds = C.c_int64(0), (C.c_int32 * 6)()
+        lp = C.POINTER(C.c_int64)
+        self._check(self._L.mpmhip_seed_histogram(self._ctx, C.byref(d), C.byref(rd) if rd is not None else None,
+                                                  hists[0].ctypes.data_as(lp), hists[1].ctypes.data_as(lp), hists[2].ctypes.data_as(lp),
+                                                  C.byref(total), bounds))
+        return hists, np.array(bounds[0:3], np.int64), np.array(bounds[3:6], np.int64), int(total.value)
 
     # ---------------------------------------------------------------- CPIC rigid bodies
     def add_rigid_body(self, cfg):

@@ -648,6 +648,23 @@ class _NativeJobBase:
     def state(self):
         return [native_state(e) for e in self.engines]
 
+    def _seed(self, cfg):
+        """add_particles(region=..., brick=True) on every rank this process holds; [(added here, added in the job)] per rank.  The
+        library marks the plan stale: the next run() begins with the planning scan, which wraps the halo boxes round the new
+        particles."""
+        out = []
+        for e in self.engines:
+            e.sim.add_particles(dict(cfg, brick=True))
+            out.append(e.sim.seed_counts)
+        return out
+
+    @staticmethod
+    def _same_job_count(counts):
+        if len(set(int(c) for c in counts)) > 1:
+            from .mpm import MPMError
+            raise MPMError("add_particles on a tiled job: the ranks disagree on the job-wide count (%s): the call is a collective — "
+                           "the same description, ctx time and next id on every rank (sync_next_id)" % sorted(set(int(c) for c in counts)))
+
 
 class NativeTiledJob(_NativeJobBase):
     """this process's rank of a tiled run on the library's own data plane: Python carries 128 bytes once (the ncclUniqueId,
@@ -718,6 +735,24 @@ class NativeTiledJob(_NativeJobBase):
         self.e.sim._check(self.e.L.mpmhip_tiled_advance(self.e.ctx, int(n)))
         self.substeps += n
 
+    def add_particles(self, cfg):
+        """this rank's share of add_particles(region=...) on the whole job (collective: every rank makes the same call, e.g. an
+        emitter before every frame); returns (added here, added in the job).  The ranks' job-wide counts are compared (max == min)."""
+        here, job = self._seed(cfg)[0]
+        if self.world > 1:
+            self._same_job_count([self.reduce([job], "max")[0], self.reduce([job], "min")[0]])
+        return here, job
+
+    def sync_next_id(self):
+        """raise this rank's creation-id counter to the job's maximum (collective).  A job whose first particles came through
+        upload(F_ID) needs it before its first add_particles: seeded ranks are in step by construction."""
+        L, e = self.e.L, self.e
+        top = e.sim._check(L.mpmhip_set_next_id(e.ctx, 0))  # (reads the counter: it is never lowered)
+        if self.world > 1:
+            top = int(self.reduce([float(top)], "max")[0])
+        e.sim._check(L.mpmhip_set_next_id(e.ctx, top))
+        return int(top)
+
     def num_particles(self):
         return self.e.num_particles()
 
@@ -773,6 +808,22 @@ class NativeVirtualJob(_NativeJobBase):
         self._group_check(int(L.mpmhip_tiled_advance_group(self._arr, len(self.engines), int(n))), "mpmhip_tiled_advance_group")
         self.substeps += n
 
+    def add_particles(self, cfg):
+        """add_particles(region=...) on the whole job — every rank fills its own brick (an emitter calls before every frame);
+        returns [(added on rank r, added in the job)], whose job-wide counts must agree"""
+        out = self._seed(cfg)
+        self._same_job_count([job for _, job in out])
+        return out
+
+    def sync_next_id(self):
+        """raise every rank's creation-id counter to the job's maximum.  A job whose first particles came through upload(F_ID)
+        needs it before its first add_particles: seeded ranks are in step by construction."""
+        tops = [[float(e.sim._check(e.L.mpmhip_set_next_id(e.ctx, 0)))] for e in self.engines]  # (reads the counters: never lowered)
+        top = int(self.reduce(tops, "max")[0][0])
+        for e in self.engines:
+            e.sim._check(e.L.mpmhip_set_next_id(e.ctx, top))
+        return top
+
     def reduce(self, rows, op="sum"):
         """rows[r] = rank r's values (<= 16 doubles): all-reduce over the local wire; returns every rank's copy of the result"""
         K, n = len(self.engines), len(rows[0])
@@ -793,6 +844,45 @@ class NativeVirtualJob(_NativeJobBase):
         L = self.engines[0].L
         self._group_check(L.mpmhip_tiled_totals_group(self._arr, len(self.engines), out), "mpmhip_tiled_totals_group")
         return {"particles": int(out[0]), "active_blocks": int(out[1]), "error": int(out[2]), "migrated": int(out[3])}
+
+
+# ---------------------------------------------------------------------------------------------------- scenes seeded on the device
+def seed_histograms(sim, cfg):
+    """(hists, cell_lo, cell_hi, total) of the particles add_particles(cfg) with a region= would create — counted on the device
+    (mpmhip_seed_histogram), nothing added: the arguments of Partition.from_histograms.  Several regions: add the histograms, join
+    the bounds."""
+    return sim.seed_histograms(cfg)
+
+
+def set_partition(sim, part, rank):
+    """mpmhip_set_partition alone: the ctx knows its brick (add_particles(brick=True) needs no more); halo boxes and the data
+    plane come with the job (HipEngine.configure, native_setup)"""
+    sim._ensure_ctx()
+    ip = C.POINTER(C.c_int32)
+    arrs = [np.asarray(c, np.int32) for c in part.cuts]
+    dims = np.asarray(part.dims, np.int32)
+    sim._check(sim._L.mpmhip_set_partition(sim._ctx, int(rank), dims.ctypes.data_as(ip), arrs[0].ctypes.data_as(ip),
+                                           arrs[1].ctypes.data_as(ip), arrs[2].ctypes.data_as(ip), part.margin))
+
+
+def build_seeded_rank_sims(tm, groups, part, ranks=None, device=0, levelset=None, max_particles=None, **sim_cfg):
+    """the ctxs of `ranks` (default: all of the partition, the virtual job of one device) with the scene seeded on the device:
+    `groups` is a list of add_particles configs with region=, made in the same order on every rank — group ids travel with
+    migrating particles, creation ids are handed out job-wide — and each rank keeps its own brick of every region.  No position
+    array exists on the host, no id is uploaded.  sim_cfg: initialize()'s keys (res, delta_x, base_delta_t, gravity, ...)."""
+    sims = []
+    for rank in (range(part.world) if ranks is None else ranks):
+        cfg = dict(sim_cfg, device=device)
+        if max_particles is not None:
+            cfg["max_particles"] = int(max_particles)
+        sim = tm.create_simulation3("mpm").initialize(cfg)
+        if levelset is not None:
+            sim.set_levelset(levelset)
+        set_partition(sim, part, rank)
+        for g in groups:
+            sim.add_particles(dict(g, brick=True))  # (grows the ctx where the brick's share does not fit)
+        sims.append(sim)
+    return sims
 
 
 # ---------------------------------------------------------------------------------------------------- bench glue
