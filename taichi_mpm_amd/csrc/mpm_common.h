@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "mpm_math.h"
+#include "tiled_plan.h"  // box_blocks_axis / box_blocks_of: one definition for the planner and the kernels
 
 namespace mpm {
 
@@ -137,11 +138,9 @@ struct DevBox {
   uint32_t *flag;      // peer-write wires: this rank's word in the peer's array of halo epochs (else nullptr)
 };
 
-// grid blocks (4^3 nodes) a halo box [lo, lo + dim) touches per axis, and in all
-__host__ __device__ __forceinline__ int box_blocks_axis(int lo, int dim) { return ((lo + dim - 1) >> 2) - (lo >> 2) + 1; }
-__host__ __device__ __forceinline__ uint32_t box_blocks_of(const int lo[3], const int dim[3]) {
-  return (uint32_t)box_blocks_axis(lo[0], dim[0]) * (uint32_t)box_blocks_axis(lo[1], dim[1]) * (uint32_t)box_blocks_axis(lo[2], dim[2]);
-}
+// grid blocks (4^3 nodes) a halo box [lo, lo + dim) touches per axis, and in all: the planner's definition (tiled_plan.h)
+using tplan::box_blocks_axis;
+using tplan::box_blocks_of;
 
 // ------------------------------------------------------------------------------------------------ Morton
 __host__ __device__ __forceinline__ uint32_t spread3(uint32_t v) {
