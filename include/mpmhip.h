@@ -543,6 +543,48 @@ int mpmhip_tiled_totals_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int64_t ou
 int mpmhip_tiled_state(mpmhip_ctx *ctx, int64_t out[8]);
 /* the current plan: boxes sorted by peer (send / recv = the library's buffers); returns the number of boxes */
 int32_t mpmhip_tiled_plan(mpmhip_ctx *ctx, int32_t capacity, mpmhip_halo_box *out);
+/* Re-cutting a running job — the bricks follow the live particles (3D; the 2D solver has no tiling).
+ *
+ * mpmhip_live_histogram: what the new partition is cut from, on any ctx, tiled or not: the outputs of mpmhip_seed_histogram, counted
+ * over the particles the ctx HOLDS.  hist_a[i] = the live particles whose base cell has index i along axis a (res[a] entries each, NULL
+ * allowed), *total their number, cell_bounds = lo3, hi3 (exclusive) of those bins (all 0 when *total == 0).
+ *   live       creation id >= 0, position finite and >= 0.5 cells on every axis: the set the migration can place.
+ *   bin        the base cell b[k] = (int)fl(fl(x[k] * fl(1 / dx)) - 0.5f), nothing contracted — the expression of the brick seeding
+ *              above, which tiled.base_cells restates to the bit —, clamped to [0, res[a] - 1].
+ * Integer counts: exact, whatever the order.  No particle state is written, no counter moves.  Synchronises.  MPMHIP_EINVAL inside a
+ * substep.  The ranks of a job add their histograms and join their bounds; mpmhip_balanced_cuts turns the sums into cuts.
+ *
+ * mpmhip_balanced_cuts: the cut planes [0, c1, .., res] of one axis for `parts` bricks from that axis's histogram (no ctx: host
+ * arithmetic, csrc/tiled_plan.h).  cut k lies behind the first cell whose cumulative count reaches total k / parts; a cut at the edge
+ * of an empty stretch moves to its middle; every brick keeps at least one cell; an empty histogram gives the even split.  What
+ * tiled.balanced_cuts computes, cut for cut.  MPMHIP_EINVAL: parts outside [1, min(MPMHIP_MAX_PARTS, res)], a negative count.
+ *
+ * mpmhip_tiled_redistribute[_group]: between two advances of a connected job, typically right after mpmhip_tiled_setup was repeated
+ * with new cuts: EVERY live particle moves to the rank that owns its base cell (the expression above) under the partition now in
+ * force.  Collective, like mpmhip_tiled_advance.  It is a migration — scan, table exchange, pack, the wire's record transfer (RCCL:
+ * grouped ncclSend / ncclRecv; IPC: peer writes + epochs; LOCAL: plain pointers), import, every wait bounded — with three differences:
+ *   margin     suspended: a particle any distance from this rank's brick is legal.  The sticky bit 1 of the error word is not raised,
+ *              and an error word already set is left as it is (only a peer's epoch that timed out ends the call).
+ *   rounds     a destination admits its sources in ascending rank order until its inbox is full (what it offers in a round: the
+ *              inbox of the set-up, or its free slots if they are fewer); a leaver beyond the quota stays for the next round; the
+ *              rounds repeat until a scan finds no leaver.  The inbox the job was set up with is enough, whatever its size.  A rank
+ *              whose free slots do not hold an inbox drops its dead slots (a sort + compaction) before it makes its offer.
+ *   capacity   checked before anything moves: from the first table every rank knows every rank's live count after the move, live -
+ *              out + in.  If one exceeds its capacity EVERY rank returns MPMHIP_ECAPACITY, nothing has moved, the message names the
+ *              first such rank and info[3] = the capacity THIS rank needs (0 where it fits): mpmhip_reserve there and repeat the
+ *              call on every rank — the convention of mpmhip_seed_particles_brick.
+ * Afterwards every live particle sits on its owner, records are bit for bit what they were (ids included; a rank's slot order is
+ * not), and the plan is stale exactly as behind a brick seeding call: the next advance begins with the planning scan, which cuts the
+ * halo boxes around the new occupancy; until then the clip box is widened to the joined bounds of all particles.  Should the
+ * migration's own (contractible) base-cell expression round differently for a particle at an exact cell face, that particle simply
+ * migrates at the next check.  A one-rank job: nothing to do.  MPMHIP_EINVAL: no set-up, not connected, inside a substep, the group
+ * form on another wire than MPMHIP_WIRE_LOCAL[_RCCL] (and the single form on a local job of more than one rank). */
+int mpmhip_live_histogram(mpmhip_ctx *ctx, int64_t *hist_x, int64_t *hist_y, int64_t *hist_z /* res[a] bins each, NULL allowed */,
+                          int64_t *total, int32_t cell_bounds[6] /* lo3, hi3 (exclusive); all 0 when total == 0 */);
+int mpmhip_balanced_cuts(int32_t res, int32_t parts, const int64_t *hist, int32_t *cuts /* parts + 1 */);
+int mpmhip_tiled_redistribute(mpmhip_ctx *ctx, int64_t info[4]);                             /* RCCL / IPC wire: collective */
+int mpmhip_tiled_redistribute_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int64_t *info);  /* LOCAL / LOCAL_RCCL: info[n_ctx][4] */
+/* info = {records sent by this rank, records received, rounds, capacity this rank needs (set on MPMHIP_ECAPACITY, else 0)} */
 /* cell bounding box [lo, hi) of the active 4^3-cell blocks of the last sort (lo > hi when there are none);
  * synchronises.  Lets the caller clip the halo boxes to the occupied part of the grid. */
 int mpmhip_active_bounds(mpmhip_ctx *ctx, int32_t lo[3], int32_t hi[3]);

@@ -189,6 +189,7 @@ MAX_HALO_BOXES = 64
 MIGRATE_FLOATS = 44
 WIRE_RCCL, WIRE_IPC, WIRE_LOCAL, WIRE_LOCAL_RCCL = 1, 2, 3, 4
 COMM_ID_BYTES, IPC_HANDLE_BYTES = 128, 64
+ECAPACITY = -4  # MPMHIP_ECAPACITY
 
 
 def lib_path():
@@ -234,6 +235,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip_substep_begin", "mpmhip_substep_end", "mpmhip_substep_interior", "mpmhip_set_overlap", "mpmhip_tiled_run", "mpmhip_leaver_counts", "mpmhip_migration_scan", "mpmhip_export_leavers",
             "mpmhip_comm_unique_id", "mpmhip_comm_init", "mpmhip_comm_destroy", "mpmhip_comm_selftest", "mpmhip_tiled_setup", "mpmhip_tiled_ipc_handle",
             "mpmhip_tiled_ipc_connect", "mpmhip_tiled_connect_local", "mpmhip_tiled_advance", "mpmhip_tiled_advance_group", "mpmhip_tiled_state", "mpmhip_tiled_plan",
+            "mpmhip_live_histogram", "mpmhip_balanced_cuts", "mpmhip_tiled_redistribute", "mpmhip_tiled_redistribute_group",
             "mpmhip_tiled_reduce", "mpmhip_tiled_reduce_group", "mpmhip_calculate_energy_group", "mpmhip_tiled_totals", "mpmhip_tiled_totals_group",
             "mpmhip_import_particles", "mpmhip_active_bounds", "mpmhip_num_slots", "mpmhip_request_compaction", "mpmhip_reserve", "mpmhip_capacity", "mpmhip_mpm88_create", "mpmhip_mpm88_destroy", "mpmhip_mpm88_last_error", "mpmhip_mpm88_add",
             "mpmhip_mpm88_num_particles", "mpmhip_mpm88_advance", "mpmhip_mpm88_download", "mpmhip_mpm88_download_grid",
@@ -345,6 +347,10 @@ def load():
     L.mpmhip_tiled_totals_group.argtypes = [P(vp), C.c_int32, P(C.c_int64)]
     L.mpmhip_tiled_state.argtypes = [vp, P(C.c_int64)]
     L.mpmhip_tiled_plan.argtypes = [vp, C.c_int32, P(HaloBox)]
+    L.mpmhip_live_histogram.argtypes = [vp, P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64), ip]
+    L.mpmhip_balanced_cuts.argtypes = [C.c_int32, C.c_int32, P(C.c_int64), ip]
+    L.mpmhip_tiled_redistribute.argtypes = [vp, P(C.c_int64)]
+    L.mpmhip_tiled_redistribute_group.argtypes = [P(vp), C.c_int32, P(C.c_int64)]
     L.mpmhip_num_slots.argtypes = [vp]
     L.mpmhip_num_slots.restype = C.c_int64
     L.mpmhip_reserve.argtypes = [vp, C.c_int64]

@@ -307,5 +307,159 @@ __global__ __launch_bounds__(256) void k_import(Params P, uint32_t n, uint32_t b
   }
 }
 
+// ------------------------------------------------------------------------------------------------ re-cutting a running job
+// Base cell of a live particle with NOTHING contracted: b[k] = (int)fl(fl(x[k] * fl(1 / dx)) - 0.5f), the expression the brick seeding
+// documents (k_seed.h: seed_base_cell) and tiled.base_cells restates to the bit — the histograms the new cuts come from and the
+// owners the redistribution moves to agree on every particle.  false: not placeable (position not finite, or below 0.5 cells on an
+// axis: dest_rank's rule).  Positions far outside the grid saturate instead of overflowing the conversion.
+__device__ __forceinline__ bool live_base_cell(const Params &P, float4 g0, int b[3]) {
+#pragma clang fp contract(off)
+  const float X[3] = {g0.x * P.idx, g0.y * P.idx, g0.z * P.idx};
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    ok = ok && isfinite(X[k]) && X[k] >= 0.5f;
+    b[k] = (int)fminf(X[k] - 0.5f, 1.0e9f);
+  }
+  return ok;
+}
+__device__ __forceinline__ int owner_rank(const Tiling &T, const int b[3]) {
+  return (part_index(T.cuts[0], T.dims[0], b[0]) * T.dims[1] + part_index(T.cuts[1], T.dims[1], b[1])) * T.dims[2] +
+         part_index(T.cuts[2], T.dims[2], b[2]);
+}
+// wave reduce -> workgroup reduce -> 6 atomics per workgroup: the epilogue of k_leaver_count, for the two kernels below
+__device__ __forceinline__ void bounds_epilogue(int lo[3], int hi[3], int *__restrict__ bounds) {
+  __shared__ int red[4][6];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      lo[k] = min(lo[k], __shfl_xor(lo[k], off));
+      hi[k] = max(hi[k], __shfl_xor(hi[k], off));
+    }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][k] = lo[k]; red[threadIdx.x >> 6][3 + k] = hi[k]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int k = threadIdx.x;
+    const int l = min(min(red[0][k], red[1][k]), min(red[2][k], red[3][k]));
+    const int h = max(max(red[0][3 + k], red[1][3 + k]), max(red[2][3 + k], red[3][3 + k]));
+    if (h >= 0) { atomicMin(&bounds[k], l); atomicMax(&bounds[3 + k], h); }
+  }
+}
+
+// one count into a histogram row (T = int32_t: a workgroup's LDS row; unsigned long long: the global row).  Particles come in the
+// order of the last sort, so the lanes of a wave mostly share a bin (a pile: thousands of particles in one y-bin): the lanes that
+// agree with the wave's first valid lane add their NUMBER with one atomic, only the others add for themselves — no lane-serialised
+// chain of 64 adds on one address.
+template <class T>
+__device__ __forceinline__ void hist_add(T *row, bool valid, int bin) {
+  const unsigned long long any = __ballot(valid);
+  if (!any) return;
+  const int first = __shfl(bin, __ffsll((long long)any) - 1);
+  const unsigned long long same = __ballot(valid && bin == first);
+  if (valid && bin != first) atomicAdd(&row[bin], (T)1);
+  if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&row[first], (T)__popcll(same));
+}
+// mpmhip_live_histogram: per-axis histograms of the base cells (clamped to the rows) of every live, placeable particle; hist =
+// [res0 + res1 + res2] 64-bit rows, bounds[0..2] / [3..5] = min / max + 1 of the bins, hist[res0 + res1 + res2] = their number.
+// Reads the position float4 and the id word of each 64-byte RecG.  USE_LDS: the three rows as int32 in the workgroup's LDS (3 res
+// words: 6 KB at res = 512), flushed once with one 64-bit global atomic per occupied bin; the host caps the grid so that a workgroup
+// counts at most 2^31 particles and the flush stays far below the particle traffic.  Else (the rows exceed 64 KB): the same wave-merged
+// adds straight to the global rows.
+template <bool USE_LDS>
+__global__ __launch_bounds__(256) void k_live_histogram(Params P, const float4 *__restrict__ rg, unsigned long long *__restrict__ hist,
+                                                        int *__restrict__ bounds) {
+  extern __shared__ int32_t live_rows[];
+  const int off[4] = {0, P.res[0], P.res[0] + P.res[1], P.res[0] + P.res[1] + P.res[2]};
+  if (USE_LDS) {
+    for (int i = threadIdx.x; i < off[3]; i += blockDim.x) live_rows[i] = 0;
+    __syncthreads();
+  }
+  int lo[3] = {1 << 30, 1 << 30, 1 << 30}, hi[3] = {-1, -1, -1};
+  uint32_t mine = 0;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  const uint32_t nloop = (P.n_slots + stride - 1) / stride;
+  for (uint32_t it = 0; it < nloop; it++) {  // uniform trip count (hist_add ballots and shuffles)
+    const uint32_t i = it * stride + blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    int b[3] = {0, 0, 0};
+    if (i < P.n_slots && __float_as_int(rg[(size_t)i * 4 + 3].z) >= 0) valid = live_base_cell(P, rg[(size_t)i * 4], b);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      b[k] = min(max(b[k], 0), P.res[k] - 1);
+      if (valid) { lo[k] = min(lo[k], b[k]); hi[k] = max(hi[k], b[k] + 1); }
+      if (USE_LDS) hist_add(live_rows + off[k], valid, b[k]);
+      else hist_add(hist + off[k], valid, b[k]);
+    }
+    mine += valid ? 1u : 0u;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+  __shared__ uint32_t wave_n[4];
+  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = mine;
+  bounds_epilogue(lo, hi, bounds);  // (synchronises the workgroup: the LDS rows and wave_n are complete behind it)
+  if (threadIdx.x == 0) {
+    const uint32_t n = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+    if (n) atomicAdd(&hist[off[3]], (unsigned long long)n);
+  }
+  if (USE_LDS)
+    for (int i = threadIdx.x; i < off[3]; i += blockDim.x) {
+      const int32_t v = live_rows[i];
+      if (v) atomicAdd(&hist[i], (unsigned long long)v);
+    }
+}
+
+// The scan of a redistribution (mpmhip_tiled_redistribute): k_leaver_count WITHOUT the margin check — after a re-cut a particle any
+// distance from this rank's brick is legal, error bit 1 is neither raised nor read — and with the owner taken from live_base_cell.
+// counts[d != rank] = the particles rank d owns now; counts[rank] = the records with an id here (what the capacity rule calls live);
+// bounds as k_leaver_count's; the speed word is left to the host (it carries this rank's capacity through the table).
+__global__ __launch_bounds__(256) void k_recut_count(Params P, Tiling T, const float4 *__restrict__ rg, uint32_t *__restrict__ counts,
+                                                     int *__restrict__ bounds) {
+  int lo[3] = {1 << 30, 1 << 30, 1 << 30}, hi[3] = {-1, -1, -1};
+  uint32_t here = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < P.n_slots; i += gridDim.x * blockDim.x) {
+    if (__float_as_int(rg[(size_t)i * 4 + 3].z) < 0) continue;
+    here++;
+    int b[3];
+    if (!live_base_cell(P, rg[(size_t)i * 4], b)) continue;
+    const int d = owner_rank(T, b);
+    if (d != T.rank) atomicAdd(&counts[d], 1u);
+#pragma unroll
+    for (int k = 0; k < 3; k++) { lo[k] = min(lo[k], b[k]); hi[k] = max(hi[k], b[k] + 1); }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) here += __shfl_xor(here, o);
+  if ((threadIdx.x & 63) == 0 && here) atomicAdd(&counts[T.rank], here);
+  bounds_epilogue(lo, hi, bounds);
+}
+// The pack of a redistribution round: k_leaver_pack with a quota per destination.  cursor[d] starts at the first record index of
+// destination d in `out`, cursor[world + d] is where its quota ends: a leaver that draws an index at or beyond it stays for the next
+// round (the cursor overshoots; nothing reads it again).
+__global__ __launch_bounds__(256) void k_recut_pack(Params P, Tiling T, int world, float4 *__restrict__ rg, const float4 *__restrict__ rp,
+                                                    const float4 *__restrict__ rb, uint32_t *__restrict__ key, uint32_t *__restrict__ cursor,
+                                                    float4 *__restrict__ out, Counters *cnt) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < P.n_slots; i += gridDim.x * blockDim.x) {
+    const float4 g3 = rg[(size_t)i * 4 + 3];
+    if (__float_as_int(g3.z) < 0) continue;
+    int b[3];
+    if (!live_base_cell(P, rg[(size_t)i * 4], b)) continue;
+    const int d = owner_rank(T, b);
+    if (d == T.rank) continue;
+    const uint32_t at = atomicAdd(&cursor[d], 1u);
+    if (at >= cursor[world + d]) continue;
+    const size_t o = (size_t)at * 11;
+#pragma unroll
+    for (int q = 0; q < 4; q++) out[o + q] = rg[(size_t)i * 4 + q];
+#pragma unroll
+    for (int q = 0; q < 4; q++) out[o + 4 + q] = rp[(size_t)i * 4 + q];
+#pragma unroll
+    for (int q = 0; q < 3; q++) out[o + 8 + q] = rb[(size_t)i * 3 + q];
+    rg[(size_t)i * 4 + 3] = make_float4(g3.x, g3.y, __int_as_float(-1), 0.0f);
+    key[i] = INVALID;
+    atomicAdd(&cnt->n_dead, 1u);
+  }
+}
+
 
 }  // namespace mpm

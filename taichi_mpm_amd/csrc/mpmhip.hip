@@ -407,6 +407,7 @@ struct mpmhip_ctx {
   DevBuf<DevBox> d_boxes;
   DevBuf<uint32_t> d_counts;
   DevBuf<int> d_bounds;
+  DevBuf<unsigned long long> d_live_hist;  // mpmhip_live_histogram: rows | total | bounds (res0 + res1 + res2 + 4 words: fixed for the ctx)
   PinnedBuf<uint32_t> h_pinned;  // 64 KiB of pinned host memory for small readbacks (counters, migration table)
   static constexpr int FILL_STATS_WORD = 16368;  // word offset of the block-fill statistics in that page (do_sort, facts)
   DevBuf<double> d_energy;
@@ -512,7 +513,7 @@ struct mpmhip_ctx {
     bool handle_valid = false;
     uint32_t *flags = nullptr, *table[2] = {nullptr, nullptr};             // views into the arena
     float4 *recv[2] = {nullptr, nullptr}, *inbox = nullptr;  // ditto
-    DevBuf<uint32_t> row, d_done;
+    DevBuf<uint32_t> row, d_done, d_recut;  // (d_recut: cursors and quota ends of a redistribution round's pack)
     DevBuf<float4> send, mig_send;
     DevBuf<DevBox> d_boxes[2];
     DevBuf<int> d_halo_idx, d_all_idx;

@@ -237,19 +237,29 @@ int tn_exchange_wait(mpmhip_ctx *c) {
 
 // ------------------------------------------------------------------------------------------------ migration
 // phase A: scan (leavers per destination, bounds, top speed) and publish this rank's row of the table
-int tn_mig_a(mpmhip_ctx *c) {
+// recut_room < 0: a migration.  >= 0: the scan of a redistribution round (k_recut_count: no margin check; the row also carries this
+// rank's live records and its capacity, tiled_plan.h: split_recut_table) which offers recut_room records of its inbox
+int tn_mig_a(mpmhip_ctx *c, int64_t recut_room = -1) {
   auto &N = c->tn;
   const int world = N.world;
   int rc = ensure_counts(c, world);
   if (rc) return rc;
   N.mig_epoch++;
   hipLaunchKernelGGL(k_scan_init, dim3((world + 8 + 255) / 256), dim3(256), 0, c->stream, c->d_counts, world,
-                     (uint32_t)std::min<uint64_t>(N.lay.inbox_cap, 0xFFFFFFFFull));
+                     (uint32_t)std::min<uint64_t>(recut_room >= 0 ? (uint64_t)recut_room : N.lay.inbox_cap, 0xFFFFFFFFull));
   int grid = particle_grid(c->n_slots);
   if (grid > 128) grid = 128;
-  hipLaunchKernelGGL(k_leaver_count, dim3(grid), dim3(256), 0, c->stream, c->P, c->T, (const float4 *)c->rg.get(), (const float4 *)c->rp.get(),
-                     c->d_counts, reinterpret_cast<int *>(c->d_counts + world), c->cnt);
-  if ((rc = launch_check(c, "leaver_count"))) return rc;
+  if (recut_room >= 0) {
+    hipLaunchKernelGGL(k_recut_count, dim3(grid), dim3(256), 0, c->stream, c->P, c->T, (const float4 *)c->rg.get(), c->d_counts,
+                       reinterpret_cast<int *>(c->d_counts + world));
+    uint32_t *pin = c->h_pinned + 1024 + 2 * tplan::MAX_WORLD;  // (behind the cursors of a round's pack; read by the copy below, waited for in tn_recut_b)
+    *pin = (uint32_t)c->cap;
+    HIPCHK(c, hipMemcpyAsync(c->d_counts + world + 6, pin, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  } else {
+    hipLaunchKernelGGL(k_leaver_count, dim3(grid), dim3(256), 0, c->stream, c->P, c->T, (const float4 *)c->rg.get(), (const float4 *)c->rp.get(),
+                       c->d_counts, reinterpret_cast<int *>(c->d_counts + world), c->cnt);
+  }
+  if ((rc = launch_check(c, recut_room >= 0 ? "recut_count" : "leaver_count"))) return rc;
   uint32_t *table = N.table[N.mig_epoch & 1];
   if (N.wire == MPMHIP_WIRE_RCCL) {
     HIPCHK(c, hipMemcpyAsync(N.row, c->d_counts, sizeof(uint32_t) * (world + 8), hipMemcpyDeviceToDevice, c->stream));
@@ -268,6 +278,7 @@ int tn_mig_a(mpmhip_ctx *c) {
   return launch_check(c, "put (migration row)");
 }
 
+int tn_send_records(mpmhip_ctx *c);
 // phase B: read the table (the ONE synchronisation of a migration), pack the leavers and send them
 int tn_mig_b(mpmhip_ctx *c) {
   auto &N = c->tn;
@@ -293,7 +304,15 @@ int tn_mig_b(mpmhip_ctx *c) {
                 (long long)over.arriving, over.dest, over.room);
   if (M.n_out && (rc = mpmhip_export_leavers(c, world, &M.counts[(size_t)me * world], N.mig_send))) return rc;
   N.migrated_out += M.n_out;
-  // this rank's records for s begin at send_off[s]; in the inbox of s they lie behind those of the ranks below this one (ahead)
+  return tn_send_records(c);
+}
+
+// the records packed into mig_send on their way, one message per destination, as the decoded table N.mig says: this rank's records
+// for s begin at send_off[s]; in the inbox of s they lie behind those of the ranks below this one (ahead)
+int tn_send_records(mpmhip_ctx *c) {
+  auto &N = c->tn;
+  auto &M = N.mig;
+  const int world = N.world, me = c->T.rank;
   if (N.wire == MPMHIP_WIRE_RCCL) {
     RcclApi *R = rccl_api();
     NCCLCHK(c, R->GroupStart());
@@ -347,6 +366,144 @@ int tn_mig_c(mpmhip_ctx *c) {
   }
   if (N.initial_scan) return MPMHIP_OK;  // (the scan in front of a job's first substep plans, it does not move the schedule)
   N.next_migration = N.k + tplan::next_interval(N.migrate_interval, N.adaptive_cap, c->T.margin, M.speed);
+  return MPMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ redistribution (after a re-cut)
+// mpmhip_tiled_redistribute: every live particle to the rank that owns its base cell under the partition in force, with the
+// migration's machinery — scan, table, pack, the wire's record transfer, import — in ROUNDS (tiled_plan.h: round_quotas), so that
+// the inbox the job was set up with is enough; no margin check (k_recut_count); the capacity rule (capacity_check) before anything
+// moves.  A round is the three phases of a migration; the ranks of a local job run each phase rank by rank.
+struct RecutRun {
+  int64_t sent = 0, received = 0, rounds = 0, need = 0;  // info[4] of the call
+  int64_t moving = 0;   // records the round in flight moves in the whole job (0: the scan found no leaver, or the call was refused)
+  int refused = 0;      // MPMHIP_ECAPACITY: every rank returns it together
+  bool any = false;     // joint bounds of all live particles, from the first round's table
+  int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+};
+// phase A of a round: make room (compact when the slots behind the live records do not hold an inbox), offer it, scan
+int tn_recut_a(mpmhip_ctx *c) {
+  auto &N = c->tn;
+  int rc;
+  if (c->rec.sorted() && (rc = invalidate_keys(c))) return rc;  // (k_import appends behind records that are not mid-substep)
+  const int64_t inbox = (int64_t)std::min<uint64_t>(N.lay.inbox_cap, 0x7fffffffull);
+  if (c->n_slots > 0 && c->n_slots + inbox > c->cap) {  // leavers of earlier rounds (and deleted particles) left dead slots: drop them
+    c->compact_requested = true;
+    if ((rc = do_sort(c)) || (rc = invalidate_keys(c))) return rc;
+  }
+  return tn_mig_a(c, std::max<int64_t>(0, std::min<int64_t>(inbox, c->cap - c->n_slots)));
+}
+// phase B: the table, the capacity rule (first round), this round's quotas, pack and send
+int tn_recut_b(mpmhip_ctx *c, RecutRun &R) {
+  auto &N = c->tn;
+  const int world = N.world, me = c->T.rank;
+  int rc;
+  R.moving = 0;
+  uint32_t *table = N.table[N.mig_epoch & 1];
+  if (N.wire != MPMHIP_WIRE_RCCL && (rc = tn_wait(c, N.flags + tplan::MAX_WORLD, N.all_ranks, N.d_all_idx, N.mig_epoch))) return rc;
+  uint32_t *h = c->h_pinned + 2048;
+  HIPCHK(c, hipMemcpyAsync(h, table, sizeof(uint32_t) * tplan::ROW * world, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint32_t err = 0;  // (only a wait that timed out ends the call: the error word is otherwise left as it is)
+  HIPCHK(c, hipMemcpy(&err, &c->cnt->error, sizeof err, hipMemcpyDeviceToHost));
+  if (err & 16u) { Counters hc; return read_counters(c, hc); }
+  std::vector<int64_t> live((size_t)world), cap((size_t)world);
+  tplan::split_recut_table(h, world, live.data(), cap.data());
+  auto &M = N.mig;
+  M.decode(h, world, me);
+  if (R.rounds == 0 && !R.any && M.lo[0] <= M.hi[0]) {  // (no particle anywhere: lo > hi)
+    R.any = true;
+    for (int a = 0; a < 3; a++) { R.lo[a] = M.lo[a]; R.hi[a] = M.hi[a]; }
+  }
+  if (M.total == 0) return MPMHIP_OK;
+  if (R.rounds == 0) {
+    const tplan::Growth g = tplan::capacity_check(world, M.counts.data(), live.data(), cap.data());
+    if (g.rank >= 0) {
+      const int64_t mine = tplan::live_after(world, M.counts.data(), live.data(), me);
+      R.need = mine > cap[(size_t)me] ? mine : 0;
+      R.refused = MPMHIP_ECAPACITY;
+      return fail(c, MPMHIP_ECAPACITY, "redistribute: rank %d holds %lld particles after the move, %lld more than its capacity of %lld (mpmhip_reserve "
+                  "on the ranks whose info[3] is set, then repeat the call on every rank); nothing has moved", g.rank, (long long)g.need,
+                  (long long)g.excess, (long long)cap[(size_t)g.rank]);
+    }
+  }
+  std::vector<int64_t> q((size_t)world * world);
+  R.moving = tplan::round_quotas(world, M.counts.data(), M.room.data(), q.data());
+  if (R.moving == 0)
+    return fail(c, MPMHIP_ECAPACITY, "redistribute: %lld particles are left to move and no rank that expects some has a free slot (mpmhip_reserve)",
+                (long long)M.total);
+  // the round's own table: the quotas in the place of the counts (send offsets, places in the inboxes, n_in / n_out follow)
+  for (int r = 0; r < world; r++)
+    for (int s = 0; s < world; s++) h[(size_t)r * tplan::ROW + s] = (uint32_t)q[(size_t)r * world + s];
+  M.decode(h, world, me);
+  if ((size_t)M.n_out > N.mig_send_cap) {
+    N.mig_send_cap = (size_t)M.n_out + (size_t)M.n_out / 2 + 4096;
+    HIPCHK(c, N.mig_send.alloc(N.mig_send_cap * tplan::MIG_FLOAT4));
+  }
+  if (M.n_out) {
+    if (!N.d_recut) HIPCHK(c, N.d_recut.alloc((size_t)2 * tplan::MAX_WORLD));
+    uint32_t *pin = c->h_pinned + 1024;  // (read by the copy below; the next write comes behind the next round's synchronisation)
+    for (int s = 0; s < world; s++) { pin[s] = (uint32_t)M.send_off[s]; pin[world + s] = (uint32_t)(M.send_off[s] + (uint64_t)M.count(me, s)); }
+    HIPCHK(c, hipMemcpyAsync(N.d_recut, pin, sizeof(uint32_t) * 2 * world, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_recut_pack, dim3(particle_grid(c->n_slots)), dim3(256), 0, c->stream, c->P, c->T, world, (float4 *)c->rg.get(),
+                       (const float4 *)c->rp.get(), (const float4 *)c->rb.get(), c->key, N.d_recut.get(), (float4 *)N.mig_send.get(), c->cnt);
+    if ((rc = launch_check(c, "recut_pack"))) return rc;
+  }
+  R.sent += M.n_out;
+  return tn_send_records(c);
+}
+// phase C: import the round's arrivals
+int tn_recut_c(mpmhip_ctx *c, RecutRun &R) {
+  auto &N = c->tn;
+  auto &M = N.mig;
+  int rc;
+  if (R.moving == 0) return MPMHIP_OK;
+  if (N.wire != MPMHIP_WIRE_RCCL && (rc = tn_wait(c, N.flags + 2 * tplan::MAX_WORLD, N.all_ranks, N.d_all_idx, N.mig_epoch))) return rc;
+  if (M.n_in && (rc = mpmhip_import_particles(c, M.n_in, N.inbox))) return rc;
+  R.received += M.n_in;
+  R.rounds++;
+  return MPMHIP_OK;
+}
+// behind the last round: the plan goes stale as behind a brick seeding call (seed_api.h: appended_to_job) — the next advance begins
+// with the planning scan — and until then the clip box holds every node a particle of the job can touch
+int tn_recut_done(mpmhip_ctx *c, const RecutRun &R) {
+  auto &N = c->tn;
+  if (R.any) {
+    const int s = tplan::clip_slack(c->T.margin);
+    for (int a = 0; a < 3; a++) {
+      N.clip_lo[a] = std::max(0, std::min(N.clip_lo[a], R.lo[a] - s));
+      N.clip_hi[a] = std::min(c->P.res[a] + 1, std::max(N.clip_hi[a], R.hi[a] + s + 2));
+    }
+  }
+  N.occ_valid = false;
+  if (c->n_slots > (int64_t)(0.85 * (double)c->cap)) c->compact_requested = true;  // (as tn_mig_c: the leavers' slots)
+  return tn_apply_plan(c);  // (synchronises)
+}
+int tn_redistribute(mpmhip_ctx *const *ctxs, int n_ctx, int64_t *info) {
+  std::vector<RecutRun> runs((size_t)n_ctx);
+  int rc = MPMHIP_OK;
+  auto report = [&]() {
+    for (int r = 0; r < n_ctx && info; r++) {
+      const RecutRun &R = runs[(size_t)r];
+      info[4 * r] = R.sent; info[4 * r + 1] = R.received; info[4 * r + 2] = R.rounds; info[4 * r + 3] = R.need;
+    }
+  };
+  for (;;) {
+    for (int ph = 0; ph < 3; ph++)
+      for (int r = 0; r < n_ctx; r++) {
+        mpmhip_ctx *c = ctxs[r];
+        HIPCHK(c, hipSetDevice(c->device));
+        const int e = ph == 0 ? tn_recut_a(c) : (ph == 1 ? tn_recut_b(c, runs[(size_t)r]) : tn_recut_c(c, runs[(size_t)r]));
+        // (the capacity rule refuses on EVERY rank, each with its own need: the phase goes on over the ranks of a local job)
+        if (e && !(e == MPMHIP_ECAPACITY && runs[(size_t)r].refused)) { report(); return e; }
+        if (e) rc = e;
+      }
+    if (rc || runs[0].moving == 0) break;
+  }
+  report();
+  if (rc) return rc;
+  for (int r = 0; r < n_ctx; r++)
+    if ((rc = tn_recut_done(ctxs[r], runs[(size_t)r]))) return rc;
   return MPMHIP_OK;
 }
 
@@ -923,6 +1080,78 @@ int mpmhip_tiled_totals_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int64_t ou
   if ((rc = mpmhip_tiled_reduce_group(ctxs, n_ctx, v.data(), 8, MPMHIP_REDUCE_SUM))) return rc;
   tn_totals_out(v.data(), out);
   return MPMHIP_OK;
+}
+
+int mpmhip_live_histogram(mpmhip_ctx *c, int64_t *hist_x, int64_t *hist_y, int64_t *hist_z, int64_t *total, int32_t cell_bounds[6]) {
+  if (!c) return MPMHIP_EINVAL;
+  if (c->in_substep) return fail(c, MPMHIP_EINVAL, "live_histogram inside a substep");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int *res = c->P.res;
+  const size_t bins = (size_t)res[0] + res[1] + res[2], words = bins + 1 + 3;  // rows | total | the six bounds as three 64-bit words
+  auto &d = c->d_live_hist;
+  if (!d) HIPCHK(c, d.alloc(words));
+  std::vector<unsigned long long> h(words, 0ull);
+  int init[6] = {1 << 30, 1 << 30, 1 << 30, -1, -1, -1};
+  memcpy(&h[bins + 1], init, sizeof init);
+  HIPCHK(c, hipMemcpyAsync(d, h.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, c->stream));
+  if (c->n_slots > 0) {
+    // few workgroups, two per CU: each flushes at most `bins` 64-bit atomics (12 KB at res = 512, as many as it has occupied bins),
+    // and at 8 M slots reads 1 MB of records: the flush stays a hundredth of the particle traffic
+    const size_t lds = sizeof(int32_t) * bins;
+    const int grid = std::max(1, std::min(particle_grid(c->n_slots), 2 * std::max(1, (int)c->n_cus)));
+    int *bounds = reinterpret_cast<int *>(d.get() + bins + 1);
+    if (lds <= 65536 - 256)
+      hipLaunchKernelGGL(k_live_histogram<true>, dim3(grid), dim3(256), lds, c->stream, c->P, (const float4 *)c->rg.get(), d.get(), bounds);
+    else
+      hipLaunchKernelGGL(k_live_histogram<false>, dim3(grid), dim3(256), 0, c->stream, c->P, (const float4 *)c->rg.get(), d.get(), bounds);
+    if (int rc = launch_check(c, "live_histogram")) return rc;
+  }
+  HIPCHK(c, hipMemcpyAsync(h.data(), d, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int64_t *out[3] = {hist_x, hist_y, hist_z};
+  size_t at = 0;
+  for (int a = 0; a < 3; at += (size_t)res[a], a++)
+    if (out[a]) for (int i = 0; i < res[a]; i++) out[a][i] = (int64_t)h[at + (size_t)i];
+  const int64_t n = (int64_t)h[bins];
+  if (total) *total = n;
+  if (cell_bounds) {
+    int b[6];
+    memcpy(b, &h[bins + 1], sizeof b);
+    for (int k = 0; k < 6; k++) cell_bounds[k] = n ? b[k] : 0;
+  }
+  return MPMHIP_OK;
+}
+
+int mpmhip_balanced_cuts(int32_t res, int32_t parts, const int64_t *hist, int32_t *cuts) {
+  if (!hist || !cuts) return MPMHIP_EINVAL;
+  if (parts < 1 || parts > MPMHIP_MAX_PARTS || res < parts) return fail(nullptr, MPMHIP_EINVAL, "balanced_cuts: 1 <= parts <= min(%d, res)", MPMHIP_MAX_PARTS);
+  for (int i = 0; i < res; i++)
+    if (hist[i] < 0) return fail(nullptr, MPMHIP_EINVAL, "balanced_cuts: a negative count");
+  int out[MPMHIP_MAX_PARTS + 1];
+  tplan::balanced_cuts(res, parts, hist, out);
+  for (int k = 0; k <= parts; k++) cuts[k] = out[k];
+  return MPMHIP_OK;
+}
+
+int mpmhip_tiled_redistribute(mpmhip_ctx *c, int64_t info[4]) {
+  if (!c) return MPMHIP_EINVAL;
+  if (info) for (int k = 0; k < 4; k++) info[k] = 0;
+  int rc = tn_check_ready(c, "tiled_redistribute");
+  if (rc) return rc;
+  if (c->in_substep) return fail(c, MPMHIP_EINVAL, "tiled_redistribute inside a substep");
+  if (c->tn.wire == MPMHIP_WIRE_LOCAL && c->tn.world > 1) return fail(c, MPMHIP_EINVAL, "ranks of a local job are redistributed together: mpmhip_tiled_redistribute_group");
+  if (c->tn.world == 1) return MPMHIP_OK;
+  mpmhip_ctx *one[1] = {c};
+  return tn_redistribute(one, 1, info);
+}
+int mpmhip_tiled_redistribute_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int64_t *info) {
+  int rc = tn_check_group(ctxs, n_ctx, "tiled_redistribute_group");
+  if (rc) return rc;
+  if (info) for (int k = 0; k < 4 * n_ctx; k++) info[k] = 0;
+  for (int r = 0; r < n_ctx; r++)
+    if (ctxs[r]->in_substep) return fail(ctxs[r], MPMHIP_EINVAL, "tiled_redistribute inside a substep");
+  if (n_ctx == 1) return MPMHIP_OK;
+  return tn_redistribute(ctxs, n_ctx, info);
 }
 
 int mpmhip_tiled_state(mpmhip_ctx *c, int64_t out[8]) {

@@ -11,6 +11,7 @@
 //   arena       [flags | reduction tables | table 0 | table 1 | recv 0 | recv 1 | inbox], laid out alike on every rank of a job
 //   migration   the table [world][ROW] every rank reads: counts, bounds, speed, inbox room; who writes where into which inbox
 //   after it    do the occupancy boxes still hold the particles, will they until the next check, are they much too wide
+//   re-cut      new cut planes from the live particles' histograms; the rounds and the capacity rule of the redistribution behind them
 //   schedule    substeps until the next migration
 #pragma once
 #include <algorithm>
@@ -376,6 +377,99 @@ inline After after_migration(const Mig &M, const int clip_lo[3], const int clip_
   }
   if (!covers || shrink) A.kind = After::REPLAN;
   return A;
+}
+
+// ------------------------------------------------------------------------------------------------ re-cutting a running job
+// Cell cut planes [0, c1, .., res] along one axis so that every part holds about the same number of particles — tiled.balanced_cuts
+// restated exactly: the cut lies behind the first cell whose cumulative count reaches total k / parts (compared as integers: cum parts
+// >= total k); a cut at the lower edge of an EMPTY stretch moves to its middle (clusters that do not touch: along the face of the
+// lower cluster every particle that moves up a cell would cross); every part keeps at least one cell; an empty histogram gives the
+// even split.  Needs 1 <= parts <= res; cuts_out holds parts + 1 entries.
+inline void balanced_cuts(int res, int parts, const int64_t *hist, int *cuts_out) {
+  int64_t total = 0;
+  for (int i = 0; i < res; i++) total += hist[i];
+  cuts_out[0] = 0;
+  int i = 0;
+  int64_t cum = hist[0];  // counts of the cells 0 .. i
+  for (int k = 1; k < parts; k++) {
+    int c;
+    if (total == 0) {
+      c = (int)((int64_t)res * k / parts);
+    } else {
+      while (cum * parts < total * k) cum += hist[++i];  // (ends: the last cell's cumulative count is the total)
+      c = i + 1;
+      if (c < res && hist[c] == 0) {
+        int nz = c;
+        while (nz < res && hist[nz] == 0) nz++;
+        if (nz < res) c += (nz - c) / 2;
+      }
+    }
+    c = std::max(c, cuts_out[k - 1] + 1);
+    c = std::min(c, res - (parts - k));
+    cuts_out[k] = c;
+  }
+  cuts_out[parts] = res;
+}
+
+// The round rule of a redistribution (mpmhip_tiled_redistribute): a re-cut may send a destination far more records than its inbox
+// holds, so the records travel in rounds.  left[src * world + dst] = records src still holds for dst (the table every rank reads),
+// room[dst] = what dst's inbox takes this round: destination dst admits its sources in ascending rank order until the inbox is full,
+// and a source never sends more than it has.  Every rank computes the same quotas from the same table, as Mig::admission is computed
+// from it.  While room[dst] >= 1, a round moves at least one record for every destination that still expects some: the rounds end.
+// Returns the records the round moves in the whole job.
+inline int64_t round_quotas(int world, const int64_t *left, const uint32_t *room, int64_t *q) {
+  int64_t moved = 0;
+  for (int dst = 0; dst < world; dst++) {
+    int64_t free_ = (int64_t)room[dst];
+    for (int src = 0; src < world; src++) {
+      const int64_t n = src == dst ? 0 : std::min(left[(size_t)src * world + dst], free_);
+      q[(size_t)src * world + dst] = n;
+      free_ -= n;
+      moved += n;
+    }
+  }
+  return moved;
+}
+// the rounds the rule needs for a table while every inbox offers the same room in every round (-1: a destination without room expects records)
+inline int64_t rounds_needed(int world, const int64_t *counts, const uint32_t *room) {
+  std::vector<int64_t> left(counts, counts + (size_t)world * world), q((size_t)world * world);
+  for (int r = 0; r < world; r++) left[(size_t)r * world + r] = 0;
+  int64_t rounds = 0;
+  for (;;) {
+    int64_t todo = 0;
+    for (int64_t v : left) todo += v;
+    if (todo == 0) return rounds;
+    if (round_quotas(world, left.data(), room, q.data()) == 0) return -1;
+    for (size_t i = 0; i < left.size(); i++) left[i] -= q[i];
+    rounds++;
+  }
+}
+// The capacity rule: from the same table every rank knows every rank's live count after the move, live - out + in.  The first rank
+// that exceeds its capacity, its count after the move and by how much it exceeds (rank < 0: all fit).
+struct Growth { int rank = -1; int64_t need = 0, excess = 0; };
+inline int64_t live_after(int world, const int64_t *counts, const int64_t *live, int r) {
+  int64_t n = live[r];
+  for (int s = 0; s < world; s++)
+    if (s != r) n += counts[(size_t)s * world + r] - counts[(size_t)r * world + s];
+  return n;
+}
+inline Growth capacity_check(int world, const int64_t *counts, const int64_t *live, const int64_t *cap) {
+  Growth g;
+  for (int r = 0; r < world; r++) {
+    const int64_t n = live_after(world, counts, live, r);
+    if (n > cap[r]) { g.rank = r; g.need = n; g.excess = n - cap[r]; return g; }
+  }
+  return g;
+}
+// The table of a redistribution's scan carries two words more than a migration's, in places a migration leaves idle: the diagonal
+// counts[r][r] = rank r's live records, and the speed word = its capacity.  Takes them out of the [world][ROW] words (h is changed:
+// what is left decodes as a migration table without a speed).
+inline void split_recut_table(uint32_t *h, int world, int64_t *live, int64_t *cap) {
+  for (int r = 0; r < world; r++) {
+    uint32_t *row = h + (size_t)r * ROW;
+    live[r] = row[r]; cap[r] = row[world + 6];
+    row[r] = 0; row[world + 6] = 0;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ schedule

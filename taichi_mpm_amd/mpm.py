@@ -1019,6 +1019,18 @@ class Simulation3D:
                                                   C.byref(total), bounds))
         return hists, np.array(bounds[0:3], np.int64), np.array(bounds[3:6], np.int64), int(total.value)
 
+    def live_histograms(self):
+        """mpmhip_live_histogram: (hists, cell_lo, cell_hi, total), the tuple seed_histograms returns, counted on the device over the
+        live particles this ctx holds — per axis the number of them with their base cell (tiled.base_cells, clamped to the grid) at
+        each index, the bounds of those cells (hi exclusive, all 0 without particles) and their number.  Nothing is written."""
+        self._ensure_ctx()
+        hists = [np.zeros(r, np.int64) for r in self.res]
+        total, bounds = C.c_int64(0), (C.c_int32 * 6)()
+        lp = C.POINTER(C.c_int64)
+        self._check(self._L.mpmhip_live_histogram(self._ctx, hists[0].ctypes.data_as(lp), hists[1].ctypes.data_as(lp),
+                                                  hists[2].ctypes.data_as(lp), C.byref(total), bounds))
+        return hists, np.array(bounds[0:3], np.int64), np.array(bounds[3:6], np.int64), int(total.value)
+
     # ---------------------------------------------------------------- CPIC rigid bodies
     def add_rigid_body(self, cfg):
         """MPM::add_rigid_particle (src/mpm_rigid_body.cpp:130-252) with the keys of the scene scripts

@@ -658,6 +658,59 @@ class _NativeJobBase:
             out.append(e.sim.seed_counts)
         return out
 
+    def rebalance(self, threshold=1.15, force=False):
+        """Re-cut the bricks from the live particles and move every particle to its new owner (collective on a process-per-rank job):
+        the job's live histograms (mpmhip_live_histogram on every rank, summed) -> Partition.from_histograms with the job's dims and
+        margin, clip box from the joined bounds -> the set-up again with the new cuts (the `rewire` path: synchronise, barrier,
+        mpmhip_tiled_setup, connect; the RCCL communicator stays, an IPC arena whose size changed is mapped again) ->
+        mpmhip_tiled_redistribute.  A rank the move would overfill is grown (mpmhip_reserve at the needed capacity plus 1/8) and the
+        redistribution repeated once.
+
+        imbalance = max(live per rank) / mean(live per rank).  Nothing is touched when it is below `threshold` and `force` is not set,
+        when the new cuts equal the current ones, on one rank or without particles.  The default threshold of 1.15 is a starting point,
+        not a measurement: a re-cut costs a set-up and a redistribution, which a job recovers only over many
+        substeps.
+
+        mpmhip_tiled_setup restarts the library's per-plan counters (state()["substeps"], ["migrations"], ["replans"], totals()
+        ["migrated"]), as `rewire` does; job.substeps goes on counting.  The next run() begins with the planning scan.
+
+        Returns dict(recut, imbalance_before, imbalance_after (from the per-rank counts after the move), cuts, moved (records, job-wide),
+        rounds, grew (the ranks that grew))."""
+        from .mpm import MPMError
+        world = self.part.world
+        hists, live = self._job_histograms()
+        total = int(sum(live))
+        imb = float(max(live)) * world / total if total else 1.0
+        out = dict(recut=False, imbalance_before=imb, imbalance_after=imb, cuts=[list(c) for c in self.part.cuts], moved=0, rounds=0, grew=[])
+        if world == 1 or total == 0 or (imb < threshold and not force):
+            return out
+        nz = [np.nonzero(h)[0] for h in hists]
+        new = Partition.from_histograms(self.part.res, world, hists, [int(z[0]) for z in nz], [int(z[-1]) + 1 for z in nz],
+                                        self.part.margin, dims=self.part.dims)
+        if new.cuts == self.part.cuts:
+            return out
+        self._recut(new)
+        grew = set()
+        for attempt in range(2):
+            info, refused = self._redistribute()
+            if not refused:
+                break
+            if attempt == 1:
+                raise MPMError("rebalance: the redistribution was refused again after the ranks grew: " + self._last_errors())
+            for e, row in zip(self.engines, info):
+                if row[3] > 0:
+                    cap = int(row[3]) + int(row[3]) // 8
+                    e.sim._check(e.L.mpmhip_reserve(e.ctx, cap))
+                    e.sim._capacity = max(e.sim._capacity, cap)
+            grew |= set(self._ranks_where([row[3] > 0 for row in info]))
+        after, moved = self._job_counts_after(live, info)
+        out.update(recut=True, cuts=[list(c) for c in new.cuts], moved=int(moved), rounds=int(info[0][2]), grew=sorted(grew),
+                   imbalance_after=float(max(after)) * world / total)
+        return out
+
+    def _last_errors(self):
+        return "; ".join(e.L.mpmhip_last_error(e.ctx).decode() for e in self.engines if e.L.mpmhip_last_error(e.ctx))
+
     @staticmethod
     def _same_job_count(counts):
         if len(set(int(c) for c in counts)) > 1:
@@ -696,11 +749,54 @@ class NativeTiledJob(_NativeJobBase):
         self.part.set_clip_from_bounds([-int(t[0]), -int(t[1]), -int(t[2])], [int(t[3]), int(t[4]), int(t[5])])
         self._connect(wire, self.overlap, use_comm)
 
+    # --- rebalance(): the job-wide sums travel over the control group, as rewire's bounds do
+    def _all_sum(self, values):
+        import torch
+        t = torch.tensor([int(v) for v in values], dtype=torch.int64)
+        if self.world > 1:
+            self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM)
+        return [int(v) for v in t]
+
+    def _job_histograms(self):
+        """(the job's histograms, live particles per rank): ONE all_reduce of [hist x | hist y | hist z | live of each rank]"""
+        hists, _, _, n = self.e.sim.live_histograms()
+        mine = [n if r == self.rank else 0 for r in range(self.world)]
+        flat = self._all_sum([v for h in hists for v in h] + mine)
+        res, at, out = self.part.res, 0, []
+        for a in range(3):
+            out.append(np.asarray(flat[at:at + res[a]], np.int64))
+            at += res[a]
+        return out, flat[at:]
+
+    def _recut(self, new):
+        self.e.synchronize()
+        if self.world > 1:
+            self._dist.barrier()  # (nobody frees or unmaps an arena a peer may still write to)
+        self.part = new
+        self._connect(self.wire, self.overlap, self._use_comm)
+
+    def _redistribute(self):
+        info = (C.c_int64 * 4)()
+        rc = int(self.e.L.mpmhip_tiled_redistribute(self.e.ctx, info))
+        refused = rc == _lib.ECAPACITY
+        if not refused:
+            self.e.sim._check(rc)
+        if self.world > 1:  # every rank repeats or none does
+            refused = self.reduce([1.0 if refused else 0.0], "max")[0] > 0
+        return [list(info)], refused
+
+    def _ranks_where(self, flags):
+        return [r for r, v in enumerate(self._all_sum([1 if (flags[0] and r == self.rank) else 0 for r in range(self.world)])) if v]
+
+    def _job_counts_after(self, live, info):
+        row = self._all_sum([live[r] - info[0][0] + info[0][1] if r == self.rank else 0 for r in range(self.world)] + [info[0][0]])
+        return row[:-1], row[-1]
+
     def _connect(self, wire, overlap, use_comm):
         import torch
         engine, part, rank, world, dist = self.e, self.part, self.rank, self.world, self._dist
         migrate_interval, inbox_records = self._setup_args
-        self.wire = wire
+        self.wire, self._use_comm = wire, use_comm
         L, sim = engine.L, engine.sim
         need_comm = (wire == "rccl" or (wire == "ipc" and use_comm)) and not self._have_comm
         if need_comm:
@@ -783,17 +879,49 @@ class NativeVirtualJob(_NativeJobBase):
         communicator and its halo boxes travel as RCCL self-sends aimed at the peer ctx's receive buffer (include/mpmhip.h)"""
         assert len(engines) == part.world
         self.engines, self.part = list(engines), part
+        self._setup_args = (migrate_interval, inbox_records, halo_by_rccl)
         if halo_by_rccl:
             for e in engines:
                 ident = (C.c_uint8 * _lib.COMM_ID_BYTES)()
                 e.sim._check(e.L.mpmhip_comm_unique_id(ident))
                 e.sim._check(e.L.mpmhip_comm_init(e.ctx, ident, 0, 1))
-        for r, e in enumerate(engines):
-            native_setup(e, part, r, _lib.WIRE_LOCAL_RCCL if halo_by_rccl else _lib.WIRE_LOCAL, migrate_interval, overlap, inbox_records)
         self._arr = (C.c_void_p * len(engines))(*[e.ctx for e in engines])
+        self._connect(overlap)
+
+    def _connect(self, overlap):
+        migrate_interval, inbox_records, halo_by_rccl = self._setup_args
+        engines = self.engines
+        for r, e in enumerate(engines):
+            native_setup(e, self.part, r, _lib.WIRE_LOCAL_RCCL if halo_by_rccl else _lib.WIRE_LOCAL, migrate_interval, overlap, inbox_records)
         L = engines[0].L
         self._group_check(L.mpmhip_tiled_connect_local(self._arr, len(engines)), "mpmhip_tiled_connect_local")
         self.overlap = bool(overlap)
+
+    # --- rebalance(): all ranks live here, the sums are numpy's
+    def _job_histograms(self):
+        rows = [e.sim.live_histograms() for e in self.engines]
+        return [sum(row[0][a] for row in rows) for a in range(3)], [row[3] for row in rows]
+
+    def _recut(self, new):
+        self.synchronize()
+        self.part = new
+        self._connect(self.overlap)  # (the one-rank communicators of halo_by_rccl stay)
+
+    def _redistribute(self):
+        K = len(self.engines)
+        info = (C.c_int64 * (4 * K))()
+        rc = int(self.engines[0].L.mpmhip_tiled_redistribute_group(self._arr, K, info))
+        if rc != _lib.ECAPACITY:
+            self._group_check(rc, "mpmhip_tiled_redistribute_group")
+        return [list(info[4 * r:4 * r + 4]) for r in range(K)], rc == _lib.ECAPACITY
+
+    @staticmethod
+    def _ranks_where(flags):
+        return [r for r, v in enumerate(flags) if v]
+
+    @staticmethod
+    def _job_counts_after(live, info):
+        return [n - row[0] + row[1] for n, row in zip(live, info)], sum(row[0] for row in info)
 
     def _group_check(self, rc, what):
         if rc < 0:  # (the failing ctx holds the message; the others may hold older ones)
@@ -847,6 +975,12 @@ class NativeVirtualJob(_NativeJobBase):
 
 
 # ---------------------------------------------------------------------------------------------------- scenes seeded on the device
+def live_histograms(sim):
+    """(hists, cell_lo, cell_hi, total) of the live particles `sim` holds — counted on the device (mpmhip_live_histogram): the tuple
+    seed_histograms returns, for a job that is already running.  Several ranks: add the histograms, join the bounds."""
+    return sim.live_histograms()
+
+
 def seed_histograms(sim, cfg):
     """(hists, cell_lo, cell_hi, total) of the particles add_particles(cfg) with a region= would create — counted on the device
     (mpmhip_seed_histogram), nothing added: the arguments of Partition.from_histograms.  Several regions: add the histograms, join
