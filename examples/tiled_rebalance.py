@@ -4,8 +4,12 @@ histograms counted on the device, mpmhip_live_histogram; new cuts, tiled.Partiti
 to its new owner, mpmhip_tiled_redistribute).  The per-rank counts are printed before and after each re-cut.  The ranks of a
 multi-GPU job make the same calls, one per process (tiled.NativeTiledJob.rebalance is the collective).  Needs an MI355X.
 
-    python examples/tiled_rebalance.py [frames]
+    python examples/tiled_rebalance.py [frames] [--frames DIR]
+
+--frames DIR: job.visualize() after every frame — DIR/0001.bgeo, 0002.bgeo, ...: ONE file per frame for all 8 ranks, the rows in
+ascending creation id (the ids are ranked on the device, mpmhip_bgeo_encode_group).
 """
+import argparse
 import os
 import sys
 
@@ -14,7 +18,11 @@ import taichi_mpm_amd as tm  # noqa: E402
 from taichi_mpm_amd import tiled  # noqa: E402
 
 if __name__ == '__main__':
-    frames = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    ap = argparse.ArgumentParser()
+    ap.add_argument('count', nargs='?', type=int, default=10, help='frames to run')
+    ap.add_argument('--frames', metavar='DIR', help='write DIR/0001.bgeo, 0002.bgeo, ... after every frame')
+    args = ap.parse_args()
+    frames = args.count
     r, world, margin = 64, 8, 2
     dx = 1.0 / r
     sim_cfg = dict(res=(r, r, r), delta_x=dx, base_delta_t=1e-4, gravity=(0, -10, 0))
@@ -34,6 +42,7 @@ if __name__ == '__main__':
     floor = LS(friction=0.4).add_plane((0, 1, 0), d=-0.2)
     sims = tiled.build_seeded_rank_sims(tm, [ball], part, levelset=floor, **sim_cfg)
     job = tiled.NativeVirtualJob([tiled.HipEngine(s, 0) for s in sims], part)
+    job.frame_directory = args.frames
     for frame in range(frames):
         job.add_particles(jet)  # every rank: the same call; the jet lands in the bricks under the nozzle
         job.run(10)  # delta_t of the emitter = 10 substeps
@@ -45,6 +54,8 @@ if __name__ == '__main__':
             print("         re-cut %s: per rank %s (max / mean %.3f), %d records moved in %d round(s)%s" % (
                 res["cuts"], after, res["imbalance_after"], res["moved"], res["rounds"],
                 ", ranks %s grew" % res["grew"] if res["grew"] else ""))
+        if args.frames:
+            print("         wrote %s" % job.visualize())
     tot = job.totals()
     print("job: %d particles after %d substeps, error word %d" % (tot["particles"], job.substeps, tot["error"]))
     del job

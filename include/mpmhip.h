@@ -362,11 +362,50 @@ int mpmhip_delete_particles_inside_level_set(mpmhip_ctx *ctx, int64_t *deleted);
  * (no rigid bodies, no async stepping) hold the reference's constructor values (src/particles.h:92-99).
  * mpmhip_bgeo_size: bytes of the file for the current state.  mpmhip_bgeo_encode: the file image into caller memory
  * (*written = bytes; MPMHIP_ECAPACITY if `capacity` is too small).  mpmhip_write_bgeo: the same to `path` (plain
- * .bgeo as the reference writes; a ".gz" suffix is MPMHIP_ENOTIMPL).  A tiled ctx encodes its own rank's particles.
- * All three synchronise. */
+ * .bgeo as the reference writes; a ".gz" suffix is MPMHIP_ENOTIMPL).  On a tiled ctx these three encode its own rank's particles; the one file
+ * of the whole job comes from the calls under "the frame of a tiled job" below.  All three synchronise. */
 int mpmhip_bgeo_size(mpmhip_ctx *ctx, int32_t verbose, size_t *bytes);
 int mpmhip_bgeo_encode(mpmhip_ctx *ctx, int32_t verbose, void *dst, size_t capacity, size_t *written);
 int mpmhip_write_bgeo(mpmhip_ctx *ctx, const char *path, int32_t verbose);
+
+/* the frame of a tiled job — MPM<dim>::write_partio (src/visualize.cpp:17-100) writes ONE file for all particles: one header, the
+ * rows in ascending creation id, one trailer whose point numbers are uint16 up to 65536 rows and int32 above.  The ranks of a tiled
+ * job each hold some of the ids, in any slot order, so the row number of a particle is the rank of its id among all live ids of
+ * the job.  It is computed on the device: top = 1 + the largest live id, a bitmap of ceil(top / 32) words in which every ctx sets
+ * the bits of its ids, the exclusive prefix of the words' popcounts, and row(id) = prefix[id / 32] + popcount of the lower bits
+ * of its word.  No id array reaches the host.
+ *
+ * mpmhip_bgeo_size_group / mpmhip_bgeo_encode_group (src/visualize.cpp:17-100): the n_ctx ctx of ONE process on ONE device (the
+ * convention of mpmhip_tiled_advance_group), which need not be connected as a job nor hold a set partition.  The image is, byte
+ * for byte, the file one ctx holding the same records would encode; n_ctx = 1 gives that ctx's file.  MPMHIP_EINVAL: ctx on
+ * different devices, ctx of different res, a ctx with rigid bodies or a resident asynchronous stepper, a creation id held by two
+ * slots (the message, on ctxs[0], names it; nothing has been written to dst).  MPMHIP_ECAPACITY as mpmhip_bgeo_encode.  Both
+ * synchronise every ctx. */
+int mpmhip_bgeo_size_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int32_t verbose, size_t *bytes);
+int mpmhip_bgeo_encode_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int32_t verbose, void *dst, size_t capacity, size_t *written);
+/* the same for a rank per process (src/visualize.cpp:17-100), in three steps without a collective inside; the caller reduces
+ * between them and places the rows:
+ *   mpmhip_live_id_top       1 + the largest live creation id of this ctx (0: no particle), or a negative error.  The id counter is
+ *                            no substitute: after mpmhip_upload(MPMHIP_F_ID) it may lie below the ctx's largest id (mpmhip_set_next_id).
+ *                            The job's top is the maximum over the ranks.
+ *   mpmhip_id_bitmap         this ctx's bitmap for the job's `top` into words_host[ceil(top / 32)], *live = its live particles.  An id
+ *                            at or beyond top, or held twice on this ctx: MPMHIP_EINVAL.  The job's bitmap is the OR over the ranks
+ *                            (the bits of a valid job are disjoint: the popcount of the OR equals the sum of the `live`).
+ *   mpmhip_bgeo_rows_ranked  this ctx's rows (12 words each, 23 verbose) in ascending id into rows_host, and into row_index_host for
+ *                            each its row number in the job's file, given the job's bitmap; *written = the rows.
+ *                            MPMHIP_ECAPACITY when capacity_rows is below the ctx's live particles, MPMHIP_EINVAL when the ctx
+ *                            holds an id the job's bitmap lacks.
+ * All three synchronise. */
+int64_t mpmhip_live_id_top(mpmhip_ctx *ctx);
+int mpmhip_id_bitmap(mpmhip_ctx *ctx, int64_t top, uint32_t *words_host, int64_t *live);
+int mpmhip_bgeo_rows_ranked(mpmhip_ctx *ctx, int32_t verbose, int64_t top, const uint32_t *union_words_host, void *rows_host,
+                            uint32_t *row_index_host, int64_t capacity_rows, int64_t *written);
+/* what stands before and behind n rows of a frame (src/visualize.cpp:17-100 through BGEO.cpp:57-194): the header and attribute
+ * tables, and the primitive attribute, the point numbers and the file's end — the bytes mpmhip_bgeo_encode writes there, from the
+ * same functions.  Host only: no ctx, no device.  head = tail = NULL: the two sizes alone.  MPMHIP_ECAPACITY when a buffer is
+ * too small (message: mpmhip_last_error(NULL)). */
+int mpmhip_bgeo_envelope(uint32_t n, int32_t verbose, void *head, size_t head_cap, size_t *head_bytes, void *tail, size_t tail_cap,
+                         size_t *tail_bytes);
 
 /* profiling — replaces TC_PROFILE / TC_PROFILE_TPE scoped timers (src/mpm.cpp:464-572).
  * level 0: off.  level 1: hipEvents bracket each phase of every substep on the ctx stream (six records per
@@ -1095,6 +1134,9 @@ int mpmhip_debug_gather_bandwidth(mpmhip_ctx *ctx, int64_t n_records, int32_t mo
  * together; the halo arena of a tiled ctx is not counted).  An object gives back what it took when the number after its destroy
  * is the number before its create.  No device call. */
 int64_t mpmhip_debug_live_buffers(void);
+/* milliseconds of the phases of the last mpmhip_bgeo_encode_group of this process, between events on its stream (src/visualize.cpp:
+ * 17-100 has no counterpart: a measuring aid): top, mark, prefix, rows, copy to the host. */
+int mpmhip_debug_frame_phases(double ms[5]);
 
 /* debug/parity helpers running the device math on host arrays (n items each) */
 int mpmhip_debug_svd3(mpmhip_ctx *ctx, int64_t n, const float *F, float *U, float *S, float *V);

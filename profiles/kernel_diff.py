@@ -1,6 +1,6 @@
 """Which device kernels differ between two builds of libmpmhip.so?
     python profiles/kernel_diff.py old/libmpmhip.so new/libmpmhip.so
-Extracts the gfx950 code object of each library (llvm-objdump --offloading), disassembles it and compares every kernel's
+Extracts the gfx950 code objects of each library (llvm-objdump --offloading), disassembles it and compares every kernel's
 instruction stream.  Used to check that an edit meant to be a no-op for the tuned kernels really is one before spending GPU
 time on it — it is not always: removing ONE unused variable from k_g2p changed its register allocation (5610 -> 5611
 instructions), so the variable stayed (k_g2p.h)."""
@@ -19,8 +19,8 @@ def kernels(lib):
     try:
         shutil.copy(lib, os.path.join(d, "lib.so"))
         subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=d, check=True, stdout=subprocess.DEVNULL)
-        co = [f for f in os.listdir(d) if f.endswith("gfx950")][0]
-        txt = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], cwd=d, check=True, capture_output=True, text=True).stdout
+        txt = "\n".join(subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], cwd=d, check=True, capture_output=True, text=True).stdout
+                        for co in sorted(f for f in os.listdir(d) if f.endswith("gfx950")))  # one code object per translation unit
     finally:
         shutil.rmtree(d)
     parts = re.split(r"^[0-9a-f]+ <([^>]+)>:$", txt, flags=re.M)
@@ -35,8 +35,8 @@ def kernel_stats(lib):
     try:
         shutil.copy(lib, os.path.join(d, "lib.so"))
         subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=d, check=True, stdout=subprocess.DEVNULL)
-        co = [f for f in os.listdir(d) if f.endswith("gfx950")][0]
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], cwd=d, check=True, capture_output=True, text=True).stdout
+        notes = "\n".join(subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], cwd=d, check=True, capture_output=True, text=True).stdout
+                          for co in sorted(f for f in os.listdir(d) if f.endswith("gfx950")))  # one code object per translation unit
     finally:
         shutil.rmtree(d)
     out, cur = {}, None

@@ -7,7 +7,10 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SRC = os.path.join(_HERE, "csrc", "mpmhip.hip")
-_DEPS = [_SRC, os.path.join(_ROOT, "include", "mpmhip.h")] + sorted(
+# the translation units of the library: the second holds the kernels of a job's frame alone, in a code object of their own, so
+# that the code object with the substep's kernels does not move when they change (csrc/frame_launch.h)
+_SRCS = [_SRC, os.path.join(_HERE, "csrc", "k_frame.hip")]
+_DEPS = _SRCS + [os.path.join(_ROOT, "include", "mpmhip.h")] + sorted(
     os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith(".h"))
 _LIBDIR = os.path.join(_HERE, "lib")
 # MPMHIP_LIB_VARIANT=<name> loads lib/libmpmhip_<name>.so: an A/B build of the same sources with extra -D flags
@@ -16,6 +19,7 @@ _VARIANT = os.environ.get("MPMHIP_LIB_VARIANT", "")
 _LIB = os.path.join(_LIBDIR, "libmpmhip%s.so" % (("_" + _VARIANT) if _VARIANT else ""))
 
 NPARAM = 16
+BGEO_W_PLAIN, BGEO_W_VERBOSE = 12, 23  # 32-bit words per row of a .bgeo frame (csrc/k_bgeo.h)
 
 # (-munsafe-fp-atomics: hardware float atomics for the 2D solvers' grid scatter (k_mpm88.h, k_mpm2d.h) and for the impulses a
 # particle hands to a rigid body (k_rigid.h); the 3D transfers themselves use no float atomics)
@@ -204,12 +208,12 @@ def _hipcc():
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/mpmhip.hip for gfx950 into lib/libmpmhip.so (in-tree, so it ships with the snapshot)."""
+    """Compile csrc/mpmhip.hip and csrc/k_frame.hip for gfx950 into lib/libmpmhip.so (in-tree, so it ships with the snapshot)."""
     os.makedirs(_LIBDIR, exist_ok=True)
     if not force and os.path.exists(_LIB):
         if all(os.path.getmtime(_LIB) >= os.path.getmtime(d) for d in _DEPS):
             return _LIB
-    cmd = [_hipcc()] + HIPCC_FLAGS + [_SRC, "-o", _LIB]
+    cmd = [_hipcc()] + HIPCC_FLAGS + _SRCS + ["-o", _LIB]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -220,7 +224,7 @@ def build_variant(name, extra_flags):
     """lib/libmpmhip_<name>.so from the same sources with extra compiler flags (A/B timing on one box)"""
     os.makedirs(_LIBDIR, exist_ok=True)
     out = os.path.join(_LIBDIR, "libmpmhip_%s.so" % name)
-    subprocess.check_call([_hipcc()] + HIPCC_FLAGS + list(extra_flags) + [_SRC, "-o", out])
+    subprocess.check_call([_hipcc()] + HIPCC_FLAGS + list(extra_flags) + _SRCS + ["-o", out])
     return out
 
 
@@ -230,7 +234,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip_add_group", "mpmhip_add_particles", "mpmhip_poisson_tile", "mpmhip_seed_particles", "mpmhip_num_particles", "mpmhip_download",
             "mpmhip_upload", "mpmhip_substep", "mpmhip_run_substeps", "mpmhip_step", "mpmhip_current_time",
             "mpmhip_synchronize", "mpmhip_sort", "mpmhip_p2g", "mpmhip_grid_update", "mpmhip_g2p",
-            "mpmhip_download_grid", "mpmhip_upload_grid", "mpmhip_calculate_energy", "mpmhip_snapshot_size", "mpmhip_snapshot_save", "mpmhip_snapshot_load", "mpmhip_delete_particles_inside_level_set", "mpmhip_bgeo_size", "mpmhip_bgeo_encode", "mpmhip_write_bgeo", "mpmhip_set_profiling", "mpmhip_profile",
+            "mpmhip_download_grid", "mpmhip_upload_grid", "mpmhip_calculate_energy", "mpmhip_snapshot_size", "mpmhip_snapshot_save", "mpmhip_snapshot_load", "mpmhip_delete_particles_inside_level_set", "mpmhip_bgeo_size", "mpmhip_bgeo_encode", "mpmhip_write_bgeo", "mpmhip_bgeo_size_group", "mpmhip_bgeo_encode_group", "mpmhip_live_id_top", "mpmhip_id_bitmap", "mpmhip_bgeo_rows_ranked", "mpmhip_bgeo_envelope", "mpmhip_set_profiling", "mpmhip_profile",
             "mpmhip_profile_reset", "mpmhip_set_partition", "mpmhip_set_halo", "mpmhip_halo_pack",
             "mpmhip_substep_begin", "mpmhip_substep_end", "mpmhip_substep_interior", "mpmhip_set_overlap", "mpmhip_tiled_run", "mpmhip_leaver_counts", "mpmhip_migration_scan", "mpmhip_export_leavers",
             "mpmhip_comm_unique_id", "mpmhip_comm_init", "mpmhip_comm_destroy", "mpmhip_comm_selftest", "mpmhip_tiled_setup", "mpmhip_tiled_ipc_handle",
@@ -251,7 +255,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip_add_articulation", "mpmhip_num_articulations", "mpmhip_set_articulation_iterations", "mpmhip_articulate",
             "mpmhip_download_boundary",
             "mpmhip_set_rigid_collision", "mpmhip_rigidify", "mpmhip_rigid_get_collisions", "mpmhip_rigid_get_hull", "mpmhip_rigid_mpr_test",
-            "mpmhip_debug_copy_bandwidth", "mpmhip_debug_live_buffers", "mpmhip_debug_g2p_is_packed", "mpmhip_debug_transfer_plan", "mpmhip_debug_scan_grid", "mpmhip_debug_cond_census", "mpmhip_debug_sort_info", "mpmhip_debug_sort_array", "mpmhip_debug_gather_bandwidth", "mpmhip_debug_svd3", "mpmhip_debug_force", "mpmhip_debug_plasticity"]
+            "mpmhip_debug_copy_bandwidth", "mpmhip_debug_live_buffers", "mpmhip_debug_frame_phases", "mpmhip_debug_g2p_is_packed", "mpmhip_debug_transfer_plan", "mpmhip_debug_scan_grid", "mpmhip_debug_cond_census", "mpmhip_debug_sort_info", "mpmhip_debug_sort_array", "mpmhip_debug_gather_bandwidth", "mpmhip_debug_svd3", "mpmhip_debug_force", "mpmhip_debug_plasticity"]
 
 
 def exported_symbols():
@@ -489,6 +493,14 @@ def load():
     L.mpmhip_bgeo_size.argtypes = [vp, C.c_int32, P(C.c_size_t)]
     L.mpmhip_bgeo_encode.argtypes = [vp, C.c_int32, C.c_void_p, C.c_size_t, P(C.c_size_t)]
     L.mpmhip_write_bgeo.argtypes = [vp, C.c_char_p, C.c_int32]
+    L.mpmhip_bgeo_size_group.argtypes = [P(vp), C.c_int32, C.c_int32, P(C.c_size_t)]
+    L.mpmhip_bgeo_encode_group.argtypes = [P(vp), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, P(C.c_size_t)]
+    L.mpmhip_live_id_top.argtypes = [vp]
+    L.mpmhip_live_id_top.restype = C.c_int64
+    L.mpmhip_id_bitmap.argtypes = [vp, C.c_int64, C.c_void_p, P(C.c_int64)]
+    L.mpmhip_bgeo_rows_ranked.argtypes = [vp, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+    L.mpmhip_bgeo_envelope.argtypes = [C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t, P(C.c_size_t), C.c_void_p, C.c_size_t, P(C.c_size_t)]
+    L.mpmhip_debug_frame_phases.argtypes = [P(C.c_double)]
     L.mpmhip_snapshot_size.argtypes = [vp]
     L.mpmhip_snapshot_size.restype = C.c_int64
     L.mpmhip_snapshot_save.argtypes = [vp, vp, C.c_size_t]

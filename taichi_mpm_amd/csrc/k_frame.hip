@@ -1,0 +1,32 @@
+// taichi_mpm_amd/csrc/k_frame.hip — the kernels of a job's frame (k_frame.h) and their launchers (frame_launch.h): the second
+// translation unit of libmpmhip.so, with a code object of its own.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/mpmhip.h"
+#define MPM_BGEO_ROW_ONLY  // of k_bgeo.h: bgeo_row, not the one-ctx kernels
+#include "k_frame.h"
+
+namespace mpm {
+
+void frame_launch_top(hipStream_t st, int grid, uint32_t n_slots, const RecG *rg, uint32_t *top) {
+  hipLaunchKernelGGL(k_live_id_top, dim3(grid), dim3(FRAME_WG), 0, st, n_slots, rg, top);
+}
+void frame_launch_mark(hipStream_t st, int grid, uint32_t n_slots, const RecG *rg, uint32_t top, uint32_t *bits, uint32_t *live, int32_t *err) {
+  hipLaunchKernelGGL(k_id_mark, dim3(grid), dim3(FRAME_WG), 0, st, n_slots, rg, top, bits, live, err);
+}
+void frame_launch_prefix(hipStream_t st, uint32_t n_words, uint32_t n_blocks, const uint32_t *bits, uint32_t *sums, uint32_t *prefix) {
+  hipLaunchKernelGGL(k_id_prefix_sums, dim3(n_blocks), dim3(FRAME_WG), 0, st, n_words, bits, sums);
+  hipLaunchKernelGGL(k_id_prefix_scan, dim3(1), dim3(FRAME_WG), 0, st, n_blocks, sums);
+  hipLaunchKernelGGL(k_id_prefix_add, dim3(n_blocks), dim3(FRAME_WG), 0, st, n_words, bits, (const uint32_t *)sums, prefix);
+}
+void frame_launch_rows(hipStream_t st, int grid, bool verbose, uint32_t n_slots, const RecG *rg, const RecP *rp, const float *rb,
+                       const GroupParams *groups, const int32_t *limits, uint32_t top, const uint32_t *bits, const uint32_t *prefix,
+                       uint32_t n_rows, uint32_t *rows, const uint32_t *job_bits, const uint32_t *job_prefix, uint32_t *row_index, int32_t *err) {
+  auto k = verbose ? k_bgeo_rows_ranked<true> : k_bgeo_rows_ranked<false>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(FRAME_WG), 0, st, n_slots, rg, rp, rb, groups, limits, top, bits, prefix, n_rows, rows, job_bits, job_prefix,
+                     row_index, err);
+}
+
+}  // namespace mpm

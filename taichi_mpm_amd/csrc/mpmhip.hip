@@ -4,7 +4,7 @@
 //   k_sort.h  k_p2g.h  k_grid.h  k_g2p.h  k_tiling.h  k_particles.h  k_debug.h
 //   k_seed.h (particle seeding from the periodic Poisson-disk tiles, poisson_tile.h; both dimensions)
 //   k_region.h (region expressions: CSG programs over level-set leaves, the region of a seeding call or sampled on a lattice)
-//   k_bgeo.h (.bgeo frame rows)   k_mpm88.h (the 2D dense-grid demo, its own small object)
+//   k_bgeo.h (.bgeo frame rows)   k_frame.h (the rows of a whole job, ranked by id: its own translation unit, k_frame.hip)   k_mpm88.h (the 2D dense-grid demo, its own small object)
 // host_mem.h: DevBuf / PinnedBuf, the owners of every device and pinned array of the objects below (a new array needs a field and
 // its allocation, nothing else); what a kernel takes by value keeps raw pointers into them.
 // record_state.h: RecordState, the owner of the ctx's validity flags (which arrays describe the current particles); the host code
@@ -105,6 +105,7 @@
 #include "k_region.h"
 #include "poisson_tile.h"
 #include "k_bgeo.h"
+#include "frame_launch.h"
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
 #include "k_mpm2d_det.h"
@@ -618,10 +619,27 @@ std::vector<uint8_t> bgeo_prim_attr() {  // the "generator" = "papi" primitive a
   put32(o, 0x8000);
   return o;
 }
+// what follows the rows: the primitive attribute, the particle system's point numbers and the file's end
+size_t bgeo_tail_bytes(uint32_t n) { return bgeo_prim_attr().size() + 4 + (size_t)n * (n > (1u << 16) ? 4 : 2) + 4 + 2; }
+uint8_t *bgeo_put_tail(uint8_t *out, uint32_t n) {
+  const std::vector<uint8_t> prim = bgeo_prim_attr();
+  std::memcpy(out, prim.data(), prim.size());
+  out += prim.size();
+  auto w32 = [&](uint32_t v) { for (int s = 24; s >= 0; s -= 8) *out++ = (uint8_t)(v >> s); };
+  w32(n);
+  if (n > (1u << 16)) {  // BGEO.cpp:175-180: point numbers as int32 above 65536 points, uint16 otherwise
+    for (uint32_t i = 0; i < n; i++) w32(i);
+  } else {
+    for (uint32_t i = 0; i < n; i++) { *out++ = (uint8_t)(i >> 8); *out++ = (uint8_t)i; }
+  }
+  w32(0);
+  *out++ = 0x00;
+  *out++ = 0xff;
+  return out;
+}
 size_t bgeo_bytes(uint32_t n, bool verbose) {
   const size_t w = verbose ? BGEO_W_VERBOSE : BGEO_W_PLAIN;
-  return bgeo_header(n, verbose).size() + (size_t)n * w * 4 + bgeo_prim_attr().size() + 4 +
-         (size_t)n * (n > (1u << 16) ? 4 : 2) + 4 + 2;
+  return bgeo_header(n, verbose).size() + (size_t)n * w * 4 + bgeo_tail_bytes(n);
 }
 }  // namespace
 
@@ -1896,20 +1914,7 @@ int mpmhip_bgeo_encode(mpmhip_ctx *c, int32_t verbose, void *dst, size_t capacit
       ir++;
     }
   }
-  out += row_bytes;
-  const std::vector<uint8_t> prim = bgeo_prim_attr();
-  std::memcpy(out, prim.data(), prim.size());
-  out += prim.size();
-  auto w32 = [&](uint32_t v) { for (int s = 24; s >= 0; s -= 8) *out++ = (uint8_t)(v >> s); };
-  w32(n);
-  if (n > (1u << 16)) {  // BGEO.cpp:175-180: point numbers as int32 above 65536 points, uint16 otherwise
-    for (uint32_t i = 0; i < n; i++) w32(i);
-  } else {
-    for (uint32_t i = 0; i < n; i++) { *out++ = (uint8_t)(i >> 8); *out++ = (uint8_t)i; }
-  }
-  w32(0);
-  *out++ = 0x00;
-  *out++ = 0xff;
+  out = bgeo_put_tail(out + row_bytes, n);
   *written = (size_t)(out - static_cast<uint8_t *>(dst));
   if (*written != total) return fail(c, MPMHIP_EINVAL, "internal: bgeo image is %zu bytes, expected %zu", *written, total);
   return MPMHIP_OK;
@@ -3576,6 +3581,7 @@ int mpmhip2d_download_grid(mpmhip2d_ctx *m, float *grid) {  // (v.x, v.y, m) per
 
 #include "async_api.h"
 #include "frame2d_api.h"
+#include "frame_job_api.h"
 // snapshot_blob.h: its copies of the device-side record geometry
 static_assert(snap::RECG_BYTES == sizeof(RecG) && snap::RECP_BYTES == sizeof(RecP) && snap::BROW_BYTES == sizeof(float) * BW, "snapshot_blob.h: records");
 static_assert(snap::RECG_GID == offsetof(RecG, gid) && snap::RECG_PID == offsetof(RecG, pid), "snapshot_blob.h: ids of a RecG");

@@ -708,6 +708,35 @@ class _NativeJobBase:
                    imbalance_after=float(max(after)) * world / total)
         return out
 
+    # --- frames of the whole job (src/visualize.cpp:17-100: one file, rows in ascending creation id)
+    def _frame_defaults(self):
+        sim = self.engines[0].sim
+        self.frame_directory = getattr(sim, "frame_directory", None)
+        self.verbose_bgeo = bool(getattr(sim, "verbose_bgeo", False))
+        self.frame_count = 0  # src/mpm.h:334
+
+    def visualize(self):
+        """the next `frame_directory/%04d.bgeo` of the WHOLE job, frame numbers starting at 1 (Simulation3D.visualize).  On a
+        rank-per-process job a collective: rank 0 writes and returns the path, the other ranks return None."""
+        if not self.frame_directory:
+            from .mpm import MPMError
+            raise MPMError("visualize() needs frame_directory (config key of rank 0's simulation, or set it on the job)")
+        self.frame_count += 1
+        path = os.path.join(self.frame_directory, "%04d.bgeo" % self.frame_count)
+        return path if self.write_partio(path) else None
+
+    def write_partio(self, path):
+        """the job's .bgeo file to `path` (collective on a rank-per-process job: rank 0 writes).  True where the file was written."""
+        data = self.bgeo_bytes()
+        if data is None:
+            return False
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(data)
+        return True
+
     def _last_errors(self):
         return "; ".join(e.L.mpmhip_last_error(e.ctx).decode() for e in self.engines if e.L.mpmhip_last_error(e.ctx))
 
@@ -728,6 +757,7 @@ class NativeTiledJob(_NativeJobBase):
                  use_comm=None):
         self.engines, self.e, self.part, self.rank, self.world = [engine], engine, part, rank, world
         self._dist, self._setup_args, self._have_comm = dist, (migrate_interval, inbox_records), False
+        self._frame_defaults()
         self._connect(wire, overlap, use_comm)
 
     def rewire(self, wire, use_comm=None):
@@ -852,6 +882,59 @@ class NativeTiledJob(_NativeJobBase):
     def num_particles(self):
         return self.e.num_particles()
 
+    def bgeo_bytes(self, verbose=None):
+        """the .bgeo image of the WHOLE job (collective): bytes on rank 0, None on the other ranks.  Every rank ranks its ids on its
+        device (mpmhip_live_id_top -> mpmhip_id_bitmap -> mpmhip_bgeo_rows_ranked); between the steps the control group carries
+        top (the job's reduce), the bitmaps (ONE all_reduce: the bits are disjoint, so the sum of the bytes is the union) and the
+        counts (all_gather); rows and row numbers go to rank 0, which places them (assemble_frame).  An id held twice makes the
+        ranks' counts exceed the popcount of the union: MPMError on every rank."""
+        from .mpm import MPMError
+        e, L, sim, dist, world = self.e, self.e.L, self.e.sim, self._dist, self.world
+        verbose = int(self.verbose_bgeo if verbose is None else verbose)
+        width = 4 * (_lib.BGEO_W_VERBOSE if verbose else _lib.BGEO_W_PLAIN)
+        top = int(sim._check(L.mpmhip_live_id_top(e.ctx)))
+        if world > 1:
+            top = int(self.reduce([float(top)], "max")[0])  # (ids stay below 2^31: exact in a double)
+        words = np.zeros((top + 31) // 32, np.uint32)
+        live = C.c_int64()
+        sim._check(L.mpmhip_id_bitmap(e.ctx, top, words.ctypes.data_as(C.c_void_p), C.byref(live)))
+        counts = [int(live.value)]
+        if world > 1:
+            import torch
+            if words.size:
+                dist.all_reduce(torch.from_numpy(words.view(np.uint8)), op=dist.ReduceOp.SUM)
+            rows = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(rows, torch.tensor([counts[0]], dtype=torch.int64))
+            counts = [int(r[0]) for r in rows]
+        held = int(np.unpackbits(words.view(np.uint8)).sum(dtype=np.int64)) if words.size else 0
+        if sum(counts) != held:
+            raise MPMError("frame of a tiled job: the ranks hold %d particles but %d different creation ids below %d — an id is held twice "
+                           "(ids uploaded per rank must be unique in the job)" % (sum(counts), held, top))
+        n = counts[self.rank]
+        mine = np.empty((n, width), np.uint8)
+        index = np.empty(n, np.uint32)
+        written = C.c_int64()
+        sim._check(L.mpmhip_bgeo_rows_ranked(e.ctx, verbose, top, words.ctypes.data_as(C.c_void_p), mine.ctypes.data_as(C.c_void_p),
+                                             index.ctypes.data_as(C.c_void_p), n, C.byref(written)))
+        if written.value != n:
+            raise MPMError("frame of a tiled job: rank %d encoded %d rows of %d particles" % (self.rank, written.value, n))
+        parts = [(index, mine)]
+        if world > 1:
+            import torch
+            if self.rank != 0:
+                if n:
+                    dist.send(torch.from_numpy(index.view(np.uint8)), dst=0)
+                    dist.send(torch.from_numpy(mine.reshape(-1)), dst=0)
+                return None
+            for r in range(1, world):
+                idx, rws = np.empty(counts[r], np.uint32), np.empty((counts[r], width), np.uint8)
+                if counts[r]:
+                    dist.recv(torch.from_numpy(idx.view(np.uint8)), src=r)
+                    dist.recv(torch.from_numpy(rws.reshape(-1)), src=r)
+                parts.append((idx, rws))
+        head, tail = frame_envelope(held, verbose)
+        return assemble_frame(head, tail, parts, width)
+
     # --- scalars of the WHOLE job, reduced inside the library (mpmhip_tiled_reduce: ncclAllReduce, or rows + epochs over the IPC wire)
     def reduce(self, values, op="sum"):
         """in-place all-reduce of up to 16 doubles over the ranks (collective); returns the reduced list"""
@@ -886,6 +969,7 @@ class NativeVirtualJob(_NativeJobBase):
                 e.sim._check(e.L.mpmhip_comm_unique_id(ident))
                 e.sim._check(e.L.mpmhip_comm_init(e.ctx, ident, 0, 1))
         self._arr = (C.c_void_p * len(engines))(*[e.ctx for e in engines])
+        self._frame_defaults()
         self._connect(overlap)
 
     def _connect(self, overlap):
@@ -967,11 +1051,66 @@ class NativeVirtualJob(_NativeJobBase):
         self._group_check(L.mpmhip_calculate_energy_group(self._arr, len(self.engines), C.byref(k), C.byref(p)), "mpmhip_calculate_energy_group")
         return k.value, p.value
 
+    def bgeo_bytes(self, verbose=None):
+        """the .bgeo image of the WHOLE job as bytes: the file one ctx holding all ranks' records would write (mpmhip_bgeo_encode_group:
+        ids ranked, rows placed and copied on the device)"""
+        L, K = self.engines[0].L, len(self.engines)
+        verbose = int(self.verbose_bgeo if verbose is None else verbose)
+        n, w = C.c_size_t(), C.c_size_t()
+        self._group_check(L.mpmhip_bgeo_size_group(self._arr, K, verbose, C.byref(n)), "mpmhip_bgeo_size_group")
+        buf = np.empty(n.value, np.uint8)
+        self._group_check(L.mpmhip_bgeo_encode_group(self._arr, K, verbose, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(w)),
+                          "mpmhip_bgeo_encode_group")
+        return buf[:w.value].tobytes()
+
     def totals(self):
         out = (C.c_int64 * 4)()
         L = self.engines[0].L
         self._group_check(L.mpmhip_tiled_totals_group(self._arr, len(self.engines), out), "mpmhip_tiled_totals_group")
         return {"particles": int(out[0]), "active_blocks": int(out[1]), "error": int(out[2]), "migrated": int(out[3])}
+
+
+# ---------------------------------------------------------------------------------------------------- frames of a job
+def frame_envelope(n, verbose):
+    """(head, tail) bytes around the n rows of a .bgeo file (mpmhip_bgeo_envelope: host only, no device)"""
+    L = _lib.load()
+    hb, tb = C.c_size_t(), C.c_size_t()
+    rc = L.mpmhip_bgeo_envelope(int(n), int(verbose), None, 0, C.byref(hb), None, 0, C.byref(tb))
+    head, tail = np.empty(hb.value, np.uint8), np.empty(tb.value, np.uint8)
+    if rc == 0:
+        rc = L.mpmhip_bgeo_envelope(int(n), int(verbose), head.ctypes.data_as(C.c_void_p), head.size, C.byref(hb),
+                                    tail.ctypes.data_as(C.c_void_p), tail.size, C.byref(tb))
+    if rc != 0:
+        from .mpm import MPMError
+        raise MPMError("mpmhip_bgeo_envelope failed (%d): %s" % (rc, L.mpmhip_last_error(None).decode()))
+    return head.tobytes(), tail.tobytes()
+
+
+def assemble_frame(head, tail, parts, width):
+    """head + rows + tail, the rows placed by their numbers: parts = [(row numbers [n_r], rows [n_r] of `width` bytes)] of every rank
+    (what mpmhip_bgeo_rows_ranked returns).  The numbers must be exactly 0 .. n - 1, n = the rows of all parts: a number taken
+    twice, or one left out, is refused (MPMError).  Pure: no device, no library."""
+    from .mpm import MPMError
+    n = sum(len(idx) for idx, _ in parts)
+    out = np.empty((n, int(width)), np.uint8)
+    seen, placed = np.zeros(n, bool), 0
+    for r, (idx, rows) in enumerate(parts):
+        idx = np.asarray(idx).astype(np.int64).reshape(-1)
+        rows = np.frombuffer(rows, np.uint8) if isinstance(rows, (bytes, bytearray, memoryview)) else np.asarray(rows, np.uint8)
+        if rows.size != idx.size * int(width):
+            raise MPMError("assemble_frame: part %d has %d row numbers and %d bytes of rows of %d" % (r, idx.size, rows.size, width))
+        if not idx.size:
+            continue
+        if idx.min() < 0 or idx.max() >= n:  # (n numbers, one of them outside 0 .. n - 1: one inside is left out)
+            raise MPMError("assemble_frame: part %d places a row at %d, the frame has %d rows: a row number is left out"
+                           % (r, int(idx.max() if idx.max() >= n else idx.min()), n))
+        taken = seen[idx]
+        seen[idx] = True
+        placed += idx.size
+        if taken.any() or int(np.count_nonzero(seen)) != placed:
+            raise MPMError("assemble_frame: part %d places two rows at one row number (every number must be taken exactly once)" % r)
+        out[idx] = rows.reshape(idx.size, int(width))
+    return bytes(head) + out.tobytes() + bytes(tail)
 
 
 # ---------------------------------------------------------------------------------------------------- scenes seeded on the device
