@@ -7,7 +7,7 @@
 static int64_t frame2d_rows(mpmhip2d_ctx *m) {
   int64_t n = m->async.resident ? mpmhip2d_async_load_pools(m) : mpmhip2d_num_particles(m);
   if (n < 0) return n;
-  if (m->rigid_enabled) n += (int64_t)m->h_smp.size();  // the boundary particles of rigid bodies are rows too (type = 1)
+  if (m->rigid_enabled) n += (int64_t)m->rigid.h_smp.size();  // the boundary particles of rigid bodies are rows too (type = 1)
   return n;
 }
 int mpmhip2d_bgeo_size(mpmhip2d_ctx *m, int32_t verbose, size_t *bytes) {
@@ -47,8 +47,8 @@ static int bgeo2d_encode(mpmhip2d_ctx *m, int32_t verbose, void *dst, size_t cap
   order.reserve(ns);
   for (size_t i = 0; i < ns; i++) if (hp[i] >= 0) order.push_back((uint32_t)i);
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hp[a] < hp[b]; });
-  const bool with_rigid = m->rigid_enabled && !m->h_smp.empty();
-  const uint32_t nm = (uint32_t)order.size(), n = nm + (with_rigid ? (uint32_t)m->h_smp.size() : 0u);
+  const bool with_rigid = m->rigid_enabled && !m->rigid.h_smp.empty();
+  const uint32_t nm = (uint32_t)order.size(), n = nm + (with_rigid ? (uint32_t)m->rigid.h_smp.size() : 0u);
   const size_t total = bgeo_bytes(n, verbose != 0);
   if (total > capacity) return fail2d(m, MPMHIP_ECAPACITY, "bgeo image larger than the buffer");
   std::vector<mpm2d::Rigid2> hb;
@@ -60,49 +60,29 @@ static int bgeo2d_encode(mpmhip2d_ctx *m, int32_t verbose, void *dst, size_t cap
   const size_t W = verbose ? BGEO_W_VERBOSE : BGEO_W_PLAIN;
   auto be32 = [](uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; };
   auto bef = [&](uint8_t *p, float f) { uint32_t u; std::memcpy(&u, &f, 4); be32(p, u); };
-  size_t im = 0, ir = 0;
-  for (uint32_t j = 0; j < n; j++, out += W * 4) {
-    std::memset(out, 0, W * 4);
-    const bool take_rigid = with_rigid && ir < m->h_smp.size() && (im >= nm || m->h_smp_id[ir] < hp[order[im]]);
-    if (take_rigid) {  // position = anchor point, type = 1, v = the body's velocity there; the rest keeps the constructor values
-      const mpm2d::Sample2 &S = m->h_smp[ir];
-      const mpm2d::Rigid2 &B = hb[S.body];
-      const float cs = std::cos(B.angle), sn = std::sin(B.angle);
-      const float r0 = cs * S.off[0] - sn * S.off[1], r1 = sn * S.off[0] + cs * S.off[1];
-      bef(out, r0 + B.pos[0]); bef(out + 4, r1 + B.pos[1]); bef(out + 12, 1.0f);
-      be32(out + 16, 1u); be32(out + 20, (uint32_t)m->h_smp_id[ir]);
-      be32(out + 24, 1u); be32(out + 28, 1u); be32(out + 32, 1u);
-      bef(out + 36, B.vel[0] - B.omega * r1); bef(out + 40, B.vel[1] + B.omega * r0);
-      ir++;
-      continue;
-    }
-    const uint32_t s = order[im++];
-    bef(out, hx[2 * s]); bef(out + 4, hx[2 * s + 1]); bef(out + 12, 1.0f);  // z = 0; homogeneous coordinate (BGEO.cpp:158-160)
-    be32(out + 20, (uint32_t)hp[s]);
+  auto put_material = [&](size_t im, uint8_t *row) {
+    std::memset(row, 0, W * 4);
+    const uint32_t s = order[im];
+    bef(row, hx[2 * s]); bef(row + 4, hx[2 * s + 1]); bef(row + 12, 1.0f);  // z = 0; homogeneous coordinate (BGEO.cpp:158-160)
+    be32(row + 20, (uint32_t)hp[s]);
     uint32_t lim[3] = {1u, 1u, 1u};
     if (!hblk.empty()) { const uint32_t b = hblk[s]; lim[0] = (uint32_t)A.continuous[b]; lim[1] = (uint32_t)A.strength[b]; lim[2] = (uint32_t)A.cfl[b]; }
-    be32(out + 24, lim[0]); be32(out + 28, lim[1]); be32(out + 32, lim[2]);
-    bef(out + 36, hv[2 * s]); bef(out + 40, hv[2 * s + 1]);
+    be32(row + 24, lim[0]); be32(row + 28, lim[1]); be32(row + 32, lim[2]);
+    bef(row + 36, hv[2 * s]); bef(row + 40, hv[2 * s + 1]);
     if (verbose) {
       const GroupParams &gp = m->groups[hg[s]];
-      bef(out + 48, gp.p[0]);  // m
+      bef(row + 48, gp.p[0]);  // m
       const float d0 = gp.type == MPMHIP_WATER ? ha[s] : gp.type == MPMHIP_ELASTIC ? gp.p[4] : 0.0f;  // get_debug_info()
-      bef(out + 64, d0); bef(out + 68, (float)gp.type);
-      be32(out + 76, hstate.empty() ? 0u : hstate[s]);
+      bef(row + 64, d0); bef(row + 68, (float)gp.type);
+      be32(row + 76, hstate.empty() ? 0u : hstate[s]);
       const float h = 0.5f * (hB[4 * s + 1] - hB[4 * s + 2]);  // || 0.5 (apic_b - apic_b^T) ||_F
-      bef(out + 88, std::sqrt(h * h + h * h));
+      bef(row + 88, std::sqrt(h * h + h * h));
     }
-  }
-  const std::vector<uint8_t> prim = bgeo_prim_attr();
-  std::memcpy(out, prim.data(), prim.size());
-  out += prim.size();
-  auto w32 = [&](uint32_t v) { for (int s = 24; s >= 0; s -= 8) *out++ = (uint8_t)(v >> s); };
-  w32(n);
-  if (n > (1u << 16)) { for (uint32_t i = 0; i < n; i++) w32(i); }  // BGEO.cpp:175-180
-  else { for (uint32_t i = 0; i < n; i++) { *out++ = (uint8_t)(i >> 8); *out++ = (uint8_t)i; } }
-  w32(0);
-  *out++ = 0x00;
-  *out++ = 0xff;
+  };
+  // merged by creation id with the boundary particles' rows (rigid_setup.h; none without bodies)
+  rigid_setup::merge_rows_by_id(out, W * 4, nm, [&](size_t im) { return hp[order[im]]; }, m->rigid.h_smp_id, put_material,
+                                [&](size_t ir, uint8_t *row) { rigid_setup::bgeo_boundary_row<2>(m->rigid, hb.data(), ir, row, W * 4); });
+  out = bgeo_put_tail(out + (size_t)n * W * 4, n);
   *written = (size_t)(out - static_cast<uint8_t *>(dst));
   if (*written != total) return fail2d(m, MPMHIP_EINVAL, "internal: bgeo image size mismatch");
   return MPMHIP_OK;

@@ -17,34 +17,15 @@
 #pragma once
 #include "mpm_common.h"
 #include "k_joints.h"
+#include "rigid_records.h"  // MAX_RIGID, RigidBodyDev, RigidSample, RigidStep(s)
 
 namespace mpm {
 
-constexpr int MAX_RIGID = 12;                    // GridState::max_num_rigid_bodies (body 0 = background, no surface)
 constexpr uint32_t CDF_TAG_MASK = 0x00FFFFFFu;   // src/mpm_fwd.h:78-82
 constexpr uint32_t CDF_STATE_MASK = 0xAAAAAAAAu; // src/mpm.h:36 (the "has colour" bit of every body)
 constexpr unsigned long long CDF_EMPTY = ~0ull;
 constexpr uint32_t CDF_LOCKED = 0xFFFFFFFEu;  // cdf.slot value while a page is being handed out (inside pass 0 of the rasterisation only)
 constexpr uint32_t CDF_POOLS = 64;            // sub-pools of the page pool, chosen by the block's Morton key
-
-struct RigidBodyDev {
-  float pos[3], vel[3], omega[3];
-  float R[9];      // body -> world, row-major
-  float q[4];      // the same rotation as a quaternion (w, x, y, z)
-  float mass, inv_mass;
-  float inv_I[9];  // body frame, row-major
-  float fric[2];
-  float lin_damp, ang_damp;
-  float axis[3];   // rotation_axis (all zero: unrestricted)
-  int scripted;    // bit 0: position follows a script, bit 1: rotation follows a script
-  float tmp_imp[3], tmp_trq[3];  // impulse / torque (about the centre of mass) collected by a transfer (apply_tmp_impulse)
-};
-struct RigidSample { float off[3]; int body; int elem; };  // boundary particle: offset from the centre of mass, body frame
-struct RigidStep {  // what the host knows about a scripted body for one substep: poses at t and t + dt
-  int has_pos, has_rot;
-  float p0[3], p1[3], q0[4], q1[4];
-};
-struct RigidSteps { RigidStep s[MAX_RIGID]; };
 
 struct CdfDev {
   uint32_t *slot;            // [8^kbits] Morton(block of 4^3 nodes) -> page, INVALID = none

@@ -8,23 +8,13 @@
 
 #include <cstdint>
 
+#include "rigid_records.h"  // MAX_RIGID2, Rigid2, Sample2, Step2, Steps2
+
 namespace mpm2d {
 
-constexpr int MAX_RIGID2 = 12;
 constexpr uint32_t TAG_MASK2 = 0x00FFFFFFu, STATE_MASK2 = 0xAAAAAAAAu;
 constexpr unsigned long long CDF2_EMPTY = ~0ull;
 
-struct Rigid2 {
-  float pos[2], vel[2], omega, angle;
-  float mass, inv_mass, inv_I;
-  float fric[2];
-  float lin_damp, ang_damp;
-  int scripted;
-  float tmp_imp[2], tmp_trq;
-};
-struct Sample2 { float off[2]; int body; int elem; };
-struct Step2 { int has_pos, has_rot; float p0[2], p1[2], a0, a1; };  // a0 / a1: radians
-struct Steps2 { Step2 s[MAX_RIGID2]; };
 struct Bnd2 { float n[2]; float dist; uint32_t near; };
 struct RigidArgs2 {
   int enabled;

@@ -87,6 +87,7 @@
 #include "sdf_lattice.h"
 #include "region_program.h"
 #include "snapshot_blob.h"
+#include "rigid_setup.h"
 #include "mpm_common.h"
 #include "k_sort.h"
 #include "k_particles.h"
@@ -425,22 +426,13 @@ struct mpmhip_ctx {
   } async;
   int64_t host_particle_bytes = 0;  // particle data copied between host and device so far (uploads, downloads, snapshots)
   // CPIC rigid coupling (rigid_api.h): bodies 1.. (0 = background), their boundary particles, the colored distance field
-  struct HostRigid {
-    mpmhip_rigid_config cfg{};
-    float mass = 0.0f, inertia[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, inv_inertia[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int first_sample = 0, n_samples = 0;
-    int64_t first_elem = 0, n_elems = 0;
-  };
   struct RigidState {
     bool enabled = false;
-    std::vector<HostRigid> bodies;
+    rigid_setup::Store<3> store;  // the bodies' host records, boundary particles (+ creation ids) and elements
     DevBuf<RigidBodyDev> d_rb;
     DevBuf<RigidSample> d_smp;
     DevBuf<float> d_elems;
     uint32_t n_smp = 0;
-    std::vector<RigidSample> h_smp;
-    std::vector<int32_t> h_smp_id;  // creation id of every boundary particle (they share the material particles' counter)
-    std::vector<float> h_elems;
     CdfDev cdf{};  // what the kernels take by value: slot / page_key / mind / tags / rpage point into the five arrays below (rigid_enable)
     DevBuf<uint32_t> cdf_slot, cdf_page_key, cdf_tags, cdf_rpage;
     DevBuf<unsigned long long> cdf_mind;
@@ -1838,7 +1830,7 @@ int mpmhip_bgeo_size(mpmhip_ctx *c, int32_t verbose, size_t *bytes) {
   if (!c || !bytes) return MPMHIP_EINVAL;
   int64_t n = mpmhip_num_particles(c);
   if (n < 0) return (int)n;
-  if (c->rigid.enabled) n += (int64_t)c->rigid.h_smp.size();  // the boundary particles of rigid bodies are rows too (type = 1)
+  if (c->rigid.enabled) n += (int64_t)c->rigid.store.h_smp.size();  // the boundary particles of rigid bodies are rows too (type = 1)
   *bytes = bgeo_bytes((uint32_t)n, verbose != 0);
   return MPMHIP_OK;
 }
@@ -1850,10 +1842,10 @@ int mpmhip_bgeo_encode(mpmhip_ctx *c, int32_t verbose, void *dst, size_t capacit
     if (int rc = ensure_b_current(c)) return rc;
   std::vector<uint32_t> order;
   std::vector<int32_t> ids;
-  const bool with_rigid = c->rigid.enabled && !c->rigid.h_smp.empty();
+  const bool with_rigid = c->rigid.enabled && !c->rigid.store.h_smp.empty();
   if (int rc = bgeo_order(c, order, with_rigid ? &ids : nullptr)) return rc;
   const uint32_t nm = (uint32_t)order.size();  // material particles
-  const uint32_t n = nm + (with_rigid ? (uint32_t)c->rigid.h_smp.size() : 0u);
+  const uint32_t n = nm + (with_rigid ? (uint32_t)c->rigid.store.h_smp.size() : 0u);
   const size_t total = bgeo_bytes(n, verbose != 0);
   int32_t *limits = nullptr;  // async stepping: per-slot (dt_limit, stiffness_limit, cfl_limit) of the particle's block
   if (c->async.enabled && c->async.limits_valid) limits = c->async.d_particle_limits;
@@ -1885,34 +1877,13 @@ int mpmhip_bgeo_encode(mpmhip_ctx *c, int32_t verbose, void *dst, size_t capacit
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   if (with_rigid) {
-    // rows of the boundary particles (RigidBoundaryParticle, src/boundary_particle.h): position = anchor point, type = 1,
-    // v = body velocity at the anchor (align_with_rigid_body); every other field keeps MPMParticle's constructor value
-    auto &R = c->rigid;
+    auto &R = c->rigid;  // (the boundary particles' rows: rigid_setup.h)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<RigidBodyDev> hb(MAX_RIGID);
     HIPCHK(c, hipMemcpy(hb.data(), R.d_rb, sizeof(RigidBodyDev) * MAX_RIGID, hipMemcpyDeviceToHost));
-    auto be32 = [](uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; };
-    auto bef = [&](uint8_t *p, float f) { uint32_t u; std::memcpy(&u, &f, 4); be32(p, u); };
-    size_t im = 0, ir = 0;
-    uint8_t *row = out;
-    for (uint32_t j = 0; j < n; j++, row += W * 4) {
-      const bool take_rigid = ir < R.h_smp.size() && (im >= nm || R.h_smp_id[ir] < ids[im]);
-      if (!take_rigid) { std::memcpy(row, mat_rows.data() + (im++) * W * 4, W * 4); continue; }
-      const RigidSample &S = R.h_smp[ir];
-      const RigidBodyDev &B = hb[S.body];
-      float ro[3], x[3], v[3];
-      for (int r = 0; r < 3; r++) ro[r] = B.R[3 * r] * S.off[0] + B.R[3 * r + 1] * S.off[1] + B.R[3 * r + 2] * S.off[2];
-      for (int r = 0; r < 3; r++) x[r] = ro[r] + B.pos[r];
-      v[0] = B.vel[0] + (B.omega[1] * ro[2] - B.omega[2] * ro[1]);
-      v[1] = B.vel[1] + (B.omega[2] * ro[0] - B.omega[0] * ro[2]);
-      v[2] = B.vel[2] + (B.omega[0] * ro[1] - B.omega[1] * ro[0]);
-      std::memset(row, 0, W * 4);
-      bef(row, x[0]); bef(row + 4, x[1]); bef(row + 8, x[2]); bef(row + 12, 1.0f);
-      be32(row + 16, 1u); be32(row + 20, (uint32_t)R.h_smp_id[ir]);
-      be32(row + 24, 1u); be32(row + 28, 1u); be32(row + 32, 1u);
-      bef(row + 36, v[0]); bef(row + 40, v[1]); bef(row + 44, v[2]);
-      ir++;
-    }
+    rigid_setup::merge_rows_by_id(out, W * 4, nm, [&](size_t im) { return ids[im]; }, R.store.h_smp_id,
+                                  [&](size_t im, uint8_t *row) { std::memcpy(row, mat_rows.data() + im * W * 4, W * 4); },
+                                  [&](size_t ir, uint8_t *row) { rigid_setup::bgeo_boundary_row<3>(R.store, hb.data(), ir, row, W * 4); });
   }
   out = bgeo_put_tail(out + row_bytes, n);
   *written = (size_t)(out - static_cast<uint8_t *>(dst));
@@ -2700,12 +2671,8 @@ struct mpmhip2d_ctx {
   hipStream_t stream = nullptr;
   std::string err;
   // CPIC rigid bodies (k_rigid2d.h): segments, boundary particles, dense colored distance field
-  struct HostRigid2 { mpmhip2d_rigid_config cfg{}; float mass = 0, inertia = 0; int64_t first_elem = 0, n_elems = 0; };
   bool rigid_enabled = false;
-  std::vector<HostRigid2> bodies;
-  std::vector<mpm2d::Sample2> h_smp;
-  std::vector<int32_t> h_smp_id;  // creation id of every boundary particle (they share the material particles' counter)
-  std::vector<float> h_elems;
+  rigid_setup::Store<2> rigid;  // the bodies' host records, boundary particles (+ creation ids) and elements
   DevBuf<mpm2d::Rigid2> d_rb;
   DevBuf<mpm2d::Sample2> d_smp;
   DevBuf<float> d_elems;
@@ -3056,7 +3023,7 @@ int mpmhip2d_add_particles(mpmhip2d_ctx *m, int32_t group, int64_t n, const floa
 static mpm2d::RigidArgs2 rigid_args2(mpmhip2d_ctx *m) {
   mpm2d::RigidArgs2 R;
   memset(&R, 0, sizeof R);
-  R.enabled = m->rigid_enabled && m->bodies.size() > 1;  // has_rigid_body()
+  R.enabled = m->rigid_enabled && m->rigid.bodies.size() > 1;  // has_rigid_body()
   R.mind = m->d_mind; R.tags = m->d_tags; R.rb = m->d_rb; R.states = m->d_states; R.bnd = m->d_bnd;
   R.penalty = m->penalty; R.pushing_force = m->pushing_force;
   return R;
@@ -3067,7 +3034,7 @@ static int rigid2_pre(mpmhip2d_ctx *m) {
   HIPCHK2D(m, hipMemsetAsync(m->d_mind, 0xFF, sizeof(unsigned long long) * nodes, m->stream));
   HIPCHK2D(m, hipMemsetAsync(m->d_tags, 0, sizeof(uint32_t) * nodes, m->stream));
   const mpm2d::RigidArgs2 R = rigid_args2(m);
-  const uint32_t ns = (uint32_t)m->h_smp.size();
+  const uint32_t ns = (uint32_t)m->rigid.h_smp.size();
   if (ns)
     hipLaunchKernelGGL(mpm2d::k2_cdf_rasterize, dim3((ns + 255) / 256), dim3(256), 0, m->stream, m->P.res[0], m->P.res[1], m->P.dx, m->P.idx, R,
                        (const mpm2d::Sample2 *)m->d_smp, (const float *)m->d_elems, ns);
@@ -3080,7 +3047,7 @@ static int rigid2_pre(mpmhip2d_ctx *m) {
 // rigid_body_levelset_collision(current_t, dt) (src/mpm_rigid_body.cpp:347-387), between normalize_grid and the grid boundary
 // condition (src/mpm.cpp:535-538); see do_rigid_ls_collision of rigid_api.h
 static int rigid2_ls_collision(mpmhip2d_ctx *m) {
-  const uint32_t n = (uint32_t)m->h_smp.size();
+  const uint32_t n = (uint32_t)m->rigid.h_smp.size();
   if (n == 0 || m->LS.n == 0) return MPMHIP_OK;
   if (m->ls_cap < n) {
     m->ls_tmp_bytes = 0;
@@ -3107,31 +3074,16 @@ static int rigid2_ls_collision(mpmhip2d_ctx *m) {
   HIPCHK2D(m, hipcub::DeviceRadixSort::SortPairs(m->d_ls_tmp, bytes, m->d_ls_keys[0].get(), m->d_ls_keys[1].get(), m->d_ls_vals[0].get(), m->d_ls_vals[1].get(), (int)n, 0, 64, m->stream));
   mpm2d::Restitution2 rest;
   memset(&rest, 0, sizeof rest);
-  for (size_t b = 1; b < m->bodies.size(); b++) rest.e[b] = m->bodies[b].cfg.restitution;
-  hipLaunchKernelGGL(mpm2d::k2_ls_collide, dim3(1), dim3(1024), 0, m->stream, m->P, m->LS, m->d_rb, (int)m->bodies.size(),
+  for (size_t b = 1; b < m->rigid.bodies.size(); b++) rest.e[b] = m->rigid.bodies[b].cfg.restitution;
+  hipLaunchKernelGGL(mpm2d::k2_ls_collide, dim3(1), dim3(1024), 0, m->stream, m->P, m->LS, m->d_rb, (int)m->rigid.bodies.size(),
                      (const mpm2d::Sample2 *)m->d_smp, (const uint32_t *)m->d_ls_vals[1], n, m->d_smp_rank, rest);
   HIPCHK2D(m, hipGetLastError());
   return MPMHIP_OK;
 }
 static int rigid2_advect(mpmhip2d_ctx *m) {
-  mpm2d::Steps2 st;
-  memset(&st, 0, sizeof st);
-  const float dt = m->P.dt, rad = (float)(M_PI / 180.0);
-  for (size_t b = 1; b < m->bodies.size(); b++) {
-    const auto &cfg = m->bodies[b].cfg;
-    float o[3];
-    if (cfg.scripted_position) {
-      st.s[b].has_pos = 1;
-      cfg.scripted_position(cfg.position_user, m->t, o); st.s[b].p0[0] = o[0]; st.s[b].p0[1] = o[1];
-      cfg.scripted_position(cfg.position_user, m->t + dt, o); st.s[b].p1[0] = o[0]; st.s[b].p1[1] = o[1];
-    }
-    if (cfg.scripted_rotation) {
-      st.s[b].has_rot = 1;
-      cfg.scripted_rotation(cfg.rotation_user, m->t, o); st.s[b].a0 = o[0] * rad;
-      cfg.scripted_rotation(cfg.rotation_user, m->t + dt, o); st.s[b].a1 = o[0] * rad;
-    }
-  }
-  hipLaunchKernelGGL(mpm2d::k2_rigid_advect, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->bodies.size(), st, dt, m->P.g[0], m->P.g[1]);
+  const float dt = m->P.dt;
+  const mpm2d::Steps2 st = rigid_setup::scripted_steps<2>(m->rigid, m->t, dt);
+  hipLaunchKernelGGL(mpm2d::k2_rigid_advect, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->rigid.bodies.size(), st, dt, m->P.g[0], m->P.g[1]);
   HIPCHK2D(m, hipGetLastError());
   return MPMHIP_OK;
 }
@@ -3204,7 +3156,7 @@ static int det2_p2g(mpmhip2d_ctx *m, const mpm2d::RigidArgs2 &R) {
                      D.unordered);
   hipLaunchKernelGGL(mpm2d::k2d_order, pg, wg, 0, m->stream, m->n, (const int32_t *)D.key, (const int32_t *)m->pid, (const uint32_t *)D.start,
                      (const uint32_t *)D.unordered, D.idx);
-  const int nb = (int)m->bodies.size();
+  const int nb = (int)m->rigid.bodies.size();
   const dim3 tg((unsigned)((m->P.res[1] + 1 + mpm2d::DET_TJ - 1) / mpm2d::DET_TJ), (unsigned)((m->P.res[0] + 1 + mpm2d::DET_TI - 1) / mpm2d::DET_TI));
   if (R.enabled) {
     hipLaunchKernelGGL(mpm2d::k2d_stage<true>, pg, wg, 0, m->stream, m->P, total, (const uint32_t *)D.idx, (const float *)m->x, m->v,
@@ -3223,7 +3175,7 @@ static int det2_p2g(mpmhip2d_ctx *m, const mpm2d::RigidArgs2 &R) {
 // the impulse rows of the launch before (k2d_stage or k2d_g2p: each is applied before the next one writes) added to the bodies
 static void det2_rows_apply(mpmhip2d_ctx *m) {
   const size_t nodes = (size_t)(m->P.res[0] + 1) * (m->P.res[1] + 1);
-  hipLaunchKernelGGL(mpm2d::k2d_rows_apply, dim3((unsigned)m->bodies.size() - 1), dim3(64), 0, m->stream, m->d_rb, (const float *)m->det.rows,
+  hipLaunchKernelGGL(mpm2d::k2d_rows_apply, dim3((unsigned)m->rigid.bodies.size() - 1), dim3(64), 0, m->stream, m->d_rb, (const float *)m->det.rows,
                      (const uint32_t *)(m->det.start + nodes));
 }
 static int substep2d(mpmhip2d_ctx *m);
@@ -3257,7 +3209,7 @@ static int substep2d(mpmhip2d_ctx *m) {
       hipLaunchKernelGGL(mpm2d::k_p2g, pg, wg, 0, m->stream, m->P, m->n, (const float *)m->x, m->v, (const float *)m->F,
                          (const float *)m->B, (const float *)m->aux, (const int32_t *)m->gid, (const int32_t *)m->pid,
                          (const GroupParams *)m->d_groups, m->grid, R);
-    if (R.enabled) hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->bodies.size());
+    if (R.enabled) hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->rigid.bodies.size());
   }
   if (R.enabled && m->ls_collision) {
     if (int rc = rigid2_ls_collision(m)) return rc;
@@ -3268,12 +3220,12 @@ static int substep2d(mpmhip2d_ctx *m) {
   if (det && R.enabled) {  // (without bodies k_g2p adds nothing across particles: the default launch is kept)
     hipLaunchKernelGGL(mpm2d::k2d_g2p, pg, wg, 0, m->stream, m->P, m->LS, (const uint32_t *)(m->det.start + nodes), (const uint32_t *)m->det.idx,
                        m->x, m->v, m->F, m->B, m->aux, (const int32_t *)m->gid, m->pid, (const GroupParams *)m->d_groups,
-                       (const float *)m->grid, m->n_dead, R, (int)m->bodies.size(), m->det.rows);
+                       (const float *)m->grid, m->n_dead, R, (int)m->rigid.bodies.size(), m->det.rows);
     det2_rows_apply(m);
   } else if (m->n) {
     hipLaunchKernelGGL(mpm2d::k_g2p, pg, wg, 0, m->stream, m->P, m->LS, m->n, m->x, m->v, m->F, m->B, m->aux, (const int32_t *)m->gid,
                        m->pid, (const GroupParams *)m->d_groups, (const float *)m->grid, m->n_dead, R);
-    if (R.enabled) hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->bodies.size());
+    if (R.enabled) hipLaunchKernelGGL(mpm2d::k2_rigid_apply_tmp, dim3(1), dim3(64), 0, m->stream, m->d_rb, (int)m->rigid.bodies.size());
   }
   if (sdf && m->P.particle_collision && m->n)  // the push g2p_particle carries for shapes (LS.n == 0 here: it skipped it)
     hipLaunchKernelGGL(mpm2d::k2_sdf_collide, pg, wg, 0, m->stream, m->P, m->LS.sdf, m->n, m->x.get(), m->v.get(), (const int32_t *)m->pid);
@@ -3313,81 +3265,21 @@ int mpmhip2d_add_rigid_body(mpmhip2d_ctx *m, const mpmhip2d_rigid_config *cfg, i
     HIPCHK2D(m, hipMemset(m->d_rb, 0, sizeof(mpm2d::Rigid2) * mpm2d::MAX_RIGID2));
     HIPCHK2D(m, hipMemset(m->d_states, 0, sizeof(uint32_t) * (size_t)m->cap));
     HIPCHK2D(m, hipMemset(m->d_bnd, 0, sizeof(mpm2d::Bnd2) * (size_t)m->cap));
-    m->bodies.clear();
-    m->bodies.emplace_back();  // the background body
+    m->rigid.bodies.clear();
+    m->rigid.bodies.emplace_back();  // the background body
     m->rigid_enabled = true;
   }
-  if ((int)m->bodies.size() >= mpm2d::MAX_RIGID2) return fail2d(m, MPMHIP_ECAPACITY, "too many rigid bodies");
-  const bool spos = cfg->scripted_position != nullptr, srot = cfg->scripted_rotation != nullptr;
-  if (!cfg->recenter && !(spos && srot)) return fail2d(m, MPMHIP_EINVAL, "recenter = 0 needs a scripted position and rotation");
-  std::vector<float> seg(segments, segments + 4 * n_segments);
-  const float sc[2] = {cfg->scale[0] != 0 ? cfg->scale[0] : 1.0f, cfg->scale[1] != 0 ? cfg->scale[1] : 1.0f};
-  for (int64_t e = 0; e < n_segments; e++) {
-    if (cfg->reverse_vertices) { std::swap(seg[4 * e], seg[4 * e + 2]); std::swap(seg[4 * e + 1], seg[4 * e + 3]); }
-    for (int q = 0; q < 2; q++) for (int k = 0; k < 2; k++) seg[4 * e + 2 * q + k] *= sc[k];
-  }
-  // mass, centre of mass, inertia: the segments as a shell of line density `density` (the rigid body the reference build
-  // is tested against, oracle/taichi_shim/.../rigid_body_shim.h, treats 2D bodies this way whether codimensional or not)
-  const double density = cfg->density > 0 ? cfg->density : (cfg->codimensional ? 40.0 : 400.0);
-  double M = 0, com[2] = {0, 0}, S00 = 0, S11 = 0;
-  for (int64_t e = 0; e < n_segments; e++) {
-    const double a[2] = {seg[4 * e], seg[4 * e + 1]}, b[2] = {seg[4 * e + 2], seg[4 * e + 3]};
-    const double mm = std::sqrt((b[0] - a[0]) * (b[0] - a[0]) + (b[1] - a[1]) * (b[1] - a[1])) * density;
-    M += mm;
-    for (int k = 0; k < 2; k++) com[k] += mm * 0.5 * (a[k] + b[k]);
-    S00 += mm / 6.0 * (a[0] * a[0] + b[0] * b[0] + (a[0] + b[0]) * (a[0] + b[0]));
-    S11 += mm / 6.0 * (a[1] * a[1] + b[1] * b[1] + (a[1] + b[1]) * (a[1] + b[1]));
-  }
-  if (!(M > 0)) return fail2d(m, MPMHIP_EINVAL, "rigid body without mass");
-  com[0] /= M; com[1] /= M;
-  const double I = (S00 - M * com[0] * com[0]) + (S11 - M * com[1] * com[1]);
-  if (!cfg->recenter) com[0] = com[1] = 0.0;
-  for (int64_t e = 0; e < n_segments; e++)
-    for (int q = 0; q < 2; q++) for (int k = 0; k < 2; k++) seg[4 * e + 2 * q + k] -= (float)com[k];
+  if ((int)m->rigid.bodies.size() >= mpm2d::MAX_RIGID2) return fail2d(m, MPMHIP_ECAPACITY, "too many rigid bodies");
   mpm2d::Rigid2 D;
-  memset(&D, 0, sizeof D);
-  float o[3] = {cfg->initial_position[0], cfg->initial_position[1], 0};
-  if (spos) cfg->scripted_position(cfg->position_user, m->t, o);
-  D.pos[0] = o[0]; D.pos[1] = o[1];
-  float ang[3] = {cfg->initial_rotation, 0, 0};
-  if (srot) cfg->scripted_rotation(cfg->rotation_user, m->t, ang);
-  D.angle = ang[0] * (float)(M_PI / 180.0);
-  D.vel[0] = spos ? 0.0f : cfg->initial_velocity[0]; D.vel[1] = spos ? 0.0f : cfg->initial_velocity[1];
-  D.omega = srot ? 0.0f : cfg->initial_angular_velocity;
-  D.mass = (float)M; D.inv_mass = spos ? 0.0f : (float)(1.0 / M); D.inv_I = srot ? 0.0f : (float)(1.0 / I);
-  D.fric[0] = cfg->friction[0]; D.fric[1] = cfg->friction[1];
-  D.lin_damp = cfg->linear_damping; D.ang_damp = cfg->angular_damping;
-  D.scripted = (spos ? 1 : 0) | (srot ? 2 : 0);
-  // boundary particles (src/mpm_rigid_body.cpp:196-207): max(ceil(length / dx), 2) per segment, at the mid points of equal parts
-  const int body = (int)m->bodies.size();
-  const size_t elem0 = m->h_elems.size() / 4;
-  const float cs = std::cos(D.angle), sn = std::sin(D.angle);
-  int32_t allocated = 0;
-  for (int64_t e = 0; e < n_segments; e++) {
-    const float a[2] = {seg[4 * e], seg[4 * e + 1]}, b[2] = {seg[4 * e + 2], seg[4 * e + 3]};
-    const float len = std::sqrt((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]));
-    const int ns = std::max((int)std::ceil(len * m->P.idx), 2);
-    for (int j = 0; j < ns; j++) {
-      const float t = (0.5f + j) / ns;
-      mpm2d::Sample2 s;
-      s.off[0] = a[0] * (1.0f - t) + b[0] * t; s.off[1] = a[1] * (1.0f - t) + b[1] * t;
-      s.body = body; s.elem = (int)(elem0 + e);
-      const float w[2] = {(cs * s.off[0] - sn * s.off[1] + D.pos[0]) * m->P.idx, (sn * s.off[0] + cs * s.off[1] + D.pos[1]) * m->P.idx};
-      const bool near_wall = w[0] < 7.0f || w[1] < 7.0f || w[0] - m->P.res[0] > -7.0f || w[1] - m->P.res[1] > -7.0f;
-      if (!near_wall) { m->h_smp.push_back(s); m->h_smp_id.push_back(m->next_pid + allocated); }
-      allocated++;
-    }
-  }
-  m->next_pid += allocated;  // boundary particles take creation ids from the same counter (src/particle_allocator.h:68-74)
-  m->h_elems.insert(m->h_elems.end(), seg.begin(), seg.end());
-  HIPCHK2D(m, m->d_smp.alloc(std::max<size_t>(m->h_smp.size(), 1)));
-  HIPCHK2D(m, m->d_elems.alloc(std::max<size_t>(m->h_elems.size(), 4)));
-  if (!m->h_smp.empty()) HIPCHK2D(m, hipMemcpy(m->d_smp, m->h_smp.data(), sizeof(mpm2d::Sample2) * m->h_smp.size(), hipMemcpyHostToDevice));
-  HIPCHK2D(m, hipMemcpy(m->d_elems, m->h_elems.data(), sizeof(float) * m->h_elems.size(), hipMemcpyHostToDevice));
+  int32_t allocated = 0, body = (int32_t)m->rigid.bodies.size();
+  if (const char *why = rigid_setup::add_body<2>(*cfg, n_segments, segments, m->P.dx, m->P.idx, m->P.res, m->t, m->next_pid, m->rigid, D, allocated))
+    return fail2d(m, MPMHIP_EINVAL, why);
+  m->next_pid += allocated;  // later material particles are numbered behind the boundary particles
+  HIPCHK2D(m, m->d_smp.alloc(std::max<size_t>(m->rigid.h_smp.size(), 1)));
+  HIPCHK2D(m, m->d_elems.alloc(std::max<size_t>(m->rigid.h_elems.size(), 4)));
+  if (!m->rigid.h_smp.empty()) HIPCHK2D(m, hipMemcpy(m->d_smp, m->rigid.h_smp.data(), sizeof(mpm2d::Sample2) * m->rigid.h_smp.size(), hipMemcpyHostToDevice));
+  HIPCHK2D(m, hipMemcpy(m->d_elems, m->rigid.h_elems.data(), sizeof(float) * m->rigid.h_elems.size(), hipMemcpyHostToDevice));
   HIPCHK2D(m, hipMemcpy(m->d_rb + body, &D, sizeof D, hipMemcpyHostToDevice));
-  mpmhip2d_ctx::HostRigid2 H;
-  H.cfg = *cfg; H.mass = (float)M; H.inertia = (float)I; H.first_elem = (int64_t)elem0; H.n_elems = n_segments;
-  m->bodies.push_back(H);
   return body;
 }
 // out[10]: position 2, angle (radians), velocity 2, angular velocity, mass, inv_mass, inertia, inv_inertia
@@ -3395,15 +3287,15 @@ int mpmhip2d_add_rigid_body(mpmhip2d_ctx *m, const mpmhip2d_rigid_config *cfg, i
 // 'stepper' are TC_NOT_IMPLEMENTED for dim = 2, src/articulation.cpp:65-67,317)
 int mpmhip2d_add_articulation(mpmhip2d_ctx *m, const mpmhip_joint_config *cfg) {
   if (!m || !cfg) return MPMHIP_EINVAL;
-  const int nb = m->rigid_enabled ? (int)m->bodies.size() : 0;
+  const int nb = m->rigid_enabled ? (int)m->rigid.bodies.size() : 0;
   if (cfg->type != MPMHIP_JOINT_ROTATION) return fail2d(m, MPMHIP_EINVAL, "add_articulation: only type='rotation' is built for 2D simulations");
   if (cfg->obj0 < 1 || cfg->obj0 >= nb) return fail2d(m, MPMHIP_EINVAL, "add_articulation: obj0 = " + std::to_string(cfg->obj0) + " is not a rigid body of this simulation");
   if (cfg->obj1 < 0 || cfg->obj1 >= nb) return fail2d(m, MPMHIP_EINVAL, "add_articulation: obj1 = " + std::to_string(cfg->obj1) + " is not a rigid body of this simulation");
   if (m->joints.n >= mpm2d::MAX_JOINTS2) return fail2d(m, MPMHIP_ECAPACITY, "at most " + std::to_string(mpm2d::MAX_JOINTS2) + " articulations");
   mpm2d::Joint2 &J = m->joints.j[m->joints.n++];
   J.obj0 = cfg->obj0; J.obj1 = cfg->obj1;
-  J.I0 = m->bodies[cfg->obj0].inertia;
-  J.I1 = cfg->obj1 == 0 ? 1.0f : m->bodies[cfg->obj1].inertia;  // (the background body: inertia 1, set_as_background)
+  J.I0 = m->rigid.bodies[cfg->obj0].inertia[0];
+  J.I1 = cfg->obj1 == 0 ? 1.0f : m->rigid.bodies[cfg->obj1].inertia[0];  // (the background body: inertia 1, set_as_background)
   return MPMHIP_OK;
 }
 int mpmhip2d_set_articulation_iterations(mpmhip2d_ctx *m, int32_t n) {
@@ -3413,39 +3305,30 @@ int mpmhip2d_set_articulation_iterations(mpmhip2d_ctx *m, int32_t n) {
 }
 int mpmhip2d_rigid_get_state(mpmhip2d_ctx *m, int32_t id, float *out) {
   if (!m || !out) return MPMHIP_EINVAL;
-  if (!m->rigid_enabled || id < 1 || id >= (int)m->bodies.size()) return fail2d(m, MPMHIP_EINVAL, "no such rigid body");
+  if (!m->rigid_enabled || id < 1 || id >= (int)m->rigid.bodies.size()) return fail2d(m, MPMHIP_EINVAL, "no such rigid body");
   HIPCHK2D(m, hipSetDevice(m->device));
   HIPCHK2D(m, hipStreamSynchronize(m->stream));
   mpm2d::Rigid2 D;
   HIPCHK2D(m, hipMemcpy(&D, m->d_rb + id, sizeof D, hipMemcpyDeviceToHost));
   out[0] = D.pos[0]; out[1] = D.pos[1]; out[2] = D.angle; out[3] = D.vel[0]; out[4] = D.vel[1]; out[5] = D.omega;
-  out[6] = D.mass; out[7] = D.inv_mass; out[8] = m->bodies[id].inertia; out[9] = D.inv_I;
+  out[6] = D.mass; out[7] = D.inv_mass; out[8] = m->rigid.bodies[id].inertia[0]; out[9] = D.inv_I;
   return MPMHIP_OK;
 }
 // the body's segments in world space (write_rigid_body's .poly file, src/visualize.cpp:105-130): 4 floats per segment
 int64_t mpmhip2d_rigid_get_mesh(mpmhip2d_ctx *m, int32_t id, int64_t cap_segments, float *out) {
   if (!m) return MPMHIP_EINVAL;
-  if (!m->rigid_enabled || id < 1 || id >= (int)m->bodies.size()) return fail2d(m, MPMHIP_EINVAL, "no such rigid body");
+  if (!m->rigid_enabled || id < 1 || id >= (int)m->rigid.bodies.size()) return fail2d(m, MPMHIP_EINVAL, "no such rigid body");
   if (hipSetDevice(m->device) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess) return MPMHIP_EHIP;
   mpm2d::Rigid2 D;
   HIPCHK2D(m, hipMemcpy(&D, m->d_rb + id, sizeof D, hipMemcpyDeviceToHost));
-  const auto &B = m->bodies[id];
-  const float cs = std::cos(D.angle), sn = std::sin(D.angle);
-  if (out)
-    for (int64_t e = 0; e < std::min<int64_t>(B.n_elems, cap_segments); e++)
-      for (int q = 0; q < 2; q++) {
-        const float *v = &m->h_elems[(size_t)(B.first_elem + e) * 4 + 2 * q];
-        out[4 * e + 2 * q] = cs * v[0] - sn * v[1] + D.pos[0];
-        out[4 * e + 2 * q + 1] = sn * v[0] + cs * v[1] + D.pos[1];
-      }
-  return B.n_elems;
+  return rigid_setup::world_elements<2>(m->rigid, id, D, cap_segments, out);
 }
 // world positions of the boundary particles of body id (id < 0: all); returns the count
 int64_t mpmhip2d_rigid_get_samples(mpmhip2d_ctx *m, int32_t id, int64_t cap, float *pos) {
   if (!m) return MPMHIP_EINVAL;
   if (!m->rigid_enabled) return 0;
   if (hipSetDevice(m->device) != hipSuccess) return MPMHIP_EHIP;
-  const uint32_t ns = (uint32_t)m->h_smp.size();
+  const uint32_t ns = (uint32_t)m->rigid.h_smp.size();
   std::vector<float> w((size_t)ns * 2);
   if (ns && pos) {
     DevBuf<float> d;
@@ -3456,8 +3339,8 @@ int64_t mpmhip2d_rigid_get_samples(mpmhip2d_ctx *m, int32_t id, int64_t cap, flo
     HIPCHK2D(m, hipStreamSynchronize(m->stream));
   }
   int64_t n = 0;
-  for (size_t s = 0; s < m->h_smp.size(); s++) {
-    if (id >= 0 && m->h_smp[s].body != id) continue;
+  for (size_t s = 0; s < m->rigid.h_smp.size(); s++) {
+    if (id >= 0 && m->rigid.h_smp[s].body != id) continue;
     if (n < cap && pos) { pos[2 * n] = w[2 * s]; pos[2 * n + 1] = w[2 * s + 1]; }
     n++;
   }
@@ -3468,7 +3351,7 @@ int64_t mpmhip2d_rigid_get_samples(mpmhip2d_ctx *m, int32_t id, int64_t cap, flo
 int mpmhip2d_cdf_phase(mpmhip2d_ctx *m) {
   if (!m) return MPMHIP_EINVAL;
   HIPCHK2D(m, hipSetDevice(m->device));
-  if (!(m->rigid_enabled && m->bodies.size() > 1)) return MPMHIP_OK;
+  if (!(m->rigid_enabled && m->rigid.bodies.size() > 1)) return MPMHIP_OK;
   return rigid2_pre(m);
 }
 int mpmhip2d_download_cdf(mpmhip2d_ctx *m, uint32_t *states, float *distance) {

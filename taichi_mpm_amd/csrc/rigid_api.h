@@ -1,87 +1,14 @@
 // taichi_mpm_amd/csrc/rigid_api.h — host side of the CPIC rigid coupling (included by mpmhip.hip inside extern "C")
 // Part of libmpmhip.  Device side: k_rigid.h (bodies, colored distance field, particle colours), k_rigid_transfer.h.
 //
-// A rigid body = triangles (mesh space) + pose + mass properties.  Creation follows MPM::add_rigid_particle
-// (src/mpm_rigid_body.cpp:130-252): scale the mesh, mass / centre of mass / inertia, recentre, sample boundary particles
-// on every triangle with the reference's own loop, drop samples near the domain wall.  The rigid-body arithmetic itself
+// A rigid body = triangles (mesh space) + pose + mass properties.  Creation (MPM::add_rigid_particle), the scripts' poses of a
+// substep and the world-space mesh are host arithmetic and live in rigid_setup.h; here: the device arrays, uploads and launches.
+// The rigid-body arithmetic itself
 // (what an impulse does, how a script becomes a velocity) belongs to the absent taichi core; the conventions used here
 // are those of the body the reference build is tested against (oracle/taichi_shim/taichi/dynamics/rigid_body_shim.h)
 // and are restated in k_rigid.h.  Joints between bodies (MPM::articulate) are in k_joints.h; rigid-rigid collisions
 // (MPM::rigidify, src/mpm.cpp:468, libccd's MPR) are in k_rigid_collide.h / rigid_collide_api.h, an opt-in pass — without it the
 // Python layer warns when a scene has more than one body that could collide.
-
-static void quat_from_euler_deg(const float deg[3], float q[4]) {  // X * Y * Z, src/mpm_rigid_body.cpp:108-114
-  const float r = (float)(M_PI / 180.0);
-  float ax[3][4];
-  for (int k = 0; k < 3; k++) {
-    const float a = deg[k] * r;
-    ax[k][0] = std::cos(a / 2); ax[k][1] = ax[k][2] = ax[k][3] = 0.0f;
-    ax[k][1 + k] = std::sin(a / 2);
-  }
-  auto mul = [](const float a[4], const float b[4], float o[4]) {
-    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-    o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-    o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-  };
-  float xy[4];
-  mul(ax[0], ax[1], xy);
-  mul(xy, ax[2], q);
-}
-static void quat_to_matrix(const float q[4], float R[9]) {
-  const float w = q[0], x = q[1], y = q[2], z = q[3];
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
-  R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-  R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
-}
-
-// mass, centre of mass, inertia about it (body frame) of a triangle mesh: a shell of surface density `density`
-// (codimensional) or the enclosed solid of volume density `density` (signed tetrahedra against the origin)
-static bool mesh_mass_properties(const std::vector<float> &tri, bool codimensional, double density, double &M, double com[3],
-                                 double I[9]) {
-  double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  M = 0; com[0] = com[1] = com[2] = 0;
-  auto add = [&](double w, const double a[3], const double b[3]) {
-    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) S[r][c] += w * 0.5 * (a[r] * b[c] + b[r] * a[c]);
-  };
-  for (size_t e = 0; e < tri.size() / 9; e++) {
-    double v[3][3];
-    for (int q = 0; q < 3; q++) for (int k = 0; k < 3; k++) v[q][k] = tri[9 * e + 3 * q + k];
-    const double s[3] = {v[0][0] + v[1][0] + v[2][0], v[0][1] + v[1][1] + v[2][1], v[0][2] + v[1][2] + v[2][2]};
-    double m, cw, sw;
-    if (codimensional) {
-      const double a[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]}, b[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
-      const double n[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-      m = 0.5 * std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]) * density; cw = 1.0 / 3.0; sw = 1.0 / 12.0;
-    } else {
-      const double det = v[0][0] * (v[1][1] * v[2][2] - v[1][2] * v[2][1]) - v[0][1] * (v[1][0] * v[2][2] - v[1][2] * v[2][0]) +
-                         v[0][2] * (v[1][0] * v[2][1] - v[1][1] * v[2][0]);
-      m = det / 6.0 * density; cw = 0.25; sw = 1.0 / 20.0;
-    }
-    M += m;
-    for (int k = 0; k < 3; k++) com[k] += m * cw * s[k];
-    for (int q = 0; q < 3; q++) add(m * sw, v[q], v[q]);
-    add(m * sw, s, s);
-  }
-  if (!(std::abs(M) > 0)) return false;
-  for (int k = 0; k < 3; k++) com[k] /= M;
-  const double flip = M < 0 ? -1.0 : 1.0;
-  M *= flip;
-  double Sc[3][3];
-  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Sc[r][c] = flip * S[r][c] - M * com[r] * com[c];
-  const double tr = Sc[0][0] + Sc[1][1] + Sc[2][2];
-  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) I[3 * r + c] = (r == c ? tr : 0.0) - Sc[r][c];
-  return true;
-}
-static bool invert3(const double a[9], double o[9]) {
-  const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
-  if (det == 0) return false;
-  const double id = 1.0 / det;
-  o[0] = (a[4] * a[8] - a[5] * a[7]) * id; o[1] = (a[2] * a[7] - a[1] * a[8]) * id; o[2] = (a[1] * a[5] - a[2] * a[4]) * id;
-  o[3] = (a[5] * a[6] - a[3] * a[8]) * id; o[4] = (a[0] * a[8] - a[2] * a[6]) * id; o[5] = (a[2] * a[3] - a[0] * a[5]) * id;
-  o[6] = (a[3] * a[7] - a[4] * a[6]) * id; o[7] = (a[1] * a[6] - a[0] * a[7]) * id; o[8] = (a[0] * a[4] - a[1] * a[3]) * id;
-  return true;
-}
 
 static int rigid_enable(mpmhip_ctx *c) {
   auto &R = c->rigid;
@@ -130,10 +57,10 @@ static int rigid_enable(mpmhip_ctx *c) {
   HIPCHK(c, hipMemset(R.cdf.rpage, 0, sizeof(uint32_t) * R.rpage_words));
   HIPCHK(c, hipMemset(R.d_bnd, 0, sizeof(BndRec) * (size_t)c->cap));
   HIPCHK(c, hipMemset(R.d_blk_rigid, 0, (size_t)c->P.max_blocks + 1));
-  R.bodies.clear();
-  R.bodies.emplace_back();  // body 0: the background (MPM::initialize, src/mpm.cpp:72-74); it has no surface
-  R.bodies[0].mass = 1.0f;
-  R.bodies[0].inertia[0] = R.bodies[0].inertia[4] = R.bodies[0].inertia[8] = 1.0f;  // set_as_background: inertia 1, inverse 0
+  R.store.bodies.clear();
+  R.store.bodies.emplace_back();  // body 0: the background (MPM::initialize, src/mpm.cpp:72-74); it has no surface
+  R.store.bodies[0].mass = 1.0f;
+  R.store.bodies[0].inertia[0] = R.store.bodies[0].inertia[4] = R.store.bodies[0].inertia[8] = 1.0f;  // set_as_background: inertia 1, inverse 0
   R.joints.clear();
   R.enabled = true;
   return MPMHIP_OK;
@@ -147,7 +74,7 @@ static RigidXfer rigid_xfer(mpmhip_ctx *c) {
   X.penalty = c->rigid.penalty; X.pushing_force = c->rigid.pushing_force;
   return X;
 }
-static inline bool rigid_active(const mpmhip_ctx *c) { return c->rigid.enabled && c->rigid.bodies.size() > 1; }  // has_rigid_body()
+static inline bool rigid_active(const mpmhip_ctx *c) { return c->rigid.enabled && c->rigid.store.bodies.size() > 1; }  // has_rigid_body()
 
 // rasterize_rigid_boundary: clear last substep's pages, then the boundary particles write colours and distances
 static int do_rigid_rasterize(mpmhip_ctx *c) {
@@ -189,11 +116,11 @@ static int rigid_imp_rows(mpmhip_ctx *c) {
 }
 static int do_rigid_apply_tmp(mpmhip_ctx *c) {
   if (c->deterministic) {  // the rows the colour-aware kernel just wrote, summed in a fixed order and applied (k_rigid.h)
-    hipLaunchKernelGGL(k_rigid_rows_apply, dim3((int)c->rigid.bodies.size() - 1), dim3(1024), 0, c->stream, c->P, (const Counters *)c->cnt,
+    hipLaunchKernelGGL(k_rigid_rows_apply, dim3((int)c->rigid.store.bodies.size() - 1), dim3(1024), 0, c->stream, c->P, (const Counters *)c->cnt,
                        (const uint8_t *)c->rigid.d_blk_rigid, (const float *)c->rigid.d_imp_rows, c->rigid.d_rb);
     return launch_check(c, "rigid apply_tmp_velocity (deterministic)");
   }
-  hipLaunchKernelGGL(k_rigid_apply_tmp, dim3(1), dim3(64), 0, c->stream, c->rigid.d_rb, (int)c->rigid.bodies.size());
+  hipLaunchKernelGGL(k_rigid_apply_tmp, dim3(1), dim3(64), 0, c->stream, c->rigid.d_rb, (int)c->rigid.store.bodies.size());
   return launch_check(c, "rigid apply_tmp_velocity");
 }
 // MPM<dim>::rigid_body_levelset_collision (src/mpm_rigid_body.cpp:347-387): the boundary particles in the reference's order
@@ -230,34 +157,16 @@ static int do_rigid_ls_collision(mpmhip_ctx *c) {
   HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(R.d_ls_tmp, bytes, R.d_ls_keys[0].get(), R.d_ls_keys[1].get(), R.d_ls_vals[0].get(), R.d_ls_vals[1].get(), (int)n, 0, 64, c->stream));
   RigidRestitution rest;
   memset(&rest, 0, sizeof rest);
-  for (size_t b = 1; b < R.bodies.size(); b++) rest.e[b] = R.bodies[b].cfg.restitution;
-  hipLaunchKernelGGL(k_rigid_ls_collide, dim3(1), dim3(1024), 0, c->stream, c->P, (const LevelSetDev *)c->d_LS, R.d_rb, (int)R.bodies.size(),
+  for (size_t b = 1; b < R.store.bodies.size(); b++) rest.e[b] = R.store.bodies[b].cfg.restitution;
+  hipLaunchKernelGGL(k_rigid_ls_collide, dim3(1), dim3(1024), 0, c->stream, c->P, (const LevelSetDev *)c->d_LS, R.d_rb, (int)R.store.bodies.size(),
                      (const RigidSample *)R.d_smp, (const uint32_t *)R.d_ls_vals[1], n, R.d_smp_rank, rest);
   return launch_check(c, "rigid_body_levelset_collision");
 }
 // advect_rigid_bodies(dt) at current_t = c->t: scripts are evaluated here, on the host, for this one substep
 static int do_rigid_advect(mpmhip_ctx *c, float dt) {
   auto &R = c->rigid;
-  RigidSteps st;
-  memset(&st, 0, sizeof st);
-  for (size_t b = 1; b < R.bodies.size(); b++) {
-    const auto &B = R.bodies[b];
-    RigidStep &s = st.s[b];
-    if (B.cfg.scripted_position) {
-      s.has_pos = 1;
-      B.cfg.scripted_position(B.cfg.position_user, c->t, s.p0);
-      B.cfg.scripted_position(B.cfg.position_user, c->t + dt, s.p1);
-    }
-    if (B.cfg.scripted_rotation) {
-      s.has_rot = 1;
-      float e0[3], e1[3];
-      B.cfg.scripted_rotation(B.cfg.rotation_user, c->t, e0);
-      B.cfg.scripted_rotation(B.cfg.rotation_user, c->t + dt, e1);
-      quat_from_euler_deg(e0, s.q0);
-      quat_from_euler_deg(e1, s.q1);
-    }
-  }
-  hipLaunchKernelGGL(k_rigid_advect, dim3(1), dim3(64), 0, c->stream, R.d_rb, (int)R.bodies.size(), st, dt, c->P.g[0], c->P.g[1], c->P.g[2]);
+  const RigidSteps st = rigid_setup::scripted_steps<3>(R.store, c->t, dt);
+  hipLaunchKernelGGL(k_rigid_advect, dim3(1), dim3(64), 0, c->stream, R.d_rb, (int)R.store.bodies.size(), st, dt, c->P.g[0], c->P.g[1], c->P.g[2]);
   return launch_check(c, "advect_rigid_bodies");
 }
 // what substep() does with rigid bodies between the sort and P2G (src/mpm.cpp:466-472, 506-508)
@@ -265,7 +174,7 @@ static int do_rigid_advect(mpmhip_ctx *c, float dt) {
 static int do_rigid_articulate(mpmhip_ctx *c, float dt) {
   auto &R = c->rigid;
   if (R.joints.empty()) return MPMHIP_OK;
-  hipLaunchKernelGGL(k_articulate, dim3(1), dim3(64), 0, c->stream, R.d_rb, (int)R.bodies.size(), (const JointDev *)R.d_joints,
+  hipLaunchKernelGGL(k_articulate, dim3(1), dim3(64), 0, c->stream, R.d_rb, (int)R.store.bodies.size(), (const JointDev *)R.d_joints,
                      (int)R.joints.size(), dt, R.joint_iterations);
   return launch_check(c, "articulate");
 }
@@ -304,106 +213,32 @@ int mpmhip_add_rigid_body(mpmhip_ctx *c, const mpmhip_rigid_config *cfg, int64_t
   if (!c || !cfg || !triangles || n_triangles <= 0) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "add_rigid_body inside a substep");
-  // check_scripting_parameters (src/mpm_rigid_body.cpp:15-56) as far as the struct can express it
   if (int rc = rigid_enable(c)) return rc;
   auto &R = c->rigid;
-  if ((int)R.bodies.size() >= MAX_RIGID) return fail(c, MPMHIP_ECAPACITY, "at most %d rigid bodies (2 colour bits each in a 24-bit word)", MAX_RIGID - 1);
+  if ((int)R.store.bodies.size() >= MAX_RIGID) return fail(c, MPMHIP_ECAPACITY, "at most %d rigid bodies (2 colour bits each in a 24-bit word)", MAX_RIGID - 1);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  mpmhip_ctx::HostRigid B;
-  B.cfg = *cfg;
-  const bool spos = cfg->scripted_position != nullptr, srot = cfg->scripted_rotation != nullptr;
-  if (!cfg->recenter && !(spos && srot)) return fail(c, MPMHIP_EINVAL, "recenter = 0 needs a scripted position and rotation (src/mpm_rigid_body.cpp:186-190)");
-  std::vector<float> tri(triangles, triangles + 9 * n_triangles);
-  const float sc[3] = {cfg->scale[0] != 0 ? cfg->scale[0] : 1.0f, cfg->scale[1] != 0 ? cfg->scale[1] : 1.0f, cfg->scale[2] != 0 ? cfg->scale[2] : 1.0f};
-  for (int64_t e = 0; e < n_triangles; e++) {
-    if (cfg->reverse_vertices) for (int k = 0; k < 3; k++) std::swap(tri[9 * e + k], tri[9 * e + 3 + k]);
-    for (int q = 0; q < 3; q++) for (int k = 0; k < 3; k++) tri[9 * e + 3 * q + k] *= sc[k];
-  }
-  const double density = cfg->density > 0 ? cfg->density : (cfg->codimensional ? 40.0 : 400.0);
-  double M, com[3], I[9], invI[9];
-  if (!mesh_mass_properties(tri, cfg->codimensional != 0, density, M, com, I) || !invert3(I, invI))
-    return fail(c, MPMHIP_EINVAL, "rigid body: the mesh has no mass or a singular inertia tensor");
-  if (!cfg->recenter) com[0] = com[1] = com[2] = 0.0;
-  const float comf[3] = {(float)com[0], (float)com[1], (float)com[2]};
-  for (int64_t e = 0; e < n_triangles; e++)
-    for (int q = 0; q < 3; q++) for (int k = 0; k < 3; k++) tri[9 * e + 3 * q + k] -= comf[k];
-  // the device record
   RigidBodyDev D;
-  memset(&D, 0, sizeof D);
-  float p0[3] = {cfg->initial_position[0], cfg->initial_position[1], cfg->initial_position[2]};
-  if (spos) cfg->scripted_position(cfg->position_user, c->t, p0);
-  float euler[3] = {cfg->initial_rotation[0], cfg->initial_rotation[1], cfg->initial_rotation[2]};
-  if (srot) cfg->scripted_rotation(cfg->rotation_user, c->t, euler);
-  quat_from_euler_deg(euler, D.q);
-  quat_to_matrix(D.q, D.R);
-  for (int k = 0; k < 3; k++) {
-    D.pos[k] = p0[k];
-    D.vel[k] = spos ? 0.0f : cfg->initial_velocity[k];
-    D.omega[k] = srot ? 0.0f : cfg->initial_angular_velocity[k];
-    D.axis[k] = cfg->rotation_axis[k];
-  }
-  D.mass = (float)M;
-  D.inv_mass = spos ? 0.0f : (float)(1.0 / M);                    // set_infinity_mass
-  for (int k = 0; k < 9; k++) D.inv_I[k] = srot ? 0.0f : (float)invI[k];  // set_infinity_inertia
-  D.fric[0] = cfg->friction[0]; D.fric[1] = cfg->friction[1];
-  D.lin_damp = cfg->linear_damping; D.ang_damp = cfg->angular_damping;
-  D.scripted = (spos ? 1 : 0) | (srot ? 2 : 0);
-  for (int k = 0; k < 9; k++) { B.inertia[k] = (float)I[k]; B.inv_inertia[k] = (float)invI[k]; }
-  B.mass = (float)M;
-  // boundary particles: the reference's sampling loop (src/mpm_rigid_body.cpp:214-235), in float like the reference
-  const int body = (int)R.bodies.size();
-  const float dx = c->P.dx;
-  const size_t elem0 = R.h_elems.size() / 9;
-  B.first_sample = (int)R.h_smp.size();
-  int32_t allocated = 0;
-  for (int64_t e = 0; e < n_triangles; e++) {
-    const float *v0 = &tri[9 * e], *v1 = v0 + 3, *v2 = v0 + 6;
-    float a[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, b[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
-    const float xl = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), yl = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-    if (!(xl > 0.0f) || !(yl > 0.0f)) continue;  // a degenerate triangle carries no boundary particles
-    for (int k = 0; k < 3; k++) { a[k] /= xl; b[k] /= yl; }
-    for (float _x = std::min(xl / 3.0f, dx / 2.0f); _x < xl + dx; _x += dx)
-      for (float _y = std::min(yl / 3.0f, dx / 2.0f); _y < yl + dx; _y += dx) {
-        const float x = (_x < xl) ? _x : _x - dx / 2.0f, y = (_y < yl) ? _y : _y - dx / 2.0f;
-        if (x / xl + y / yl > 1.0f - 1e-6f) continue;
-        RigidSample s;
-        for (int k = 0; k < 3; k++) s.off[k] = v0[k] + a[k] * x + b[k] * y;
-        s.body = body; s.elem = (int)(elem0 + e);
-        // align_with_rigid_body + near_boundary(*p) (:237-247): samples near the domain wall are not created
-        float w[3];
-        bool near_wall = false;
-        for (int r = 0; r < 3; r++) {
-          w[r] = (D.R[3 * r] * s.off[0] + D.R[3 * r + 1] * s.off[1] + D.R[3 * r + 2] * s.off[2] + D.pos[r]) * c->P.idx;
-          near_wall = near_wall || w[r] < 7.0f || w[r] - (float)c->P.res[r] > -7.0f;
-        }
-        if (!near_wall) { R.h_smp.push_back(s); R.h_smp_id.push_back(c->next_pid + allocated); }
-        allocated++;
-      }
-  }
-  // every boundary particle took a creation id from the same counter as the material particles
-  // (allocator.allocate_particle, src/particle_allocator.h:68-74): later material particles are numbered behind them
-  c->next_pid += allocated;
-  B.n_samples = (int)R.h_smp.size() - B.first_sample;
-  B.first_elem = (int64_t)elem0; B.n_elems = n_triangles;
-  R.h_elems.insert(R.h_elems.end(), tri.begin(), tri.end());
+  int32_t allocated = 0, body = (int32_t)R.store.bodies.size();
+  if (const char *why = rigid_setup::add_body<3>(*cfg, n_triangles, triangles, c->P.dx, c->P.idx, c->P.res, c->t, c->next_pid, R.store, D, allocated))
+    return fail(c, MPMHIP_EINVAL, "%s", why);
+  c->next_pid += allocated;  // later material particles are numbered behind the boundary particles
   // (re)upload samples and elements
-  HIPCHK(c, R.d_smp.alloc(std::max<size_t>(R.h_smp.size(), 1)));
-  HIPCHK(c, R.d_elems.alloc(std::max<size_t>(R.h_elems.size(), 9)));
-  if (!R.h_smp.empty()) HIPCHK(c, hipMemcpy(R.d_smp, R.h_smp.data(), sizeof(RigidSample) * R.h_smp.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(R.d_elems, R.h_elems.data(), sizeof(float) * R.h_elems.size(), hipMemcpyHostToDevice));
-  R.n_smp = (uint32_t)R.h_smp.size();
+  HIPCHK(c, R.d_smp.alloc(std::max<size_t>(R.store.h_smp.size(), 1)));
+  HIPCHK(c, R.d_elems.alloc(std::max<size_t>(R.store.h_elems.size(), 9)));
+  if (!R.store.h_smp.empty()) HIPCHK(c, hipMemcpy(R.d_smp, R.store.h_smp.data(), sizeof(RigidSample) * R.store.h_smp.size(), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(R.d_elems, R.store.h_elems.data(), sizeof(float) * R.store.h_elems.size(), hipMemcpyHostToDevice));
+  R.n_smp = (uint32_t)R.store.h_smp.size();
   HIPCHK(c, hipMemcpy(R.d_rb + body, &D, sizeof D, hipMemcpyHostToDevice));
-  R.bodies.push_back(B);
   return body;
 }
 
-int32_t mpmhip_num_rigid_bodies(const mpmhip_ctx *c) { return c && c->rigid.enabled ? (int32_t)c->rigid.bodies.size() : 1; }
+int32_t mpmhip_num_rigid_bodies(const mpmhip_ctx *c) { return c && c->rigid.enabled ? (int32_t)c->rigid.store.bodies.size() : 1; }
 
 // out[33]: position 3, quaternion (w, x, y, z) 4, velocity 3, angular velocity 3, mass, inv_mass, inertia 9 (body frame,
 // row-major), inv_inertia 9 — the fields of RigidBody the coupling reads
 int mpmhip_rigid_get_state(mpmhip_ctx *c, int32_t id, float *out) {
   if (!c || !out) return MPMHIP_EINVAL;
-  if (!c->rigid.enabled || id < 1 || id >= (int)c->rigid.bodies.size()) return fail(c, MPMHIP_EINVAL, "no rigid body %d", id);
+  if (!c->rigid.enabled || id < 1 || id >= (int)c->rigid.store.bodies.size()) return fail(c, MPMHIP_EINVAL, "no rigid body %d", id);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RigidBodyDev D;
@@ -414,13 +249,13 @@ int mpmhip_rigid_get_state(mpmhip_ctx *c, int32_t id, float *out) {
   for (int i = 0; i < 3; i++) out[k++] = D.vel[i];
   for (int i = 0; i < 3; i++) out[k++] = D.omega[i];
   out[k++] = D.mass; out[k++] = D.inv_mass;
-  for (int i = 0; i < 9; i++) out[k++] = c->rigid.bodies[id].inertia[i];
+  for (int i = 0; i < 9; i++) out[k++] = c->rigid.store.bodies[id].inertia[i];
   for (int i = 0; i < 9; i++) out[k++] = D.inv_I[i];
   return MPMHIP_OK;
 }
 int mpmhip_rigid_set_velocity(mpmhip_ctx *c, int32_t id, const float *v, const float *w) {
   if (!c) return MPMHIP_EINVAL;
-  if (!c->rigid.enabled || id < 1 || id >= (int)c->rigid.bodies.size()) return fail(c, MPMHIP_EINVAL, "no rigid body %d", id);
+  if (!c->rigid.enabled || id < 1 || id >= (int)c->rigid.store.bodies.size()) return fail(c, MPMHIP_EINVAL, "no rigid body %d", id);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RigidBodyDev D;
@@ -445,11 +280,11 @@ int64_t mpmhip_rigid_get_samples(mpmhip_ctx *c, int32_t id, int64_t cap, float *
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   int64_t n = 0;
-  for (size_t s = 0; s < R.h_smp.size(); s++) {
-    if (id >= 0 && R.h_smp[s].body != id) continue;
+  for (size_t s = 0; s < R.store.h_smp.size(); s++) {
+    if (id >= 0 && R.store.h_smp[s].body != id) continue;
     if (n < cap) {
-      for (int k = 0; k < 3; k++) { if (pos) pos[3 * n + k] = w[3 * s + k]; if (offset) offset[3 * n + k] = R.h_smp[s].off[k]; }
-      if (body) body[n] = R.h_smp[s].body;
+      for (int k = 0; k < 3; k++) { if (pos) pos[3 * n + k] = w[3 * s + k]; if (offset) offset[3 * n + k] = R.store.h_smp[s].off[k]; }
+      if (body) body[n] = R.store.h_smp[s].body;
     }
     n++;
   }
@@ -461,20 +296,12 @@ int64_t mpmhip_rigid_get_samples(mpmhip_ctx *c, int32_t id, int64_t cap, float *
 // out: 9 floats per triangle; returns the body's triangle count.
 int64_t mpmhip_rigid_get_mesh(mpmhip_ctx *c, int32_t id, int64_t cap_triangles, float *out) {
   if (!c) return MPMHIP_EINVAL;
-  if (!c->rigid.enabled || id < 1 || id >= (int)c->rigid.bodies.size()) return fail(c, MPMHIP_EINVAL, "no rigid body %d", id);
+  if (!c->rigid.enabled || id < 1 || id >= (int)c->rigid.store.bodies.size()) return fail(c, MPMHIP_EINVAL, "no rigid body %d", id);
   if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return MPMHIP_EHIP;
   auto &R = c->rigid;
   RigidBodyDev D;
   HIPCHK(c, hipMemcpy(&D, R.d_rb + id, sizeof D, hipMemcpyDeviceToHost));
-  const auto &B = R.bodies[id];
-  if (out) {
-    for (int64_t e = 0; e < std::min<int64_t>(B.n_elems, cap_triangles); e++)
-      for (int q = 0; q < 3; q++) {
-        const float *v = &R.h_elems[(size_t)(B.first_elem + e) * 9 + 3 * q];
-        for (int r = 0; r < 3; r++) out[9 * e + 3 * q + r] = D.R[3 * r] * v[0] + D.R[3 * r + 1] * v[1] + D.R[3 * r + 2] * v[2] + D.pos[r];
-      }
-  }
-  return B.n_elems;
+  return rigid_setup::world_elements<3>(R.store, id, D, cap_triangles, out);
 }
 
 // phase-level entry points (parity tests; substep() runs them itself)
@@ -497,7 +324,7 @@ int mpmhip_add_articulation(mpmhip_ctx *c, const mpmhip_joint_config *cfg) {
   if (!c || !cfg) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   auto &R = c->rigid;
-  const int nb = R.enabled ? (int)R.bodies.size() : 0;
+  const int nb = R.enabled ? (int)R.store.bodies.size() : 0;
   if (cfg->obj0 < 1 || cfg->obj0 >= nb) return fail(c, MPMHIP_EINVAL, "add_articulation: obj0 = %d is not a rigid body of this simulation", cfg->obj0);
   if (cfg->obj1 < 0 || cfg->obj1 >= nb) return fail(c, MPMHIP_EINVAL, "add_articulation: obj1 = %d is not a rigid body of this simulation", cfg->obj1);
   if (cfg->type < JOINT_ROTATION || cfg->type > JOINT_STEPPER) return fail(c, MPMHIP_EINVAL, "add_articulation: unknown type %d", cfg->type);
@@ -519,7 +346,7 @@ int mpmhip_add_articulation(mpmhip_ctx *c, const mpmhip_joint_config *cfg) {
   jc.target_distance = cfg->target_distance; jc.penalty = cfg->penalty; jc.axis_length = cfg->axis_length;
   jc.power = cfg->power; jc.angular_velocity = cfg->angular_velocity;
   JointDev J;
-  if (const char *why = joint_init(J, jc, jb[0], jb[1], R.bodies[cfg->obj0].inertia, R.bodies[cfg->obj1].inertia))
+  if (const char *why = joint_init(J, jc, jb[0], jb[1], R.store.bodies[cfg->obj0].inertia, R.store.bodies[cfg->obj1].inertia))
     return fail(c, MPMHIP_EINVAL, "add_articulation: %s", why);
   R.joints.push_back(J);
   HIPCHK(c, hipMemcpy(R.d_joints, R.joints.data(), sizeof(JointDev) * R.joints.size(), hipMemcpyHostToDevice));

@@ -14,14 +14,14 @@
 static int rigid_collide_prepare(mpmhip_ctx *c) {
   auto &R = c->rigid;
   auto &K = R.col;
-  const size_t nv = R.h_elems.size() / 3;
-  const int nb = (int)R.bodies.size();
+  const size_t nv = R.store.h_elems.size() / 3;
+  const int nb = (int)R.store.bodies.size();
   if (K.n_verts == nv && K.n_bodies == nb && K.d_cols) return MPMHIP_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::vector<int> body(nv), first(MAX_RIGID, 0), count(MAX_RIGID, 0);
   for (int b = 1; b < nb; b++) {
-    first[b] = (int)(R.bodies[b].first_elem * 3);
-    count[b] = (int)(R.bodies[b].n_elems * 3);
+    first[b] = (int)(R.store.bodies[b].first_elem * 3);
+    count[b] = (int)(R.store.bodies[b].n_elems * 3);
     for (int v = 0; v < count[b]; v++) body[(size_t)first[b] + v] = b;
   }
   hipError_t e = hipSuccess;
@@ -46,14 +46,14 @@ static int rigid_collide_prepare(mpmhip_ctx *c) {
   return MPMHIP_OK;
 }
 // at least two bodies beside the background, and the pass switched on
-static inline bool rigid_collide_active(const mpmhip_ctx *c) { return c->rigid.enabled && c->rigid.col.on && c->rigid.bodies.size() > 2; }
+static inline bool rigid_collide_active(const mpmhip_ctx *c) { return c->rigid.enabled && c->rigid.col.on && c->rigid.store.bodies.size() > 2; }
 
 static int do_rigid_rigidify(mpmhip_ctx *c, float dt) {
   if (!rigid_collide_active(c)) return MPMHIP_OK;
   if (int rc = rigid_collide_prepare(c)) return rc;
   auto &R = c->rigid;
   auto &K = R.col;
-  const int nb = (int)R.bodies.size(), np = rigid_pair_count(nb), nv = (int)K.n_verts;
+  const int nb = (int)R.store.bodies.size(), np = rigid_pair_count(nb), nv = (int)K.n_verts;
   hipLaunchKernelGGL(k_rigid_pairs, dim3(1), dim3(64), 0, c->stream, (const RigidBodyDev *)R.d_rb, nb, K.d_pairs.get(), K.d_ctr.get());
   hipLaunchKernelGGL(k_rigid_hull_pose, dim3(std::min(particle_grid(nv), 1024)), dim3(256), 0, c->stream, (const RigidBodyDev *)R.d_rb,
                      (const float *)R.d_elems, (const int *)K.d_body, nv, K.d_r.get(), K.d_p.get());
@@ -62,7 +62,7 @@ static int do_rigid_rigidify(mpmhip_ctx *c, float dt) {
                      &c->cnt->error);
   RigidContactParams cp;
   memset(&cp, 0, sizeof cp);
-  for (int b = 1; b < nb; b++) { cp.fric[b] = R.bodies[b].cfg.friction[0]; cp.rest[b] = R.bodies[b].cfg.restitution; }
+  for (int b = 1; b < nb; b++) { cp.fric[b] = R.store.bodies[b].cfg.friction[0]; cp.rest[b] = R.store.bodies[b].cfg.restitution; }
   const RigidSolveConfig cfg{K.iterations, K.position_iterations ? 1 : 0, K.penalty, dt};
   hipLaunchKernelGGL(k_rigid_resolve, dim3(1), dim3(64), 0, c->stream, R.d_rb.get(), nb, (const RigidCollision *)K.d_cols, np,
                      K.d_hits.get(), K.d_nhits.get(), cp, cfg);
@@ -115,10 +115,10 @@ int64_t mpmhip_rigid_get_collisions(mpmhip_ctx *c, int64_t cap, float *out) {
 // order.  out: 3 floats per vertex; returns the body's vertex count.
 int64_t mpmhip_rigid_get_hull(mpmhip_ctx *c, int32_t id, int64_t cap_vertices, float *out) {
   if (!c) return MPMHIP_EINVAL;
-  if (!c->rigid.enabled || id < 1 || id >= (int)c->rigid.bodies.size()) return fail(c, MPMHIP_EINVAL, "no rigid body %d", id);
-  const auto &B = c->rigid.bodies[id];
+  if (!c->rigid.enabled || id < 1 || id >= (int)c->rigid.store.bodies.size()) return fail(c, MPMHIP_EINVAL, "no rigid body %d", id);
+  const auto &B = c->rigid.store.bodies[id];
   const int64_t n = B.n_elems * 3;
-  if (out) memcpy(out, &c->rigid.h_elems[(size_t)B.first_elem * 9], sizeof(float) * 3 * (size_t)std::min<int64_t>(n, std::max<int64_t>(cap_vertices, 0)));
+  if (out) memcpy(out, &c->rigid.store.h_elems[(size_t)B.first_elem * 9], sizeof(float) * 3 * (size_t)std::min<int64_t>(n, std::max<int64_t>(cap_vertices, 0)));
   return n;
 }
 

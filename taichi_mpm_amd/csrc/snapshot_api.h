@@ -72,7 +72,7 @@ static snap::Layout3D snap3d_layout(const mpmhip_ctx *c) {
   snap::Counts3D n;
   n.n_groups = c->groups.size(); n.n_slots = (uint64_t)c->n_slots;
   n.rigid = n.collide = rigid_active(c);
-  n.n_bodies = c->rigid.bodies.size(); n.n_joints = c->rigid.joints.size();
+  n.n_bodies = c->rigid.store.bodies.size(); n.n_joints = c->rigid.joints.size();
   snap::Layout3D L;
   snap::layout3d(n, snap::NO_LIMIT, L);
   return L;
@@ -109,7 +109,7 @@ int mpmhip_snapshot_save(mpmhip_ctx *c, void *dst, size_t cap) {
   if (L.rigid.len) {
     snap::SnapRigid r;
     memcpy(r.magic, "MPMRIGID", 8);
-    r.n_bodies = (uint32_t)c->rigid.bodies.size(); r.n_joints = (uint32_t)c->rigid.joints.size();
+    r.n_bodies = (uint32_t)c->rigid.store.bodies.size(); r.n_joints = (uint32_t)c->rigid.joints.size();
     r.sizeof_body = (uint32_t)snap::BODY3_BYTES; r.sizeof_joint = (uint32_t)snap::JOINT3_BYTES;
     snap_put(dst, L.rigid, &r);
     HIPCHK(c, snap_from_dev(dst, L.bodies, c->rigid.d_rb));
@@ -130,7 +130,7 @@ int mpmhip_snapshot_load(mpmhip_ctx *c, const void *src, size_t size) {
   snap::Facts f;
   for (int k = 0; k < 3; k++) f.res[k] = c->P.res[k];
   f.dx = c->P.dx; f.dt = c->P.dt; f.capacity = c->cap; f.groups_cap = c->groups_cap;
-  f.n_bodies = rigid_active(c) ? (int64_t)c->rigid.bodies.size() : 0;
+  f.n_bodies = rigid_active(c) ? (int64_t)c->rigid.store.bodies.size() : 0;
   snap::Blob3D B;
   const snap::Verdict v = snap::check3d(src, size, f, B);
   if (!v.ok()) return fail(c, v.rc, "%s", v.msg.c_str());
@@ -241,7 +241,7 @@ static int snap2d_prepare(mpmhip2d_ctx *m) {
 static snap::Layout2D snap2d_layout(const mpmhip2d_ctx *m) {
   snap::Counts2D n;
   n.n_groups = m->groups.size(); n.n = (uint64_t)m->n;
-  if (m->rigid_enabled) { n.n_bodies = m->bodies.size(); n.n_ranked = m->n_ranked; }
+  if (m->rigid_enabled) { n.n_bodies = m->rigid.bodies.size(); n.n_ranked = m->n_ranked; }
   n.has_async = m->async.resident; n.nblk = m->async.nblk(); n.containers = m->async.store.size;
   snap::Layout2D L;
   snap::layout2d(n, snap::NO_LIMIT, L);
@@ -268,7 +268,7 @@ int mpmhip2d_snapshot_save(mpmhip2d_ctx *m, void *dst, size_t cap) {
   memcpy(h.magic, "MPM2DSNP", 8);
   h.abi = MPMHIP_ABI_VERSION; h.n_groups = (uint32_t)m->groups.size();
   h.res[0] = m->P.res[0]; h.res[1] = m->P.res[1]; h.next_pid = m->next_pid;
-  h.n_bodies = m->rigid_enabled ? (int32_t)m->bodies.size() : 0; h.n_joints = m->joints.n; h.has_async = A.resident ? 1 : 0;
+  h.n_bodies = m->rigid_enabled ? (int32_t)m->rigid.bodies.size() : 0; h.n_joints = m->joints.n; h.has_async = A.resident ? 1 : 0;
   h.n = m->n; h.dx = m->P.dx; h.base_dt = m->base_dt; h.t = m->t; h.request_t = m->request_t; h.n_ranked = m->rigid_enabled ? m->n_ranked : 0;
   HIPCHK2D(m, hipMemcpy(&h.n_dead, m->n_dead, 4, hipMemcpyDeviceToHost));
   if (A.resident) {
@@ -304,9 +304,9 @@ static int snap2d_load(mpmhip2d_ctx *m, const void *src, size_t size) {
   auto &A = m->async;
   snap::Facts f;
   f.res[0] = m->P.res[0]; f.res[1] = m->P.res[1]; f.dx = m->P.dx;
-  f.n_bodies = m->rigid_enabled ? (int64_t)m->bodies.size() : 0;
+  f.n_bodies = m->rigid_enabled ? (int64_t)m->rigid.bodies.size() : 0;
   f.resident = A.resident; f.nb[0] = A.nb[0]; f.nb[1] = A.nb[1]; f.nblk = (int64_t)A.nblk(); f.unit_delta_t = A.cfg.unit_delta_t;
-  f.n_boundary = m->h_smp.size();
+  f.n_boundary = m->rigid.h_smp.size();
   snap::Blob2D B;
   const snap::Verdict v = snap::check2d(src, size, f, B);
   if (!v.ok()) return fail2d(m, v.rc, v.msg);
@@ -325,7 +325,7 @@ static int snap2d_load(mpmhip2d_ctx *m, const void *src, size_t size) {
     snap_get(&m->joints, src, L.joints);
     m->d_smp_rank.reset(); m->n_ranked = 0;
     if (h.n_ranked) {
-      HIPCHK2D(m, m->d_smp_rank.alloc((size_t)m->h_smp.size() + m->h_smp.size() / 4 + 1024));
+      HIPCHK2D(m, m->d_smp_rank.alloc((size_t)m->rigid.h_smp.size() + m->rigid.h_smp.size() / 4 + 1024));
       HIPCHK2D(m, snap_to_dev(m->d_smp_rank, src, L.ranks));
       m->n_ranked = h.n_ranked;
     }
