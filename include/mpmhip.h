@@ -338,6 +338,44 @@ int mpmhip_upload_grid(mpmhip_ctx *ctx, const float *src);
 int64_t mpmhip_snapshot_size(mpmhip_ctx *ctx);
 int mpmhip_snapshot_save(mpmhip_ctx *ctx, void *dst, size_t capacity);
 int mpmhip_snapshot_load(mpmhip_ctx *ctx, const void *src, size_t size);
+/* The snapshot of a whole tiled job (3D): ONE blob of the format above, whatever the job's rank count and cuts, in the format's
+ * canonical form — no dead slot (n_slots = the job's live particles, n_dead = 0), the records in ascending creation id (the order
+ * of the job's .bgeo frame), next_pid = max(the ranks' next ids, 1 + the largest live id).  mpmhip_snapshot_load on one ctx accepts
+ * it unchanged; the blob is byte-identical for every partition over the same records.  Before anything is copied every rank makes
+ * RecP.A current and, where it keeps apic_b (store_b), apic_b too: b_stale is 0 then, the ctx's own flag otherwise.
+ *   mpmhip_snapshot_size_group / mpmhip_snapshot_save_group   the n_ctx ctx of one process on one device.  Ranked and placed on the
+ *       device (the kernels of the frame of a job, below), one copy per section behind the header.  *written = the blob's bytes.
+ *       MPMHIP_EINVAL, with the field and the rank in the message: substeps, t, request_t, dx, dt, res, store_b, b_stale or the
+ *       group table differ between the ranks.  Refused as the frame of a job is: a ctx with rigid bodies, a resident asynchronous
+ *       stepper, inside a substep, ctx on different devices or of different res, an id held twice.  A short dst: MPMHIP_ECAPACITY.
+ *       dst is untouched on every refusal.
+ *   mpmhip_snapshot_head         a rank per process: this rank's header (n_slots = its own live particles) and group table into dst,
+ *                                *bytes = their size (dst NULL: the size alone).  The caller compares the ranks' heads.
+ *   mpmhip_snapshot_rows_ranked  this ctx's records in ascending id into rows_host — 176 bytes a row: RecG | RecP | apic_b row — and
+ *                                into row_index_host the number of each in the job's blob, between mpmhip_live_id_top /
+ *                                mpmhip_id_bitmap and the caller's placement, as mpmhip_bgeo_rows_ranked. */
+int mpmhip_snapshot_size_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, size_t *bytes);
+int mpmhip_snapshot_save_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, void *dst, size_t capacity, size_t *written);
+int mpmhip_snapshot_head(mpmhip_ctx *ctx, void *dst, size_t capacity, size_t *bytes);
+int mpmhip_snapshot_rows_ranked(mpmhip_ctx *ctx, int64_t top, const uint32_t *union_words_host, void *rows_host, uint32_t *row_index_host,
+                                int64_t capacity_rows, int64_t *written);
+/* Loading a snapshot into a job of ANY rank count and cuts: every rank calls mpmhip_snapshot_load_brick with the same bytes — a job's
+ * blob, or a one-ctx blob with dead slots; one with a rigid section is refused — on a ctx with a partition (mpmhip_set_partition or
+ * mpmhip_tiled_setup; MPMHIP_EINVAL without).  The rank keeps exactly the live records whose base cell lies in its brick, by the
+ * re-cut's rule to the bit, in slots [0, kept) in blob order: the ctx afterwards is a function of (blob, partition, rank).  The group
+ * table, the particles and the clocks are replaced; next_pid is the header's on every rank; no slot is dead.  The blob passes the
+ * device in chunks of records (1 Mi; MPMHIP_SNAP_CHUNK=n is a test knob read per call), twice: a rank never holds the whole blob.
+ * info = {records kept here, live records of the blob, capacity this rank needs (MPMHIP_ECAPACITY only), live records no rank can
+ * place (position not finite, or below 0.5 cells on an axis)}.  MPMHIP_ECAPACITY: the rank owns more records than its capacity;
+ * nothing of the ctx was written — mpmhip_reserve, then repeat the call on every rank.  A ctx with the native data plane ends as
+ * behind mpmhip_tiled_redistribute: clip box from the joint bounds of the blob's particles (the same on every rank, no message is
+ * passed), the next advance begins with the planning scan.
+ * mpmhip_snapshot_histogram: the per-axis histograms, cell bounds and number of the blob's live, placeable records — the outputs of
+ * mpmhip_live_histogram, counted on the device from the staged chunks — on any ctx of the blob's grid, tiled or not; nothing of the
+ * ctx is written.  What a restart on another rank count cuts its bricks from before any rank holds a particle. */
+int mpmhip_snapshot_load_brick(mpmhip_ctx *ctx, const void *src, size_t size, int64_t info[4]);
+int mpmhip_snapshot_histogram(mpmhip_ctx *ctx, const void *src, size_t size, int64_t *hist_x, int64_t *hist_y, int64_t *hist_z,
+                              int32_t lo[3], int32_t hi[3], int64_t *total);
 
 /* replaces MPM<3>::calculate_energy (src/mpm.cpp:1078-1110; general_action "calculate_energy", :936-938): sorts and
  * rasterizes, then kinetic = sum over grid nodes of 1/2 m |v|^2, potential = sum of MPMParticle::potential_energy()

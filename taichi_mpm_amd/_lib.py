@@ -7,8 +7,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SRC = os.path.join(_HERE, "csrc", "mpmhip.hip")
-# the translation units of the library: the second holds the kernels of a job's frame alone, in a code object of their own, so
-# that the code object with the substep's kernels does not move when they change (csrc/frame_launch.h)
+# the translation units of the library: the second holds the kernels of a job's frame and of a job's snapshot, in a code object of
+# their own, so that the code object with the substep's kernels does not move when they change (csrc/frame_launch.h)
 _SRCS = [_SRC, os.path.join(_HERE, "csrc", "k_frame.hip")]
 _DEPS = _SRCS + [os.path.join(_ROOT, "include", "mpmhip.h")] + sorted(
     os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith(".h"))
@@ -234,7 +234,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip_add_group", "mpmhip_add_particles", "mpmhip_poisson_tile", "mpmhip_seed_particles", "mpmhip_num_particles", "mpmhip_download",
             "mpmhip_upload", "mpmhip_substep", "mpmhip_run_substeps", "mpmhip_step", "mpmhip_current_time",
             "mpmhip_synchronize", "mpmhip_sort", "mpmhip_p2g", "mpmhip_grid_update", "mpmhip_g2p",
-            "mpmhip_download_grid", "mpmhip_upload_grid", "mpmhip_calculate_energy", "mpmhip_snapshot_size", "mpmhip_snapshot_save", "mpmhip_snapshot_load", "mpmhip_delete_particles_inside_level_set", "mpmhip_bgeo_size", "mpmhip_bgeo_encode", "mpmhip_write_bgeo", "mpmhip_bgeo_size_group", "mpmhip_bgeo_encode_group", "mpmhip_live_id_top", "mpmhip_id_bitmap", "mpmhip_bgeo_rows_ranked", "mpmhip_bgeo_envelope", "mpmhip_set_profiling", "mpmhip_profile",
+            "mpmhip_download_grid", "mpmhip_upload_grid", "mpmhip_calculate_energy", "mpmhip_snapshot_size", "mpmhip_snapshot_save", "mpmhip_snapshot_load", "mpmhip_snapshot_size_group", "mpmhip_snapshot_save_group", "mpmhip_snapshot_head", "mpmhip_snapshot_rows_ranked", "mpmhip_snapshot_load_brick", "mpmhip_snapshot_histogram", "mpmhip_delete_particles_inside_level_set", "mpmhip_bgeo_size", "mpmhip_bgeo_encode", "mpmhip_write_bgeo", "mpmhip_bgeo_size_group", "mpmhip_bgeo_encode_group", "mpmhip_live_id_top", "mpmhip_id_bitmap", "mpmhip_bgeo_rows_ranked", "mpmhip_bgeo_envelope", "mpmhip_set_profiling", "mpmhip_profile",
             "mpmhip_profile_reset", "mpmhip_set_partition", "mpmhip_set_halo", "mpmhip_halo_pack",
             "mpmhip_substep_begin", "mpmhip_substep_end", "mpmhip_substep_interior", "mpmhip_set_overlap", "mpmhip_tiled_run", "mpmhip_leaver_counts", "mpmhip_migration_scan", "mpmhip_export_leavers",
             "mpmhip_comm_unique_id", "mpmhip_comm_init", "mpmhip_comm_destroy", "mpmhip_comm_selftest", "mpmhip_tiled_setup", "mpmhip_tiled_ipc_handle",
@@ -505,6 +505,12 @@ def load():
     L.mpmhip_snapshot_size.restype = C.c_int64
     L.mpmhip_snapshot_save.argtypes = [vp, vp, C.c_size_t]
     L.mpmhip_snapshot_load.argtypes = [vp, vp, C.c_size_t]
+    L.mpmhip_snapshot_size_group.argtypes = [P(vp), C.c_int32, P(C.c_size_t)]
+    L.mpmhip_snapshot_save_group.argtypes = [P(vp), C.c_int32, C.c_void_p, C.c_size_t, P(C.c_size_t)]
+    L.mpmhip_snapshot_head.argtypes = [vp, C.c_void_p, C.c_size_t, P(C.c_size_t)]
+    L.mpmhip_snapshot_rows_ranked.argtypes = [vp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+    L.mpmhip_snapshot_load_brick.argtypes = [vp, C.c_void_p, C.c_size_t, P(C.c_int64)]
+    L.mpmhip_snapshot_histogram.argtypes = [vp, C.c_void_p, C.c_size_t, lp, lp, lp, ip, ip, lp]
     L.mpmhip_set_profiling.argtypes = [vp, C.c_int32]
     L.mpmhip_set_profile_sampling.argtypes = [vp, C.c_int32]
     L.mpmhip_profile.argtypes = [vp, C.c_char_p, C.c_size_t]

@@ -1,5 +1,5 @@
-// taichi_mpm_amd/csrc/k_frame.hip — the kernels of a job's frame (k_frame.h) and their launchers (frame_launch.h): the second
-// translation unit of libmpmhip.so, with a code object of its own.
+// taichi_mpm_amd/csrc/k_frame.hip — the kernels of a job's frame (k_frame.h) and of a job's snapshot (k_snapshot_job.h) with their
+// launchers (frame_launch.h, snapshot_job_launch.h): the second translation unit of libmpmhip.so, with a code object of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -7,6 +7,7 @@
 #include "../../include/mpmhip.h"
 #define MPM_BGEO_ROW_ONLY  // of k_bgeo.h: bgeo_row, not the one-ctx kernels
 #include "k_frame.h"
+#include "k_snapshot_job.h"
 
 namespace mpm {
 
@@ -27,6 +28,20 @@ void frame_launch_rows(hipStream_t st, int grid, bool verbose, uint32_t n_slots,
   auto k = verbose ? k_bgeo_rows_ranked<true> : k_bgeo_rows_ranked<false>;
   hipLaunchKernelGGL(k, dim3(grid), dim3(FRAME_WG), 0, st, n_slots, rg, rp, rb, groups, limits, top, bits, prefix, n_rows, rows, job_bits, job_prefix,
                      row_index, err);
+}
+
+void snap_launch_rows(hipStream_t st, int grid, uint32_t n_slots, const float4 *rg, const float4 *rp, const float4 *rb, uint32_t top,
+                      const uint32_t *bits, const uint32_t *prefix, uint32_t n_rows, float4 *out_rg, float4 *out_rp, float4 *out_rb,
+                      const uint32_t *job_bits, const uint32_t *job_prefix, uint32_t *row_index, int32_t *err) {
+  hipLaunchKernelGGL(k_snap_rows_ranked, dim3(grid), dim3(FRAME_WG), 0, st, n_slots, rg, rp, rb, top, bits, prefix, n_rows, out_rg, out_rp, out_rb,
+                     job_bits, job_prefix, row_index, err);
+}
+void snap_launch_own_count(hipStream_t st, const Params &P, const Tiling &T, uint32_t n, const float4 *rg, uint32_t *totals, uint32_t *small) {
+  hipLaunchKernelGGL(k_snap_own_count, dim3(snap_spans(n)), dim3(256), 0, st, P, T, n, rg, totals, small);
+}
+void snap_launch_own_emit(hipStream_t st, const Params &P, const Tiling &T, uint32_t n, const float4 *rg, const float4 *rp, const float4 *rb,
+                          const uint32_t *offs, uint32_t cap, float4 *out_rg, float4 *out_rp, float4 *out_rb, uint32_t *small) {
+  hipLaunchKernelGGL(k_snap_own_emit, dim3(snap_spans(n)), dim3(256), 0, st, P, T, n, rg, rp, rb, offs, cap, out_rg, out_rp, out_rb, small);
 }
 
 }  // namespace mpm

@@ -5,6 +5,7 @@
 
 namespace mpm {
 
+#ifndef MPM_TILING_RULES_ONLY  // (k_frame.hip takes the ownership rules alone: the kernels here belong to mpmhip.hip's code object)
 // ------------------------------------------------------------------------------------------------ tiling
 // This rank's partial (m v, m) sums on every halo box -> the box's send buffer.  One WAVE per grid block (4^3 nodes) a box touches,
 // one lane per node: lanes 0..7 look the <= 8 active source blocks c - q up whose 6^3 tiles overlap the block (once per wave — until
@@ -174,11 +175,13 @@ __global__ __launch_bounds__(256) void k_active_bounds(Params P, const Counters 
   }
 }
 
+#endif  // MPM_TILING_RULES_ONLY
 __device__ __forceinline__ int part_index(const int *cuts, int n, int c) {
   int p = 0;
   while (p + 1 < n && c >= cuts[p + 1]) p++;
   return p;
 }
+#ifndef MPM_TILING_RULES_ONLY
 // destination rank of a live particle at x (brick containing its base cell); -1 if it is not representable
 __device__ __forceinline__ int dest_rank(const Params &P, const Tiling &T, float4 g0, bool &beyond_margin) {
   int b[3];
@@ -307,6 +310,7 @@ __global__ __launch_bounds__(256) void k_import(Params P, uint32_t n, uint32_t b
   }
 }
 
+#endif  // MPM_TILING_RULES_ONLY
 // ------------------------------------------------------------------------------------------------ re-cutting a running job
 // Base cell of a live particle with NOTHING contracted: b[k] = (int)fl(fl(x[k] * fl(1 / dx)) - 0.5f), the expression the brick seeding
 // documents (k_seed.h: seed_base_cell) and tiled.base_cells restates to the bit — the histograms the new cuts come from and the
@@ -348,6 +352,7 @@ __device__ __forceinline__ void bounds_epilogue(int lo[3], int hi[3], int *__res
   }
 }
 
+#ifndef MPM_TILING_RULES_ONLY
 // one count into a histogram row (T = int32_t: a workgroup's LDS row; unsigned long long: the global row).  Particles come in the
 // order of the last sort, so the lanes of a wave mostly share a bin (a pile: thousands of particles in one y-bin): the lanes that
 // agree with the wave's first valid lane add their NUMBER with one atomic, only the others add for themselves — no lane-serialised
@@ -461,5 +466,6 @@ __global__ __launch_bounds__(256) void k_recut_pack(Params P, Tiling T, int worl
   }
 }
 
+#endif  // MPM_TILING_RULES_ONLY
 
 }  // namespace mpm

@@ -107,6 +107,7 @@
 #include "poisson_tile.h"
 #include "k_bgeo.h"
 #include "frame_launch.h"
+#include "snapshot_job_launch.h"
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
 #include "k_mpm2d_det.h"
@@ -3577,3 +3578,4 @@ int mpmhip_debug_plasticity(mpmhip_ctx *c, int32_t material, const float params[
 }  // extern "C"
 
 #include "tiled_api.h"
+#include "snapshot_job_api.h"

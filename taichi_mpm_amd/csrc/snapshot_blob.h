@@ -407,4 +407,19 @@ inline Verdict check2d(const void *src, uint64_t size, const Facts &f, Blob2D &B
   return Verdict();
 }
 
+// ------------------------------------------------------------------------------------------------ a 3D blob loaded brick by brick
+// mpmhip_snapshot_load_brick / mpmhip_snapshot_histogram (snapshot_job_api.h): check3d with two differences.  The blob's slot count
+// is not held against the ctx's capacity — a rank keeps the records of its own brick, counted on the device — but against 2^31 - 1,
+// what the kernels index with 32 bits; and a blob with a rigid section is refused whatever f.n_bodies says (a tiled ctx has no
+// rigid bodies).  Everything else is check3d's own verdict.
+constexpr int64_t BRICK_MAX_SLOTS = 0x7fffffffll;
+inline Verdict check3d_brick(const void *src, uint64_t size, const Facts &f, Blob3D &B) {
+  Facts g = f;
+  g.capacity = BRICK_MAX_SLOTS;
+  g.n_bodies = 0;
+  const Verdict v = check3d(src, size, g, B);
+  if (!v.ok() && B.has_rigid) return refuse(MPMHIP_EINVAL, "snapshot holds %u rigid bodies: a tiled job loads no rigid-body snapshot", B.r.n_bodies ? B.r.n_bodies - 1 : 0u);
+  return v;
+}
+
 }  // namespace snap

@@ -737,6 +737,68 @@ class _NativeJobBase:
             f.write(data)
         return True
 
+    # --- snapshots of the whole job (general_action save / load, src/mpm.cpp:940-960): ONE file whatever the bricks
+    def save_snapshot(self, path):
+        """the job's snapshot to `path`: the file Simulation3D.save_snapshot writes — one leading int64 (job.frame_count), then the
+        MPMHIP01 blob in its canonical form (snapshot_bytes).  Collective on a rank-per-process job: rank 0 writes.  True where the
+        file was written."""
+        blob = self.snapshot_bytes()
+        if blob is None:
+            return False
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(np.array([self.frame_count], np.int64).tobytes())
+            f.write(blob)
+        return True
+
+    def load_snapshot(self, src):
+        """a snapshot file — a job's, of any rank count and cuts, or a plain Simulation3D's — into this job: every rank keeps the live
+        records of its own brick (mpmhip_snapshot_load_brick), in blob order; groups, particles and clocks are replaced.  `src`: a
+        path, or the file's bytes.  Collective: every rank reads the same file.  A rank whose share exceeds its capacity is grown
+        (mpmhip_reserve at the need plus 1/8, as rebalance does) and the call repeated once on every rank.  Sets job.frame_count from
+        the leading word; the next run() begins with the planning scan.
+        Returns dict(kept=[per rank], total, unplaceable, grew=[ranks])."""
+        import warnings
+
+        from .mpm import MPMError, snapshot_groups
+        raw = np.frombuffer(src, np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.fromfile(src, np.uint8)
+        hsize = C.sizeof(_lib.SnapHeader)
+        if len(raw) < 8 + hsize:
+            raise MPMError("load_snapshot: %d bytes, less than the header of a snapshot" % len(raw))
+        frame, blob = int(raw[:8].view(np.int64)[0]), np.ascontiguousarray(raw[8:])
+        grew = set()
+        for attempt in range(2):
+            info, refused = self._load_brick(blob)
+            if not refused:
+                break
+            if attempt == 1:
+                raise MPMError("load_snapshot: refused again after the ranks grew: " + self._last_errors())
+            for e, row in zip(self.engines, info):
+                if row[2] > 0:
+                    cap = int(row[2]) + int(row[2]) // 8
+                    e.sim._check(e.L.mpmhip_reserve(e.ctx, cap))
+                    e.sim._capacity = max(e.sim._capacity, cap)
+            grew |= set(self._ranks_where([row[2] > 0 for row in info]))
+        h = _lib.SnapHeader.from_buffer_copy(blob[:hsize].tobytes())
+        for e, row in zip(self.engines, info):
+            e.sim._groups, e.sim._n_added, e.sim._time_offset = snapshot_groups(blob, h), int(row[0]), 0.0
+        self.frame_count = frame
+        out = dict(kept=self._job_kept(info), total=int(info[0][1]), unplaceable=int(info[0][3]), grew=sorted(grew))
+        if out["unplaceable"]:
+            warnings.warn("load_snapshot: %d live particles of the snapshot have no finite position at or above half a cell on every axis: "
+                          "no rank keeps them" % out["unplaceable"])
+        return out
+
+    def _load_rank(self, e, blob):
+        """mpmhip_snapshot_load_brick on one rank: (info row, refused for capacity)"""
+        info = (C.c_int64 * 4)()
+        rc = int(e.L.mpmhip_snapshot_load_brick(e.ctx, blob.ctypes.data_as(C.c_void_p), blob.size, info))
+        if rc != _lib.ECAPACITY:
+            e.sim._check(rc)
+        return list(info), rc == _lib.ECAPACITY
+
     def _last_errors(self):
         return "; ".join(e.L.mpmhip_last_error(e.ctx).decode() for e in self.engines if e.L.mpmhip_last_error(e.ctx))
 
@@ -935,6 +997,83 @@ class NativeTiledJob(_NativeJobBase):
         head, tail = frame_envelope(held, verbose)
         return assemble_frame(head, tail, parts, width)
 
+    def snapshot_bytes(self):
+        """the snapshot blob of the WHOLE job (collective): bytes on rank 0, None on the other ranks — the blob one ctx holding all
+        ranks' live records in id order would save.  The control group carries the ranks' heads (all_gather, compared on every rank:
+        clocks, grid, dt, store_b and group table must agree), top (the job's reduce), the bitmaps (ONE all_reduce) and the counts;
+        records and row numbers go to rank 0, which places them (assemble_snapshot)."""
+        from .mpm import MPMError
+        e, L, sim, dist, world = self.e, self.e.L, self.e.sim, self._dist, self.world
+        nb = C.c_size_t()
+        sim._check(L.mpmhip_snapshot_head(e.ctx, None, 0, C.byref(nb)))
+        head = np.empty(nb.value, np.uint8)
+        sim._check(L.mpmhip_snapshot_head(e.ctx, head.ctypes.data_as(C.c_void_p), head.size, C.byref(nb)))
+        heads = [head.tobytes()]
+        if world > 1:
+            import torch
+            sizes = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(sizes, torch.tensor([head.size], dtype=torch.int64))
+            most = max(int(v[0]) for v in sizes)
+            rows = [torch.zeros(most, dtype=torch.uint8) for _ in range(world)]
+            dist.all_gather(rows, torch.from_numpy(np.concatenate([head, np.zeros(most - head.size, np.uint8)])))
+            heads = [r.numpy()[:int(v[0])].tobytes() for r, v in zip(rows, sizes)]
+        for r in range(1, world):
+            what = snapshot_head_differs(heads[0], heads[r])
+            if what:
+                raise MPMError("snapshot of a tiled job: %s of rank %d differs from rank 0's (a job's snapshot has one clock, one grid and "
+                               "one group table)" % (what, r))
+        top = int(sim._check(L.mpmhip_live_id_top(e.ctx)))
+        if world > 1:
+            top = int(self.reduce([float(top)], "max")[0])
+        words = np.zeros((top + 31) // 32, np.uint32)
+        live = C.c_int64()
+        sim._check(L.mpmhip_id_bitmap(e.ctx, top, words.ctypes.data_as(C.c_void_p), C.byref(live)))
+        counts = [int(live.value)]
+        if world > 1:
+            if words.size:
+                dist.all_reduce(torch.from_numpy(words.view(np.uint8)), op=dist.ReduceOp.SUM)
+            rows = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(rows, torch.tensor([counts[0]], dtype=torch.int64))
+            counts = [int(r[0]) for r in rows]
+        held = int(np.unpackbits(words.view(np.uint8)).sum(dtype=np.int64)) if words.size else 0
+        if sum(counts) != held:
+            raise MPMError("snapshot of a tiled job: the ranks hold %d particles but %d different creation ids below %d — an id is held "
+                           "twice (ids uploaded per rank must be unique in the job)" % (sum(counts), held, top))
+        n = counts[self.rank]
+        mine = np.empty((n, SNAP_ROW_BYTES), np.uint8)
+        index = np.empty(n, np.uint32)
+        written = C.c_int64()
+        sim._check(L.mpmhip_snapshot_rows_ranked(e.ctx, top, words.ctypes.data_as(C.c_void_p), mine.ctypes.data_as(C.c_void_p),
+                                                 index.ctypes.data_as(C.c_void_p), n, C.byref(written)))
+        if written.value != n:
+            raise MPMError("snapshot of a tiled job: rank %d placed %d records of %d particles" % (self.rank, written.value, n))
+        parts = [(index, mine)]
+        if world > 1:
+            if self.rank != 0:
+                if n:
+                    dist.send(torch.from_numpy(index.view(np.uint8)), dst=0)
+                    dist.send(torch.from_numpy(mine.reshape(-1)), dst=0)
+                return None
+            for r in range(1, world):
+                idx, rws = np.empty(counts[r], np.uint32), np.empty((counts[r], SNAP_ROW_BYTES), np.uint8)
+                if counts[r]:
+                    dist.recv(torch.from_numpy(idx.view(np.uint8)), src=r)
+                    dist.recv(torch.from_numpy(rws.reshape(-1)), src=r)
+                parts.append((idx, rws))
+        hsize = C.sizeof(_lib.SnapHeader)
+        h = _lib.SnapHeader.from_buffer_copy(heads[0][:hsize])
+        h.next_pid = max(int(_lib.SnapHeader.from_buffer_copy(b[:hsize]).next_pid) for b in heads)
+        return assemble_snapshot(bytes(h), heads[0][hsize:], parts)
+
+    def _load_brick(self, blob):
+        info, refused = self._load_rank(self.e, blob)
+        if self.world > 1:  # every rank repeats or none does
+            refused = self.reduce([1.0 if refused else 0.0], "max")[0] > 0
+        return [info], refused
+
+    def _job_kept(self, info):
+        return self._all_sum([info[0][0] if r == self.rank else 0 for r in range(self.world)])
+
     # --- scalars of the WHOLE job, reduced inside the library (mpmhip_tiled_reduce: ncclAllReduce, or rows + epochs over the IPC wire)
     def reduce(self, values, op="sum"):
         """in-place all-reduce of up to 16 doubles over the ranks (collective); returns the reduced list"""
@@ -1063,6 +1202,26 @@ class NativeVirtualJob(_NativeJobBase):
                           "mpmhip_bgeo_encode_group")
         return buf[:w.value].tobytes()
 
+    def snapshot_bytes(self):
+        """the snapshot blob of the WHOLE job as bytes: the MPMHIP01 blob one ctx holding all ranks' live records in id order would
+        save — no dead slot, byte-identical for every rank count and every set of cuts (mpmhip_snapshot_save_group: ids ranked,
+        records placed and copied on the device)"""
+        L, K = self.engines[0].L, len(self.engines)
+        n, w = C.c_size_t(), C.c_size_t()
+        self._group_check(L.mpmhip_snapshot_size_group(self._arr, K, C.byref(n)), "mpmhip_snapshot_size_group")
+        buf = np.empty(n.value, np.uint8)
+        self._group_check(L.mpmhip_snapshot_save_group(self._arr, K, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(w)),
+                          "mpmhip_snapshot_save_group")
+        return buf[:w.value].tobytes()
+
+    def _load_brick(self, blob):
+        rows = [self._load_rank(e, blob) for e in self.engines]  # (a rank that refuses for capacity is untouched; the others loaded)
+        return [row for row, _ in rows], any(refused for _, refused in rows)
+
+    @staticmethod
+    def _job_kept(info):
+        return [int(row[0]) for row in info]
+
     def totals(self):
         out = (C.c_int64 * 4)()
         L = self.engines[0].L
@@ -1111,6 +1270,78 @@ def assemble_frame(head, tail, parts, width):
             raise MPMError("assemble_frame: part %d places two rows at one row number (every number must be taken exactly once)" % r)
         out[idx] = rows.reshape(idx.size, int(width))
     return bytes(head) + out.tobytes() + bytes(tail)
+
+
+# ---------------------------------------------------------------------------------------------------- snapshots of a job
+SNAP_ROW_BYTES = 176  # a record as mpmhip_snapshot_rows_ranked hands it over: RecG 64 | RecP 64 | apic_b row 48
+_SNAP_RG, _SNAP_RP, _SNAP_PID = 64, 64, 56  # bytes of RecG, of RecP; the creation id inside a RecG (csrc/snapshot_blob.h)
+
+
+def snapshot_head_differs(a, b):
+    """the first of substeps, t, request_t, dx, dt, res, store_b, b_stale, "group table" in which two heads (mpmhip_snapshot_head:
+    header + group table) differ, or None.  Floats are compared as bits.  Pure."""
+    hsize = C.sizeof(_lib.SnapHeader)
+    ha, hb = _lib.SnapHeader.from_buffer_copy(bytes(a)[:hsize]), _lib.SnapHeader.from_buffer_copy(bytes(b)[:hsize])
+    for name in ("substeps", "t", "request_t", "dx", "dt", "res", "store_b", "b_stale"):
+        off, size = getattr(_lib.SnapHeader, name).offset, getattr(_lib.SnapHeader, name).size
+        if bytes(ha)[off:off + size] != bytes(hb)[off:off + size]:
+            return name
+    if bytes(a)[hsize:] != bytes(b)[hsize:]:
+        return "group table"
+    return None
+
+
+def assemble_snapshot(head, groups, parts):
+    """the job's MPMHIP01 blob from the ranks' records: head = the 80 header bytes of a rank, with next_pid raised to the ranks'
+    maximum; groups = the group table's bytes; parts = [(row numbers [n_r], records [n_r] of 176 bytes)] of every rank (what
+    mpmhip_snapshot_rows_ranked returns).  n_slots = the records of all parts, n_dead = 0, next_pid = max(head's, 1 + the largest
+    creation id).  The numbers must be exactly 0 .. n - 1: one taken twice, or one left out, is refused (MPMError).  Pure: no device,
+    no library."""
+    from .mpm import MPMError
+    hsize = C.sizeof(_lib.SnapHeader)
+    if len(head) != hsize or len(groups) % C.sizeof(_lib.GroupParams):
+        raise MPMError("assemble_snapshot: a head of %d bytes (%d) and a group table of %d" % (len(head), hsize, len(groups)))
+    n = sum(len(idx) for idx, _ in parts)
+    out = np.empty((n, SNAP_ROW_BYTES), np.uint8)
+    seen, placed = np.zeros(n, bool), 0
+    for r, (idx, rows) in enumerate(parts):
+        idx = np.asarray(idx).astype(np.int64).reshape(-1)
+        rows = np.frombuffer(rows, np.uint8) if isinstance(rows, (bytes, bytearray, memoryview)) else np.asarray(rows, np.uint8)
+        if rows.size != idx.size * SNAP_ROW_BYTES:
+            raise MPMError("assemble_snapshot: part %d has %d row numbers and %d bytes of records of %d" % (r, idx.size, rows.size, SNAP_ROW_BYTES))
+        if not idx.size:
+            continue
+        if idx.min() < 0 or idx.max() >= n:
+            raise MPMError("assemble_snapshot: part %d places a record at %d, the snapshot has %d: a row number is left out"
+                           % (r, int(idx.max() if idx.max() >= n else idx.min()), n))
+        taken = seen[idx]
+        seen[idx] = True
+        placed += idx.size
+        if taken.any() or int(np.count_nonzero(seen)) != placed:
+            raise MPMError("assemble_snapshot: part %d places two records at one row number (every number must be taken exactly once)" % r)
+        out[idx] = rows.reshape(idx.size, SNAP_ROW_BYTES)
+    h = _lib.SnapHeader.from_buffer_copy(bytes(head))
+    ids = np.ascontiguousarray(out[:, _SNAP_PID:_SNAP_PID + 4]).view(np.int32).ravel()
+    h.n_slots, h.n_dead = n, 0
+    h.next_pid = max(int(h.next_pid), int(ids.max()) + 1 if n else 0)
+    return (bytes(h) + bytes(groups) + out[:, :_SNAP_RG].tobytes() + out[:, _SNAP_RG:_SNAP_RG + _SNAP_RP].tobytes()
+            + out[:, _SNAP_RG + _SNAP_RP:].tobytes())
+
+
+def snapshot_histograms(sim, src):
+    """(hists, cell_lo, cell_hi, total) of the live, placeable particles of a snapshot file (`src`: a path, or the file's bytes) —
+    counted on the device from staged chunks of the blob (mpmhip_snapshot_histogram), nothing of `sim` is written: the tuple
+    seed_histograms returns, and what a restart on another rank count cuts its bricks from (Partition.from_histograms) before any
+    rank holds a particle.  `sim`: any simulation of the snapshot's grid."""
+    raw = np.frombuffer(src, np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.fromfile(src, np.uint8)
+    blob = np.ascontiguousarray(raw[8:])
+    sim._ensure_ctx()
+    hists = [np.zeros(r, np.int64) for r in sim.res]
+    total, lo, hi = C.c_int64(0), (C.c_int32 * 3)(), (C.c_int32 * 3)()
+    lp = C.POINTER(C.c_int64)
+    sim._check(sim._L.mpmhip_snapshot_histogram(sim._ctx, blob.ctypes.data_as(C.c_void_p), blob.size, hists[0].ctypes.data_as(lp),
+                                                hists[1].ctypes.data_as(lp), hists[2].ctypes.data_as(lp), lo, hi, C.byref(total)))
+    return hists, np.array(lo[:], np.int64), np.array(hi[:], np.int64), int(total.value)
 
 
 # ---------------------------------------------------------------------------------------------------- scenes seeded on the device
