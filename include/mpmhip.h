@@ -1219,7 +1219,7 @@ int64_t mpmhip2d_download_colours(mpmhip2d_ctx *ctx, int64_t capacity, uint32_t 
  * the transfers (block_op_rigid, src/transfer.cpp:367-463,706-835) and advect_rigid_bodies (src/mpm_rigid_body.cpp:255-286).
  * Once a body exists, every substep runs: sort | rasterize_rigid_boundary | gather_cdf | P2G | grid | G2P | advect.
  * Rigid-rigid collisions (rigidify) are an opt-in pass: mpmhip_set_rigid_collision at the end of this section; joints:
- * mpmhip_add_articulation below.  Rigid bodies cannot be combined with the multi-GPU tiling or asynchronous stepping.
+ * mpmhip_add_articulation below.  Rigid bodies cannot be combined with asynchronous stepping; on a tiled job: "Bodies on a job".
  * ------------------------------------------------------------------------------------------------------------------ */
 /* scripted_position(t) -> world position; scripted_rotation(t) -> Euler angles in degrees (applied X * Y * Z):
  * tc.function13 objects in the scene scripts (scripts/mls-cpic/sand_paddles.py:27, src/mpm_rigid_body.cpp:79-92) */
@@ -1249,6 +1249,11 @@ int32_t mpmhip_num_rigid_bodies(const mpmhip_ctx *ctx); /* including the backgro
  * inertia 9 (body frame, row-major), inv_inertia 9 */
 int mpmhip_rigid_get_state(mpmhip_ctx *ctx, int32_t id, float *out);
 int mpmhip_rigid_set_velocity(mpmhip_ctx *ctx, int32_t id, const float *velocity, const float *angular_velocity);
+/* A digest of the bodies as this ctx holds them: the device records of all bodies (pose, velocities, mass properties), the numeric
+ * part of their configs, the boundary particles with their creation ids, the elements, the joints and the coupling's settings.
+ * Every rank of a tiled job holds ALL bodies ("Bodies on a job", below): ranks compare digests instead of shipping records.
+ * Synchronises the ctx's stream. */
+int mpmhip_rigid_digest(mpmhip_ctx *ctx, uint64_t out[2]);
 /* the boundary particles sampled on the body's triangles (RigidBoundaryParticle, src/boundary_particle.h): world
  * position, offset from the centre of mass in the body frame, body index; id < 0: all bodies.  Returns the count. */
 int64_t mpmhip_rigid_get_samples(mpmhip_ctx *ctx, int32_t id, int64_t capacity, float *position, float *offset, int32_t *body);
@@ -1294,6 +1299,26 @@ int mpmhip_download_cdf(mpmhip_ctx *ctx, uint32_t *states, float *distance);
 /* gather_cdf's per-particle results, live particles in slot order, 5 floats each: boundary_normal 3, boundary_distance,
  * near_boundary.  Valid between mpmhip_gather_cdf and the next G2P (a G2P moves the records). */
 int64_t mpmhip_download_boundary(mpmhip_ctx *ctx, float *out, int64_t n_capacity);
+
+/* Bodies on a job — CPIC rigid bodies on a tiled ctx with the native data plane (mpmhip_tiled_setup; csrc/tiled_api.h, csrc/k_rigid_rows.h).
+ * Every rank of the job holds ALL bodies: add the same bodies (and joints), in the same order, on every rank BEFORE mpmhip_tiled_setup
+ * (mpmhip_set_partition alone may come first).  The set-up sizes the arena for the bodies' impulse rows; a body added afterwards is
+ * refused (add the bodies first, or set the job up again).  The records of the bodies are byte-identical on all ranks at every
+ * substep boundary: compare mpmhip_rigid_digest across the ranks.
+ *   Per substep everything that acts on the bodies alone (joints, the colored distance field of all bodies, the level-set collision,
+ *   the advection, the scripts) runs replicated on every rank.  What a rank's colour-aware transfer kernels hand the bodies is the
+ *   rank's impulse ROW, 12 bodies (the most a simulation holds, the background included) x 6 floats = 288 bytes: twice a substep — behind the rigid P2G and behind the rigid
+ *   G2P — the rows of all ranks reach every rank, which adds them in RANK ORDER and applies the sum.  Peer wires (IPC, LOCAL): peer
+ *   writes and epoch words of their own, behind the same bounded wait as the halo boxes (MPMHIP_TILE_WAIT_S; error bit 16).  RCCL:
+ *   one send / receive pair per peer (MPMHIP_WIRE_LOCAL_RCCL: the same pairs as self-sends).  No host synchronisation per substep.
+ *   mpmhip_set_overlap(1) is accepted and ignored: a ctx with bodies runs its substeps unsplit.
+ *   mpmhip_config.deterministic: the rows are fixed-order sums; two runs of a job end byte-identical.
+ * Refused, each with a message and the ctx untouched: the callback path (mpmhip_set_halo, mpmhip_tiled_run) on a ctx with bodies;
+ * rigid_body_collision (mpmhip_set_rigid_collision) on a tiled ctx; the asynchronous stepper; mpmhip_tiled_redistribute(_group), the
+ * frames and snapshots of a job (mpmhip_bgeo_*_group, mpmhip_bgeo_rows_ranked, mpmhip_snapshot_*_group, mpmhip_snapshot_load_brick)
+ * and mpmhip_calculate_energy(_group) of a job with bodies.  mpmhip_seed_particles_brick keeps working (an emitter onto a wheel).
+ * The multi-rank RCCL transport of the rows has not been on more than one GPU: on one it is reached through
+ * MPMHIP_WIRE_LOCAL_RCCL and the one-rank case. */
 
 /* ---- rigid-rigid collisions: MPM::rigidify (src/mpm_rigid_body.cpp:306-345), 3D only as in the reference
  * (RigidSolver<2>::detect_rigid_collision is TC_NOT_IMPLEMENTED, src/rigid_body_solver.h:154-158).

@@ -250,7 +250,7 @@ _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create"
             "mpmhip2d_async_state", "mpmhip2d_async_current_time", "mpmhip2d_async_table", "mpmhip2d_bgeo_size", "mpmhip2d_bgeo_encode", "mpmhip2d_write_bgeo", "mpmhip2d_snapshot_size", "mpmhip2d_snapshot_save", "mpmhip2d_snapshot_load",
             "mpmhip2d_set_rigid_coupling", "mpmhip2d_set_rigid_levelset_collision", "mpmhip2d_add_articulation", "mpmhip2d_set_articulation_iterations", "mpmhip2d_add_rigid_body", "mpmhip2d_rigid_get_state", "mpmhip2d_rigid_get_samples", "mpmhip2d_cdf_phase",
             "mpmhip2d_download_cdf", "mpmhip2d_download_colours", "mpmhip2d_poisson_tile", "mpmhip2d_seed_particles", "mpmhip2d_reserve", "mpmhip_seed_particles_region", "mpmhip2d_seed_particles_region", "mpmhip_region_sample", "mpmhip_region_bake", "mpmhip_seed_particles_brick", "mpmhip_seed_histogram", "mpmhip_set_next_id", "mpmhip2d_num_slots", "mpmhip2d_capacity", "mpmhip2d_set_levelset_sdf", "mpmhip2d_delete_particles_inside_level_set", "mpmhip2d_debug_levelset_sample", "mpmhip2d_debug_force", "mpmhip2d_debug_plasticity", "mpmhip2d_debug_svd2",
-            "mpmhip_set_rigid_coupling", "mpmhip_add_rigid_body", "mpmhip_num_rigid_bodies", "mpmhip_rigid_get_state", "mpmhip_rigid_set_velocity",
+            "mpmhip_set_rigid_coupling", "mpmhip_add_rigid_body", "mpmhip_num_rigid_bodies", "mpmhip_rigid_get_state", "mpmhip_rigid_set_velocity", "mpmhip_rigid_digest",
             "mpmhip_rigid_get_samples", "mpmhip_rigid_get_mesh", "mpmhip2d_rigid_get_mesh", "mpmhip_rasterize_rigid_boundary", "mpmhip_gather_cdf", "mpmhip_advect_rigid_bodies", "mpmhip_download_cdf",
             "mpmhip_add_articulation", "mpmhip_num_articulations", "mpmhip_set_articulation_iterations", "mpmhip_articulate",
             "mpmhip_download_boundary",
@@ -519,6 +519,7 @@ def load():
     L.mpmhip_add_rigid_body.argtypes = [vp, P(RigidConfig), C.c_int64, fp]
     L.mpmhip_num_rigid_bodies.argtypes = [vp]
     L.mpmhip_rigid_get_state.argtypes = [vp, C.c_int32, fp]
+    L.mpmhip_rigid_digest.argtypes = [vp, P(C.c_uint64)]
     L.mpmhip_rigid_set_velocity.argtypes = [vp, C.c_int32, fp, fp]
     L.mpmhip_rigid_get_samples.argtypes = [vp, C.c_int32, C.c_int64, fp, fp, ip]
     L.mpmhip_rigid_get_samples.restype = C.c_int64

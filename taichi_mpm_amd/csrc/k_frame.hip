@@ -1,5 +1,6 @@
 // taichi_mpm_amd/csrc/k_frame.hip — the kernels of a job's frame (k_frame.h) and of a job's snapshot (k_snapshot_job.h) with their
-// launchers (frame_launch.h, snapshot_job_launch.h): the second translation unit of libmpmhip.so, with a code object of its own.
+// launchers (frame_launch.h, snapshot_job_launch.h), and the impulse rows of a job with CPIC rigid bodies (k_rigid_rows.h,
+// rigid_rows_launch.h): the second translation unit of libmpmhip.so, with a code object of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -8,6 +9,7 @@
 #define MPM_BGEO_ROW_ONLY  // of k_bgeo.h: bgeo_row, not the one-ctx kernels
 #include "k_frame.h"
 #include "k_snapshot_job.h"
+#include "k_rigid_rows.h"
 
 namespace mpm {
 
@@ -42,6 +44,18 @@ void snap_launch_own_count(hipStream_t st, const Params &P, const Tiling &T, uin
 void snap_launch_own_emit(hipStream_t st, const Params &P, const Tiling &T, uint32_t n, const float4 *rg, const float4 *rp, const float4 *rb,
                           const uint32_t *offs, uint32_t cap, float4 *out_rg, float4 *out_rp, float4 *out_rb, uint32_t *small) {
   hipLaunchKernelGGL(k_snap_own_emit, dim3(snap_spans(n)), dim3(256), 0, st, P, T, n, rg, rp, rb, offs, cap, out_rg, out_rp, out_rb, small);
+}
+
+
+void rows_launch_sum(hipStream_t st, int nb, const Params &P, const Counters *cnt, const uint8_t *blk_rigid, const float *rows, RigidBodyDev *rb) {
+  hipLaunchKernelGGL(k_rigid_rows_sum, dim3(nb - 1), dim3(ROWS_SUM_WG), 0, st, P, cnt, blk_rigid, rows, rb);
+}
+void rows_launch_out(hipStream_t st, RigidBodyDev *rb, int nb, const RowPut &L, int world, float *stage, uint32_t epoch) {
+  hipLaunchKernelGGL(k_rigid_row_out, dim3(1), dim3(ROW_OUT_WG), 0, st, rb, nb, L, world, stage, epoch);
+}
+void rows_launch_apply(hipStream_t st, RigidBodyDev *rb, int nb, const float *table, int world, const uint32_t *words, int n_wait,
+                       uint32_t epoch, unsigned long long timeout_ticks, Counters *cnt) {
+  hipLaunchKernelGGL(k_rigid_rows_world, dim3(1), dim3(64), 0, st, rb, nb, table, world, words, n_wait, epoch, timeout_ticks, cnt);
 }
 
 }  // namespace mpm

@@ -108,6 +108,7 @@
 #include "k_bgeo.h"
 #include "frame_launch.h"
 #include "snapshot_job_launch.h"
+#include "rigid_rows_launch.h"
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
 #include "k_mpm2d_det.h"
@@ -521,9 +522,20 @@ struct mpmhip_ctx {
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
     int64_t k = 0, next_migration = 0, migrated_out = 0, migrations = 0, replans = 0;
     int migrate_interval = 4, adaptive_cap = 64;
+    // CPIC rigid bodies on the job (tiled_plan.h: impulse rows): set by mpmhip_tiled_setup on a ctx that holds bodies
+    bool rows = false;
+    bool defer_finish = false;        // mpmhip_tiled_advance_group: substep_end stops behind G2P, the group finishes every rank
+    uint32_t row_epoch[tplan::ROW_EXCHANGES] = {0, 0};
+    DevBuf<float> d_row_stage;        // the RCCL wires send the row from here
   } tn;
+  bool rows_substep = false;  // the substep in flight hands its impulse rows to the job instead of applying them (tn.rows)
 };
-namespace { void tn_free(mpmhip_ctx *c); void tn_begin_substep(mpmhip_ctx *c); }
+namespace {
+void tn_free(mpmhip_ctx *c);
+void tn_begin_substep(mpmhip_ctx *c);
+int tn_row_out(mpmhip_ctx *c, int exchange);
+int tn_rows_apply(mpmhip_ctx *c, int exchange);
+}
 
 // what Params mirrors of the ctx: the slot count, and the id cache beside key[] while the deterministic mode is on
 static void set_slots(mpmhip_ctx *c, int64_t n) {
@@ -1468,7 +1480,8 @@ static int do_p2g(mpmhip_ctx *c, int phase = 0) {
     hipLaunchKernelGGL(rigid_p2g_kernel(plan.rigid_mats), dim3(plan.rigid_wgs), dim3(64), 0, rs, c->P, (const float4 *)c->rp.get(),
                        (const float4 *)c->rg.get(), c->cnt, c->act_blk, c->cell_start, c->perm, c->d_groups, c->tiles, rigid_xfer(c));
     if (int rc = rigid_join(c, rs)) return rc;
-    if (int rc = do_rigid_apply_tmp(c)) return rc;
+    // (a job with bodies: this rank's sums go out as its row, the sum over the ranks is applied behind the wait — tn_rows_apply)
+    if (int rc = c->rows_substep ? tn_row_out(c, 0) : do_rigid_apply_tmp(c)) return rc;
   }
   return launch_check(c, "p2g");
 }
@@ -1512,7 +1525,7 @@ static int do_g2p(mpmhip_ctx *c, int phase = 0) {
     if (plan.rigid_mats.kind == lp::MatSet::ALL_DET) { if (int rc = rigid_imp_rows(c)) return rc; }
     launch(rigid_g2p_kernel(plan.rigid_mats), plan.rigid_wgs, rs, rigid_xfer(c));
     if (int rc = rigid_join(c, rs)) return rc;
-    if (int rc = do_rigid_apply_tmp(c)) return rc;
+    if (int rc = c->rows_substep ? tn_row_out(c, 1) : do_rigid_apply_tmp(c)) return rc;
   }
   c->rec.g2p_done(plan.store_b, c->P.pidc != nullptr);
   return launch_check(c, "g2p");
@@ -1632,8 +1645,11 @@ int mpmhip_substep_begin(mpmhip_ctx *c) {
   int rc;
   mpmhip_ctx::Ev *ev = nullptr;
   int lvl = c->profiling;
-  c->ov_active = c->overlap && c->T.n_boxes > 0 && lvl != 1;
+  const bool bodies = rigid_active(c);
+  // (the colour-aware kernels have no phase argument: a ctx with bodies runs its substeps unsplit, whatever mpmhip_set_overlap said)
+  c->ov_active = c->overlap && c->T.n_boxes > 0 && lvl != 1 && !bodies;
   c->interior_done = false;
+  c->rows_substep = c->tn.on && c->tn.rows;
   if ((lvl == 2 || lvl == 3) && c->prof_every > 1 && (c->substeps % c->prof_every) != 0) lvl = 0;  // not a sampled substep
   if (lvl) {
     if (c->ev_used >= 4096 && (rc = collect_events(c))) return rc;
@@ -1642,7 +1658,6 @@ int mpmhip_substep_begin(mpmhip_ctx *c) {
     if (lvl == 1 || lvl == 4) HIPCHK(c, hipEventRecord(ev->e[0], c->stream));
   }
   // articulate + rasterize_rigid_boundary (src/mpm.cpp:466-472) next to the sort, gather_cdf (:506-508) behind both
-  const bool bodies = rigid_active(c);
   hipStream_t rs = c->stream;
   if (bodies && (rc = do_rigid_rigidify(c, c->P.dt))) return rc;  // rigidify opens the block (:468), on the ctx stream, before the fork
   if (bodies && ((rc = rigid_fork(c, &rs, 4)) || (rc = do_rigid_pre_a(c, rs)))) return rc;
@@ -1681,6 +1696,20 @@ int mpmhip_substep_interior(mpmhip_ctx *c) {
   return MPMHIP_OK;
 }
 
+// behind the G2P of a substep whose impulse rows went to the job (tn.rows): the rows of the rigid G2P summed and applied, then what
+// substep_end does behind the records' swap.  mpmhip_tiled_advance_group calls it for every rank once every rank's G2P is enqueued.
+static int substep_finish_rows(mpmhip_ctx *c) {
+  int rc;
+  if (!c->rows_substep) return MPMHIP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->rows_substep = false;
+  if ((rc = tn_rows_apply(c, 1))) return rc;
+  if ((rc = do_rigid_advect(c, c->P.dt))) return rc;  // src/mpm.cpp:570-572
+  c->t += c->P.dt;  // src/mpm.cpp:573
+  c->substeps++;
+  return MPMHIP_OK;
+}
+
 int mpmhip_substep_end(mpmhip_ctx *c) {  // grid (+ halo sum), G2P
   if (!c) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1691,6 +1720,7 @@ int mpmhip_substep_end(mpmhip_ctx *c) {  // grid (+ halo sum), G2P
   c->cur_ev = nullptr;
   c->in_substep = false;
   const int lvl = c->profiling, ph = c->ov_active ? 1 : 0;
+  if (c->rows_substep && (rc = tn_rows_apply(c, 0))) return rc;  // (the rigid P2G's impulses of ALL ranks: RigidBody::apply_tmp_velocity)
   if (rigid_active(c) && c->rigid.ls_collision && (rc = do_rigid_ls_collision(c))) return rc;  // src/mpm.cpp:535-538
   if (ev && lvl == 1) HIPCHK(c, hipEventRecord(ev->e[3], c->stream));
   if (ev && lvl == 4) HIPCHK(c, hipEventRecord(ev->e[4], c->stream));
@@ -1700,6 +1730,7 @@ int mpmhip_substep_end(mpmhip_ctx *c) {  // grid (+ halo sum), G2P
   if ((rc = do_sdf_collide(c))) return rc;
   if (ev && (lvl == 1 || lvl == 2 || lvl == 4)) HIPCHK(c, hipEventRecord(ev->e[5], c->stream));
   swap_records(c);
+  if (c->rows_substep) return c->tn.defer_finish ? MPMHIP_OK : substep_finish_rows(c);
   if (rigid_active(c) && (rc = do_rigid_advect(c, c->P.dt))) return rc;  // src/mpm.cpp:570-572
   c->t += c->P.dt;  // src/mpm.cpp:573
   c->substeps++;
@@ -1717,6 +1748,8 @@ int64_t mpmhip_tiled_run(mpmhip_ctx *c, int64_t n, int64_t until_migration, mpmh
   if (!c || n < 0) return MPMHIP_EINVAL;
   if (c->tn.on) return fail(c, MPMHIP_EINVAL, "this ctx has a native plan (mpmhip_tiled_setup): advance it with mpmhip_tiled_advance");
   if (c->T.n_boxes > 0 && !exchange) return fail(c, MPMHIP_EINVAL, "this ctx has halo boxes: tiled_run needs an exchange callback");
+  if (c->T.enabled && c->rigid.enabled)
+    return fail(c, MPMHIP_EINVAL, "tiled_run: a tiled ctx with rigid bodies advances through the native plan only (mpmhip_tiled_setup, mpmhip_tiled_advance): the callback path does not carry the bodies' impulses");
   if (until_migration > 0 && until_migration < n) n = until_migration;
   for (int64_t i = 0; i < n; i++) {
     int rc = mpmhip_substep_begin(c);
@@ -2033,8 +2066,7 @@ int mpmhip_profile(mpmhip_ctx *c, char *json, size_t cap) {
 int mpmhip_set_partition(mpmhip_ctx *c, int32_t rank, const int32_t dims[3], const int32_t *cuts_x,
                          const int32_t *cuts_y, const int32_t *cuts_z, int32_t margin) {
   if (!c || !dims || !cuts_x || !cuts_y || !cuts_z) return MPMHIP_EINVAL;
-  if (c->rigid.enabled) return fail(c, MPMHIP_EINVAL, "a ctx with rigid bodies cannot be tiled");
-  if (c->rigid.col.on) return fail(c, MPMHIP_EINVAL, "rigid_body_collision: a tiled (multi-GPU) ctx has no rigid bodies");
+  if (c->rigid.col.on) return fail(c, MPMHIP_EINVAL, "rigid_body_collision is not supported on a tiled (multi-GPU) ctx: the bodies of a job meet no other body");
   const int32_t *const cuts[3] = {cuts_x, cuts_y, cuts_z};
   tplan::Partition part;
   const std::string refused = part.init(c->P.res, dims, cuts, margin, rank);
@@ -2053,6 +2085,8 @@ int mpmhip_set_halo(mpmhip_ctx *c, int32_t n, const mpmhip_halo_box *boxes) {
   if (!c || n < 0 || n > MPMHIP_MAX_HALO_BOXES || (n > 0 && !boxes)) return MPMHIP_EINVAL;
   if (n > 0 && !c->T.enabled) return fail(c, MPMHIP_EINVAL, "set_halo needs set_partition first");
   if (c->tn.on) return fail(c, MPMHIP_EINVAL, "this ctx has a native plan (mpmhip_tiled_setup): its halo boxes are the library's");
+  if (n > 0 && c->rigid.enabled)
+    return fail(c, MPMHIP_EINVAL, "set_halo: a ctx with rigid bodies exchanges its halo through the native plan only (mpmhip_tiled_setup): the callback path does not carry the bodies' impulses");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   Tiling &T = c->T;

@@ -13,7 +13,11 @@
 static int rigid_enable(mpmhip_ctx *c) {
   auto &R = c->rigid;
   if (R.enabled) return MPMHIP_OK;
-  if (c->T.enabled) return fail(c, MPMHIP_EINVAL, "rigid bodies are not supported on a tiled (multi-GPU) ctx");
+  // bodies on a tiled ctx: every rank of the job holds ALL bodies and mpmhip_tiled_setup sizes the arena for their impulse rows
+  // (tiled_plan.h), so they come before it; the callback path (mpmhip_set_halo) does not carry the rows
+  if (c->tn.on) return fail(c, MPMHIP_EINVAL, "rigid bodies on a tiled job: add the bodies before mpmhip_tiled_setup, or set the job up again");
+  if (c->T.n_boxes > 0) return fail(c, MPMHIP_EINVAL, "rigid bodies on a tiled ctx need the native plan (mpmhip_tiled_setup): the callback path (mpmhip_set_halo) does not carry the bodies' impulses");
+  if (c->rigid.col.on && c->T.enabled) return fail(c, MPMHIP_EINVAL, "rigid_body_collision is not supported on a tiled (multi-GPU) ctx");
   if (c->async.enabled) return fail(c, MPMHIP_EINVAL, "rigid bodies are not supported with asynchronous stepping");
   hipError_t e = hipSuccess;
   auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
@@ -213,6 +217,7 @@ int mpmhip_add_rigid_body(mpmhip_ctx *c, const mpmhip_rigid_config *cfg, int64_t
   if (!c || !cfg || !triangles || n_triangles <= 0) return MPMHIP_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "add_rigid_body inside a substep");
+  if (c->tn.on) return fail(c, MPMHIP_EINVAL, "rigid bodies on a tiled job: add the bodies before mpmhip_tiled_setup, or set the job up again");
   if (int rc = rigid_enable(c)) return rc;
   auto &R = c->rigid;
   if ((int)R.store.bodies.size() >= MAX_RIGID) return fail(c, MPMHIP_ECAPACITY, "at most %d rigid bodies (2 colour bits each in a 24-bit word)", MAX_RIGID - 1);
@@ -251,6 +256,52 @@ int mpmhip_rigid_get_state(mpmhip_ctx *c, int32_t id, float *out) {
   out[k++] = D.mass; out[k++] = D.inv_mass;
   for (int i = 0; i < 9; i++) out[k++] = c->rigid.store.bodies[id].inertia[i];
   for (int i = 0; i < 9; i++) out[k++] = D.inv_I[i];
+  return MPMHIP_OK;
+}
+// a digest of the bodies as this ctx holds them: the device records of all bodies (pose, velocities, mass properties, pending
+// impulses), the numeric part of their configs, the boundary particles with their creation ids, the elements, the joints and the
+// coupling's settings — two 64-bit FNV-1a sums from different offsets.  The ranks of a tiled job, which all hold all bodies, compare
+// digests instead of shipping records (tiled.py).  A ctx without bodies: the digest of nothing.
+int mpmhip_rigid_digest(mpmhip_ctx *c, uint64_t out[2]) {
+  if (!c || !out) return MPMHIP_EINVAL;
+  uint64_t h[2] = {0xcbf29ce484222325ull, 0x84222325cbf29ce4ull};
+  auto eat = [&](const void *p, size_t n) {
+    const uint8_t *b = static_cast<const uint8_t *>(p);
+    for (size_t i = 0; i < n; i++) {
+      h[0] = (h[0] ^ b[i]) * 0x100000001b3ull;
+      h[1] = (h[1] ^ (uint64_t)(b[i] + 0x9e)) * 0x100000001b3ull;
+    }
+  };
+  auto &R = c->rigid;
+  const int32_t nb = rigid_active(c) ? (int32_t)R.store.bodies.size() : 1;
+  eat(&nb, sizeof nb);
+  if (nb > 1) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<RigidBodyDev> hb((size_t)nb);
+    HIPCHK(c, hipMemcpy(hb.data(), R.d_rb, sizeof(RigidBodyDev) * (size_t)nb, hipMemcpyDeviceToHost));
+    static_assert(sizeof(RigidBodyDev) % 4 == 0 && sizeof(RigidSample) == 20 && sizeof(JointDev) % 4 == 0, "records without padding");
+    eat(hb.data(), sizeof(RigidBodyDev) * (size_t)nb);
+    for (int b = 1; b < nb; b++) {
+      const auto &H = R.store.bodies[(size_t)b];
+      const int32_t flags[4] = {H.cfg.codimensional, H.cfg.scripted_position ? 1 : 0, H.cfg.scripted_rotation ? 1 : 0, (int32_t)H.n_samples};
+      eat(flags, sizeof flags);
+      eat(H.cfg.friction, sizeof H.cfg.friction);
+      eat(&H.cfg.restitution, sizeof H.cfg.restitution);
+      eat(H.inertia, sizeof H.inertia);
+    }
+    eat(R.store.h_smp.data(), sizeof(RigidSample) * R.store.h_smp.size());
+    eat(R.store.h_smp_id.data(), sizeof(int32_t) * R.store.h_smp_id.size());
+    eat(R.store.h_elems.data(), sizeof(float) * R.store.h_elems.size());
+    const int32_t nj = (int32_t)R.joints.size();
+    eat(&nj, sizeof nj);
+    eat(R.joints.data(), sizeof(JointDev) * R.joints.size());
+    const float k[2] = {R.penalty, R.pushing_force};
+    const int32_t s[2] = {R.ls_collision ? 1 : 0, R.joint_iterations};
+    eat(k, sizeof k);
+    eat(s, sizeof s);
+  }
+  out[0] = h[0]; out[1] = h[1];
   return MPMHIP_OK;
 }
 int mpmhip_rigid_set_velocity(mpmhip_ctx *c, int32_t id, const float *v, const float *w) {

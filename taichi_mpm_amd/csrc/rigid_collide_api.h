@@ -72,7 +72,7 @@ static int do_rigid_rigidify(mpmhip_ctx *c, float dt) {
 int mpmhip_set_rigid_collision(mpmhip_ctx *c, int32_t enabled, int32_t iterations, float rigid_penalty, int32_t position_iterations) {
   if (!c) return MPMHIP_EINVAL;
   if (iterations < 0) return fail(c, MPMHIP_EINVAL, "rigid_body_iterations = %d: must not be negative", iterations);
-  if (enabled && c->T.enabled) return fail(c, MPMHIP_EINVAL, "rigid_body_collision: a tiled (multi-GPU) ctx has no rigid bodies");
+  if (enabled && c->T.enabled) return fail(c, MPMHIP_EINVAL, "rigid_body_collision is not supported on a tiled (multi-GPU) ctx: the bodies of a job meet no other body");
   if (enabled && c->async.enabled) return fail(c, MPMHIP_EINVAL, "rigid_body_collision: asynchronous stepping has no rigid bodies");
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "set_rigid_collision inside a substep");
   auto &K = c->rigid.col;

@@ -18,6 +18,8 @@
 //             e + 2 only after it has seen the reader's epoch e + 1, which the reader publishes after its reads of substep e.
 //             Migrations carry their own epoch m (tables alternate by m & 1; records wait for the whole table of m, which
 //             every rank contributes to only after its import of m - 1).
+//   bodies    a job with CPIC rigid bodies: every rank holds all bodies; the ranks' impulse rows travel twice a substep and are added
+//             in rank order (the section "impulse rows" below; layout in tiled_plan.h, kernels in k_rigid_rows.h).
 #pragma once
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl is dlopen'ed, libmpmhip does not link it
@@ -113,10 +115,12 @@ int tn_apply_plan(mpmhip_ctx *c) {
   Tiling &T = c->T;
   const tplan::Partition part = tn_part(c);
   N.plan = tplan::plan(part, N.clip_lo, N.clip_hi, tn_occ(N), T.rank);
-  const tplan::PlanFault f = tplan::link(N.plan, part, N.clip_lo, N.clip_hi, tn_occ(N), T.rank, N.lay.halo_cap);
+  // (a job with bodies keeps its impulse rows behind the nodes of the receive buffers: the boxes are held against what is left)
+  const uint64_t node_cap = tplan::rows_node_cap(N.lay.halo_cap, N.world, N.rows);
+  const tplan::PlanFault f = tplan::link(N.plan, part, N.clip_lo, N.clip_hi, tn_occ(N), T.rank, node_cap);
   const size_t n = N.plan.boxes.size();
   if (f.kind == tplan::PlanFault::TOO_MANY_BOXES) return fail(c, MPMHIP_EINVAL, "too many halo boxes (%zu)", n);
-  if (f.kind == tplan::PlanFault::EXCEEDS_ARENA) return fail(c, MPMHIP_ECAPACITY, "internal: halo plan of %llu nodes exceeds the arena (%llu)", (unsigned long long)N.plan.total, (unsigned long long)N.lay.halo_cap);
+  if (f.kind == tplan::PlanFault::EXCEEDS_ARENA) return fail(c, MPMHIP_ECAPACITY, "internal: halo plan of %llu nodes exceeds the arena (%llu)", (unsigned long long)N.plan.total, (unsigned long long)node_cap);
   if (f.kind == tplan::PlanFault::NO_COUNTERPART) return fail(c, MPMHIP_EINVAL, "internal: halo box towards rank %d has no counterpart", f.peer);
   // the overlap-free interior of this rank's node box — the node box as the boxes were cut from it (tiled_plan.h: interior_of;
   // until round 6 the uncut brick box stood here, and at configs[3] over 8 bricks every block was boundary work) — and the device tables
@@ -233,6 +237,70 @@ int tn_exchange_wait(mpmhip_ctx *c) {
   }
   if (N.wait_merged) return MPMHIP_OK;  // (tn_exchange_start's launch has waited already)
   return tn_wait(c, N.flags, N.halo_peers, N.d_halo_idx, N.epoch);
+}
+
+// ------------------------------------------------------------------------------------------------ impulse rows (bodies on a job)
+// Every rank holds all bodies; a rank's colour-aware transfer kernels collect what ITS particles hand them.  Twice a substep — exchange
+// 0 behind the rigid P2G, exchange 1 behind the rigid G2P — the rank's row goes to every rank (tn_row_out) and, once the rows of all
+// ranks are there, every rank adds them in rank order and applies the sum (tn_rows_apply): DESIGN section 5, "Bodies on a job".
+//   peer wires   k_rigid_row_out writes the row into every rank's table (its own included) and publishes the exchange's epoch in
+//                every rank's flag page; k_rigid_rows_world waits for all ranks' epochs (the bounded wait of the halo boxes)
+//   RCCL         the row is staged and travels as one send / receive pair per peer (an all-reduce would add in its own order);
+//                stream order is the wait.  MPMHIP_WIRE_LOCAL_RCCL: the same pairs as self-sends aimed at the peer ctx's table
+//   epochs       one counter per exchange; the tables of parity (epoch & 1) live in recv[parity], behind the nodes.  A rank reaches
+//                epoch e + 2 of an exchange only after it has seen every rank's epoch e + 1, published behind that rank's reads of e.
+// No host synchronisation: everything is enqueued on the ctx's stream.  The ranks of a local job share the device's queues, so
+// mpmhip_tiled_advance_group enqueues EVERY rank's tn_row_out of an exchange before the first tn_rows_apply of it.
+float *tn_rows_at(const mpmhip_ctx::TiledNative &N, const mpmhip_ctx::TiledNative::Peer &P, int par, int exchange, int rank) {
+  return reinterpret_cast<float *>(P.recv[par] + tplan::rows_off(N.lay.halo_cap, N.world, exchange, rank));
+}
+bool tn_rows_by_rccl(const mpmhip_ctx::TiledNative &N) { return N.wire == MPMHIP_WIRE_RCCL || N.loop_rccl; }
+
+int tn_row_out(mpmhip_ctx *c, int x) {
+  auto &N = c->tn;
+  auto &R = c->rigid;
+  const int me = c->T.rank, world = N.world, nb = (int)R.store.bodies.size();
+  const uint32_t epoch = ++N.row_epoch[x];
+  const int par = (int)(epoch & 1u);
+  if (c->deterministic)  // (the rows of the flagged blocks, in k_rigid_rows_apply's fixed order, stand in for the atomics' sums)
+    rows_launch_sum(c->stream, nb, c->P, (const Counters *)c->cnt, (const uint8_t *)R.d_blk_rigid, (const float *)R.d_imp_rows, R.d_rb);
+  RowPut L;
+  memset(&L, 0, sizeof L);
+  const bool by_rccl = tn_rows_by_rccl(N);
+  for (int p = 0; p < world; p++) {
+    if (by_rccl && p != me) continue;  // (its own row a rank always writes itself)
+    L.dst[p] = tn_rows_at(N, N.peers[p], par, x, me);
+    L.flag[p] = by_rccl ? nullptr : N.peers[p].flags + tplan::rows_flag_word(x, me);
+  }
+  rows_launch_out(c->stream, R.d_rb, nb, L, world, by_rccl ? N.d_row_stage.get() : nullptr, epoch);
+  if (int rc = launch_check(c, "rigid_row_out")) return rc;
+  if (!by_rccl || world == 1) return MPMHIP_OK;
+  RcclApi *A = rccl_api();
+  NCCLCHK(c, A->GroupStart());
+  for (int p = 0; p < world; p++) {
+    if (p == me) continue;
+    if (N.loop_rccl) {  // (one-rank communicator: a send to itself whose receive is aimed at the peer ctx's table — tn_exchange_start)
+      NCCLCHK(c, A->Send(N.d_row_stage.get(), tplan::IMP_ROW_FLOATS, ncclFloat, 0, (ncclComm_t)N.comm, c->stream));
+      NCCLCHK(c, A->Recv(tn_rows_at(N, N.peers[p], par, x, me), tplan::IMP_ROW_FLOATS, ncclFloat, 0, (ncclComm_t)N.comm, c->stream));
+      continue;
+    }
+    NCCLCHK(c, A->Send(N.d_row_stage.get(), tplan::IMP_ROW_FLOATS, ncclFloat, p, (ncclComm_t)N.comm, c->stream));
+    NCCLCHK(c, A->Recv(tn_rows_at(N, N.peers[me], par, x, p), tplan::IMP_ROW_FLOATS, ncclFloat, p, (ncclComm_t)N.comm, c->stream));
+  }
+  NCCLCHK(c, A->GroupEnd());
+  return MPMHIP_OK;
+}
+
+int tn_rows_apply(mpmhip_ctx *c, int x) {
+  auto &N = c->tn;
+  auto &R = c->rigid;
+  const int me = c->T.rank;
+  const uint32_t epoch = N.row_epoch[x];
+  // (the RCCL wires: the receives were enqueued on this stream — MPMHIP_WIRE_LOCAL_RCCL: on the ONE stream the ranks share — in front of this launch)
+  const int n_wait = tn_rows_by_rccl(N) ? 0 : N.world;
+  rows_launch_apply(c->stream, R.d_rb, (int)R.store.bodies.size(), tn_rows_at(N, N.peers[me], (int)(epoch & 1u), x, 0), N.world,
+                    N.flags + tplan::rows_flag_word(x, 0), n_wait, epoch, N.timeout_ticks, c->cnt);
+  return launch_check(c, "rigid_rows_world");
 }
 
 // ------------------------------------------------------------------------------------------------ migration
@@ -580,6 +648,7 @@ int tn_energy(mpmhip_ctx *c, double out[3]) {
   int rc = tn_check_ready(c, "calculate_energy");
   if (rc) return rc;
   if (c->tn.wire == MPMHIP_WIRE_LOCAL) return fail(c, MPMHIP_EINVAL, "ranks of a local job compute their energy together: mpmhip_calculate_energy_group");
+  if (c->tn.rows) return fail(c, MPMHIP_EINVAL, "calculate_energy of a tiled job with rigid bodies is not supported (its rasterization hands the bodies impulses)");
   if ((rc = energy_begin(c)) || (rc = tn_exchange_start(c)) || (rc = tn_exchange_wait(c)) || (rc = energy_end(c, out))) return rc;
   if ((rc = tn_reduce_put(c, out, 3, MPMHIP_REDUCE_SUM))) return rc;
   return tn_reduce_finish(c, out, 3, MPMHIP_REDUCE_SUM);
@@ -741,6 +810,10 @@ int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int3
   // the arena, sized for the worst-case halo volume over all ranks (tiled_plan.h: Arena; every rank lays its arena out alike)
   uint64_t halo_cap = 0;
   if (const char *refused = tplan::worst_halo_cap(tn_part(c), &halo_cap)) return fail(c, MPMHIP_EINVAL, "%s", refused);
+  // (a ctx that holds bodies: the impulse rows of all ranks, both exchanges, behind the nodes of each receive buffer — tiled_plan.h.
+  // Every rank of the job must hold the same bodies: the ranks' arenas are then laid out alike)
+  N.rows = rigid_active(c);
+  if (N.rows) halo_cap += tplan::rows_extra_cap(N.world);
   N.lay = tplan::Arena(halo_cap, cfg->inbox_records > 0 ? (uint64_t)cfg->inbox_records : std::max<uint64_t>(65536, (uint64_t)c->cap / 8));
   if (N.arena && (kept_bytes != N.lay.total || N.peers.size() != (size_t)N.world)) tn_drop_arena(N);
   std::vector<mpmhip_ctx::TiledNative::Peer> mapped;  // (the kept mappings of the peers' arenas)
@@ -771,6 +844,7 @@ int mpmhip_tiled_setup(mpmhip_ctx *c, const mpmhip_tiled_config *cfg, const int3
       memcpy(N.peers[p].handle, mapped[p].handle, sizeof mapped[p].handle);
     }
   if (!tn_peer_wire(N)) HIPCHK(c, N.send.alloc((size_t)N.lay.halo_cap));
+  if (N.rows) HIPCHK(c, N.d_row_stage.alloc((size_t)tplan::IMP_ROW_FLOATS));
   HIPCHK(c, N.row.alloc((size_t)tplan::ROW));
   HIPCHK(c, hipMemset(N.row, 0, sizeof(uint32_t) * tplan::ROW));
   for (int k = 0; k < 2; k++) HIPCHK(c, N.d_boxes[k].alloc((size_t)MPMHIP_MAX_HALO_BOXES));
@@ -859,6 +933,7 @@ int mpmhip_tiled_connect_local(mpmhip_ctx *const *ctxs, int32_t n) {
     if (!c->tn.on || c->tn.wire != MPMHIP_WIRE_LOCAL || c->tn.world != n || c->T.rank != r)
       return fail(c, MPMHIP_EINVAL, "connect_local: ctx %d must be set up as rank %d of %d with MPMHIP_WIRE_LOCAL", r, r, n);
     if (c->device != ctxs[0]->device) return fail(c, MPMHIP_EINVAL, "connect_local: all ctx must live on one device");
+    if (c->tn.rows != ctxs[0]->tn.rows) return fail(c, MPMHIP_EINVAL, "connect_local: rank %d and rank 0 do not both hold rigid bodies: every rank of a job holds all bodies", r);
     if (c->tn.lay.halo_cap != ctxs[0]->tn.lay.halo_cap) return fail(c, MPMHIP_EINVAL, "connect_local: the ranks' arenas are laid out differently (not the same partition?)");
   }
   for (int r = 0; r < n; r++) {
@@ -874,8 +949,10 @@ int mpmhip_tiled_connect_local(mpmhip_ctx *const *ctxs, int32_t n) {
   return MPMHIP_OK;
 }
 
-static int tn_substep_parts(mpmhip_ctx *c, int part) {  // 0 begin (+ start of the exchange), 1 interior, 2 wait + end
+// 0 begin (+ start of the exchange), 1 interior, 2 wait + end, 3 (a job with bodies) the rigid G2P's rows summed + the bodies' advection
+static int tn_substep_parts(mpmhip_ctx *c, int part) {
   int rc;
+  if (part == 3) return substep_finish_rows(c);
   if (part == 0) {
     if ((rc = mpmhip_substep_begin(c))) return rc;
     return tn_exchange_start(c);
@@ -903,8 +980,8 @@ int64_t mpmhip_tiled_advance(mpmhip_ctx *c, int64_t n) {
     if (rc) return rc;
   }
   for (int64_t i = 0; i < n; i++) {
-    for (int part = 0; part < 3; part++)
-      if ((rc = tn_substep_parts(c, part))) { c->in_substep = false; c->cur_ev = nullptr; return rc; }
+    for (int part = 0; part < 4; part++)
+      if ((rc = tn_substep_parts(c, part))) { c->in_substep = false; c->cur_ev = nullptr; c->rows_substep = false; return rc; }
     N.k++;
     if (N.k >= N.next_migration && N.world > 1) {
       if ((rc = tn_mig_a(c)) || (rc = tn_mig_b(c)) || (rc = tn_mig_c(c))) return rc;
@@ -948,7 +1025,7 @@ int64_t mpmhip_tiled_advance_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int64
       ctxs[r]->tn.signal_deferred = false;
       int rc = tn_substep_parts(ctxs[r], 0);
       ctxs[r]->tn.defer_signal = false;
-      if (rc) { ctxs[r]->in_substep = false; ctxs[r]->cur_ev = nullptr; return rc; }
+      if (rc) { ctxs[r]->in_substep = false; ctxs[r]->cur_ev = nullptr; ctxs[r]->rows_substep = false; return rc; }
     }
     {
       SignalGroup G;
@@ -968,9 +1045,13 @@ int64_t mpmhip_tiled_advance_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int64
     }
     for (int r = 0; r < n_ctx; r++)
       for (int part = 1; part < 3; part++) {
+        ctxs[r]->tn.defer_finish = true;  // (a job with bodies: every rank's G2P — its row out — is enqueued before the first rank sums them)
         int rc = tn_substep_parts(ctxs[r], part);
-        if (rc) { ctxs[r]->in_substep = false; ctxs[r]->cur_ev = nullptr; return rc; }
+        ctxs[r]->tn.defer_finish = false;
+        if (rc) { ctxs[r]->in_substep = false; ctxs[r]->cur_ev = nullptr; ctxs[r]->rows_substep = false; return rc; }
       }
+    for (int r = 0; r < n_ctx; r++)
+      if (int rc = tn_substep_parts(ctxs[r], 3)) { ctxs[r]->rows_substep = false; return rc; }
     bool due = false;
     for (int r = 0; r < n_ctx; r++) { ctxs[r]->tn.k++; due = due || ctxs[r]->tn.k >= ctxs[r]->tn.next_migration; }
     if (due && n_ctx > 1) {
@@ -1028,6 +1109,7 @@ int mpmhip_calculate_energy_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, double
     mpmhip_ctx *c = ctxs[r];
     HIPCHK(c, hipSetDevice(c->device));
     if (c->in_substep) return fail(c, MPMHIP_EINVAL, "calculate_energy inside a substep");
+    if (c->tn.rows) return fail(c, MPMHIP_EINVAL, "calculate_energy of a tiled job with rigid bodies is not supported (its rasterization hands the bodies impulses)");
     if ((rc = energy_begin(c)) || (rc = tn_exchange_start(c))) return rc;
   }
   for (int r = 0; r < n_ctx; r++)
@@ -1140,6 +1222,7 @@ int mpmhip_tiled_redistribute(mpmhip_ctx *c, int64_t info[4]) {
   if (rc) return rc;
   if (c->in_substep) return fail(c, MPMHIP_EINVAL, "tiled_redistribute inside a substep");
   if (c->tn.wire == MPMHIP_WIRE_LOCAL && c->tn.world > 1) return fail(c, MPMHIP_EINVAL, "ranks of a local job are redistributed together: mpmhip_tiled_redistribute_group");
+  if (c->tn.rows) return fail(c, MPMHIP_EINVAL, "tiled_redistribute: a job with rigid bodies is not re-cut (a follow-up)");
   if (c->tn.world == 1) return MPMHIP_OK;
   mpmhip_ctx *one[1] = {c};
   return tn_redistribute(one, 1, info);
@@ -1150,6 +1233,8 @@ int mpmhip_tiled_redistribute_group(mpmhip_ctx *const *ctxs, int32_t n_ctx, int6
   if (info) for (int k = 0; k < 4 * n_ctx; k++) info[k] = 0;
   for (int r = 0; r < n_ctx; r++)
     if (ctxs[r]->in_substep) return fail(ctxs[r], MPMHIP_EINVAL, "tiled_redistribute inside a substep");
+  for (int r = 0; r < n_ctx; r++)
+    if (ctxs[r]->tn.rows) return fail(ctxs[r], MPMHIP_EINVAL, "tiled_redistribute: a job with rigid bodies is not re-cut (a follow-up)");
   if (n_ctx == 1) return MPMHIP_OK;
   return tn_redistribute(ctxs, n_ctx, info);
 }

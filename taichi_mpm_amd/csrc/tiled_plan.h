@@ -9,6 +9,7 @@
 //               where a box lives in its reader's buffers (link)
 //   interior    the part of a node box that no halo box touches: what the overlap split runs beside the exchange
 //   arena       [flags | reduction tables | table 0 | table 1 | recv 0 | recv 1 | inbox], laid out alike on every rank of a job
+//   rows        a job with CPIC rigid bodies: where the ranks' impulse rows live behind the nodes of recv 0 / recv 1, and their epoch words
 //   migration   the table [world][ROW] every rank reads: counts, bounds, speed, inbox room; who writes where into which inbox
 //   after it    do the occupancy boxes still hold the particles, will they until the next check, are they much too wide
 //   re-cut      new cut planes from the live particles' histograms; the rounds and the capacity rule of the redistribution behind them
@@ -230,6 +231,32 @@ inline const char *worst_halo_cap(const Partition &part, uint64_t *halo_cap) {
   *halo_cap = std::max<uint64_t>(cap, 1);
   return nullptr;
 }
+
+// ------------------------------------------------------------------------------------------------ impulse rows (bodies on a job)
+// Every rank of a job with CPIC rigid bodies holds all bodies.  What a rank's colour-aware transfer kernels hand the bodies is the
+// rank's ROW: impulse and torque of every body, IMP_ROW_FLOATS floats.  Twice a substep — behind the rigid P2G (exchange 0) and
+// behind the rigid G2P (exchange 1) — the rows of all ranks reach every rank, which adds them in RANK ORDER and applies the sum.
+// The rows live in the arena BEHIND the halo nodes: a job with bodies asks Arena() for a halo capacity larger by rows_extra_cap(world)
+// float4s, the planner links its boxes against the capacity without them (rows_node_cap), and the table of exchange x and parity p
+// begins rows_table_off(...) float4s into recv[p].  Arena(halo_cap, inbox) itself is what it was: a job without bodies asks for
+// the capacity it asked for before.  The rows' epochs have words of their own in the flag page, behind the four arrays of [MAX_WORLD].
+constexpr int IMP_ROW_FLOATS = 72;   // = MAX_RIGID * 6 (rigid_records.h; asserted where both are seen)
+constexpr int IMP_ROW_FLOAT4 = IMP_ROW_FLOATS / 4;
+constexpr int ROW_EXCHANGES = 2;     // 0: behind the rigid P2G, 1: behind the rigid G2P
+static_assert(IMP_ROW_FLOATS % 4 == 0, "a row is whole float4s");
+// float4s of one table: the rows of `world` ranks of one exchange and one parity
+MPM_HD uint64_t rows_table_float4(int world) { return (uint64_t)world * IMP_ROW_FLOAT4; }
+// float4s a job with bodies adds to the halo capacity it asks Arena() for: both exchanges' tables (the two recv buffers are the parities)
+MPM_HD uint64_t rows_extra_cap(int world) { return ROW_EXCHANGES * rows_table_float4(world); }
+// the halo capacity left for the nodes of an arena whose capacity includes the rows (bodies) or does not
+MPM_HD uint64_t rows_node_cap(uint64_t halo_cap, int world, bool bodies) { return bodies ? halo_cap - rows_extra_cap(world) : halo_cap; }
+// where rank `rank`'s row of exchange `exchange` begins, in float4s from recv[parity] of an arena with bodies
+MPM_HD uint64_t rows_off(uint64_t halo_cap, int world, int exchange, int rank) {
+  return rows_node_cap(halo_cap, world, true) + (uint64_t)exchange * rows_table_float4(world) + (uint64_t)rank * IMP_ROW_FLOAT4;
+}
+// the word of the flag page in which rank `rank` publishes the epoch of its row of `exchange` (on every rank's page)
+MPM_HD uint32_t rows_flag_word(int exchange, int rank) { return (uint32_t)((4 + exchange) * MAX_WORLD + rank); }
+static_assert((4 + ROW_EXCHANGES) * MAX_WORLD * sizeof(uint32_t) <= FLAG_BYTES, "the rows' epochs fit the flag page");
 
 // ------------------------------------------------------------------------------------------------ migration table
 struct Mig {

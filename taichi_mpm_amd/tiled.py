@@ -430,11 +430,32 @@ def _finish_migration(table, world, ranks, exchange):
         r.schedule(speed)
 
 
+def engine_bodies(engine):
+    """CPIC rigid bodies the engine's ctx holds (the background body does not count)"""
+    n = getattr(engine, "L", None) and int(engine.L.mpmhip_num_rigid_bodies(engine.ctx))
+    return max(0, (n or 1) - 1)
+
+
+def engine_digest(engine):
+    """mpmhip_rigid_digest of the engine's ctx as a pair of ints"""
+    d = (C.c_uint64 * 2)()
+    engine.sim._check(engine.L.mpmhip_rigid_digest(engine.ctx, d))
+    return int(d[0]), int(d[1])
+
+
+def _refuse_bodies_on_callback_path(engines, who):
+    if any(engine_bodies(e) for e in engines):
+        from .mpm import MPMError
+        raise MPMError("%s: a job with rigid bodies runs on the library's own data plane only (NativeVirtualJob / NativeTiledJob): "
+                       "the callback path does not carry the bodies' impulses between the ranks" % who)
+
+
 class TiledJob:
     """bench.py job: this process's rank of the tiled run (torch.distributed)"""
     scaling = "strong"
 
     def __init__(self, engine, part, comm, migrate_interval=None, overlap=True):
+        _refuse_bodies_on_callback_path([engine], "TiledJob")
         self.r = TiledRank(engine, part, comm.rank, migrate_interval)
         self.comm, self.e = comm, engine
         self.overlap = bool(overlap) and hasattr(engine, "set_overlap")
@@ -541,6 +562,7 @@ class VirtualTiledJob:
 
     def __init__(self, engines, part, migrate_interval=None, overlap=False):
         assert len(engines) == part.world
+        _refuse_bodies_on_callback_path(engines, "VirtualTiledJob")
         self.part = part
         self.ranks = [TiledRank(e, part, i, migrate_interval) for i, e in enumerate(engines)]
         self.overlap = bool(overlap)
@@ -626,9 +648,47 @@ class _NativeJobBase:
     substeps = 0
 
     def set_overlap(self, flag):
+        """boundary / interior split of the substep on or off.  A job with rigid bodies accepts the call and ignores it: the
+        colour-aware transfer kernels have no phase argument, its substeps run unsplit ("Bodies on a job")."""
         for e in self.engines:
             e.set_overlap(flag)
         self.overlap = bool(flag)
+
+    # --- CPIC rigid bodies on the job: every rank holds ALL bodies, byte-identical at every substep boundary
+    def has_bodies(self):
+        return any(engine_bodies(e) for e in self.engines)
+
+    def get_rigid_state(self, rid):
+        """the state of body `rid` (Simulation3D.get_rigid_state) as the job's first rank here holds it — rank 0's on a virtual job
+        and on rank 0 of a rank-per-process job; every rank holds the same bits (rigid_digests)"""
+        return self.engines[0].sim.get_rigid_state(rid)
+
+    def _local_body_rows(self):
+        return [(engine_bodies(e),) + engine_digest(e) for e in self.engines]
+
+    def _job_body_rows(self):
+        """[(bodies, digest word 0, digest word 1)] of every rank of the job"""
+        return self._local_body_rows()
+
+    def rigid_digests(self):
+        """mpmhip_rigid_digest of every rank of the job, in rank order (collective on a rank-per-process job): all equal while the
+        replicas are one"""
+        return [row[1:] for row in self._job_body_rows()]
+
+    def _check_same_bodies(self):
+        """at connect: every rank holds the same bodies (count and digest), else MPMError naming the first rank that differs"""
+        rows = self._job_body_rows()
+        for r, row in enumerate(rows):
+            if row != rows[0]:
+                from .mpm import MPMError
+                raise MPMError("tiled job: rank %d holds %d rigid bodies with digest %016x%016x, rank 0 holds %d with %016x%016x: every rank "
+                               "of a job adds the same bodies, in the same order, before the job is set up"
+                               % (r, row[0], row[1], row[2], rows[0][0], rows[0][1], rows[0][2]))
+
+    def _no_bodies(self, who):
+        if self.has_bodies():
+            from .mpm import MPMError
+            raise MPMError("%s: not supported on a job with rigid bodies (a follow-up); the job is untouched" % who)
 
     def num_particles(self):
         return sum(e.num_particles() for e in self.engines)
@@ -677,6 +737,7 @@ class _NativeJobBase:
         Returns dict(recut, imbalance_before, imbalance_after (from the per-rank counts after the move), cuts, moved (records, job-wide),
         rounds, grew (the ranks that grew))."""
         from .mpm import MPMError
+        self._no_bodies("rebalance")
         world = self.part.world
         hists, live = self._job_histograms()
         total = int(sum(live))
@@ -718,6 +779,7 @@ class _NativeJobBase:
     def visualize(self):
         """the next `frame_directory/%04d.bgeo` of the WHOLE job, frame numbers starting at 1 (Simulation3D.visualize).  On a
         rank-per-process job a collective: rank 0 writes and returns the path, the other ranks return None."""
+        self._no_bodies("visualize")
         if not self.frame_directory:
             from .mpm import MPMError
             raise MPMError("visualize() needs frame_directory (config key of rank 0's simulation, or set it on the job)")
@@ -727,6 +789,7 @@ class _NativeJobBase:
 
     def write_partio(self, path):
         """the job's .bgeo file to `path` (collective on a rank-per-process job: rank 0 writes).  True where the file was written."""
+        self._no_bodies("write_partio")
         data = self.bgeo_bytes()
         if data is None:
             return False
@@ -742,6 +805,7 @@ class _NativeJobBase:
         """the job's snapshot to `path`: the file Simulation3D.save_snapshot writes — one leading int64 (job.frame_count), then the
         MPMHIP01 blob in its canonical form (snapshot_bytes).  Collective on a rank-per-process job: rank 0 writes.  True where the
         file was written."""
+        self._no_bodies("save_snapshot")
         blob = self.snapshot_bytes()
         if blob is None:
             return False
@@ -763,6 +827,7 @@ class _NativeJobBase:
         import warnings
 
         from .mpm import MPMError, snapshot_groups
+        self._no_bodies("load_snapshot")
         raw = np.frombuffer(src, np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.fromfile(src, np.uint8)
         hsize = C.sizeof(_lib.SnapHeader)
         if len(raw) < 8 + hsize:
@@ -889,6 +954,7 @@ class NativeTiledJob(_NativeJobBase):
         engine, part, rank, world, dist = self.e, self.part, self.rank, self.world, self._dist
         migrate_interval, inbox_records = self._setup_args
         self.wire, self._use_comm = wire, use_comm
+        self._check_same_bodies()  # (before the arenas are sized: a rank without the bodies would lay its arena out differently)
         L, sim = engine.L, engine.sim
         need_comm = (wire == "rccl" or (wire == "ipc" and use_comm)) and not self._have_comm
         if need_comm:
@@ -918,6 +984,17 @@ class NativeTiledJob(_NativeJobBase):
         self.overlap = bool(overlap)
         self.parallelism = "%dx%dx%d bricks, one rank per GPU, halo + migration on the library's own data plane (%s)" % (
             part.dims + ({"rccl": "ncclSend / ncclRecv groups over xGMI", "ipc": "peer writes into IPC-mapped buffers"}[wire],))
+
+    def _job_body_rows(self):
+        """every rank's (bodies, digest words) over the control group (gloo): three int64 per rank"""
+        mine = self._local_body_rows()[0]
+        if self.world == 1:
+            return [mine]
+        import torch
+        t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in mine], dtype=torch.int64)
+        rows = [torch.zeros(3, dtype=torch.int64) for _ in range(self.world)]
+        self._dist.all_gather(rows, t)
+        return [tuple(int(v) & ((1 << 64) - 1) for v in row) for row in rows]
 
     def run(self, n):
         self.e.sim._check(self.e.L.mpmhip_tiled_advance(self.e.ctx, int(n)))
@@ -951,6 +1028,7 @@ class NativeTiledJob(_NativeJobBase):
         counts (all_gather); rows and row numbers go to rank 0, which places them (assemble_frame).  An id held twice makes the
         ranks' counts exceed the popcount of the union: MPMError on every rank."""
         from .mpm import MPMError
+        self._no_bodies("bgeo_bytes")
         e, L, sim, dist, world = self.e, self.e.L, self.e.sim, self._dist, self.world
         verbose = int(self.verbose_bgeo if verbose is None else verbose)
         width = 4 * (_lib.BGEO_W_VERBOSE if verbose else _lib.BGEO_W_PLAIN)
@@ -1003,6 +1081,7 @@ class NativeTiledJob(_NativeJobBase):
         clocks, grid, dt, store_b and group table must agree), top (the job's reduce), the bitmaps (ONE all_reduce) and the counts;
         records and row numbers go to rank 0, which places them (assemble_snapshot)."""
         from .mpm import MPMError
+        self._no_bodies("snapshot_bytes")
         e, L, sim, dist, world = self.e, self.e.L, self.e.sim, self._dist, self.world
         nb = C.c_size_t()
         sim._check(L.mpmhip_snapshot_head(e.ctx, None, 0, C.byref(nb)))
@@ -1118,6 +1197,7 @@ class NativeVirtualJob(_NativeJobBase):
             native_setup(e, self.part, r, _lib.WIRE_LOCAL_RCCL if halo_by_rccl else _lib.WIRE_LOCAL, migrate_interval, overlap, inbox_records)
         L = engines[0].L
         self._group_check(L.mpmhip_tiled_connect_local(self._arr, len(engines)), "mpmhip_tiled_connect_local")
+        self._check_same_bodies()
         self.overlap = bool(overlap)
 
     # --- rebalance(): all ranks live here, the sums are numpy's
@@ -1193,6 +1273,7 @@ class NativeVirtualJob(_NativeJobBase):
     def bgeo_bytes(self, verbose=None):
         """the .bgeo image of the WHOLE job as bytes: the file one ctx holding all ranks' records would write (mpmhip_bgeo_encode_group:
         ids ranked, rows placed and copied on the device)"""
+        self._no_bodies("bgeo_bytes")
         L, K = self.engines[0].L, len(self.engines)
         verbose = int(self.verbose_bgeo if verbose is None else verbose)
         n, w = C.c_size_t(), C.c_size_t()
@@ -1206,6 +1287,7 @@ class NativeVirtualJob(_NativeJobBase):
         """the snapshot blob of the WHOLE job as bytes: the MPMHIP01 blob one ctx holding all ranks' live records in id order would
         save — no dead slot, byte-identical for every rank count and every set of cuts (mpmhip_snapshot_save_group: ids ranked,
         records placed and copied on the device)"""
+        self._no_bodies("snapshot_bytes")
         L, K = self.engines[0].L, len(self.engines)
         n, w = C.c_size_t(), C.c_size_t()
         self._group_check(L.mpmhip_snapshot_size_group(self._arr, K, C.byref(n)), "mpmhip_snapshot_size_group")
@@ -1369,11 +1451,13 @@ def set_partition(sim, part, rank):
                                            arrs[1].ctypes.data_as(ip), arrs[2].ctypes.data_as(ip), part.margin))
 
 
-def build_seeded_rank_sims(tm, groups, part, ranks=None, device=0, levelset=None, max_particles=None, **sim_cfg):
+def build_seeded_rank_sims(tm, groups, part, ranks=None, device=0, levelset=None, max_particles=None, bodies=(), **sim_cfg):
     """the ctxs of `ranks` (default: all of the partition, the virtual job of one device) with the scene seeded on the device:
     `groups` is a list of add_particles configs with region=, made in the same order on every rank — group ids travel with
     migrating particles, creation ids are handed out job-wide — and each rank keeps its own brick of every region.  No position
-    array exists on the host, no id is uploaded.  sim_cfg: initialize()'s keys (res, delta_x, base_delta_t, gravity, ...)."""
+    array exists on the host, no id is uploaded.  sim_cfg: initialize()'s keys (res, delta_x, base_delta_t, gravity, ...).
+    bodies: add_particles configs of type='rigid', added on EVERY rank in this order and in front of the groups — every rank of a job
+    holds all bodies, and their boundary particles take the same creation ids everywhere."""
     sims = []
     for rank in (range(part.world) if ranks is None else ranks):
         cfg = dict(sim_cfg, device=device)
@@ -1383,6 +1467,8 @@ def build_seeded_rank_sims(tm, groups, part, ranks=None, device=0, levelset=None
         if levelset is not None:
             sim.set_levelset(levelset)
         set_partition(sim, part, rank)
+        for b in bodies:
+            sim.add_particles(dict(b))
         for g in groups:
             sim.add_particles(dict(g, brick=True))  # (grows the ctx where the brick's share does not fit)
         sims.append(sim)
