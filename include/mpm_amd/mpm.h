@@ -360,6 +360,16 @@ class MPM<3> {
     return out;
   }
 
+  // --- particle fields in DEVICE memory (mpmhip_download_dev / mpmhip_upload_dev; no reference counterpart: its particles live on
+  // the host).  Tables of eight device pointers, index = MPMHIP_F_*, nullptr = not wanted; by_id: rows in ascending creation id, the
+  // order that survives a substep, else slot order.  download_device returns the rows written.
+  int64_t download_device(void *const dst[8], int64_t capacity, bool by_id) const {
+    const int64_t n = mpmhip_download_dev(ctx_, dst, capacity, by_id ? 1 : 0);
+    check((int)std::min<int64_t>(n, 0), ctx_);
+    return n;
+  }
+  void upload_device(const void *const src[8], int64_t n, bool by_id) { check(mpmhip_upload_dev(ctx_, src, n, by_id ? 1 : 0), ctx_); }
+
   // --- frame output: visualize() -> write_bgeo() -> write_partio(file) (src/visualize.cpp:156-159, src/mpm.h:333-337,
   // src/visualize.cpp:17-100).  The Houdini .bgeo bytes equal the reference's (rows assembled on the device).
   virtual void write_partio(const std::string &file_name) const { check(mpmhip_write_bgeo(ctx_, file_name.c_str(), verbose_bgeo), ctx_); }

@@ -12,7 +12,8 @@
  *   - every function returns 0 on success or a negative MPMHIP_E* code; it never throws.
  *     `mpmhip_last_error()` returns a human-readable message for the last failure on that ctx
  *     (reference behaviour: TC_ASSERT/TC_ERROR abort, e.g. src/mpm.cpp:41-42,154,162,775).
- *   - host buffers are caller-owned; `*_dev` variants take device pointers.
+ *   - host buffers are caller-owned; the `*_dev` variants (mpmhip_download_dev, mpmhip_upload_dev, mpmhip_download_grid_dev)
+ *     take caller-owned device pointers of the ctx's device.
  *   - one ctx per GPU; calls on one ctx must be serialised by the caller (reference: not
  *     re-entrant either).
  *   - 3x3 matrices are row-major float[9]; `B` is the reference's `apic_b` (sign/units of
@@ -308,6 +309,30 @@ int mpmhip_seed_particles(mpmhip_ctx *ctx, int32_t group, const mpmhip_seed_desc
 int64_t mpmhip_num_particles(mpmhip_ctx *ctx); /* synchronises; <0 on error */
 int mpmhip_download(mpmhip_ctx *ctx, int32_t field, void *dst, int64_t n_capacity); /* returns n written */
 int mpmhip_upload(mpmhip_ctx *ctx, int32_t field, const void *src, int64_t n);
+/* The same between the ctx and caller-owned DEVICE arrays (no reference counterpart: its particles live in host memory).  No record
+ * and no row passes through host memory: mpmhip_host_particle_bytes does not change.
+ * field tables: index = MPMHIP_F_*, NULL = field not wanted; device pointers of the ctx's device; row widths and scalar types as for
+ * mpmhip_download (float[3], [3], [9], [9], [1]; int32 gid, id, states).  One call moves any subset of the fields and reads the
+ * records once.
+ *   order 0   slot order, live slots only: exactly the rows of mpmhip_download, in its order
+ *   order 1   ascending creation id: row r holds the particle whose id has rank r among the live ids — the only order that survives a
+ *             substep (the sort moves slots).  Needs unique live ids: MPMHIP_EINVAL ("the creation ids are not unique") otherwise,
+ *             before a field or a destination is written (the recovery of stale apic_b rows, which mpmhip_upload_dev runs first
+ *             as mpmhip_upload does, may have run by then; the same holds for an upload's wrong row count).
+ * mpmhip_download_dev returns the rows written.  The live particles are counted first: n_capacity below them is MPMHIP_ECAPACITY
+ * and no destination byte is touched; nothing is ever written behind the last row.  B runs the recovery of discard_apic_b first, as
+ * the host call does.
+ * mpmhip_upload_dev has the value semantics of mpmhip_upload per field (x into both records, a negative id stored as 0, the id
+ * counter raised to 1 + the largest uploaded id and never lowered; MPMHIP_F_GID refused; n must be the live count) and changes only
+ * the named fields of a record.  With order 1 the rows are matched to the ids the particles held BEFORE the call, also when ids
+ * are uploaded.
+ * Streams: the work runs on the ctx's stream and the call returns when that stream has drained, so the destinations are ready for any
+ * stream; an upload's sources, and whatever else was enqueued on the arrays of either call, must be complete when the call is made.
+ * MPMHIP_EINVAL with a message, nothing touched: a NULL table, a table of eight NULLs, an unknown order, inside a substep, a ctx with
+ * a resident asynchronous stepper (the records only mirror the pools there: the host calls remain the way in).
+ * The 2D solver has no such calls yet. */
+int64_t mpmhip_download_dev(mpmhip_ctx *ctx, void *const dst[8], int64_t n_capacity, int32_t order); /* rows written, or < 0 */
+int mpmhip_upload_dev(mpmhip_ctx *ctx, const void *const src[8], int64_t n, int32_t order);
 
 /* time stepping — replaces MPM<3>::step / substep (src/mpm.cpp:428-450, 452-575) */
 int mpmhip_substep(mpmhip_ctx *ctx);                 /* one substep, asynchronous on the ctx stream */
@@ -326,6 +351,9 @@ int mpmhip_g2p(mpmhip_ctx *ctx);         /* resample_optimized                sr
  *   which=0: (m*v, m) accumulated by P2G;  which=1: (v, m) after grid_update.
  * upload_grid installs a dense (v, m) field as the input of the next mpmhip_g2p (needs a prior sort). */
 int mpmhip_download_grid(mpmhip_ctx *ctx, int32_t which, float *dst);
+/* the array of mpmhip_download_grid into device memory of the ctx's device (copied device to device on the ctx's stream, which has
+ * drained on return) */
+int mpmhip_download_grid_dev(mpmhip_ctx *ctx, int32_t which, float *dst_dev);
 int mpmhip_upload_grid(mpmhip_ctx *ctx, const float *src);
 
 /* whole-state snapshots — replaces the TC_IO serialization behind general_action "save" / "load"
@@ -479,7 +507,9 @@ int mpmhip_profile_reset(mpmhip_ctx *ctx);
  *               at its rank position), so all holders of a node compute bit-identical values.
  *   migration : mpmhip_leaver_counts -> per-destination counts (synchronises); mpmhip_export_leavers packs the
  *               MPMHIP_MIGRATE_FLOATS-float records grouped by destination rank (ascending) into a device buffer
- *               and removes them locally; mpmhip_import_particles appends received records.
+ *               and removes them locally; mpmhip_import_particles appends received records.  On a ctx whose apic_b rows are
+ *               behind the affine matrices (discard_apic_b, after a substep) the arrivals' rows are stored as zero: a stale row
+ *               says nothing, and its place in the buffer depends on the order of arrival.
  */
 #define MPMHIP_MAX_PARTS 16       /* bricks per axis */
 #define MPMHIP_MAX_HALO_BOXES 64

@@ -7,8 +7,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _SRC = os.path.join(_HERE, "csrc", "mpmhip.hip")
-# the translation units of the library: the second holds the kernels of a job's frame and of a job's snapshot, in a code object of
-# their own, so that the code object with the substep's kernels does not move when they change (csrc/frame_launch.h)
+# the translation units of the library: the second holds the kernels of a job's frame, of a job's snapshot and of the device-pointer
+# field calls, in a code object of their own, so that the code object with the substep's kernels does not move when they change (csrc/frame_launch.h)
 _SRCS = [_SRC, os.path.join(_HERE, "csrc", "k_frame.hip")]
 _DEPS = _SRCS + [os.path.join(_ROOT, "include", "mpmhip.h")] + sorted(
     os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith(".h"))
@@ -232,7 +232,7 @@ _lib = None
 
 _SYMBOLS = ["mpmhip_abi_version", "mpmhip_set_profile_sampling", "mpmhip_create", "mpmhip_destroy", "mpmhip_last_error", "mpmhip_set_stream", "mpmhip_set_deterministic", "mpmhip_set_levelset", "mpmhip_set_rigid_levelset_collision", "mpmhip_set_dirichlet", "mpmhip2d_set_dirichlet", "mpmhip_set_levelset_shapes", "mpmhip_set_levelset_keyframes", "mpmhip_set_levelset_sdf", "mpmhip_debug_levelset_sample", "mpmhip_mesh_to_sdf", "mpmhip_set_levelset_mesh", "mpmhip_download_levelset_sdf",
             "mpmhip_add_group", "mpmhip_add_particles", "mpmhip_poisson_tile", "mpmhip_seed_particles", "mpmhip_num_particles", "mpmhip_download",
-            "mpmhip_upload", "mpmhip_substep", "mpmhip_run_substeps", "mpmhip_step", "mpmhip_current_time",
+            "mpmhip_upload", "mpmhip_download_dev", "mpmhip_upload_dev", "mpmhip_download_grid_dev", "mpmhip_substep", "mpmhip_run_substeps", "mpmhip_step", "mpmhip_current_time",
             "mpmhip_synchronize", "mpmhip_sort", "mpmhip_p2g", "mpmhip_grid_update", "mpmhip_g2p",
             "mpmhip_download_grid", "mpmhip_upload_grid", "mpmhip_calculate_energy", "mpmhip_snapshot_size", "mpmhip_snapshot_save", "mpmhip_snapshot_load", "mpmhip_snapshot_size_group", "mpmhip_snapshot_save_group", "mpmhip_snapshot_head", "mpmhip_snapshot_rows_ranked", "mpmhip_snapshot_load_brick", "mpmhip_snapshot_histogram", "mpmhip_delete_particles_inside_level_set", "mpmhip_bgeo_size", "mpmhip_bgeo_encode", "mpmhip_write_bgeo", "mpmhip_bgeo_size_group", "mpmhip_bgeo_encode_group", "mpmhip_live_id_top", "mpmhip_id_bitmap", "mpmhip_bgeo_rows_ranked", "mpmhip_bgeo_envelope", "mpmhip_set_profiling", "mpmhip_profile",
             "mpmhip_profile_reset", "mpmhip_set_partition", "mpmhip_set_halo", "mpmhip_halo_pack",
@@ -320,6 +320,10 @@ def load():
     L.mpmhip_num_particles.restype = C.c_int64
     L.mpmhip_download.argtypes = [vp, C.c_int32, vp, C.c_int64]
     L.mpmhip_upload.argtypes = [vp, C.c_int32, vp, C.c_int64]
+    L.mpmhip_download_dev.argtypes = [vp, P(vp), C.c_int64, C.c_int32]  # (tables: (c_void_p * 8) of device addresses)
+    L.mpmhip_download_dev.restype = C.c_int64
+    L.mpmhip_upload_dev.argtypes = [vp, P(vp), C.c_int64, C.c_int32]
+    L.mpmhip_download_grid_dev.argtypes = [vp, C.c_int32, vp]
     ip = P(C.c_int32)
     L.mpmhip_set_partition.argtypes = [vp, C.c_int32, ip, ip, ip, ip, C.c_int32]
     L.mpmhip_set_halo.argtypes = [vp, C.c_int32, P(HaloBox)]

@@ -1,6 +1,7 @@
 // taichi_mpm_amd/csrc/k_frame.hip — the kernels of a job's frame (k_frame.h) and of a job's snapshot (k_snapshot_job.h) with their
-// launchers (frame_launch.h, snapshot_job_launch.h), and the impulse rows of a job with CPIC rigid bodies (k_rigid_rows.h,
-// rigid_rows_launch.h): the second translation unit of libmpmhip.so, with a code object of its own.
+// launchers (frame_launch.h, snapshot_job_launch.h), the impulse rows of a job with CPIC rigid bodies (k_rigid_rows.h,
+// rigid_rows_launch.h) and the device-pointer field calls (k_fields.h, fields_launch.h): the second translation unit of libmpmhip.so,
+// with a code object of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -10,6 +11,7 @@
 #include "k_frame.h"
 #include "k_snapshot_job.h"
 #include "k_rigid_rows.h"
+#include "k_fields.h"
 
 namespace mpm {
 
@@ -56,6 +58,25 @@ void rows_launch_out(hipStream_t st, RigidBodyDev *rb, int nb, const RowPut &L, 
 void rows_launch_apply(hipStream_t st, RigidBodyDev *rb, int nb, const float *table, int world, const uint32_t *words, int n_wait,
                        uint32_t epoch, unsigned long long timeout_ticks, Counters *cnt) {
   hipLaunchKernelGGL(k_rigid_rows_world, dim3(1), dim3(64), 0, st, rb, nb, table, world, words, n_wait, epoch, timeout_ticks, cnt);
+}
+
+void fields_launch_count(hipStream_t st, uint32_t n_slots, const RecG *rg, uint32_t *totals) {
+  const uint32_t spans = fields_spans(n_slots);
+  hipLaunchKernelGGL(k_fields_count, dim3(spans), dim3(FIELDS_WG), 0, st, n_slots, rg, totals);
+  hipLaunchKernelGGL(k_id_prefix_scan, dim3(1), dim3(FRAME_WG), 0, st, spans, totals);
+}
+void fields_launch_emit(hipStream_t st, uint32_t n_slots, const float4 *rg, const float4 *rp, const float4 *rb, const uint32_t *offs,
+                        uint32_t n_rows, const FieldTable &dst) {
+  hipLaunchKernelGGL(k_fields_emit, dim3(fields_spans(n_slots)), dim3(FIELDS_WG), 0, st, n_slots, rg, rp, rb, offs, n_rows, dst);
+}
+void fields_launch_emit_ranked(hipStream_t st, uint32_t n_slots, const float4 *rg, const float4 *rp, const float4 *rb, uint32_t top,
+                               const uint32_t *bits, const uint32_t *prefix, uint32_t n_rows, const FieldTable &dst, int32_t *err) {
+  hipLaunchKernelGGL(k_fields_emit_ranked, dim3(fields_spans(n_slots)), dim3(FIELDS_WG), 0, st, n_slots, rg, rp, rb, top, bits, prefix, n_rows, dst, err);
+}
+void fields_launch_put(hipStream_t st, bool ranked, uint32_t n_slots, RecG *rg, RecP *rp, float *rb, const uint32_t *offs, uint32_t top,
+                       const uint32_t *bits, const uint32_t *prefix, uint32_t n_rows, const FieldTable &src, uint32_t *small) {
+  auto k = ranked ? k_fields_put<true> : k_fields_put<false>;
+  hipLaunchKernelGGL(k, dim3(fields_spans(n_slots)), dim3(FIELDS_WG), 0, st, n_slots, rg, rp, rb, offs, top, bits, prefix, n_rows, src, small);
 }
 
 }  // namespace mpm

@@ -5,6 +5,7 @@
 //   k_seed.h (particle seeding from the periodic Poisson-disk tiles, poisson_tile.h; both dimensions)
 //   k_region.h (region expressions: CSG programs over level-set leaves, the region of a seeding call or sampled on a lattice)
 //   k_bgeo.h (.bgeo frame rows)   k_frame.h (the rows of a whole job, ranked by id: its own translation unit, k_frame.hip)   k_mpm88.h (the 2D dense-grid demo, its own small object)
+//   k_fields.h (particle fields to and from caller-owned device arrays; in k_frame.hip too; host driver fields_api.h)
 // host_mem.h: DevBuf / PinnedBuf, the owners of every device and pinned array of the objects below (a new array needs a field and
 // its allocation, nothing else); what a kernel takes by value keeps raw pointers into them.
 // record_state.h: RecordState, the owner of the ctx's validity flags (which arrays describe the current particles); the host code
@@ -109,6 +110,7 @@
 #include "frame_launch.h"
 #include "snapshot_job_launch.h"
 #include "rigid_rows_launch.h"
+#include "fields_launch.h"
 #include "k_mpm88.h"
 #include "k_mpm2d.h"
 #include "k_mpm2d_det.h"
@@ -2206,6 +2208,11 @@ int mpmhip_import_particles(mpmhip_ctx *c, int64_t n, const void *dev_records) {
   hipLaunchKernelGGL(k_import, dim3(particle_grid(n)), dim3(256), 0, c->stream, c->P, (uint32_t)n, (uint32_t)c->n_slots,
                      (const float4 *)dev_records, (float4 *)c->rg.get(), (float4 *)c->rp.get(), (float4 *)c->rb.get(), c->key, c->blk_flag,
                      c->cnt);
+  // discard_apic_b, rows behind RecP.A: what arrived in a record's apic_b row is the sender's stale row, and the pack hands out the
+  // places in the buffer by atomics, so WHICH stale row lands at which slot differs from run to run.  Nobody reads a stale row before
+  // k_recover_b has rewritten it — except a job's snapshot, which copies the rows as they lie and must be the same bytes in two runs
+  // of the deterministic mode: the arrivals' rows are zero.  (Current rows, b_stale off, are kept: they are the particles' apic_b.)
+  if (c->rec.b_stale()) HIPCHK(c, hipMemsetAsync(c->rb.get() + (size_t)c->n_slots * BW, 0, (size_t)n * BW * sizeof(float), c->stream));
   set_slots(c, c->n_slots + n);
   c->rec.records_imported();
   return launch_check(c, "import");
@@ -3500,6 +3507,7 @@ int mpmhip2d_download_grid(mpmhip2d_ctx *m, float *grid) {  // (v.x, v.y, m) per
 #include "async_api.h"
 #include "frame2d_api.h"
 #include "frame_job_api.h"
+#include "fields_api.h"
 // snapshot_blob.h: its copies of the device-side record geometry
 static_assert(snap::RECG_BYTES == sizeof(RecG) && snap::RECP_BYTES == sizeof(RecP) && snap::BROW_BYTES == sizeof(float) * BW, "snapshot_blob.h: records");
 static_assert(snap::RECG_GID == offsetof(RecG, gid) && snap::RECG_PID == offsetof(RecG, pid), "snapshot_blob.h: ids of a RecG");

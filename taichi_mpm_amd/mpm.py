@@ -34,6 +34,40 @@ class MPMError(RuntimeError):
     pass
 
 
+# the names of get_particle_tensors / set_particle_tensors (those of get_particles) -> MPMHIP_F_*
+_TENSOR_FIELDS = dict(x=F_X, v=F_V, B=F_B, F=F_F, aux=F_AUX, gid=F_GID, id=F_ID, states=F_STATES)
+
+
+def check_particle_tensors(tensors, device):
+    """the argument checks of Simulation3D.set_particle_tensors, which need no ctx: [(field, tensor, rows)] or an MPMError that names the
+    key — an unknown or not uploadable key, no tensor, another dtype than the field's, another shape than (n,) / (n, width) with one
+    n for all, a tensor that is not on cuda:<device>"""
+    import torch
+    out, n = [], None
+    for k, t in dict(tensors).items():
+        if k == "gid":
+            raise MPMError("set_particle_tensors: 'gid' cannot be uploaded (a particle keeps its group)")
+        if k not in _TENSOR_FIELDS:
+            raise MPMError("set_particle_tensors: unknown field %r (fields: %s)" % (k, ", ".join(f for f in _TENSOR_FIELDS if f != "gid")))
+        f = _TENSOR_FIELDS[k]
+        w = _WIDTH[f]
+        if not isinstance(t, torch.Tensor):
+            raise MPMError("set_particle_tensors: %r must be a torch.Tensor, got %s" % (k, type(t).__name__))
+        want = torch.int32 if f in (F_ID, F_STATES) else torch.float32
+        if t.dtype != want:
+            raise MPMError("set_particle_tensors: %r must be of dtype %s, got %s" % (k, want, t.dtype))
+        if not ((t.dim() == 1 and w == 1) or (t.dim() == 2 and t.shape[1] == w)):
+            raise MPMError("set_particle_tensors: %r must be of shape %s, got %r" % (k, "(n,) or (n, 1)" if w == 1 else "(n, %d)" % w, tuple(t.shape)))
+        if n is not None and t.shape[0] != n:
+            raise MPMError("set_particle_tensors: %r has %d rows, the tensors before it %d" % (k, t.shape[0], n))
+        n = int(t.shape[0])
+        out.append((f, t, n))
+    for k, t in dict(tensors).items():
+        if t.device.type != "cuda" or t.device.index != int(device):
+            raise MPMError("set_particle_tensors: %r is on %s, the simulation on cuda:%d" % (k, t.device, int(device)))
+    return out
+
+
 def read_snapshot(path, header, frame_words=1):
     """(the Python layer's int64 words in front, the library's blob, the blob's header) of a snapshot file; `header` is the ctypes
     mirror of the blob's header (_lib.SnapHeader, SnapAsync, Snap2DHeader)"""
@@ -1410,6 +1444,73 @@ class Simulation3D:
         self._ensure_ctx()
         a = np.ascontiguousarray(array, np.int32 if field in (F_GID, F_ID, F_STATES) else np.float32)
         self._check(self._L.mpmhip_upload(self._ctx, field, a.ctypes.data_as(C.c_void_p), len(a)))
+
+    # ---------------------------------------------------------------- particle fields as torch tensors on the device
+    # (include/mpmhip.h: mpmhip_download_dev / mpmhip_upload_dev / mpmhip_download_grid_dev — no host copy of a record or a row.
+    # torch is imported inside these methods only: the module imports without it.)
+    def _torch_sync(self, torch):
+        """the library works on the ctx's own stream: what torch has enqueued on the ctx's device (the fill of a tensor to upload,
+        a kernel still reading a block the allocator hands out again) is complete before the library touches the arrays"""
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+
+    def get_particle_tensors(self, fields=None, sort_by_id=True):
+        """dict name -> torch.Tensor on cuda:<device>, freshly allocated and owned by the caller: names, shapes and dtypes of
+        get_particles (width-1 fields 1-D, float32 / int32).  fields: any subset of _TENSOR_FIELDS, default all; the records are read
+        in one call.  sort_by_id=True: rows in ascending creation id (the order that survives a substep), else slot order."""
+        names = tuple(_TENSOR_FIELDS) if fields is None else tuple(fields)
+        for k in names:
+            if k not in _TENSOR_FIELDS:
+                raise MPMError("get_particle_tensors: unknown field %r (fields: %s)" % (k, ", ".join(_TENSOR_FIELDS)))
+        if not names:
+            raise MPMError("get_particle_tensors: no field asked for")
+        import torch
+        self._ensure_ctx()
+        n = self.get_num_particles()
+        dev = torch.device("cuda", self.device)
+        out, table = {}, (C.c_void_p * 8)()
+        for k in names:
+            f = _TENSOR_FIELDS[k]
+            w = _WIDTH[f]
+            out[k] = torch.empty((n,) if w == 1 else (n, w), dtype=torch.int32 if f in (F_GID, F_ID, F_STATES) else torch.float32, device=dev)
+            table[f] = out[k].data_ptr() if n else None
+        if n:
+            self._torch_sync(torch)
+            got = self._check(self._L.mpmhip_download_dev(self._ctx, table, n, 1 if sort_by_id else 0))
+            if got != n:
+                raise MPMError("get_particle_tensors: %d rows written, %d particles are alive" % (got, n))
+        return out
+
+    def set_particle_tensors(self, tensors, sort_by_id=True):
+        """the inverse of get_particle_tensors for the uploadable fields (all but "gid"): a dict name -> tensor on the ctx's device, of
+        exactly the field's dtype and of shape (n,) or (n, width), n = the live particles.  Rows are matched to particles by slot
+        order, or (sort_by_id=True) by the rank of the creation ids the particles hold before the call.  torch's current stream
+        on that device is synchronised before the call."""
+        checked = check_particle_tensors(tensors, self.device)  # (before a ctx is created or touched)
+        if not checked:
+            raise MPMError("set_particle_tensors: no field given")
+        import torch
+        self._ensure_ctx()
+        table, keep = (C.c_void_p * 8)(), []
+        n = checked[0][2]
+        for f, t, _ in checked:
+            t = t.contiguous()
+            keep.append(t)
+            table[f] = t.data_ptr() if n else None
+        if n == 0:
+            if self.get_num_particles() != 0:
+                raise MPMError("set_particle_tensors: 0 rows but the simulation holds %d particles" % self.get_num_particles())
+            return
+        self._torch_sync(torch)
+        self._check(self._L.mpmhip_upload_dev(self._ctx, table, n, 1 if sort_by_id else 0))
+
+    def get_grid_tensor(self, which=1):
+        """get_grid(which) as a float32 torch tensor of shape (rx+1, ry+1, rz+1, 4) on cuda:<device>"""
+        import torch
+        self._ensure_ctx()
+        g = torch.empty((self.res[0] + 1, self.res[1] + 1, self.res[2] + 1, 4), dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._torch_sync(torch)
+        self._check(self._L.mpmhip_download_grid_dev(self._ctx, int(which), g.data_ptr()))
+        return g
 
     # ---------------------------------------------------------------- profiling (TC_PROFILE, src/mpm.cpp:464-572)
     def set_profiling(self, level=1, every=1):
