@@ -640,11 +640,26 @@ def joints_fixture(here):
     print("ref_joints.npz:", ", ".join(cs.JOINT_CASES))
 
 
+def cpic_transfer_fixture(here):
+    """the colour-aware transfers stage by stage on the scenes of tests/cpic_transfer_scenes.py (FIXTURE_CASES): per case the colour
+    field after sort + rasterize_rigid_boundary + gather_cdf (the input of tests/cpic_transfer_model.py), the grid after P2G and after
+    the grid update, the particles after G2P and the bodies between the stages -> ref_cpic_transfer.npz"""
+    from tests import cpic_transfer_runs as ctr
+    from tests import cpic_transfer_scenes as cts
+    out = {}
+    for name, mats, perturb in cts.FIXTURE_CASES:
+        rec = ctr.record_reference(ref, cts.scene(name, mats, perturb))
+        for k, v in rec.items():
+            out["%s/%s" % (cts.case_id(name, mats, perturb), k)] = v
+        print("cpic_transfer", cts.case_id(name, mats, perturb), len(rec["x"]), "particles,", len(rec["cdf_idx"]), "coloured nodes")
+    np.savez_compressed(os.path.join(here, "ref_cpic_transfer.npz"), **out)
+
+
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
     ref.set_threads(1)  # the generic P2G of the reference is racy with more than one thread (SURVEY quirk 5)
     what = sys.argv[1:] or (list(MATS) + ["materials", "illcond", "kernels", "shapes", "mpm2d", "cpic", "cpic2d", "joints",
-                                  "materials2d", "illcond2d", "mpm2d_stretch"])
+                                  "cpic_transfer", "materials2d", "illcond2d", "mpm2d_stretch"])
     for w in what:
         if w in MATS:
             substep_fixture(here, w)
@@ -666,6 +681,8 @@ def main():
             cpic2d_fixture(here)
         elif w == "joints":
             joints_fixture(here)
+        elif w == "cpic_transfer":
+            cpic_transfer_fixture(here)
         elif w == "materials2d":
             materials2d_fixture(here)
         elif w == "illcond2d":

@@ -9,7 +9,8 @@ facts; colours, distances, projections and the impulses themselves are the refer
 Tolerances: grid colour words and particle colour words bit-exact except where a triangle edge or the zero level of the
 fitted distance passes within rounding of a node / particle (a handful of entries allowed to flip); distances 2e-7 (grid),
 5e-7 (particles, least-squares fit), normals 2e-4; after whole substeps x abs 5e-6, v rel-L2 2e-4, F 1e-4, body velocities
-2e-4 relative to the scale of the single impulse terms."""
+2e-4 relative to the scale of the single impulse terms.  (The transfers value by value — every node, particle and body impulse against
+its own bound, on the paths these scenes never reach: tests/test_gpu_cpic_transfer_edges.py.)"""
 import os
 
 import numpy as np
